@@ -17,6 +17,9 @@ timed on this node's host cores on a bounded sample of the same workload, batch 
 path's step on a synthetic device-resident batch after the inference measurement -- N=1: YOLOv8s-seg, batch 64 @640
 (BASELINE config 3) with the forward / loss / backward / optimizer split; N>1: YOLOv8m-seg data parallel, 64 images per
 GPU (config 4), with the gradient all-reduce time alone, the part of it not hidden under backward and the overlap fraction.
+
+`--dump-outputs DIR` writes the outputs of the last timed step as .npy files (`dump_outputs`); inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -57,7 +60,11 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=4,
                     help="event-sampled steps (forward alone, a HIP event pair per launch) run AFTER the timed region; at least 2")
     ap.add_argument("--profile-every", type=int, default=100, help="(ignored since round 4: no step of the timed region is event-sampled)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))     # plain `python bench.py --gpus N`: one child launcher, before any GPU call
@@ -125,6 +132,7 @@ def main():
     ev_post = [[torch.cuda.Event() for _ in range(nbuf)] for _ in range(n_eng)]
     P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     step_no = [0]
+    last_buf = [None]     # (engine, buffer set) the most recent step wrote its outputs to
     last_fwd = [None]     # event after the most recent forward (any engine)
     last_post = [None] * n_eng   # event after the most recent post-processing of each engine
 
@@ -136,6 +144,7 @@ def main():
         i = step_no[0]
         step_no[0] += 1
         e, k = i % n_eng, (i // n_eng) % nbuf
+        last_buf[0] = (e, k)
         sf, sp = s_fwd[e], s_post[e]
         if nbuf == 2:
             sf.wait_event(ev_post[e][k])          # the post-processing that last read this buffer set is done
@@ -184,6 +193,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before the event-sampled steps: they take the buffer sets in turn and would overwrite the last timed step's outputs
+        e, k = last_buf[0]
+        dump_outputs(args.dump_outputs, preds[e][k], protos[e][k], dets[e][k], counts_b[e][k], masks[e][k])
     # Event-sampled steps, AFTER the clock has been read: each runs its forward alone (no other forward, no post-processing beside
     # it) with a HIP event pair around every launch, on the stream the kernels are launched on.
     sampled = 0
@@ -319,6 +332,38 @@ def self_launch(n):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "1")
     return subprocess.run(cmd, env=env).returncode
+
+
+DUMP_IMAGES = 32        # images of the batch that are written (all of them at the default batch)
+DUMP_SAMPLES = 1024     # seeded anchors (preds) and proto pixels (protos) per image
+DUMP_MASK_SLOTS = 32    # detections per image in masks.npy (the bench line's mean is about 22)
+DUMP_MASK_STRIDE = 8    # every 8th row and column of each 640x640 mask
+
+
+def dump_outputs(out_dir, preds, protos, dets, counts, masks):
+    """Write what the caller of the timed path receives from one step, as float32 DIR/<name>.npy (about 37 MB in all):
+    counts (B,), dets (B,max_det,38), masks (B,DUMP_MASK_SLOTS,80,80) strided, and seeded samples of preds (B,DUMP_SAMPLES,4+nc+32)
+    and protos (B,DUMP_SAMPLES,32) -- the same anchors and pixels in every run, so two builds compare element for element.
+    Rows of dets and masks at or past counts[b] are undefined (never written by the kernels) and are written as zeros."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(preds.shape[0], DUMP_IMAGES)
+    rng = np.random.default_rng(0)
+    A, hw = preds.shape[1], protos.shape[1] * protos.shape[2]
+    anchors = torch.from_numpy(np.sort(rng.choice(A, min(A, DUMP_SAMPLES), replace=False))).to(preds.device)
+    pixels = torch.from_numpy(np.sort(rng.choice(hw, min(hw, DUMP_SAMPLES), replace=False))).to(preds.device)
+    counts = counts[:n].long()
+    valid = torch.arange(dets.shape[1], device=dets.device)[None, :] < counts[:, None]          # (n, max_det)
+    s = min(DUMP_MASK_SLOTS, masks.shape[1])
+    m = masks[:n, :s, ::DUMP_MASK_STRIDE, ::DUMP_MASK_STRIDE]
+    out = {"preds": preds[:n, anchors],
+           "protos": protos[:n].reshape(n, hw, -1)[:, pixels],
+           "dets": torch.where(valid[..., None], dets[:n], torch.zeros((), dtype=dets.dtype, device=dets.device)),
+           "counts": counts,
+           "masks": torch.where(valid[:, :s, None, None], m, torch.zeros((), dtype=m.dtype, device=m.device))}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def train_step_bench(world, dist, steps=4, warm=2):
