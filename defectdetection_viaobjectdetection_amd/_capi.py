@@ -100,6 +100,7 @@ SIGNATURES = {
     "m355_grad_sumsq_workspace_floats": (C.c_size_t, []),
     "m355_convt2x2_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "m355_stem_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "m355_stem6_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "m355_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "m355_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "m355_head_decode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

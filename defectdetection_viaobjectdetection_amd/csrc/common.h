@@ -195,6 +195,16 @@ struct StemArgs {
   half_t* y; long y_bstride; int ldy; int Cout;
 };
 int launch_stem(const StemArgs& a, hipStream_t s);
+// YOLOv5u stem: Conv 6x6 / s2 / p2, 3 -> C0 (16, 32, 48) on the uint8 image (conv_stem6_s2.hip)
+struct Stem6Args {
+  const uint8_t* x; int B, H, W;     // uint8 NHWC (B,H,W,3); W a multiple of 16, H even
+  const half_t* w;                   // [C0][128] fp16 in the kernel's row order (pack_stem6_weights); NOT scaled by 1/255
+  const float* bias;                 // [C0], channel order
+  half_t* y; long y_bstride; int ldy; int C0;
+};
+bool stem6_ok(const Stem6Args& a);
+int launch_stem6(const Stem6Args& a, hipStream_t s);
+void pack_stem6_weights(const float* w, int C0, half_t* out);   // (C0,3,6,6) fp32 -> [C0][128] fp16 (host)
 // stem + model.1 + model.2.cv1 in one launch (conv_stem_s2c32.hip): a = the model.1 + cv1 launch, st = the stem launch
 bool stem_s2c32_ok(const ConvArgs& a, const StemArgs& st);
 int launch_stem_s2c32(const ConvArgs& a, const StemArgs& st, hipStream_t s);

@@ -243,6 +243,15 @@ struct Builder {
     add_macs(op, e->phys[op.conv]);
     e->ops.push_back(op);
   }
+  // one launch of an existing physical conv (logicals created by the caller, e.g. C3's cv2 || cv1 pair)
+  void conv_phys(int phys, Slice in, Slice out, Slice res = Slice(), Slice in2 = Slice()) {
+    Op op{};
+    op.kind = OP_CONV;
+    op.conv = phys;
+    op.in = in; op.out = out; op.res = res; op.in2 = in2;
+    add_macs(op, e->phys[op.conv]);
+    e->ops.push_back(op);
+  }
   // C2f: in -> out
   void c2f(const std::string& name, Slice in, Slice out, int n, bool shortcut, Slice up_src = Slice()) {
     const Tensor& ti = e->tensors[in.t];
@@ -538,8 +547,165 @@ int build_graph_v9c(m355_engine* e) {
   return build_segment_head(e, b, feats, fch, 256);
 }
 
+// model.24 = Detect(nc) of YOLOv5u (box-only, nm = 0): per level the two first 3x3 convs (cv2.l.0, cv3.l.0) share their input
+// and run as one launch, the two second convs write side by side, and the two 1x1 output convs run as one block-diagonal launch
+// writing whole raw rows of 64 + nc.  The decode launch turns them into prediction rows of 4 + nc.
+int build_detect_head(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const std::string& pre) {
+  const int nc = e->nc;
+  const int hc2 = std::max(std::max(16, fch[0] / 4), 64);
+  const int hc3 = std::max(fch[0], std::min(nc, 100));
+  int HW[3][2];
+  for (int l = 0; l < 3; ++l) { HW[l][0] = e->tensors[feats[l]].H; HW[l][1] = e->tensors[feats[l]].W; }
+  e->n3 = HW[0][0] * HW[0][1]; e->n4 = HW[1][0] * HW[1][1]; e->n5 = HW[2][0] * HW[2][1];
+  e->A = e->n3 + e->n4 + e->n5;
+  const int lvl_off[3] = {0, e->n3, e->n3 + e->n4};
+  int l_cv2[3][3], l_cv3[3][3];
+  for (int l = 0; l < 3; ++l) {
+    const std::string p = pre + ".cv2." + std::to_string(l);
+    l_cv2[l][0] = b.logical(p + ".0", fch[l], hc2, 3, 1, 1, 0, 1);
+    l_cv2[l][1] = b.logical(p + ".1", hc2, hc2, 3, 1, 1, 0, 1);
+    l_cv2[l][2] = b.logical(p + ".2", hc2, 64, 1, 1, 0, 0, 0);
+  }
+  for (int l = 0; l < 3; ++l) {
+    const std::string p = pre + ".cv3." + std::to_string(l);
+    l_cv3[l][0] = b.logical(p + ".0", fch[l], hc3, 3, 1, 1, 0, 1);
+    l_cv3[l][1] = b.logical(p + ".1", hc3, hc3, 3, 1, 1, 0, 1);
+    l_cv3[l][2] = b.logical(p + ".2", hc3, nc, 1, 1, 0, 0, 0);
+  }
+  const int lane_plan[3] = {1, 1, 0};   // the stride-8 and stride-16 levels beside the stride-32 level on the caller's stream
+  for (int l = 0; l < 3; ++l) {
+    const size_t lvl_first = e->ops.size();
+    const int hcat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3), ucat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3);
+    b.conv_phys(b.phys_from({l_cv2[l][0], l_cv3[l][0]}), Slice{feats[l], 0, fch[l]}, Slice{hcat, 0, hc2 + hc3});
+    b.conv_phys(b.phys_from({l_cv2[l][1]}), Slice{hcat, 0, hc2}, Slice{ucat, 0, hc2});
+    b.conv_phys(b.phys_from({l_cv3[l][1]}), Slice{hcat, hc2, hc3}, Slice{ucat, hc2, hc3});
+    Op op{};
+    op.kind = OP_CONV;
+    op.conv = b.phys_diag({l_cv2[l][2], l_cv3[l][2]});
+    op.in = Slice{ucat, 0, hc2 + hc3};
+    op.out = Slice{-1, 0, 64 + nc};
+    op.out_ext = 1; op.raw_off = 0; op.level_off = lvl_off[l];
+    b.add_macs(op, e->phys[op.conv]);
+    e->ops.push_back(op);
+    for (size_t i = lvl_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[l];
+  }
+  Op op{};
+  op.kind = OP_DECODE;
+  e->ops.push_back(op);
+  e->proto_h = e->proto_w = 0;
+  return 0;
+}
+
+// C3(c1 -> c2, n, shortcut) of YOLOv5u in ONE buffer X = [m out | cv2 out | cv1 out] (3 c_ channels, c_ = c2 / 2): cv2 || cv1
+// are one 1x1 launch into X[c_, 3 c_); the Bottleneck chain (1x1 then 3x3, + input when shortcut) reads X[2 c_:] and leaves its
+// result in X[:c_] (ping-pong tensors in between for n > 1: a residual never aliases its own output); cv3 reads X[:2 c_], which is
+// upstream's cat(m(cv1 x), cv2 x) without a copy.
+void build_c3(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out, int n, bool shortcut, Slice up_src = Slice()) {
+  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c_ = out.c / 2;
+  const int X = b.tensor(H, W, 3 * c_);
+  const int l1 = b.logical(name + ".cv1", in.c, c_, 1, 1, 1, 0, 1);
+  const int l2 = b.logical(name + ".cv2", in.c, c_, 1, 1, 1, 0, 1);
+  const int l3 = b.logical(name + ".cv3", 2 * c_, out.c, 1, 1, 1, 0, 1);
+  b.conv_phys(b.phys_from({l2, l1}), in, Slice{X, c_, 2 * c_}, Slice(), up_src);
+  const int tmp = b.tensor(H, W, c_);
+  int pp[2] = {-1, -1};
+  if (n > 1) { pp[0] = b.tensor(H, W, c_); pp[1] = n > 2 ? b.tensor(H, W, c_) : -1; }
+  Slice src{X, 2 * c_, c_};
+  for (int j = 0; j < n; ++j) {
+    const std::string mn = name + ".m." + std::to_string(j);
+    const int la = b.logical(mn + ".cv1", c_, c_, 1, 1, 1, 0, 1), lb = b.logical(mn + ".cv2", c_, c_, 3, 1, 1, 0, 1);
+    const Slice dst = j == n - 1 ? Slice{X, 0, c_} : Slice{pp[j & 1], 0, c_};
+    b.conv_phys(b.phys_from({la}), src, Slice{tmp, 0, c_});
+    b.conv_phys(b.phys_from({lb}), Slice{tmp, 0, c_}, dst, shortcut ? src : Slice());
+    src = dst;
+  }
+  b.conv_phys(b.phys_from({l3}), Slice{X, 0, 2 * c_}, out);
+}
+
+// YOLOv5u (/root/reference/BscanBased/yolo5s_retrain.py:6 loads yolov5su.pt; upstream cfg/models/v5/yolov5.yaml with
+// the anchor-free Detect head).  model.0 is the 6x6 / s2 / p2 stem (conv_stem6_s2.hip); every other conv goes through the planner's
+// usual kernel rules.  Names and canonical order: spec.py conv_specs_v5u; block structure: tests/yolov5u_det_ref.py.
+int build_graph_v5u(m355_engine* e) {
+  const m355_model_desc& d = e->desc;
+  Builder b{e, 0, 0, 1024};
+  switch (d.scale & 0xff) {
+    case 'n': b.depth = 0.33; b.width = 0.25; break;
+    case 's': b.depth = 0.33; b.width = 0.50; break;
+    case 'm': b.depth = 0.67; b.width = 0.75; break;
+    default: return e->fail(M355_ERR_INVALID, "YOLOv5u scale must be n, s or m (l and x are not built)");
+  }
+  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 64 || d.in_w < 64)
+    return e->fail(M355_ERR_INVALID, "in_h/in_w must be multiples of 32, at least 64");
+  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
+  e->nc = d.nc; e->nm = 0;
+  const int c64 = b.ch(64), c128 = b.ch(128), c256 = b.ch(256), c512 = b.ch(512), c1024 = b.ch(1024);
+  const int H = d.in_h, W = d.in_w;
+  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16, H5 = H / 32, W5 = W / 32;
+  // zero-copy concat buffers: cat12 = [up(x10), x6], cat16 = [up(x14), x4], cat19 = [x18, x14], cat22 = [x21, x10]
+  const int cat12 = b.tensor(H4, W4, 2 * c512), cat16 = b.tensor(H3, W3, 2 * c256);
+  const int cat19 = b.tensor(H4, W4, 2 * c256), cat22 = b.tensor(H5, W5, 2 * c512);
+  const Slice x4{cat16, c256, c256}, x6{cat12, c512, c512}, x10{cat22, c512, c512}, x14{cat19, c256, c256};
+  const int t0 = b.tensor(H1, W1, c64);
+  {
+    const int li = b.logical("model.0", 3, c64, 6, 2, 1, 0, 1);
+    Op op{};
+    op.kind = OP_STEM;
+    op.conv = b.phys_from({li});
+    op.out = Slice{t0, 0, c64};
+    op.Hi = H; op.Wi = W;
+    e->macs += (double)H1 * W1 * c64 * 108;
+    e->ops.push_back(op);
+  }
+  const int t1 = b.tensor(H2, W2, c128), t2 = b.tensor(H2, W2, c128), t3 = b.tensor(H3, W3, c256), t5 = b.tensor(H4, W4, c512),
+            t7 = b.tensor(H5, W5, c1024), t8 = b.tensor(H5, W5, c1024), t9 = b.tensor(H5, W5, c1024);
+  b.conv("model.1", Slice{t0, 0, c64}, Slice{t1, 0, c128}, 3, 2);
+  build_c3(e, b, "model.2", Slice{t1, 0, c128}, Slice{t2, 0, c128}, b.rep(3), true);
+  b.conv("model.3", Slice{t2, 0, c128}, Slice{t3, 0, c256}, 3, 2);
+  build_c3(e, b, "model.4", Slice{t3, 0, c256}, x4, b.rep(6), true);
+  b.conv("model.5", x4, Slice{t5, 0, c512}, 3, 2);
+  build_c3(e, b, "model.6", Slice{t5, 0, c512}, x6, b.rep(9), true);
+  b.conv("model.7", x6, Slice{t7, 0, c1024}, 3, 2);
+  build_c3(e, b, "model.8", Slice{t7, 0, c1024}, Slice{t8, 0, c1024}, b.rep(3), true);
+  {
+    const int c_ = c1024 / 2;
+    const int sp = b.tensor(H5, W5, 4 * c_);                   // SPPF: cv1 -> three serial 5x5 max pools -> cv2
+    b.conv("model.9.cv1", Slice{t8, 0, c1024}, Slice{sp, 0, c_}, 1, 1);
+    Op op{};
+    op.kind = OP_POOL;
+    op.in = Slice{sp, 0, c_};
+    op.out = Slice{sp, c_, 3 * c_};
+    e->ops.push_back(op);
+    b.conv("model.9.cv2", Slice{sp, 0, 4 * c_}, Slice{t9, 0, c1024}, 1, 1);
+  }
+  b.conv("model.10", Slice{t9, 0, c1024}, x10, 1, 1);
+  // 11/12 and 15/16: Upsample + Concat read through by the next C3's cv2 || cv1 (M355_NO_UPFUSE: materialised by upsample2x)
+  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  auto up = [&](Slice src, Slice dst) {
+    if (upfuse) return;
+    Op op{};
+    op.kind = OP_UP;
+    op.in = src; op.out = dst;
+    e->ops.push_back(op);
+  };
+  const int t13 = b.tensor(H4, W4, c512), t17 = b.tensor(H3, W3, c256), t20 = b.tensor(H4, W4, c512), t23 = b.tensor(H5, W5, c1024);
+  up(x10, Slice{cat12, 0, c512});
+  build_c3(e, b, "model.13", Slice{cat12, 0, 2 * c512}, Slice{t13, 0, c512}, b.rep(3), false, upfuse ? x10 : Slice());
+  b.conv("model.14", Slice{t13, 0, c512}, x14, 1, 1);
+  up(x14, Slice{cat16, 0, c256});
+  build_c3(e, b, "model.17", Slice{cat16, 0, 2 * c256}, Slice{t17, 0, c256}, b.rep(3), false, upfuse ? x14 : Slice());
+  b.conv("model.18", Slice{t17, 0, c256}, Slice{cat19, 0, c256}, 3, 2);
+  build_c3(e, b, "model.20", Slice{cat19, 0, 2 * c256}, Slice{t20, 0, c512}, b.rep(3), false);
+  b.conv("model.21", Slice{t20, 0, c512}, Slice{cat22, 0, c512}, 3, 2);
+  build_c3(e, b, "model.23", Slice{cat22, 0, 2 * c512}, Slice{t23, 0, c1024}, b.rep(3), false);
+  const int feats[3] = {t17, t20, t23};
+  const int fch[3] = {c256, c512, c1024};
+  return build_detect_head(e, b, feats, fch, "model.24");
+}
+
 int build_graph(m355_engine* e) {
   const m355_model_desc& d = e->desc;
+  if ((d.scale >> 8) == '5') return build_graph_v5u(e);
+  if ((d.scale >> 8) != 0) return e->fail(M355_ERR_INVALID, "unknown model family in the high byte of m355_model_desc.scale");
   if (d.scale == 'c') return build_graph_v9c(e);
   Builder b{e, 0, 0, 0};
   switch (d.scale) {
@@ -814,6 +980,12 @@ int alloc_all(m355_engine* e) {
   HIP_TRY(e, hipMalloc(&e->nms_ws, e->nms_ws_bytes));
   total += e->nms_ws_bytes + 4096;
   for (PhysConv& p : e->phys) {
+    if (p.cin == 3 && p.k == 6) {   // YOLOv5u stem: [C0][128] fp16 in the kernel's row order + fp32 bias
+      HIP_TRY(e, hipMalloc((void**)&p.w, (size_t)p.cout * 128 * sizeof(half_t)));
+      HIP_TRY(e, hipMalloc((void**)&p.bias, p.cout * sizeof(float)));
+      total += (size_t)p.cout * (128 * sizeof(half_t) + sizeof(float));
+      continue;
+    }
     const bool stem = (p.cin == 3);
     if (stem) {
       HIP_TRY(e, hipMalloc((void**)&p.stem_w, 27 * p.cout * sizeof(float)));
@@ -854,6 +1026,11 @@ void annotate_ops(m355_engine* e) {
         op.flops = 2.0 * to.H * to.W * p.cout * 27;
         op.bytes = (double)op.Hi * op.Wi * 3 + (double)to.H * to.W * p.cout * 2;
         op.wbytes = 28.0 * p.cout * 4;
+        if (p.k == 6) {
+          snprintf(op.kernel, sizeof(op.kernel), "stem6_s2<k6s2p2,u8,mfma>");
+          op.flops = 2.0 * to.H * to.W * p.cout * 108;
+          op.wbytes = (double)p.cout * (128 * 2 + 4);
+        }
         break;
       }
       case OP_CONV:
@@ -1034,7 +1211,7 @@ void annotate_ops(m355_engine* e) {
       }
       case OP_DECODE:
         snprintf(op.kernel, sizeof(op.kernel), "head_decode");
-        snprintf(op.layer, sizeof(op.layer), "model.22.decode");
+        snprintf(op.layer, sizeof(op.layer), e->nm == 0 ? "model.24.decode" : "model.22.decode");
         op.bytes = (double)e->A * ((64 + e->nc + e->nm) + (4 + e->nc + e->nm)) * 4;
         break;
     }
@@ -1043,7 +1220,7 @@ void annotate_ops(m355_engine* e) {
   for (size_t i = 0; i + 1 < e->ops.size(); ++i) {
     Op& st = e->ops[i];
     Op& nx = e->ops[i + 1];
-    if (st.kind != OP_STEM || !nx.s2c32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || getenv("M355_NO_STEMFUSE")) continue;
+    if (st.kind != OP_STEM || e->phys[st.conv].k != 3 || !nx.s2c32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || getenv("M355_NO_STEMFUSE")) continue;
     bool other = false;
     for (size_t j = i + 2; j < e->ops.size(); ++j)
       if (e->ops[j].in.t == st.out.t || e->ops[j].res.t == st.out.t || e->ops[j].in2.t == st.out.t) other = true;
@@ -1327,7 +1504,12 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
     }
     return M355_OK;
   }
-  if (ci.cin == 3) {  // stem: [cout][32] fp16, k = (kh*3+kw)*3+c; 1/255 is applied in the kernel's epilogue
+  if (ci.cin == 3 && ci.k == 6) {   // YOLOv5u stem (conv_stem6_s2.hip): [C0][128] fp16 rows in the kernel's order
+    std::vector<half_t> sw((size_t)ci.cout * 128);
+    pack_stem6_weights(w, ci.cout, sw.data());
+    HIP_TRY(e, hipMemcpy(p.w, sw.data(), sw.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(p.bias, bias, ci.cout * sizeof(float), hipMemcpyHostToDevice));
+  } else if (ci.cin == 3) {  // stem: [cout][32] fp16, k = (kh*3+kw)*3+c; 1/255 is applied in the kernel's epilogue
     std::vector<half_t> sw((size_t)ci.cout * 32, (half_t)0.f);
     for (int co = 0; co < ci.cout; ++co)
       for (int c = 0; c < 3; ++c)
@@ -1407,7 +1589,7 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
 
 int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* d_protos, void* stream) {
   if (!e) return M355_ERR_INVALID;
-  if (!d_in || !d_preds || !d_protos) return e->fail(M355_ERR_INVALID, "null device pointer");
+  if (!d_in || !d_preds || (!d_protos && e->nm > 0)) return e->fail(M355_ERR_INVALID, "null device pointer");
   if (B < 1 || B > e->desc.max_batch) return e->fail(M355_ERR_STATE, "batch exceeds max_batch");
   for (size_t i = 0; i < e->conv_loaded.size(); ++i)
     if (!e->conv_loaded[i]) return e->fail(M355_ERR_STATE, std::string("weights not set for ") + e->convs[i].name);
@@ -1454,6 +1636,15 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
       case OP_STEM: {
         const PhysConv& p = e->phys[op.conv];
         const Tensor& to = e->tensors[op.out.t];
+        if (p.k == 6) {
+          Stem6Args a{};
+          a.x = (const uint8_t*)d_in + (long)b0 * op.Hi * op.Wi * 3; a.B = Bq; a.H = op.Hi; a.W = op.Wi;
+          a.w = p.w; a.bias = p.bias; a.C0 = p.cout;
+          a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C;
+          a.y = to.p + op.out.off + b0 * a.y_bstride;
+          rc = launch_stem6(a, s);
+          break;
+        }
         StemArgs a{};
         a.x = (const uint8_t*)d_in + (long)b0 * op.Hi * op.Wi * 3; a.B = Bq; a.H = op.Hi; a.W = op.Wi;
         a.w16 = (const half_t*)p.stem_w; a.bias = p.bias;
@@ -1775,6 +1966,7 @@ int m355_postprocess(m355_engine* e, const float* d_preds, const void* d_protos,
   if (!e) return M355_ERR_INVALID;
   if (!d_preds || !d_dets || !d_counts) return e->fail(M355_ERR_INVALID, "null device pointer");
   if (B < 1 || B > e->desc.max_batch) return e->fail(M355_ERR_STATE, "batch exceeds max_batch");
+  if (d_masks && e->nm == 0) return e->fail(M355_ERR_INVALID, "a detection engine has no masks: pass d_masks = NULL");
   hipStream_t s = (hipStream_t)stream;
   int rc = launch_nms(d_preds, B, e->A, e->nc, e->nm, conf, iou, max_det, d_dets, d_counts, e->nms_ws,
                       e->nms_ws_bytes, s);
@@ -2336,6 +2528,24 @@ int m355_stem_fwd(const void* d_in, int B, int H, int W, const float* h_w, const
   if (rc != 0) return set_err(M355_ERR_HIP, "stem launch failed: " + std::to_string(rc));
   if (se != hipSuccess) return set_err(M355_ERR_HIP, std::string("stem kernel: ") + hipGetErrorString(se));
   return M355_OK;
+}
+
+int m355_stem6_fwd(const void* d_x, int B, int H, int W, const float* h_w, const float* h_bias, int C0, void* d_y, void* stream) {
+  // every argument before any HIP call
+  if (!d_x || !h_w || !h_bias || !d_y) return set_err(M355_ERR_INVALID, "stem6: null pointer");
+  if (C0 != 16 && C0 != 32 && C0 != 48) return set_err(M355_ERR_INVALID, "stem6: C0 must be 16, 32 or 48");
+  if (B < 1 || B > 65535 || H < 2 || W < 16 || H % 2 || W % 16)
+    return set_err(M355_ERR_INVALID, "stem6: B >= 1, H even and positive, W a positive multiple of 16");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<half_t> sw((size_t)C0 * 128);
+  pack_stem6_weights(h_w, C0, sw.data());
+  DevBuf d;
+  Stem6Args a{};
+  a.x = (const uint8_t*)d_x; a.B = B; a.H = H; a.W = W; a.C0 = C0;
+  a.w = d.put(sw); a.bias = d.put(std::vector<float>(h_bias, h_bias + C0));
+  a.y = (half_t*)d_y; a.ldy = C0; a.y_bstride = (long)(H / 2) * (W / 2) * C0;
+  if (!a.w || !a.bias) return set_err(M355_ERR_HIP, "allocation failed");
+  return finish_entry(launch_stem6(a, s), s, "stem6_s2");
 }
 
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream) {

@@ -13,7 +13,7 @@ import torch
 
 from . import _capi
 from ._capi import ConvInfo, ModelDesc, OpInfo, check, lib
-from .spec import V9C, ConvSpec, conv_specs, fold_bn
+from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_v5u
 
 
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -24,8 +24,18 @@ def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def scale_code(scale: str) -> int:
+    """m355_model_desc.scale of a scale tag: 'n'..'x' (yolov8-seg), 'c' (yolov9c-seg), ('5' << 8) | n/s/m (YOLOv5u)."""
+    if scale == V9C:
+        return ord("c")
+    if is_v5u(scale):
+        return (ord("5") << 8) | ord(scale[1])
+    return ord(scale)
+
+
 class SegEngine:
-    """One engine per device.  Not thread-safe (one handle, one caller)."""
+    """One engine per device.  Not thread-safe (one handle, one caller).  Serves the segmentation graphs (nm = 32 mask
+    coefficients, prototypes) and the YOLOv5u detection graphs (nm = 0: no prototypes, no masks)."""
 
     def __init__(self, scale: str = "s", nc: int = 1, imgsz: Tuple[int, int] = (640, 640),
                  max_batch: int = 32, device: int = 0, keep_raw: bool = True):
@@ -38,7 +48,7 @@ class SegEngine:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
-            desc = ModelDesc(ord("c" if scale == V9C else scale), nc, imgsz[0], imgsz[1], max_batch)   # 'c': yolov9c-seg
+            desc = ModelDesc(scale_code(scale), nc, imgsz[0], imgsz[1], max_batch)
             check(lib.m355_create(C.byref(desc), C.byref(self._h)))
             check(lib.m355_set_keep_raw(self._h, int(keep_raw)), self._h)
         self.num_anchors = lib.m355_num_anchors(self._h)
@@ -46,7 +56,7 @@ class SegEngine:
         ph, pw = C.c_int(), C.c_int()
         check(lib.m355_proto_hw(self._h, C.byref(ph), C.byref(pw)), self._h)
         self.proto_hw = (ph.value, pw.value)
-        self.nm = 32
+        self.nm = self.pred_width - 4 - nc      # 32 mask coefficients, or 0 for a detection graph
         self.flops_per_image = lib.m355_flops_per_image(self._h)
         self.workspace_bytes = lib.m355_workspace_bytes(self._h)
         self.specs: List[ConvSpec] = conv_specs(scale, nc)
@@ -61,6 +71,8 @@ class SegEngine:
         from .spec import SCALES
         if scale == V9C:
             return "M355_NO_PROTOFUSE" not in os.environ      # 256 prototype channels
+        if is_v5u(scale):
+            return False                                      # no Proto at all
         _, width, maxc = SCALES[scale]
         npr = int(math.ceil(min(256, maxc) * width / 8) * 8)
         return npr % 64 == 0 and "M355_NO_PROTOFUSE" not in os.environ
@@ -95,7 +107,7 @@ class SegEngine:
 
     # ------------------------------------------------------------------ forward / postprocess
     def forward(self, images_u8_nhwc: torch.Tensor):
-        """images: uint8 (B,H,W,3) on this device.  Returns preds f32 (B,A,4+nc+32), protos f16 (B,h,w,32)."""
+        """images: uint8 (B,H,W,3) on this device.  Returns preds f32 (B,A,4+nc+nm), protos f16 (B,h,w,32) (None when nm = 0)."""
         x = images_u8_nhwc
         if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or tuple(x.shape[1:3]) != self.imgsz:
             raise ValueError(f"expected uint8 (B,{self.imgsz[0]},{self.imgsz[1]},3), got {x.dtype} {tuple(x.shape)}")
@@ -103,7 +115,9 @@ class SegEngine:
             raise ValueError("input must be a contiguous CUDA tensor")
         B = x.shape[0]
         preds = torch.empty((B, self.num_anchors, self.pred_width), dtype=torch.float32, device=x.device)
-        protos = torch.empty((B, self.proto_hw[0], self.proto_hw[1], self.nm), dtype=torch.float16, device=x.device)
+        protos = None
+        if self.nm:
+            protos = torch.empty((B, self.proto_hw[0], self.proto_hw[1], self.nm), dtype=torch.float16, device=x.device)
         check(lib.m355_forward(self._h, _ptr(x), B, _ptr(preds), _ptr(protos), _stream()), self._h)
         return preds, protos
 
@@ -117,9 +131,10 @@ class SegEngine:
 
     def postprocess(self, preds: torch.Tensor, protos: Optional[torch.Tensor], conf: float = 0.25,
                     iou: float = 0.7, max_det: int = 300, masks: bool = True, multi_label: bool = False, max_nms: int = 30000):
-        """Batched NMS + mask assembly.  Returns dets f32 (B,max_det,38), counts i32 (B),
-        masks u8 (B,max_det,H,W) or None.  Only rows < counts[b] are defined.
+        """Batched NMS + mask assembly.  Returns dets f32 (B,max_det,6+nm), counts i32 (B),
+        masks u8 (B,max_det,H,W) or None (always None for a detection graph).  Only rows < counts[b] are defined.
         ``multi_label`` (upstream's validator mode, nc > 1): every (anchor, class) pair above ``conf`` is a candidate."""
+        masks = masks and self.nm > 0
         if multi_label and self.nc > 1:
             return self._postprocess_multilabel(preds, protos, conf, iou, max_det, masks, max_nms)
         B = preds.shape[0]

@@ -22,10 +22,11 @@ import torch
 
 from .preprocess import expand_sources, letterbox, letterbox_shape, scale_boxes_to_original
 from .results import Results
-from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, state_dict_keys
+from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_v5u, state_dict_keys
 
 _YAML_RE = re.compile(r"^yolov8([nsmlx])?-seg\.ya?ml$")
 _V9C_RE = re.compile(r"^yolov9c-seg\.ya?ml$")
+_V5U_RE = re.compile(r"^yolov5([nsmlx])u\.ya?ml$")
 CKPT_FORMAT = "mi355yolo-seg-v1"
 
 
@@ -66,10 +67,22 @@ class YOLO:
             if os.path.isfile(model):
                 self._read_yaml_overrides(model)
             self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
+        elif _V5U_RE.match(name):
+            # the detection family the reference retrains (/root/reference/BscanBased/yolo5s_retrain.py:6: yolov5su.pt)
+            sc = _V5U_RE.match(name).group(1)
+            if sc in "lx":
+                raise NotImplementedError(f"'{name}': YOLOv5u scales l and x are not built (n, s and m are)")
+            self.scale = "5" + sc
+            self.task = "detect"
+            self.nc = 80
+            self.names = {i: f"class{i}" for i in range(self.nc)}
+            if os.path.isfile(model):
+                self._read_yaml_overrides(model)
+            self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
         elif name.endswith((".yaml", ".yml")):
             raise NotImplementedError(
-                f"architecture '{name}' is not built: this package implements the YOLOv8{{n,s,m,l,x}}-seg and YOLOv9c-seg "
-                "graphs; the detect-task families (yolov5u / yolo11) are listed as next rows in SURVEY.md 8(f) N4")
+                f"architecture '{name}' is not built: this package implements the YOLOv8{{n,s,m,l,x}}-seg, YOLOv9c-seg and "
+                "YOLOv5{n,s,m}u graphs; yolo11 is listed as a next row in SURVEY.md 8(f) N4")
         elif name.endswith(".pt"):
             if not os.path.isfile(model):
                 raise OfflineModelError(
@@ -123,12 +136,14 @@ class YOLO:
             self.train_args = up["train_args"]
             self.state_dict = up["state_dict"]
             self.ckpt_path = path
+            self.task = "detect" if is_v5u(self.scale) else "segment"
             return
         self.scale, self.nc = ck["scale"], int(ck["nc"])
         self.names = {int(k): v for k, v in ck["names"].items()}
         self.train_args = ck.get("train_args", {})
         self.state_dict = ck["model"]
         self.ckpt_path = path
+        self.task = "detect" if is_v5u(self.scale) else "segment"
         self._resume_state = ck.get("trainer")       # present in weights/last.pt: lets train(resume=True) continue
 
     def save(self, path: str, upstream: bool = False) -> str:
@@ -137,6 +152,8 @@ class YOLO:
         is this package's plain state-dict format."""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         if upstream:
+            if is_v5u(self.scale):
+                raise NotImplementedError("upstream export of a YOLOv5u detection model is not built")
             from .upstream_export import export_upstream_checkpoint
             return export_upstream_checkpoint(path, self.scale, self.nc, self.names, self.state_dict, self.train_args)
         torch.save({"format": CKPT_FORMAT, "scale": self.scale, "nc": self.nc, "names": self.names,
@@ -189,7 +206,7 @@ class YOLO:
         results: List[Results] = []
         save_dir = None
         if save:
-            save_dir = _increment_dir(os.path.join(project or os.path.join("runs", "segment"), name or "predict"))
+            save_dir = _increment_dir(os.path.join(project or os.path.join("runs", self.task), name or "predict"))
             os.makedirs(save_dir, exist_ok=True)
         t_pre = (time.perf_counter() - t0) * 1e3 / len(imgs)
         for i0 in range(0, len(imgs), batch):
@@ -208,7 +225,7 @@ class YOLO:
                 d = dets[j, :n, :6].cpu().numpy()
                 orig = imgs[i0 + j]
                 d[:, :4] = scale_boxes_to_original(d[:, :4], net_shape, orig.shape[:2])
-                m = masks[j, :n].cpu()
+                m = masks[j, :n].cpu() if masks is not None else None
                 speed = {"preprocess": t_pre, "inference": (t2 - t1) * 1e3 / len(chunk),
                          "postprocess": (t3 - t2) * 1e3 / len(chunk)}
                 r = Results(orig, paths[i0 + j], self.names, torch.from_numpy(d), m, speed, net_shape)
@@ -228,10 +245,17 @@ class YOLO:
     # ------------------------------------------------------------------ training
     def train(self, data: Optional[str] = None, epochs: int = 100, imgsz: int = 640, batch: int = 16,
               project: Optional[str] = None, name: Optional[str] = None, device=0, **kwargs):
+        self._require_segment("train")
         from .train import train as _train  # lazy: training pulls in the loss / dataset modules
         return _train(self, data=data, epochs=epochs, imgsz=imgsz, batch=batch, project=project, name=name,
                       device=device, **kwargs)
 
     def val(self, data: Optional[str] = None, imgsz: Optional[int] = None, batch: int = 16, device=0, **kwargs):
+        self._require_segment("val")
         from .train import validate as _validate
         return _validate(self, data=data, imgsz=imgsz, batch=batch, device=device, **kwargs)
+
+    def _require_segment(self, what: str) -> None:
+        if self.task != "segment":
+            raise NotImplementedError(f"{what}() of a {self.task} model: detect training and validation (YOLOv5u) are not built "
+                                      "yet; this package trains and validates the segmentation graphs only")

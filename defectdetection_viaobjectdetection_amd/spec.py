@@ -19,6 +19,9 @@ import torch
 SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768),
           "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)}
 V9C = "9c"     # the `scale` tag of the yolov9c-seg graph (SURVEY next row N4); the C-ABI descriptor carries it as 'c'
+# YOLOv5u detection graphs (/root/reference/BscanBased/yolo5s_retrain.py:6 loads yolov5su.pt): scale tags
+# "5n" / "5s" / "5m", (depth, width, max channels) of upstream's yolov5.yaml.  The C-ABI descriptor carries ('5' << 8) | n/s/m.
+V5U_SCALES = {"5n": (0.33, 0.25, 1024), "5s": (0.33, 0.50, 1024), "5m": (0.67, 0.75, 1024)}
 REG_MAX = 16
 NM = 32
 BN_EPS = 1e-3
@@ -93,6 +96,83 @@ def conv_specs_v9c(nc: int = 1) -> List[ConvSpec]:
     return out
 
 
+def is_v5u(scale: str) -> bool:
+    return scale in V5U_SCALES
+
+
+def head_prefix(scale: str) -> str:
+    """State-dict prefix of the head: model.24 = Detect of YOLOv5u, model.22 = Segment of the seg graphs."""
+    return "model.24" if is_v5u(scale) else "model.22"
+
+
+def v5u_widths(scale: str):
+    """(C0, P3, P4, P5) channel widths of a YOLOv5u scale: 16/64/128/256, 32/128/256/512, 48/192/384/768."""
+    _, width, maxc = V5U_SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
+    return ch(64), ch(256), ch(512), ch(1024)
+
+
+def conv_specs_v5u(scale: str, nc: int = 1) -> List[ConvSpec]:
+    """Canonical list of every convolution of YOLOv5u (upstream cfg/models/v5/yolov5.yaml, the `u` anchor-free head) in the
+    order ``libmi355yolo`` reports them = upstream's state-dict order.  C3(c1, c2, n): cv1 / cv2 1x1 c1 -> c2/2, cv3 1x1 over
+    cat(m(cv1 x), cv2 x), m = n Bottlenecks (1x1 then 3x3, c2/2 -> c2/2).  Block structure: tests/yolov5u_det_ref.py."""
+    if scale not in V5U_SCALES:
+        raise ValueError(f"YOLOv5u scale '{scale}' is not built: one of {sorted(V5U_SCALES)} (l and x are out of scope)")
+    depth, width, maxc = V5U_SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
+    rep = lambda n: max(round(n * depth), 1) if n > 1 else n  # noqa: E731
+    c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    out: List[ConvSpec] = []
+
+    def conv(name, cin, cout, k, s):
+        out.append(ConvSpec(name, cin, cout, k, s, True))
+
+    def c3(name, c1, c2, n):
+        c_ = c2 // 2
+        conv(f"{name}.cv1", c1, c_, 1, 1)
+        conv(f"{name}.cv2", c1, c_, 1, 1)
+        conv(f"{name}.cv3", 2 * c_, c2, 1, 1)
+        for j in range(n):
+            conv(f"{name}.m.{j}.cv1", c_, c_, 1, 1)
+            conv(f"{name}.m.{j}.cv2", c_, c_, 3, 1)
+
+    conv("model.0", 3, c64, 6, 2)
+    conv("model.1", c64, c128, 3, 2)
+    c3("model.2", c128, c128, rep(3))
+    conv("model.3", c128, c256, 3, 2)
+    c3("model.4", c256, c256, rep(6))
+    conv("model.5", c256, c512, 3, 2)
+    c3("model.6", c512, c512, rep(9))
+    conv("model.7", c512, c1024, 3, 2)
+    c3("model.8", c1024, c1024, rep(3))
+    conv("model.9.cv1", c1024, c1024 // 2, 1, 1)
+    conv("model.9.cv2", c1024 * 2, c1024, 1, 1)
+    conv("model.10", c1024, c512, 1, 1)
+    c3("model.13", c512 + c512, c512, rep(3))
+    conv("model.14", c512, c256, 1, 1)
+    c3("model.17", c256 + c256, c256, rep(3))
+    conv("model.18", c256, c256, 3, 2)
+    c3("model.20", c256 + c256, c512, rep(3))
+    conv("model.21", c512, c512, 3, 2)
+    c3("model.23", c512 + c512, c1024, rep(3))
+    _detect_specs(out, nc, (c256, c512, c1024), "model.24")
+    return out
+
+
+def _detect_specs(out: List[ConvSpec], nc: int, fch, pre: str) -> None:
+    """Detect head (box-only, no mask coefficients): cv2.{l}.{0,1,2} box branches, cv3.{l}.{0,1,2} class branches."""
+    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
+    hc3 = max(fch[0], min(nc, 100))
+    for l in range(3):
+        out.append(ConvSpec(f"{pre}.cv2.{l}.0", fch[l], hc2, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.cv2.{l}.1", hc2, hc2, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
+    for l in range(3):
+        out.append(ConvSpec(f"{pre}.cv3.{l}.0", fch[l], hc3, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.cv3.{l}.1", hc3, hc3, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.cv3.{l}.2", hc3, nc, 1, 1, False))
+
+
 def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
     """model.22 = Segment: the box / class / coefficient branches per level and Proto (A9/A10), upstream state-dict order."""
     hc2 = max(16, fch[0] // 4, REG_MAX * 4)
@@ -120,9 +200,11 @@ def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
 
 
 def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
-    """Canonical list of every convolution of yolov8{scale}-seg (A5/A9/A10); scale "9c": yolov9c-seg."""
+    """Canonical list of every convolution of yolov8{scale}-seg (A5/A9/A10); scale "9c": yolov9c-seg; "5n/5s/5m": YOLOv5u."""
     if scale == V9C:
         return conv_specs_v9c(nc)
+    if is_v5u(scale):
+        return conv_specs_v5u(scale, nc)
     depth, width, maxc = SCALES[scale]
     ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
     rep = lambda n: max(round(n * depth), 1) if n > 1 else n  # noqa: E731
@@ -195,7 +277,7 @@ def state_dict_keys(scale: str, nc: int) -> List[str]:
                                                   ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
         else:
             keys += [f"{s.name}.weight", f"{s.name}.bias"]
-    keys.append("model.22.dfl.conv.weight")
+    keys.append(f"{head_prefix(scale)}.dfl.conv.weight")
     return keys
 
 
@@ -205,11 +287,11 @@ def count_parameters(sd: Dict[str, torch.Tensor]) -> int:
                if not k.endswith(("running_mean", "running_var", "num_batches_tracked")))
 
 
-def _bias_init(sd: Dict[str, torch.Tensor], nc: int, imgsz: int = 640) -> None:
+def _bias_init(sd: Dict[str, torch.Tensor], nc: int, imgsz: int = 640, pre: str = "model.22") -> None:
     """A.1 head bias init: box branch 1.0, class branch log(5/nc/(imgsz/stride)^2)."""
     for l, s in enumerate((8, 16, 32)):
-        sd[f"model.22.cv2.{l}.2.bias"].fill_(1.0)
-        sd[f"model.22.cv3.{l}.2.bias"][:nc] = math.log(5 / nc / (imgsz / s) ** 2)
+        sd[f"{pre}.cv2.{l}.2.bias"].fill_(1.0)
+        sd[f"{pre}.cv3.{l}.2.bias"][:nc] = math.log(5 / nc / (imgsz / s) ** 2)
 
 
 def init_state_dict(scale: str = "s", nc: int = 1, seed: int = 0) -> Dict[str, torch.Tensor]:
@@ -236,8 +318,8 @@ def init_state_dict(scale: str = "s", nc: int = 1, seed: int = 0) -> Dict[str, t
         else:
             sd[f"{s.name}.weight"] = w
             sd[f"{s.name}.bias"] = (torch.rand(s.cout, generator=g) * 2 - 1) * bound
-    sd["model.22.dfl.conv.weight"] = torch.arange(REG_MAX, dtype=torch.float32).view(1, REG_MAX, 1, 1)
-    _bias_init(sd, nc)
+    sd[f"{head_prefix(scale)}.dfl.conv.weight"] = torch.arange(REG_MAX, dtype=torch.float32).view(1, REG_MAX, 1, 1)
+    _bias_init(sd, nc, pre=head_prefix(scale))
     return sd
 
 
@@ -284,10 +366,11 @@ def synthetic_state_dict(scale: str = "s", nc: int = 1, seed: int = 0, cls_bias:
         else:
             sd[f"{s.name}.weight"] = w
             sd[f"{s.name}.bias"] = 0.2 * torch.rand(s.cout, generator=g) - 0.1
-    sd["model.22.dfl.conv.weight"] = torch.arange(REG_MAX, dtype=torch.float32).view(1, REG_MAX, 1, 1)
+    pre = head_prefix(scale)
+    sd[f"{pre}.dfl.conv.weight"] = torch.arange(REG_MAX, dtype=torch.float32).view(1, REG_MAX, 1, 1)
     for l in range(3):
-        sd[f"model.22.cv2.{l}.2.bias"].fill_(1.0)
-        sd[f"model.22.cv3.{l}.2.bias"].fill_(cls_bias)
+        sd[f"{pre}.cv2.{l}.2.bias"].fill_(1.0)
+        sd[f"{pre}.cv3.{l}.2.bias"].fill_(cls_bias)
     return sd
 
 

@@ -163,8 +163,9 @@ def module_state_dict(module_like) -> "OrderedDict[str, torch.Tensor]":
 
 
 def load_upstream_checkpoint(path: str) -> Dict:
-    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg checkpoint."""
-    from .spec import SCALES, conv_specs, state_dict_keys
+    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg, YOLOv9c-seg or YOLOv5u
+    detection checkpoint."""
+    from .spec import SCALES, conv_specs, head_prefix, state_dict_keys
     ck = torch.load(path, map_location="cpu", pickle_module=_PickleModule, weights_only=False)
     if not isinstance(ck, dict):
         raise ValueError(f"{path}: expected a checkpoint dict, got {type(ck).__name__}")
@@ -176,19 +177,29 @@ def load_upstream_checkpoint(path: str) -> Dict:
     stem = sd.get("model.0.conv.weight")
     cls0 = sd.get("model.22.cv3.0.2.weight")
     is_v9c = "model.2.cv2.0.m.0.cv1.conv1.conv.weight" in sd and "model.9.cv5.conv.weight" in sd    # GELAN blocks
-    if stem is None or cls0 is None or "model.22.proto.cv1.conv.weight" not in sd:
+    # YOLOv5u DetectionModel: the 6x6 stem, C3 blocks (cv3) and the Detect head at model.24
+    is_v5u = (stem is not None and tuple(stem.shape[1:]) == (3, 6, 6) and "model.2.cv3.conv.weight" in sd and
+              "model.24.cv3.0.2.weight" in sd)
+    if is_v5u:
+        cls0 = sd["model.24.cv3.0.2.weight"]
+    if stem is None or cls0 is None or ("model.22.proto.cv1.conv.weight" not in sd and not is_v5u):
         kind = getattr(type(model), "_upstream", type(model).__name__)
-        raise ValueError(f"{path}: not a YOLOv8-seg graph ({kind}); only yolov8{{n,s,m,l,x}}-seg is implemented "
-                         "(SURVEY.md next row N4 lists yolov9c-seg / yolov5u / yolo11)")
+        raise ValueError(f"{path}: not a YOLOv8-seg graph ({kind}); yolov8{{n,s,m,l,x}}-seg, yolov9c-seg and yolov5{{n,s,m}}u "
+                         "are implemented (SURVEY.md next row N4 lists yolo11)")
     width = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(int(stem.shape[0]))
-    if is_v9c:
+    if is_v5u:
+        width = {16: "5n", 32: "5s", 48: "5m"}.get(int(stem.shape[0]))
+        if width is None:
+            raise ValueError(f"{path}: YOLOv5u stem width {int(stem.shape[0])}: only the n, s and m scales (16 / 32 / 48) are built")
+    elif is_v9c:
         from .spec import V9C
         width = V9C
-    if width is None or (width not in SCALES and not is_v9c):
+    if width is None or (width not in SCALES and not is_v9c and not is_v5u):
         raise ValueError(f"{path}: stem width {int(stem.shape[0])} does not belong to a YOLOv8 scale")
     nc = int(cls0.shape[0])
     keys = state_dict_keys(width, nc)
-    missing = [k for k in keys if k not in sd and not k.endswith("num_batches_tracked") and k != "model.22.dfl.conv.weight"]
+    dfl = f"{head_prefix(width)}.dfl.conv.weight"
+    missing = [k for k in keys if k not in sd and not k.endswith("num_batches_tracked") and k != dfl]
     if missing:
         raise ValueError(f"{path}: {len(missing)} tensors of yolov8{width}-seg are missing, e.g. {missing[:3]}")
     for s in conv_specs(width, nc):

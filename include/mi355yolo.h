@@ -39,9 +39,11 @@ typedef enum {
 } m355_status;
 
 /* Model description: replaces `YOLO("yolov8{n,s,m,l,x}-seg.yaml")` graph construction
- * (yolo_seg_train.py:7).  nc = number of classes (data-seg.yaml:4-5 -> 1). */
+ * (yolo_seg_train.py:7).  nc = number of classes (data-seg.yaml:4-5 -> 1).
+ * scale selects the graph: 'n','s','m','l','x' = yolov8{scale}-seg; 'c' = yolov9c-seg; ('5' << 8) | 'n','s','m' = YOLOv5u
+ * {n,s,m} (detection: box-only head, no prototypes or mask coefficients).  Any other high byte is M355_ERR_INVALID. */
 typedef struct {
-  int scale;      /* 'n','s','m','l','x' */
+  int scale;      /* low byte: 'n','s','m','l','x','c'; high byte: 0 (segmentation families) or '5' (YOLOv5u) */
   int nc;         /* classes */
   int in_h, in_w; /* network input size, multiples of 32 (640x640 headline) */
   int max_batch;  /* workspace is sized for this many images */
@@ -52,7 +54,7 @@ typedef struct {
   char name[64];   /* ultralytics state-dict prefix, e.g. "model.2.m.0.cv1" (conv+bn) or
                       "model.22.cv2.0.2" (plain conv2d with bias) or "model.22.proto.upsample" */
   int cin, cout;   /* logical channels */
-  int k, stride;   /* kernel size (1,2,3), stride */
+  int k, stride;   /* kernel size (1,2,3; 6 for the YOLOv5u stem model.0), stride */
   int has_bn;      /* 1: Conv2d(bias=False)+BN+SiLU (fold BN before m355_set_conv_weights) */
   int transposed;  /* 1: ConvTranspose2d(k=2,s=2,bias) -- weight layout (cin,cout,2,2) */
   int act;         /* 1: SiLU epilogue */
@@ -72,8 +74,8 @@ void m355_destroy(m355_engine* e);
 int m355_num_convs(const m355_engine* e);
 int m355_get_conv_info(const m355_engine* e, int idx, m355_conv_info* out);
 int m355_num_anchors(const m355_engine* e);           /* 8400 at 640x640 */
-int m355_pred_width(const m355_engine* e);            /* 4 + nc + 32 */
-int m355_proto_hw(const m355_engine* e, int* h, int* w); /* 160x160 at 640 */
+int m355_pred_width(const m355_engine* e);            /* 4 + nc + nm: nm = 32 (segmentation) or 0 (YOLOv5u detection) */
+int m355_proto_hw(const m355_engine* e, int* h, int* w); /* 160x160 at 640; 0x0 for a detection engine */
 size_t m355_workspace_bytes(const m355_engine* e);
 double m355_flops_per_image(const m355_engine* e);    /* 2 * conv MACs */
 
@@ -84,8 +86,8 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
 
 /* Inference forward: d_in is uint8 NHWC (B,in_h,in_w,3) letterboxed pixels in
  * [0,255] (the /255 normalisation is folded into the stem conv).  Outputs:
- *   d_preds  float32 (B, A, 4+nc+32): [cx,cy,w,h (pixels), class scores (sigmoid), 32 mask coefs]
- *   d_protos float16 (B, H/4, W/4, 32) NHWC
+ *   d_preds  float32 (B, A, 4+nc+nm): [cx,cy,w,h (pixels), class scores (sigmoid), nm mask coefs]
+ *   d_protos float16 (B, H/4, W/4, 32) NHWC; a detection engine (nm = 0) writes none and takes d_protos = NULL
  * This is upstream's (B,4+nc+32,A) / (B,32,H/4,W/4) pair in anchor-major / NHWC order. */
 int m355_forward(m355_engine* e, const void* d_in_u8_nhwc, int batch, float* d_preds, void* d_protos,
                  void* stream);
@@ -106,8 +108,8 @@ int m355_get_op_info(const m355_engine* e, int idx, m355_op_info* out);
 int m355_set_profiling(m355_engine* e, int enable);
 int m355_collect_op_times(m355_engine* e, double* ms_sum, long* counts);                  /* [sync] */
 
-/* Train-mode style raw head maps: float32 (B, A, 64+nc+32) = [box DFL logits(64),
- * class logits(nc), mask coefs(32)] before decode.  Valid after m355_forward on the same stream. */
+/* Train-mode style raw head maps: float32 (B, A, 64+nc+nm) = [box DFL logits(64),
+ * class logits(nc), mask coefs(nm)] before decode.  Valid after m355_forward on the same stream. */
 int m355_get_raw_head(m355_engine* e, const float** d_raw, int* width);
 /* Asynchronous device-to-device copy of the first `batch` images of the raw head maps into d_out. */
 int m355_copy_raw_head(m355_engine* e, int batch, float* d_out, void* stream);
@@ -118,10 +120,11 @@ int m355_copy_raw_head(m355_engine* e, int batch, float* d_out, void* stream);
 int m355_set_keep_raw(m355_engine* e, int keep);
 
 /* Post-processing: batched NMS + mask assembly.
- *   d_dets   float32 (B, max_det, 6+32)  rows [x1,y1,x2,y2,conf,cls,coefs] in letterboxed pixels,
+ *   d_dets   float32 (B, max_det, 6+nm)  rows [x1,y1,x2,y2,conf,cls,coefs] in letterboxed pixels,
  *            sorted by confidence descending
  *   d_counts int32 (B)
- *   d_masks  uint8 (B, max_det, in_h, in_w) binary masks (may be NULL to skip mask assembly) */
+ *   d_masks  uint8 (B, max_det, in_h, in_w) binary masks (may be NULL to skip mask assembly; MUST be NULL for a detection
+ *            engine, else M355_ERR_INVALID) */
 int m355_postprocess(m355_engine* e, const float* d_preds, const void* d_protos, int batch, float conf,
                      float iou, int max_det, float* d_dets, int* d_counts, uint8_t* d_masks, void* stream);
 
@@ -229,6 +232,11 @@ int m355_convt2x2_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int cin, co
  * h_w fp32 (cout,3,3,3) is applied to pixel/255.                                            [sync] */
 int m355_stem_fwd(const void* d_in_u8, int B, int H, int W, const float* h_w, const float* h_bias, int cout,
                   void* d_y_f16_nhwc, void* stream);
+/* YOLOv5u stem (model.0, conv_stem6_s2.hip): uint8 NHWC (B,H,W,3) -> fp16 NHWC (B,H/2,W/2,C0),
+ * Conv 6x6 / s2 / p2 + bias + SiLU; h_w fp32 (C0,3,6,6), BN folded, is applied to pixel/255.  C0 in {16,32,48}; H even and
+ * positive, W a positive multiple of 16.  Every argument is checked before any HIP call (-1 = M355_ERR_INVALID).   [sync] */
+int m355_stem6_fwd(const void* d_x_u8_nhwc, int B, int H, int W, const float* h_w, const float* h_bias, int C0,
+                   void* d_y_f16_nhwc, void* stream);
 /* SPPF pooling: x fp16 NHWC (B,H,W,C) -> y (B,H,W,3C) = [mp5(x), mp5(mp5(x)), mp5^3(x)]. */
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
 /* Nearest 2x upsample, fp16 NHWC (B,H,W,C) -> (B,2H,2W,C). */

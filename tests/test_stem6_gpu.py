@@ -1,0 +1,50 @@
+"""The YOLOv5u stem kernel (conv_stem6_s2.hip) through m355_stem6_fwd against
+F.conv2d(x_u8, w.half(), stride 2, padding 2) / 255 + b, SiLU: the whole map by rel-L2 (the CONV_CASES bound) and the border rows
+and columns on their own (a padding error hides in a global norm)."""
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+
+def _ref(x_u8, w, b):
+    x = x_u8.permute(0, 3, 1, 2).float()
+    y = F.conv2d(x, w.half().float(), stride=2, padding=2) / 255.0 + b.view(1, -1, 1, 1)
+    return F.silu(y).permute(0, 2, 3, 1)
+
+
+def rel_l2(a, b):
+    return float((a - b).norm() / (b.norm() + 1e-12))
+
+
+@pytest.mark.parametrize("c0", [16, 32, 48])
+@pytest.mark.parametrize("shape,batch", [((640, 640), 1), ((320, 320), 4), ((256, 384), 3), ((640, 640), 2)])
+def test_stem6_matches_conv2d(c0, shape, batch, cuda_device):
+    from defectdetection_viaobjectdetection_amd import _capi
+    g = torch.Generator().manual_seed(c0 * 7 + batch)
+    H, W = shape
+    x = torch.randint(0, 256, (batch, H, W, 3), generator=g, dtype=torch.uint8)
+    w = (torch.rand((c0, 3, 6, 6), generator=g) * 2 - 1) * 0.05
+    b = torch.rand(c0, generator=g) * 0.4 - 0.2
+    xd = x.to(cuda_device)
+    y = torch.full((batch, H // 2, W // 2, c0), float("nan"), dtype=torch.float16, device=cuda_device)
+    wc, bc = w.contiguous(), b.contiguous()
+    rc = _capi.lib.m355_stem6_fwd(ctypes.c_void_p(xd.data_ptr()), batch, H, W, ctypes.c_void_p(wc.data_ptr()),
+                                  ctypes.c_void_p(bc.data_ptr()), c0, ctypes.c_void_p(y.data_ptr()),
+                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    _capi.check(rc)
+    got = y.float().cpu()
+    want = _ref(x, w, b)
+    assert torch.isfinite(got).all()
+    e = rel_l2(got, want)
+    borders = {"top": (slice(None), 0), "bottom": (slice(None), -1), "left": (slice(None), slice(None), 0),
+               "right": (slice(None), slice(None), -1)}
+    eb = {k: rel_l2(got[v], want[v]) for k, v in borders.items()}
+    print(f"stem6 C0={c0} {shape} b={batch}: rel-L2 {e:.2e} borders " + " ".join(f"{k} {v:.2e}" for k, v in eb.items()) +
+          f" max abs {float((got - want).abs().max()):.2e}")
+    assert e <= 1e-3
+    for k, v in eb.items():
+        assert v <= 1e-3, (k, v)
