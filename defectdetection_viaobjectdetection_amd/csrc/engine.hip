@@ -2386,6 +2386,18 @@ int m355_head_tail_fwd(const void* d_x, int B, int H, int W, int nc, float strid
   return finish_entry(head_tail_ok(ha) ? launch_head_tail(ha, s) : -1, s, "head_tail");
 }
 
+// Phase form of the stride-2 3x3 input gradient (four 2x2 phase convs over dY, conv_igemm.hip) that launch_conv_igemm can tile,
+// for forward input channels cin (the phase width, convt_co) and forward output channels cout (the GEMM's K channels):
+//   3 = compact taps: a channel tile inside one phase (cin % 64 == 0) and whole BK = 64 K slices per tap (cout % 64 == 0);
+//   2 = window slots: a channel tile inside one phase, or whole phases inside a 64-channel tile (4 cin >= 64) without a residual
+//       (phases sharing a tile take the generic epilogue, which does not accumulate);
+//   0 = neither: the masked transposed-stride gather (tmode 1) is the form for that shape.
+static int dgrad_phase_form(int cin, int cout, bool res) {
+  if (cin <= 0 || cin % 8 || cout <= 0 || cout % 8) return 0;
+  if (cin % 64 == 0) return cout % 64 == 0 ? 3 : 2;
+  return (128 % cin == 0 && 4 * cin >= 64 && !res) ? 2 : 0;
+}
+
 int m355_conv2d_dgrad(const void* d_dy, int B, int H, int W, int cin, const float* h_w, int cout, int k, int stride,
                       void* d_dx, void* stream) {
   if (!d_dy || !h_w || !d_dx) return set_err(M355_ERR_INVALID, "null pointer");
@@ -2399,8 +2411,9 @@ int m355_conv2d_dgrad(const void* d_dy, int B, int H, int W, int cin, const floa
   //   stride 1: tap' = flipped tap (kh' = k-1-kh);  stride 2 (transposed-stride gather): tap' = tap
   // stride 2 on even maps: four 2x2 phase convs over dY (conv_igemm.hip, phase == 2) -- rows [phase][ci], columns [(ty, tx)][co];
   // dX row 2i takes tap kh = 1 from dY row i, row 2i + 1 takes kh = 2 from row i and kh = 0 from row i + 1 (columns alike)
-  const bool phases = stride == 2 && k == 3 && H == 2 * Ho && W == 2 * Wo && (cin % 64 == 0 || 128 % cin == 0) &&
-                      !getenv("M355_NO_DGRAD_PHASES");
+  // (which phase form, if any, launch_conv_igemm can tile: dgrad_phase_form; the masked gather otherwise)
+  const int form = stride == 2 && k == 3 && H == 2 * Ho && W == 2 * Wo && !getenv("M355_NO_DGRAD_PHASES") ? dgrad_phase_form(cin, cout, false) : 0;
+  const bool phases = form != 0;
   const int cout_pad = conv_cout_pad(phases ? 4 * cin : cin);
   const int Kpad = phases ? conv_kpad(cout, 2) : conv_kpad(cout, k);
   std::vector<half_t> rows((size_t)cout_pad * Kpad, (half_t)0.f);
@@ -2411,7 +2424,7 @@ int m355_conv2d_dgrad(const void* d_dy, int B, int H, int W, int cin, const floa
           const half_t v = (half_t)h_w[(((size_t)co * cin + ci) * k + kh) * k + kw];
           if (phases) {
             const int pa = kh == 1 ? 0 : 1, ty = kh == 0 ? 1 : 0, pb = kw == 1 ? 0 : 1, tx = kw == 0 ? 1 : 0;
-            const int slot = cin % 64 == 0 ? ty * (1 + pb) + tx : ty * 2 + tx;     // compact taps (phase 3) / window slots (phase 2)
+            const int slot = form == 3 ? ty * (1 + pb) + tx : ty * 2 + tx;         // compact taps (phase 3) / window slots (phase 2)
             rows[(size_t)((2 * pa + pb) * cin + ci) * Kpad + (size_t)slot * cout + co] = v;
           } else {
             const int t = (stride == 1) ? ((k - 1 - kh) * k + (k - 1 - kw)) : (kh * k + kw);
@@ -2434,7 +2447,7 @@ int m355_conv2d_dgrad(const void* d_dy, int B, int H, int W, int cin, const floa
   a.ksize = k; a.stride = 1; a.pad = pad; a.tmode = (stride == 2) ? 1 : 0;
   a.M = B * H * W;
   if (phases) {
-    a.Ho = Ho; a.Wo = Wo; a.Cout = 4 * cin; a.convt_co = cin; a.ksize = 2; a.pad = 0; a.tmode = 0; a.phase = cin % 64 == 0 ? 3 : 2;
+    a.Ho = Ho; a.Wo = Wo; a.Cout = 4 * cin; a.convt_co = cin; a.ksize = 2; a.pad = 0; a.tmode = 0; a.phase = form;
     a.M = B * Ho * Wo;
   }
   int rc;
@@ -2600,9 +2613,17 @@ int m355_conv_launch(const m355_conv_args* c, void* stream) {
   a.ksize = c->ksize; a.stride = c->stride; a.pad = c->pad; a.M = c->batch * c->ho * c->wo;
   a.act = c->act; a.out_f32 = c->out_f32; a.convt_co = c->convt_co; a.tmode = c->tmode;
   a.zero = (const half_t*)c->zero_page;
+  // ConvTranspose (convt_co, ksize 1): the residual would be read at the virtual (pre-shuffle) pixel, not at the output pixel the
+  // result is stored to -- refused rather than computed wrong (the training step adds nothing to a ConvT output)
+  if (c->convt_co > 0 && c->tmode == 0 && c->ksize == 1 && c->res)
+    return set_err(M355_ERR_INVALID, "ConvTranspose (convt_co > 0, ksize 1) takes no residual");
   if (c->tmode == 2) {   // input gradient of a 3x3 / stride-2 / pad-1 conv as four 2x2 phase convs over dY (conv_igemm.hip, phase 2 / 3)
     a.tmode = 0;
-    a.phase = c->convt_co % 64 == 0 ? 3 : 2;   // compact tap layout where a channel tile lies inside one phase
+    // compact tap layout where a channel tile lies inside one phase and the K axis is whole BK = 64 slices (the forward cout = cin here)
+    a.phase = dgrad_phase_form(c->convt_co, c->cin, c->res != nullptr);
+    if (!a.phase)
+      return set_err(M355_ERR_INVALID, "tmode 2 needs convt_co % 64 == 0, or 128 % convt_co == 0 with convt_co >= 16 and no res "
+                                       "(use the tmode 1 gather)");
   }
   int rc;
   // 1x1 convs of the training step (forward and input gradients) on conv1x1_wreg.hip where it applies (the weights are gathered

@@ -382,14 +382,16 @@ class TrainEngine:
                     v = self._pack_view(s.name + ":dgrad4", 4 * cin_p, 4 * cout_p, (4, cin_p, 2, 2, cout_p))
                     wt = w.permute(3, 1, 2, 0)                               # (cin, kh, kw, cout)
                     taps = {0: ((0, 1),), 1: ((0, 2), (1, 0))}              # parity -> ((window slot, forward tap), ...)
-                    # forward input channels in multiples of 64: a phase's taps COMPACT on its K axis (slot ty * (1 + b) + tx), its K loop
-                    # ends behind them (9 tap slots over the four phases instead of 16); otherwise window slots ty * 2 + tx
+                    # forward input and output channels in multiples of 64: a phase's taps COMPACT on its K axis (slot ty * (1 + b) + tx),
+                    # its K loop ends behind them (9 tap slots over the four phases instead of 16); otherwise window slots ty * 2 + tx
+                    # (the rule of m355_conv_launch's tmode 2, include/mi355yolo.h)
+                    compact = cin_p % 64 == 0 and cout_p % 64 == 0
                     vf = v.view(4, cin_p, 4, cout_p)
                     for a in (0, 1):
                         for b in (0, 1):
                             for ty, kh in taps[a]:
                                 for tx, kw in taps[b]:
-                                    slot = ty * (1 + b) + tx if cin_p % 64 == 0 else ty * 2 + tx
+                                    slot = ty * (1 + b) + tx if compact else ty * 2 + tx
                                     out.append((vf[2 * a + b, :, slot:slot + 1, :s.cout].unsqueeze(2), wt[:, kh:kh + 1, kw:kw + 1, :], ()))
         return out
 
@@ -740,7 +742,7 @@ class TrainEngine:
                     gp, gbs, ldg = self._slice_ptr(self.gtensors, src)
                     acc = 0 if self._claim(written, src) else gp
                     if (s.stride == 2 and s.k == 3 and self._dgrad_phases and hi == 2 * ho and wi == 2 * wo
-                            and (cin % 64 == 0 or (128 % cin == 0 and not acc))):
+                            and (cin % 64 == 0 or (128 % cin == 0 and 4 * cin >= 64 and not acc))):
                         self._conv_launch(sv["dz"].data_ptr(), ho * wo * cout, cout, ho, wo, cout, self.packed[name + ":dgrad4"],
                                           gp, gbs, ldg, ho, wo, 4 * cin, 2, 1, 0, res_ptr=acc, r_bs=gbs, ldr=ldg, convt_co=cin, tmode=2)
                     else:

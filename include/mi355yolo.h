@@ -204,9 +204,10 @@ int m355_head_tail_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int nc, fl
                        void* stream);
 /* Data gradient of Conv2d(k in {1,3}, stride in {1,2}, pad k/2, no bias) (SURVEY A13 backward): dY fp16 NHWC
  * (B,Ho,Wo,cout) -> dX fp16 NHWC (B,H,W,cin).  Runs on the same implicit-GEMM kernel: stride 1 = convolution
- * with the spatially flipped, channel-transposed weights; stride 2 = four 2x2 phase convs over dY on even maps (tmode 2 of
- * m355_conv_launch), the masked transposed-stride gather otherwise (or with M355_NO_DGRAD_PHASES=1).  h_w is the
- * FORWARD weight fp32 (cout,cin,k,k) on the host.                                                   [sync] */
+ * with the spatially flipped, channel-transposed weights; stride 2 = four 2x2 phase convs over dY on even maps where
+ * tmode 2 of m355_conv_launch takes the channels (cin % 64 == 0, or 128 % cin == 0 with cin >= 16; compact taps when cin and
+ * cout are both multiples of 64), the masked transposed-stride gather otherwise (or with M355_NO_DGRAD_PHASES=1).  cin and
+ * cout any multiples of 8.  h_w is the FORWARD weight fp32 (cout,cin,k,k) on the host.              [sync] */
 int m355_conv2d_dgrad(const void* d_dy_f16_nhwc, int B, int H, int W, int cin, const float* h_w, int cout, int k,
                       int stride, void* d_dx_f16_nhwc, void* stream);
 /* Weight gradient of Conv2d(k in {1,3}, stride in {1,2}, pad k/2) (SURVEY A13 backward): X fp16 NHWC (B,H,W,cin),
@@ -265,14 +266,18 @@ typedef struct {
   const void* zero_page;                /* >= 16 zero bytes */
 } m355_conv_args;
 /* Convolution / dgrad / ConvTranspose forward on the implicit-GEMM or halo kernel (chosen by shape).
+ * ConvTranspose forward (tmode 0, ksize 1, convt_co > 0): cout = 4 * convt_co virtual channels (dy, dx, co), w_packed rows in that
+ *          order, y = the (2 hi) x (2 wi) output slice of convt_co channels, bias [co]; no res (M355_ERR_INVALID).
  * tmode 1: input gradient of a 3x3 / stride-2 / pad-1 conv by a transposed-stride gather (x = dY, y = dX, all nine taps masked per
  *          output parity; any size).
  * tmode 2: the same gradient as FOUR 2x2 phase convs over dY (one per parity class of the dX pixel): ksize = 2, stride = 1, pad = 0,
  *          hi x wi = ho x wo = the dY map, cout = 4 * convt_co virtual channels (phase-major), convt_co = the forward input channels,
  *          y = the (2 ho) x (2 wo) dX slice, w_packed = [4 * convt_co][(ty, tx, forward cout)] with zero rows for the taps a phase does
- *          not have (16 tap slots for 9 taps; tmode 1 multiplies 36).  Needs convt_co % 64 == 0, or 128 % convt_co == 0 and no res.
- *          With convt_co % 64 == 0 the K axis of a phase is COMPACT -- tap (ty, tx) of phase (a, b) at slot ty * (1 + b) + tx, zeros
- *          behind -- and the phase's K loop ends after its (1 + a)(1 + b) taps: 9 tap slots in all.  Otherwise slot = ty * 2 + tx. */
+ *          not have (16 tap slots for 9 taps; tmode 1 multiplies 36).  Needs convt_co % 64 == 0, or 128 % convt_co == 0 with
+ *          convt_co >= 16 and no res; M355_ERR_INVALID otherwise (tmode 1 takes any such shape).  With convt_co % 64 == 0 AND
+ *          cin % 64 == 0 (cin = the forward cout) the K axis of a phase is COMPACT -- tap (ty, tx) of phase (a, b) at slot
+ *          ty * (1 + b) + tx, zeros behind -- and the phase's K loop ends after its (1 + a)(1 + b) taps: 9 tap slots in all.
+ *          Otherwise slot = ty * 2 + tx. */
 int m355_conv_launch(const m355_conv_args* a, void* stream);
 
 typedef struct {

@@ -34,6 +34,8 @@ DGRAD_CASES = [
     (9, 320, 320, 32, 64, 3, 2),     # ... more chunks (7 200) than waves in flight (2 048): the register prefetch of a wave's next chunk
     (2, 33, 21, 64, 128, 3, 2),      # odd input sizes: the transposed-stride gather (all nine taps masked per output parity)
     (1, 48, 80, 256, 512, 3, 2),
+    (2, 32, 32, 64, 96, 3, 2),       # cin % 64 == 0 but cout 96 (not whole 64-wide K slices): window-slot phases, not compact
+    (2, 32, 32, 8, 32, 3, 2),        # cin 8: no phase form tiles 4 x 8 virtual channels -> the transposed-stride gather
 ]
 
 
