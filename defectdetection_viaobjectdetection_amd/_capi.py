@@ -23,7 +23,8 @@ class ModelDesc(C.Structure):
 
 class ConvInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int),
-                ("stride", C.c_int), ("has_bn", C.c_int), ("transposed", C.c_int), ("act", C.c_int)]
+                ("stride", C.c_int), ("has_bn", C.c_int), ("transposed", C.c_int), ("act", C.c_int),
+                ("groups", C.c_int)]
 
 
 class OpInfo(C.Structure):
@@ -101,6 +102,8 @@ SIGNATURES = {
     "m355_convt2x2_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "m355_stem_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "m355_stem6_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "m355_dwconv3x3_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "m355_psa_attn_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "m355_sppf_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "m355_upsample2x": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "m355_head_decode": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -205,6 +205,29 @@ struct Stem6Args {
 bool stem6_ok(const Stem6Args& a);
 int launch_stem6(const Stem6Args& a, hipStream_t s);
 void pack_stem6_weights(const float* w, int C0, half_t* out);   // (C0,3,6,6) fp32 -> [C0][128] fp16 (host)
+// YOLO11 depthwise 3x3 / s1 / p1 conv on fp16 NHWC channel slices (dwconv3x3.hip)
+struct DwConvArgs {
+  const half_t* x; long x_bstride; int ldx;   // first channel of the input slice; ldx a multiple of 8
+  int B, H, W, C;                             // C a multiple of 8
+  const half_t* w;                            // [9][C] fp16, tap k = dy * 3 + dx (pack_dw3x3_weights)
+  const float* bias;                          // [C] (BN folded)
+  int act;                                    // 1: SiLU
+  half_t* y; long y_bstride; int ldy;         // first channel of the output slice; ldy a multiple of 8
+};
+bool dwconv3x3_ok(const DwConvArgs& a);
+int launch_dwconv3x3(const DwConvArgs& a, hipStream_t s);
+void pack_dw3x3_weights(const float* w, int C, half_t* out);   // (C,1,3,3) fp32 -> [9][C] fp16 (host)
+// YOLO11 C2PSA attention: o + pe(v) of every head in one launch (psa_attn.hip); key_dim 32, head_dim 64
+struct PsaArgs {
+  const half_t* qkv; long q_bstride; int ldq; // (B, H, W, ldq): head h's [q 32 | k 32 | v 64] at channel 128 h
+  int B, H, W, heads, C;                      // C = 64 heads (channels of the result and of pe)
+  const half_t* pe_w;                         // [9][C] fp16 (pack_dw3x3_weights of attn.pe, BN folded)
+  const float* pe_b;                          // [C]
+  float scale_log2e;                          // key_dim^-0.5 * log2(e)
+  half_t* y; long y_bstride; int ldy;         // (B, H, W, ldy): channel 64 h + c
+};
+bool psa_attn_ok(const PsaArgs& a);
+int launch_psa_attn(const PsaArgs& a, hipStream_t s);
 // stem + model.1 + model.2.cv1 in one launch (conv_stem_s2c32.hip): a = the model.1 + cv1 launch, st = the stem launch
 bool stem_s2c32_ok(const ConvArgs& a, const StemArgs& st);
 int launch_stem_s2c32(const ConvArgs& a, const StemArgs& st, hipStream_t s);

@@ -39,7 +39,7 @@ struct ConvLayer {
   // fused group: logical convs that were merged into this physical conv (head first-layer fusion)
 };
 
-enum OpKind { OP_STEM, OP_CONV, OP_CONVT, OP_PHASE, OP_POOL, OP_UP, OP_DECODE, OP_ADOWN, OP_C2F32, OP_PAIR };
+enum OpKind { OP_STEM, OP_CONV, OP_CONVT, OP_PHASE, OP_POOL, OP_UP, OP_DECODE, OP_ADOWN, OP_C2F32, OP_PAIR, OP_DWCONV, OP_PSA_ATTN };
 
 struct Op {
   OpKind kind;
@@ -47,6 +47,7 @@ struct Op {
   int conv2 = -1, conv3 = -1;   // OP_C2F32: Bottleneck.cv2 and C2f.cv2 (conv = Bottleneck.cv1); `in` = the [y0, y1] slice C2f.cv1 wrote
                                 // OP_PAIR: conv = Bottleneck.cv1, conv2 = Bottleneck.cv2 in one launch (conv3x3_planes.hip); out2 = the hidden tensor of the two-launch fallback
   int shortcut = 0;
+  int heads = 0;       // OP_PSA_ATTN: attention heads (conv = the attn.pe depthwise conv, in = the qkv tensor)
   Slice in, out, res;  // tensor slices
   Slice in2;           // upsample read-through: channels [0, in2.c) of `in` come from this half-resolution slice
   Slice out2;          // OP_ADOWN: second output (max-pooled half); `out` is the average-pooled half
@@ -79,6 +80,7 @@ struct Op {
 struct PhysConv {
   std::vector<int> logical;  // indices into convs_
   int cin = 0, cout = 0, k = 1, stride = 1, act = 1, transposed = 0;
+  int groups = 1;            // > 1: depthwise 3x3 (groups = cin = cout): w = [9][cout] fp16 (pack_dw3x3_weights), bias [cout]
   int composed = 0;          // 1: ConvTranspose(2x2,s2) -> Conv(3x3) composed into four 2x2 phase convs (proto)
   int l3 = -1;               // composed + this logical 1x1 conv (proto.cv3) applied in the same kernel's epilogue
   half_t* w2 = nullptr;      // its weights, fp16 [cout2][cin] in logical order, and bias
@@ -175,11 +177,11 @@ struct Builder {
     e->tensors.push_back(t);
     return (int)e->tensors.size() - 1;
   }
-  int logical(const std::string& name, int cin, int cout, int k, int s, int has_bn, int transposed, int act) {
+  int logical(const std::string& name, int cin, int cout, int k, int s, int has_bn, int transposed, int act, int groups = 1) {
     m355_conv_info ci{};
     snprintf(ci.name, sizeof(ci.name), "%s", name.c_str());
     ci.cin = cin; ci.cout = cout; ci.k = k; ci.stride = s; ci.has_bn = has_bn; ci.transposed = transposed;
-    ci.act = act;
+    ci.act = act; ci.groups = groups;
     e->convs.push_back(ci);
     e->conv_loaded.push_back(false);
     e->conv_phys.push_back(-1);
@@ -191,7 +193,7 @@ struct Builder {
     PhysConv p;
     p.logical = logicals;
     const m355_conv_info& c0 = e->convs[logicals[0]];
-    p.cin = c0.cin; p.k = c0.k; p.stride = c0.stride; p.act = c0.act; p.transposed = c0.transposed;
+    p.cin = c0.cin; p.k = c0.k; p.stride = c0.stride; p.act = c0.act; p.transposed = c0.transposed; p.groups = c0.groups;
     int off = 0;
     for (int li : logicals) {
       e->conv_phys[li] = (int)e->phys.size();
@@ -199,7 +201,7 @@ struct Builder {
       off += e->convs[li].cout;
     }
     p.cout = off;
-    p.macs_px = (double)p.cin * p.cout * p.k * p.k;
+    p.macs_px = (double)(p.cin / p.groups) * p.cout * p.k * p.k;
     e->phys.push_back(p);
     return (int)e->phys.size() - 1;
   }
@@ -702,9 +704,230 @@ int build_graph_v5u(m355_engine* e) {
   return build_detect_head(e, b, feats, fch, "model.24");
 }
 
+// One depthwise 3x3 launch (dwconv3x3.hip) of the logical conv li: in -> out, both channel slices
+void dwconv_op(m355_engine* e, Builder& b, int li, Slice in, Slice out) {
+  Op op{};
+  op.kind = OP_DWCONV;
+  op.conv = b.phys_from({li});
+  op.in = in; op.out = out;
+  b.add_macs(op, e->phys[op.conv]);
+  e->ops.push_back(op);
+}
+
+// model.23 = Detect(nc) of YOLO11 (box-only, nm = 0).  Box branch as YOLOv8's; the class branch is DWConv 3x3 -> 1x1 ->
+// DWConv 3x3 -> 1x1 (cv3.l.0.0 .. cv3.l.1.1), so cv2.l.0 no longer shares its launch with the class branch's first conv.  The
+// two second stages write side by side and the two output 1x1 convs run as one block-diagonal launch writing raw rows of
+// 64 + nc, as in build_detect_head.
+int build_detect_head_y11(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const std::string& pre) {
+  const int nc = e->nc;
+  const int hc2 = std::max(std::max(16, fch[0] / 4), 64);
+  const int hc3 = std::max(fch[0], std::min(nc, 100));
+  if (hc3 % 8)
+    return e->fail(M355_ERR_INVALID, "YOLO11: the class branch width max(P3 channels, min(nc, 100)) must be a multiple of 8 "
+                                     "(the depthwise kernel's 16-byte channel groups): n scale with nc in 65..100 not a multiple of 8");
+  int HW[3][2];
+  for (int l = 0; l < 3; ++l) { HW[l][0] = e->tensors[feats[l]].H; HW[l][1] = e->tensors[feats[l]].W; }
+  e->n3 = HW[0][0] * HW[0][1]; e->n4 = HW[1][0] * HW[1][1]; e->n5 = HW[2][0] * HW[2][1];
+  e->A = e->n3 + e->n4 + e->n5;
+  const int lvl_off[3] = {0, e->n3, e->n3 + e->n4};
+  int l_cv2[3][3], l_cv3[3][5];
+  for (int l = 0; l < 3; ++l) {
+    const std::string p = pre + ".cv2." + std::to_string(l);
+    l_cv2[l][0] = b.logical(p + ".0", fch[l], hc2, 3, 1, 1, 0, 1);
+    l_cv2[l][1] = b.logical(p + ".1", hc2, hc2, 3, 1, 1, 0, 1);
+    l_cv2[l][2] = b.logical(p + ".2", hc2, 64, 1, 1, 0, 0, 0);
+  }
+  for (int l = 0; l < 3; ++l) {
+    const std::string p = pre + ".cv3." + std::to_string(l);
+    l_cv3[l][0] = b.logical(p + ".0.0", fch[l], fch[l], 3, 1, 1, 0, 1, fch[l]);
+    l_cv3[l][1] = b.logical(p + ".0.1", fch[l], hc3, 1, 1, 1, 0, 1);
+    l_cv3[l][2] = b.logical(p + ".1.0", hc3, hc3, 3, 1, 1, 0, 1, hc3);
+    l_cv3[l][3] = b.logical(p + ".1.1", hc3, hc3, 1, 1, 1, 0, 1);
+    l_cv3[l][4] = b.logical(p + ".2", hc3, nc, 1, 1, 0, 0, 0);
+  }
+  const int lane_plan[3] = {1, 1, 0};   // as build_detect_head
+  for (int l = 0; l < 3; ++l) {
+    const size_t lvl_first = e->ops.size();
+    const int H = HW[l][0], W = HW[l][1];
+    const int hb = b.tensor(H, W, hc2), ucat = b.tensor(H, W, hc2 + hc3);
+    const int d0 = b.tensor(H, W, fch[l]), e0 = b.tensor(H, W, hc3), d1 = b.tensor(H, W, hc3);
+    b.conv_phys(b.phys_from({l_cv2[l][0]}), Slice{feats[l], 0, fch[l]}, Slice{hb, 0, hc2});
+    b.conv_phys(b.phys_from({l_cv2[l][1]}), Slice{hb, 0, hc2}, Slice{ucat, 0, hc2});
+    dwconv_op(e, b, l_cv3[l][0], Slice{feats[l], 0, fch[l]}, Slice{d0, 0, fch[l]});
+    b.conv_phys(b.phys_from({l_cv3[l][1]}), Slice{d0, 0, fch[l]}, Slice{e0, 0, hc3});
+    dwconv_op(e, b, l_cv3[l][2], Slice{e0, 0, hc3}, Slice{d1, 0, hc3});
+    b.conv_phys(b.phys_from({l_cv3[l][3]}), Slice{d1, 0, hc3}, Slice{ucat, hc2, hc3});
+    Op op{};
+    op.kind = OP_CONV;
+    op.conv = b.phys_diag({l_cv2[l][2], l_cv3[l][4]});
+    op.in = Slice{ucat, 0, hc2 + hc3};
+    op.out = Slice{-1, 0, 64 + nc};
+    op.out_ext = 1; op.raw_off = 0; op.level_off = lvl_off[l];
+    b.add_macs(op, e->phys[op.conv]);
+    e->ops.push_back(op);
+    for (size_t i = lvl_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[l];
+  }
+  Op op{};
+  op.kind = OP_DECODE;
+  e->ops.push_back(op);
+  e->proto_h = e->proto_w = 0;
+  return 0;
+}
+
+// C3k2(c1 -> c2, c3k, e) of YOLO11 (shortcut on) in ONE buffer X = [cv1 out (2c) | m.0 out (c)], c = int(c2 e): C2f's
+// zero-copy layout, cv2 reads X whole.  m.0 = Bottleneck(c, c, e=0.5): 3x3 c -> c/2, 3x3 c/2 -> c + its input; or, with c3k,
+// C3k(c, c, n=2) in a buffer Y = [m out | cv2 out | cv1 out] (c/2 each) as build_c3, with two 3x3 -> 3x3 Bottlenecks.
+void build_c3k2(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out, bool c3k, double ew, Slice up_src = Slice()) {
+  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c = (int)(out.c * ew);
+  const int X = b.tensor(H, W, 3 * c);
+  const int l1 = b.logical(name + ".cv1", in.c, 2 * c, 1, 1, 1, 0, 1);
+  const int l2 = b.logical(name + ".cv2", 3 * c, out.c, 1, 1, 1, 0, 1);
+  b.conv_phys(b.phys_from({l1}), in, Slice{X, 0, 2 * c}, Slice(), up_src);
+  const Slice src{X, c, c}, dst{X, 2 * c, c};
+  const std::string mn = name + ".m.0";
+  if (!c3k) {
+    const int h = c / 2;
+    const int la = b.logical(mn + ".cv1", c, h, 3, 1, 1, 0, 1), lb = b.logical(mn + ".cv2", h, c, 3, 1, 1, 0, 1);
+    const int tmp = b.tensor(H, W, h);
+    b.conv_phys(b.phys_from({la}), src, Slice{tmp, 0, h});
+    b.conv_phys(b.phys_from({lb}), Slice{tmp, 0, h}, dst, src);
+  } else {
+    const int c_ = c / 2;
+    const int k1 = b.logical(mn + ".cv1", c, c_, 1, 1, 1, 0, 1), k2 = b.logical(mn + ".cv2", c, c_, 1, 1, 1, 0, 1);
+    const int k3 = b.logical(mn + ".cv3", 2 * c_, c, 1, 1, 1, 0, 1);
+    int la[2], lb[2];
+    for (int j = 0; j < 2; ++j) {
+      la[j] = b.logical(mn + ".m." + std::to_string(j) + ".cv1", c_, c_, 3, 1, 1, 0, 1);
+      lb[j] = b.logical(mn + ".m." + std::to_string(j) + ".cv2", c_, c_, 3, 1, 1, 0, 1);
+    }
+    const int Y = b.tensor(H, W, 3 * c_), tmp = b.tensor(H, W, c_), mid = b.tensor(H, W, c_);
+    b.conv_phys(b.phys_from({k2, k1}), src, Slice{Y, c_, 2 * c_});
+    b.conv_phys(b.phys_from({la[0]}), Slice{Y, 2 * c_, c_}, Slice{tmp, 0, c_});
+    b.conv_phys(b.phys_from({lb[0]}), Slice{tmp, 0, c_}, Slice{mid, 0, c_}, Slice{Y, 2 * c_, c_});
+    b.conv_phys(b.phys_from({la[1]}), Slice{mid, 0, c_}, Slice{tmp, 0, c_});
+    b.conv_phys(b.phys_from({lb[1]}), Slice{tmp, 0, c_}, Slice{Y, 0, c_}, Slice{mid, 0, c_});
+    b.conv_phys(b.phys_from({k3}), Slice{Y, 0, 2 * c_}, dst);
+  }
+  b.conv_phys(b.phys_from({l2}), Slice{X, 0, 3 * c}, out);
+}
+
+// C2PSA(c1) of YOLO11 with one PSABlock, c = c1 / 2, heads = c / 64.  X = [a | b] is cv1's output; the block's result b2
+// overwrites b in place (b's last readers, qkv and proj's residual, run before), so cv2 reads X = cat(a, b2) without a copy.
+//   qkv (1x1, BN, no act) -> QKV;  OP_PSA_ATTN: O = attention + pe(v) (psa_attn.hip);  proj (1x1, no act) + b -> B1;
+//   ffn.0 (1x1 + SiLU) -> F;  ffn.1 (1x1, no act) + B1 -> X[c:];  cv2 -> out.  The two residuals are epilogue adds.
+void build_c2psa(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out) {
+  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c1 = in.c, c = c1 / 2;
+  const std::string pre = name + ".m.0.";
+  const int l_cv1 = b.logical(name + ".cv1", c1, 2 * c, 1, 1, 1, 0, 1), l_cv2 = b.logical(name + ".cv2", 2 * c, c1, 1, 1, 1, 0, 1);
+  const int l_qkv = b.logical(pre + "attn.qkv", c, 2 * c, 1, 1, 1, 0, 0);
+  const int l_proj = b.logical(pre + "attn.proj", c, c, 1, 1, 1, 0, 0);
+  const int l_pe = b.logical(pre + "attn.pe", c, c, 3, 1, 1, 0, 0, c);
+  const int l_f0 = b.logical(pre + "ffn.0", c, 2 * c, 1, 1, 1, 0, 1);
+  const int l_f1 = b.logical(pre + "ffn.1", 2 * c, c, 1, 1, 1, 0, 0);
+  const int X = b.tensor(H, W, 2 * c), QKV = b.tensor(H, W, 2 * c), O = b.tensor(H, W, c), B1 = b.tensor(H, W, c), F = b.tensor(H, W, 2 * c);
+  b.conv_phys(b.phys_from({l_cv1}), in, Slice{X, 0, 2 * c});
+  b.conv_phys(b.phys_from({l_qkv}), Slice{X, c, c}, Slice{QKV, 0, 2 * c});
+  {
+    Op op{};
+    op.kind = OP_PSA_ATTN;
+    op.conv = b.phys_from({l_pe});
+    op.heads = c / 64;
+    op.in = Slice{QKV, 0, 2 * c};
+    op.out = Slice{O, 0, c};
+    b.add_macs(op, e->phys[op.conv]);   // the pe conv; the two attention products are in the op table's FLOPs
+    e->ops.push_back(op);
+  }
+  b.conv_phys(b.phys_from({l_proj}), Slice{O, 0, c}, Slice{B1, 0, c}, Slice{X, c, c});
+  b.conv_phys(b.phys_from({l_f0}), Slice{B1, 0, c}, Slice{F, 0, 2 * c});
+  b.conv_phys(b.phys_from({l_f1}), Slice{F, 0, 2 * c}, Slice{X, c, c}, Slice{B1, 0, c});
+  b.conv_phys(b.phys_from({l_cv2}), Slice{X, 0, 2 * c}, out);
+}
+
+// YOLO11 (BscanBased/yolo/yolo_bbox_retrain.py trains yolo11n; upstream cfg/models/11/yolo11.yaml, Detect at
+// model.23).  Depth 0.5: every repeated block has n = 1.  Names and canonical order: spec.py conv_specs_y11; block structure:
+// tests/yolo11_det_ref.py.  The stem and every plain conv go through the planner's usual rules; the depthwise convs run on
+// dwconv3x3.hip and the attention core on psa_attn.hip.
+int build_graph_y11(m355_engine* e) {
+  const m355_model_desc& d = e->desc;
+  Builder b{e, 0.5, 0, 1024};
+  bool c3k_all = false;    // upstream parse_model: every C3k2 of the m (l, x) scale uses C3k
+  switch (d.scale & 0xff) {
+    case 'n': b.width = 0.25; break;
+    case 's': b.width = 0.50; break;
+    case 'm': b.width = 1.00; b.maxc = 512; c3k_all = true; break;
+    default: return e->fail(M355_ERR_INVALID, "YOLO11 scale must be n, s or m (l and x are not built)");
+  }
+  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 64 || d.in_w < 64)
+    return e->fail(M355_ERR_INVALID, "in_h/in_w must be multiples of 32, at least 64");
+  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
+  e->nc = d.nc; e->nm = 0;
+  const int c64 = b.ch(64), c128 = b.ch(128), c256 = b.ch(256), c512 = b.ch(512), c1024 = b.ch(1024);
+  const int H = d.in_h, W = d.in_w;
+  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16, H5 = H / 32, W5 = W / 32;
+  // zero-copy concat buffers: cat12 = [up(x10), x6], cat15 = [up(x13), x4], cat18 = [x17, x13], cat21 = [x20, x10]
+  const int cat12 = b.tensor(H4, W4, c1024 + c512), cat15 = b.tensor(H3, W3, c512 + c512);
+  const int cat18 = b.tensor(H4, W4, c256 + c512), cat21 = b.tensor(H5, W5, c512 + c1024);
+  const Slice x4{cat15, c512, c512}, x6{cat12, c1024, c512}, x10{cat21, c512, c1024}, x13{cat18, c256, c512};
+  const int t0 = b.tensor(H1, W1, c64);
+  {
+    const int li = b.logical("model.0", 3, c64, 3, 2, 1, 0, 1);
+    Op op{};
+    op.kind = OP_STEM;
+    op.conv = b.phys_from({li});
+    op.out = Slice{t0, 0, c64};
+    op.Hi = H; op.Wi = W;
+    e->macs += (double)H1 * W1 * c64 * 27;
+    e->ops.push_back(op);
+  }
+  const int t1 = b.tensor(H2, W2, c128), t2 = b.tensor(H2, W2, c256), t3 = b.tensor(H3, W3, c256), t5 = b.tensor(H4, W4, c512),
+            t7 = b.tensor(H5, W5, c1024), t8 = b.tensor(H5, W5, c1024), t9 = b.tensor(H5, W5, c1024);
+  b.conv("model.1", Slice{t0, 0, c64}, Slice{t1, 0, c128}, 3, 2);
+  build_c3k2(e, b, "model.2", Slice{t1, 0, c128}, Slice{t2, 0, c256}, c3k_all, 0.25);
+  b.conv("model.3", Slice{t2, 0, c256}, Slice{t3, 0, c256}, 3, 2);
+  build_c3k2(e, b, "model.4", Slice{t3, 0, c256}, x4, c3k_all, 0.25);
+  b.conv("model.5", x4, Slice{t5, 0, c512}, 3, 2);
+  build_c3k2(e, b, "model.6", Slice{t5, 0, c512}, x6, true, 0.5);
+  b.conv("model.7", x6, Slice{t7, 0, c1024}, 3, 2);
+  build_c3k2(e, b, "model.8", Slice{t7, 0, c1024}, Slice{t8, 0, c1024}, true, 0.5);
+  {
+    const int c_ = c1024 / 2;
+    const int sp = b.tensor(H5, W5, 4 * c_);                   // SPPF: cv1 -> three serial 5x5 max pools -> cv2
+    b.conv("model.9.cv1", Slice{t8, 0, c1024}, Slice{sp, 0, c_}, 1, 1);
+    Op op{};
+    op.kind = OP_POOL;
+    op.in = Slice{sp, 0, c_};
+    op.out = Slice{sp, c_, 3 * c_};
+    e->ops.push_back(op);
+    b.conv("model.9.cv2", Slice{sp, 0, 4 * c_}, Slice{t9, 0, c1024}, 1, 1);
+  }
+  build_c2psa(e, b, "model.10", Slice{t9, 0, c1024}, x10);
+  // 11/12 and 14/15: Upsample + Concat read through by the next C3k2's cv1 (M355_NO_UPFUSE: materialised by upsample2x)
+  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  auto up = [&](Slice src, Slice dst) {
+    if (upfuse) return;
+    Op op{};
+    op.kind = OP_UP;
+    op.in = src; op.out = dst;
+    e->ops.push_back(op);
+  };
+  const int t16 = b.tensor(H3, W3, c256), t19 = b.tensor(H4, W4, c512), t22 = b.tensor(H5, W5, c1024);
+  up(x10, Slice{cat12, 0, c1024});
+  build_c3k2(e, b, "model.13", Slice{cat12, 0, c1024 + c512}, x13, c3k_all, 0.5, upfuse ? x10 : Slice());
+  up(x13, Slice{cat15, 0, c512});
+  build_c3k2(e, b, "model.16", Slice{cat15, 0, c512 + c512}, Slice{t16, 0, c256}, c3k_all, 0.5, upfuse ? x13 : Slice());
+  b.conv("model.17", Slice{t16, 0, c256}, Slice{cat18, 0, c256}, 3, 2);
+  build_c3k2(e, b, "model.19", Slice{cat18, 0, c256 + c512}, Slice{t19, 0, c512}, c3k_all, 0.5);
+  b.conv("model.20", Slice{t19, 0, c512}, Slice{cat21, 0, c512}, 3, 2);
+  build_c3k2(e, b, "model.22", Slice{cat21, 0, c512 + c1024}, Slice{t22, 0, c1024}, true, 0.5);
+  const int feats[3] = {t16, t19, t22};
+  const int fch[3] = {c256, c512, c1024};
+  return build_detect_head_y11(e, b, feats, fch, "model.23");
+}
+
 int build_graph(m355_engine* e) {
   const m355_model_desc& d = e->desc;
   if ((d.scale >> 8) == '5') return build_graph_v5u(e);
+  if ((d.scale >> 8) == '1') return build_graph_y11(e);
   if ((d.scale >> 8) != 0) return e->fail(M355_ERR_INVALID, "unknown model family in the high byte of m355_model_desc.scale");
   if (d.scale == 'c') return build_graph_v9c(e);
   Builder b{e, 0, 0, 0};
@@ -980,6 +1203,12 @@ int alloc_all(m355_engine* e) {
   HIP_TRY(e, hipMalloc(&e->nms_ws, e->nms_ws_bytes));
   total += e->nms_ws_bytes + 4096;
   for (PhysConv& p : e->phys) {
+    if (p.groups > 1) {   // depthwise 3x3: [9][C] fp16 + fp32 bias
+      HIP_TRY(e, hipMalloc((void**)&p.w, (size_t)9 * p.cout * sizeof(half_t)));
+      HIP_TRY(e, hipMalloc((void**)&p.bias, p.cout * sizeof(float)));
+      total += (size_t)p.cout * (9 * sizeof(half_t) + sizeof(float));
+      continue;
+    }
     if (p.cin == 3 && p.k == 6) {   // YOLOv5u stem: [C0][128] fp16 in the kernel's row order + fp32 bias
       HIP_TRY(e, hipMalloc((void**)&p.w, (size_t)p.cout * 128 * sizeof(half_t)));
       HIP_TRY(e, hipMalloc((void**)&p.bias, p.cout * sizeof(float)));
@@ -1209,9 +1438,31 @@ void annotate_ops(m355_engine* e) {
         op.bytes = (double)t.H * t.W * op.in.c * 2 * 5;
         break;
       }
+      case OP_DWCONV: {
+        const PhysConv& p = e->phys[op.conv];
+        const Tensor& ti = e->tensors[op.in.t];
+        snprintf(op.kernel, sizeof(op.kernel), "dwconv3x3<%dch%s>", p.cout, p.act ? ",silu" : "");
+        op.flops = 2.0 * ti.H * ti.W * p.cout * 9;
+        op.bytes = (double)ti.H * ti.W * p.cout * 2 * 2;
+        op.wbytes = (double)p.cout * (9 * 2 + 4);
+        break;
+      }
+      case OP_PSA_ATTN: {
+        const PhysConv& p = e->phys[op.conv];
+        const Tensor& ti = e->tensors[op.in.t];
+        const double N = (double)ti.H * ti.W;
+        snprintf(op.kernel, sizeof(op.kernel), "psa_attn<%d,%d>", op.heads, ti.H * ti.W);
+        snprintf(op.layer, sizeof(op.layer), "%s", e->convs[p.logical[0]].name);
+        char* dot = strstr(op.layer, ".pe");
+        if (dot) snprintf(dot, sizeof(op.layer) - (dot - op.layer), "+pe");
+        op.flops = op.heads * 2.0 * N * N * (32 + 64) + 2.0 * N * p.cout * 9;
+        op.bytes = N * (op.in.c + op.out.c) * 2;
+        op.wbytes = (double)p.cout * (9 * 2 + 4);
+        break;
+      }
       case OP_DECODE:
         snprintf(op.kernel, sizeof(op.kernel), "head_decode");
-        snprintf(op.layer, sizeof(op.layer), e->nm == 0 ? "model.24.decode" : "model.22.decode");
+        snprintf(op.layer, sizeof(op.layer), e->nm > 0 ? "model.22.decode" : (e->desc.scale >> 8) == '1' ? "model.23.decode" : "model.24.decode");
         op.bytes = (double)e->A * ((64 + e->nc + e->nm) + (4 + e->nc + e->nm)) * 4;
         break;
     }
@@ -1363,6 +1614,15 @@ int m355_create(const m355_model_desc* desc, m355_engine** out) {
     return M355_ERR_INVALID;
   }
   *out = nullptr;
+  {   // the family / scale code is checked before the device is: a bad descriptor is M355_ERR_INVALID on any machine
+    const int fam = desc->scale >> 8, sc = desc->scale & 0xff;
+    const bool ok = fam == 0 ? (sc == 'n' || sc == 's' || sc == 'm' || sc == 'l' || sc == 'x' || sc == 'c')
+                             : (fam == '5' || fam == '1') && (sc == 'n' || sc == 's' || sc == 'm');
+    if (!ok) {
+      g_err = "m355_model_desc.scale: unknown family or scale (0 | n,s,m,l,x,c; ('5' << 8) | n,s,m; ('1' << 8) | n,s,m)";
+      return M355_ERR_INVALID;
+    }
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     g_err = "no HIP device visible: libmi355yolo has no CPU fallback";
@@ -1504,7 +1764,12 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
     }
     return M355_OK;
   }
-  if (ci.cin == 3 && ci.k == 6) {   // YOLOv5u stem (conv_stem6_s2.hip): [C0][128] fp16 rows in the kernel's order
+  if (p.groups > 1) {   // depthwise 3x3 (dwconv3x3.hip, psa_attn.hip's pe): (C,1,3,3) -> [9][C] fp16
+    std::vector<half_t> dw((size_t)9 * ci.cout);
+    pack_dw3x3_weights(w, ci.cout, dw.data());
+    HIP_TRY(e, hipMemcpy(p.w, dw.data(), dw.size() * sizeof(half_t), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(p.bias, bias, ci.cout * sizeof(float), hipMemcpyHostToDevice));
+  } else if (ci.cin == 3 && ci.k == 6) {   // YOLOv5u stem (conv_stem6_s2.hip): [C0][128] fp16 rows in the kernel's order
     std::vector<half_t> sw((size_t)ci.cout * 128);
     pack_stem6_weights(w, ci.cout, sw.data());
     HIP_TRY(e, hipMemcpy(p.w, sw.data(), sw.size() * sizeof(half_t), hipMemcpyHostToDevice));
@@ -1846,6 +2111,30 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
         const Tensor& to = e->tensors[op.out.t];
         rc = launch_upsample2x(ti.p + op.in.off, (long)ti.H * ti.W * ti.C, ti.C, to.p + op.out.off,
                                (long)to.H * to.W * to.C, to.C, Bq, ti.H, ti.W, op.in.c, s);
+        break;
+      }
+      case OP_DWCONV: {
+        const PhysConv& p = e->phys[op.conv];
+        const Tensor& ti = e->tensors[op.in.t];
+        const Tensor& to = e->tensors[op.out.t];
+        DwConvArgs a{};
+        a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C; a.x = ti.p + op.in.off + b0 * a.x_bstride;
+        a.B = Bq; a.H = ti.H; a.W = ti.W; a.C = p.cout;
+        a.w = p.w; a.bias = p.bias; a.act = p.act;
+        a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.y = to.p + op.out.off + b0 * a.y_bstride;
+        rc = launch_dwconv3x3(a, s);
+        break;
+      }
+      case OP_PSA_ATTN: {
+        const PhysConv& p = e->phys[op.conv];
+        const Tensor& ti = e->tensors[op.in.t];
+        const Tensor& to = e->tensors[op.out.t];
+        PsaArgs a{};
+        a.q_bstride = (long)ti.H * ti.W * ti.C; a.ldq = ti.C; a.qkv = ti.p + op.in.off + b0 * a.q_bstride;
+        a.B = Bq; a.H = ti.H; a.W = ti.W; a.heads = op.heads; a.C = p.cout;
+        a.pe_w = p.w; a.pe_b = p.bias; a.scale_log2e = (float)(1.4426950408889634 / sqrt(32.0));
+        a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.y = to.p + op.out.off + b0 * a.y_bstride;
+        rc = launch_psa_attn(a, s);
         break;
       }
       case OP_DECODE:
@@ -2559,6 +2848,53 @@ int m355_stem6_fwd(const void* d_x, int B, int H, int W, const float* h_w, const
   a.y = (half_t*)d_y; a.ldy = C0; a.y_bstride = (long)(H / 2) * (W / 2) * C0;
   if (!a.w || !a.bias) return set_err(M355_ERR_HIP, "allocation failed");
   return finish_entry(launch_stem6(a, s), s, "stem6_s2");
+}
+
+int m355_dwconv3x3_fwd(const void* d_x, int B, int H, int W, int C, int ldx, const float* h_w, const float* h_b, int act, void* d_y,
+                       int ldy, void* stream) {
+  // every argument before any HIP call
+  if (!d_x || !h_w || !h_b || !d_y) return set_err(M355_ERR_INVALID, "dwconv3x3: null pointer");
+  if (C < 8 || C % 8) return set_err(M355_ERR_INVALID, "dwconv3x3: C must be a positive multiple of 8");
+  if (ldx < C || ldy < C || ldx % 8 || ldy % 8) return set_err(M355_ERR_INVALID, "dwconv3x3: ldx and ldy must be multiples of 8, >= C");
+  if (B < 1 || H < 1 || W < 1) return set_err(M355_ERR_INVALID, "dwconv3x3: B, H, W must be >= 1");
+  if (act != 0 && act != 1) return set_err(M355_ERR_INVALID, "dwconv3x3: act must be 0 or 1");
+  if (((uintptr_t)d_x | (uintptr_t)d_y) & 15) return set_err(M355_ERR_INVALID, "dwconv3x3: x and y must be 16-byte aligned");
+  if ((long)B * ((H + 7) / 8) * W * (C / 8) > (1L << 38)) return set_err(M355_ERR_INVALID, "dwconv3x3: too large");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<half_t> dw((size_t)9 * C);
+  pack_dw3x3_weights(h_w, C, dw.data());
+  DevBuf d;
+  DwConvArgs a{};
+  a.x = (const half_t*)d_x; a.x_bstride = (long)H * W * ldx; a.ldx = ldx;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.act = act;
+  a.w = d.put(dw); a.bias = d.put(std::vector<float>(h_b, h_b + C));
+  a.y = (half_t*)d_y; a.y_bstride = (long)H * W * ldy; a.ldy = ldy;
+  if (!a.w || !a.bias) return set_err(M355_ERR_HIP, "allocation failed");
+  return finish_entry(launch_dwconv3x3(a, s), s, "dwconv3x3");
+}
+
+int m355_psa_attn_fwd(const void* d_qkv, int B, int H, int W, int heads, int key_dim, int head_dim, const float* h_pe_w,
+                      const float* h_pe_b, void* d_y, void* stream) {
+  // every argument before any HIP call
+  if (!d_qkv || !h_pe_w || !h_pe_b || !d_y) return set_err(M355_ERR_INVALID, "psa_attn: null pointer");
+  if (key_dim != 32 || head_dim != 64) return set_err(M355_ERR_INVALID, "psa_attn: key_dim must be 32 and head_dim 64");
+  if (heads < 1 || heads > 64) return set_err(M355_ERR_INVALID, "psa_attn: heads must be 1..64");
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || (long)H * W > (1L << 24))
+    return set_err(M355_ERR_INVALID, "psa_attn: B 1..65535, H, W >= 1, H * W <= 2^24");
+  if (((uintptr_t)d_qkv & 15) || ((uintptr_t)d_y & 7)) return set_err(M355_ERR_INVALID, "psa_attn: qkv 16-byte, y 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int C = 64 * heads;
+  std::vector<half_t> dw((size_t)9 * C);
+  pack_dw3x3_weights(h_pe_w, C, dw.data());
+  DevBuf d;
+  PsaArgs a{};
+  a.qkv = (const half_t*)d_qkv; a.ldq = 2 * C; a.q_bstride = (long)H * W * a.ldq;
+  a.B = B; a.H = H; a.W = W; a.heads = heads; a.C = C;
+  a.pe_w = d.put(dw); a.pe_b = d.put(std::vector<float>(h_pe_b, h_pe_b + C));
+  a.scale_log2e = (float)(1.4426950408889634 / sqrt(32.0));
+  a.y = (half_t*)d_y; a.ldy = C; a.y_bstride = (long)H * W * C;
+  if (!a.pe_w || !a.pe_b) return set_err(M355_ERR_HIP, "allocation failed");
+  return finish_entry(launch_psa_attn(a, s), s, "psa_attn");
 }
 
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream) {

@@ -13,7 +13,7 @@ import torch
 
 from . import _capi
 from ._capi import ConvInfo, ModelDesc, OpInfo, check, lib
-from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_v5u
+from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_detect, is_v5u, is_y11
 
 
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -25,17 +25,20 @@ def _stream() -> C.c_void_p:
 
 
 def scale_code(scale: str) -> int:
-    """m355_model_desc.scale of a scale tag: 'n'..'x' (yolov8-seg), 'c' (yolov9c-seg), ('5' << 8) | n/s/m (YOLOv5u)."""
+    """m355_model_desc.scale of a scale tag: 'n'..'x' (yolov8-seg), 'c' (yolov9c-seg), ('5' << 8) | n/s/m (YOLOv5u),
+    ('1' << 8) | n/s/m (YOLO11)."""
     if scale == V9C:
         return ord("c")
     if is_v5u(scale):
         return (ord("5") << 8) | ord(scale[1])
+    if is_y11(scale):
+        return (ord("1") << 8) | ord(scale[2])
     return ord(scale)
 
 
 class SegEngine:
     """One engine per device.  Not thread-safe (one handle, one caller).  Serves the segmentation graphs (nm = 32 mask
-    coefficients, prototypes) and the YOLOv5u detection graphs (nm = 0: no prototypes, no masks)."""
+    coefficients, prototypes) and the YOLOv5u and YOLO11 detection graphs (nm = 0: no prototypes, no masks)."""
 
     def __init__(self, scale: str = "s", nc: int = 1, imgsz: Tuple[int, int] = (640, 640),
                  max_batch: int = 32, device: int = 0, keep_raw: bool = True):
@@ -71,7 +74,7 @@ class SegEngine:
         from .spec import SCALES
         if scale == V9C:
             return "M355_NO_PROTOFUSE" not in os.environ      # 256 prototype channels
-        if is_v5u(scale):
+        if is_detect(scale):
             return False                                      # no Proto at all
         _, width, maxc = SCALES[scale]
         npr = int(math.ceil(min(256, maxc) * width / 8) * 8)
@@ -91,8 +94,8 @@ class SegEngine:
         if len(infos) != len(self.specs):
             raise RuntimeError(f"engine reports {len(infos)} convs, host spec has {len(self.specs)}")
         for ci, s in zip(infos, self.specs):
-            got = (ci.name.decode(), ci.cin, ci.cout, ci.k, ci.stride, bool(ci.has_bn), bool(ci.transposed))
-            want = (s.name, s.cin, s.cout, s.k, s.stride, s.has_bn, s.transposed)
+            got = (ci.name.decode(), ci.cin, ci.cout, ci.k, ci.stride, bool(ci.has_bn), bool(ci.transposed), ci.groups)
+            want = (s.name, s.cin, s.cout, s.k, s.stride, s.has_bn, s.transposed, s.groups)
             if got != want:
                 raise RuntimeError(f"engine/host graph mismatch: {got} vs {want}")
 

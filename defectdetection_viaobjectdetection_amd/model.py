@@ -22,11 +22,12 @@ import torch
 
 from .preprocess import expand_sources, letterbox, letterbox_shape, scale_boxes_to_original
 from .results import Results
-from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_v5u, state_dict_keys
+from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_detect, state_dict_keys
 
 _YAML_RE = re.compile(r"^yolov8([nsmlx])?-seg\.ya?ml$")
 _V9C_RE = re.compile(r"^yolov9c-seg\.ya?ml$")
 _V5U_RE = re.compile(r"^yolov5([nsmlx])u\.ya?ml$")
+_Y11_RE = re.compile(r"^yolo11([nsmlx])\.ya?ml$")
 CKPT_FORMAT = "mi355yolo-seg-v1"
 
 
@@ -79,10 +80,22 @@ class YOLO:
             if os.path.isfile(model):
                 self._read_yaml_overrides(model)
             self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
+        elif _Y11_RE.match(name):
+            # the detection family the reference trains (BscanBased/yolo/yolo_bbox_retrain.py: yolo11n)
+            sc = _Y11_RE.match(name).group(1)
+            if sc in "lx":
+                raise NotImplementedError(f"'{name}': YOLO11 scales l and x are not built (n, s and m are)")
+            self.scale = "11" + sc
+            self.task = "detect"
+            self.nc = 80
+            self.names = {i: f"class{i}" for i in range(self.nc)}
+            if os.path.isfile(model):
+                self._read_yaml_overrides(model)
+            self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
         elif name.endswith((".yaml", ".yml")):
             raise NotImplementedError(
-                f"architecture '{name}' is not built: this package implements the YOLOv8{{n,s,m,l,x}}-seg, YOLOv9c-seg and "
-                "YOLOv5{n,s,m}u graphs; yolo11 is listed as a next row in SURVEY.md 8(f) N4")
+                f"architecture '{name}' is not built: this package implements the YOLOv8{{n,s,m,l,x}}-seg, YOLOv9c-seg, "
+                "YOLOv5{n,s,m}u and YOLO11{n,s,m} (detection) graphs")
         elif name.endswith(".pt"):
             if not os.path.isfile(model):
                 raise OfflineModelError(
@@ -136,14 +149,14 @@ class YOLO:
             self.train_args = up["train_args"]
             self.state_dict = up["state_dict"]
             self.ckpt_path = path
-            self.task = "detect" if is_v5u(self.scale) else "segment"
+            self.task = "detect" if is_detect(self.scale) else "segment"
             return
         self.scale, self.nc = ck["scale"], int(ck["nc"])
         self.names = {int(k): v for k, v in ck["names"].items()}
         self.train_args = ck.get("train_args", {})
         self.state_dict = ck["model"]
         self.ckpt_path = path
-        self.task = "detect" if is_v5u(self.scale) else "segment"
+        self.task = "detect" if is_detect(self.scale) else "segment"
         self._resume_state = ck.get("trainer")       # present in weights/last.pt: lets train(resume=True) continue
 
     def save(self, path: str, upstream: bool = False) -> str:
@@ -152,8 +165,8 @@ class YOLO:
         is this package's plain state-dict format."""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         if upstream:
-            if is_v5u(self.scale):
-                raise NotImplementedError("upstream export of a YOLOv5u detection model is not built")
+            if is_detect(self.scale):
+                raise NotImplementedError("upstream export of a detection model (YOLOv5u, YOLO11) is not built")
             from .upstream_export import export_upstream_checkpoint
             return export_upstream_checkpoint(path, self.scale, self.nc, self.names, self.state_dict, self.train_args)
         torch.save({"format": CKPT_FORMAT, "scale": self.scale, "nc": self.nc, "names": self.names,
@@ -257,5 +270,5 @@ class YOLO:
 
     def _require_segment(self, what: str) -> None:
         if self.task != "segment":
-            raise NotImplementedError(f"{what}() of a {self.task} model: detect training and validation (YOLOv5u) are not built "
+            raise NotImplementedError(f"{what}() of a {self.task} model: detect training and validation (YOLOv5u, YOLO11) are not built "
                                       "yet; this package trains and validates the segmentation graphs only")

@@ -22,6 +22,9 @@ V9C = "9c"     # the `scale` tag of the yolov9c-seg graph (SURVEY next row N4); 
 # YOLOv5u detection graphs (/root/reference/BscanBased/yolo5s_retrain.py:6 loads yolov5su.pt): scale tags
 # "5n" / "5s" / "5m", (depth, width, max channels) of upstream's yolov5.yaml.  The C-ABI descriptor carries ('5' << 8) | n/s/m.
 V5U_SCALES = {"5n": (0.33, 0.25, 1024), "5s": (0.33, 0.50, 1024), "5m": (0.67, 0.75, 1024)}
+# YOLO11 detection graphs (BscanBased/yolo/yolo_bbox_retrain.py trains yolo11n): scale tags "11n" / "11s" /
+# "11m", (depth, width, max channels) of upstream's cfg/models/11/yolo11.yaml.  The C-ABI descriptor carries ('1' << 8) | n/s/m.
+Y11_SCALES = {"11n": (0.50, 0.25, 1024), "11s": (0.50, 0.50, 1024), "11m": (0.50, 1.00, 512)}
 REG_MAX = 16
 NM = 32
 BN_EPS = 1e-3
@@ -37,10 +40,12 @@ class ConvSpec:
     has_bn: bool       # Conv2d(bias=False)+BN+SiLU  vs plain Conv2d/ConvTranspose2d with bias
     transposed: bool = False
     rep: bool = False  # RepConvN: act(Conv3x3+BN [name.conv1] + Conv1x1+BN [name.conv2]); the engine runs the merged 3x3
+    groups: int = 1    # Conv2d groups: cin for a depthwise conv (weight (cout, cin / groups, k, k))
+    act: bool = True   # Conv+BN only: SiLU after BN (False: upstream Conv(..., act=False), e.g. the attention's qkv / proj / pe)
 
     @property
     def weight_shape(self):
-        return (self.cin, self.cout, 2, 2) if self.transposed else (self.cout, self.cin, self.k, self.k)
+        return (self.cin, self.cout, 2, 2) if self.transposed else (self.cout, self.cin // self.groups, self.k, self.k)
 
 
 def _make_divisible(x: float, d: int) -> int:
@@ -100,9 +105,19 @@ def is_v5u(scale: str) -> bool:
     return scale in V5U_SCALES
 
 
+def is_y11(scale: str) -> bool:
+    return scale in Y11_SCALES
+
+
+def is_detect(scale: str) -> bool:
+    """True for the box-only detection graphs (YOLOv5u, YOLO11): no mask coefficients, no Proto."""
+    return is_v5u(scale) or is_y11(scale)
+
+
 def head_prefix(scale: str) -> str:
-    """State-dict prefix of the head: model.24 = Detect of YOLOv5u, model.22 = Segment of the seg graphs."""
-    return "model.24" if is_v5u(scale) else "model.22"
+    """State-dict prefix of the head: model.24 = Detect of YOLOv5u, model.23 = Detect of YOLO11, model.22 = Segment of the
+    seg graphs."""
+    return "model.24" if is_v5u(scale) else "model.23" if is_y11(scale) else "model.22"
 
 
 def v5u_widths(scale: str):
@@ -173,6 +188,105 @@ def _detect_specs(out: List[ConvSpec], nc: int, fch, pre: str) -> None:
         out.append(ConvSpec(f"{pre}.cv3.{l}.2", hc3, nc, 1, 1, False))
 
 
+def conv_specs_y11(scale: str, nc: int = 1) -> List[ConvSpec]:
+    """Canonical list of every convolution of YOLO11 (upstream cfg/models/11/yolo11.yaml, Detect at model.23) in upstream's
+    state-dict order = the order ``libmi355yolo`` reports them.  Every repeated block has n = 1 (depth 0.5).
+      C3k2(c1, c2, c3k, e): c = int(c2 e); cv1 1x1 c1 -> 2c, cv2 1x1 3c -> c2, m.0 = Bottleneck(c, c, e=0.5) (3x3 c -> c/2,
+        3x3 c/2 -> c) or, with c3k (always at the m scale), C3k(c, c, n=2): cv1 / cv2 1x1 c -> c/2, cv3 1x1 c -> c, m.0 / m.1
+        = Bottleneck(c/2, c/2, e=1.0).
+      C2PSA(c1): c = c1/2; cv1 1x1 c1 -> 2c, cv2 1x1 2c -> c1, m.0 = PSABlock(c): attn.qkv 1x1 c -> 2c (no act), attn.proj 1x1
+        (no act), attn.pe depthwise 3x3 (no act), ffn.0 1x1 c -> 2c, ffn.1 1x1 2c -> c (no act).
+      Detect: YOLOv8's box branch; class branch cv3.l.0.0 depthwise 3x3, .0.1 1x1 -> c3, .1.0 depthwise 3x3, .1.1 1x1, .2.
+    Block structure: tests/yolo11_det_ref.py."""
+    if scale not in Y11_SCALES:
+        raise ValueError(f"YOLO11 scale '{scale}' is not built: one of {sorted(Y11_SCALES)} (l and x are out of scope)")
+    _, width, maxc = Y11_SCALES[scale]
+    ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
+    c3k_all = scale[-1] == "m"      # upstream parse_model forces c3k = True for the m / l / x scales
+    c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
+    out: List[ConvSpec] = []
+
+    def conv(name, cin, cout, k, s, groups=1, act=True):
+        out.append(ConvSpec(name, cin, cout, k, s, True, groups=groups, act=act))
+
+    def c3k2(name, c1, c2, c3k, e=0.5):
+        c = int(c2 * e)
+        conv(f"{name}.cv1", c1, 2 * c, 1, 1)
+        conv(f"{name}.cv2", 3 * c, c2, 1, 1)
+        if c3k or c3k_all:
+            c_ = c // 2
+            conv(f"{name}.m.0.cv1", c, c_, 1, 1)
+            conv(f"{name}.m.0.cv2", c, c_, 1, 1)
+            conv(f"{name}.m.0.cv3", 2 * c_, c, 1, 1)
+            for j in range(2):
+                conv(f"{name}.m.0.m.{j}.cv1", c_, c_, 3, 1)
+                conv(f"{name}.m.0.m.{j}.cv2", c_, c_, 3, 1)
+        else:
+            conv(f"{name}.m.0.cv1", c, c // 2, 3, 1)
+            conv(f"{name}.m.0.cv2", c // 2, c, 3, 1)
+
+    conv("model.0", 3, c64, 3, 2)
+    conv("model.1", c64, c128, 3, 2)
+    c3k2("model.2", c128, c256, False, 0.25)
+    conv("model.3", c256, c256, 3, 2)
+    c3k2("model.4", c256, c512, False, 0.25)
+    conv("model.5", c512, c512, 3, 2)
+    c3k2("model.6", c512, c512, True)
+    conv("model.7", c512, c1024, 3, 2)
+    c3k2("model.8", c1024, c1024, True)
+    conv("model.9.cv1", c1024, c1024 // 2, 1, 1)
+    conv("model.9.cv2", c1024 * 2, c1024, 1, 1)
+    c = c1024 // 2
+    conv("model.10.cv1", c1024, 2 * c, 1, 1)
+    conv("model.10.cv2", 2 * c, c1024, 1, 1)
+    conv("model.10.m.0.attn.qkv", c, 2 * c, 1, 1, act=False)
+    conv("model.10.m.0.attn.proj", c, c, 1, 1, act=False)
+    conv("model.10.m.0.attn.pe", c, c, 3, 1, groups=c, act=False)
+    conv("model.10.m.0.ffn.0", c, 2 * c, 1, 1)
+    conv("model.10.m.0.ffn.1", 2 * c, c, 1, 1, act=False)
+    c3k2("model.13", c1024 + c512, c512, False)
+    c3k2("model.16", c512 + c512, c256, False)
+    conv("model.17", c256, c256, 3, 2)
+    c3k2("model.19", c256 + c512, c512, False)
+    conv("model.20", c512, c512, 3, 2)
+    c3k2("model.22", c512 + c1024, c1024, True)
+    fch = (c256, c512, c1024)
+    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
+    hc3 = max(fch[0], min(nc, 100))
+    for l in range(3):
+        conv(f"model.23.cv2.{l}.0", fch[l], hc2, 3, 1)
+        conv(f"model.23.cv2.{l}.1", hc2, hc2, 3, 1)
+        out.append(ConvSpec(f"model.23.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
+    for l in range(3):
+        conv(f"model.23.cv3.{l}.0.0", fch[l], fch[l], 3, 1, groups=fch[l])
+        conv(f"model.23.cv3.{l}.0.1", fch[l], hc3, 1, 1)
+        conv(f"model.23.cv3.{l}.1.0", hc3, hc3, 3, 1, groups=hc3)
+        conv(f"model.23.cv3.{l}.1.1", hc3, hc3, 1, 1)
+        out.append(ConvSpec(f"model.23.cv3.{l}.2", hc3, nc, 1, 1, False))
+    return out
+
+
+def _y11_out_stride(name: str) -> int:
+    """Output stride of a YOLO11 conv, from its block index (and the head level)."""
+    parts = name.split(".")
+    i = int(parts[1])
+    if i == 23:
+        return 8 << int(parts[3])
+    return {0: 2, 1: 4, 2: 4, 3: 8, 4: 8, 5: 16, 6: 16, 13: 16, 16: 8, 17: 16, 19: 16}.get(i, 32)
+
+
+def y11_gflops(scale: str, nc: int = 80, imgsz: int = 640) -> float:
+    """Upstream's GFLOPs figure of a YOLO11 spec: its thop count of the unfused model -- 2 x conv MACs (a grouped conv counts
+    cin / groups per output) plus 8 x the elements every BatchNorm2d writes (thop counts 2 x 2 ops per element of an affine
+    norm, doubled again like the MACs).  The attention's two matrix products, SiLU, pooling and upsampling count nothing."""
+    macs = bn = 0
+    for s in conv_specs_y11(scale, nc):
+        hw = (imgsz // _y11_out_stride(s.name)) ** 2
+        macs += hw * s.cout * (s.cin // s.groups) * s.k * s.k
+        bn += hw * s.cout if s.has_bn else 0
+    return (2 * macs + 8 * bn) / 1e9
+
+
 def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
     """model.22 = Segment: the box / class / coefficient branches per level and Proto (A9/A10), upstream state-dict order."""
     hc2 = max(16, fch[0] // 4, REG_MAX * 4)
@@ -200,11 +314,14 @@ def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
 
 
 def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
-    """Canonical list of every convolution of yolov8{scale}-seg (A5/A9/A10); scale "9c": yolov9c-seg; "5n/5s/5m": YOLOv5u."""
+    """Canonical list of every convolution of yolov8{scale}-seg (A5/A9/A10); scale "9c": yolov9c-seg; "5n/5s/5m": YOLOv5u;
+    "11n/11s/11m": YOLO11."""
     if scale == V9C:
         return conv_specs_v9c(nc)
     if is_v5u(scale):
         return conv_specs_v5u(scale, nc)
+    if is_y11(scale):
+        return conv_specs_y11(scale, nc)
     depth, width, maxc = SCALES[scale]
     ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
     rep = lambda n: max(round(n * depth), 1) if n > 1 else n  # noqa: E731
@@ -301,7 +418,7 @@ def init_state_dict(scale: str = "s", nc: int = 1, seed: int = 0) -> Dict[str, t
     sd: Dict[str, torch.Tensor] = {}
     for s in conv_specs(scale, nc):
         shape = s.weight_shape
-        fan_in = shape[1] * shape[2] * shape[3]
+        fan_in = shape[1] * shape[2] * shape[3]     # (cin / groups) k k
         bound = 1.0 / math.sqrt(fan_in)
         w = (torch.rand(shape, generator=g) * 2 - 1) * bound
         if s.has_bn:
@@ -376,7 +493,8 @@ def synthetic_state_dict(scale: str = "s", nc: int = 1, seed: int = 0, cls_bias:
 
 def fold_bn(sd: Dict[str, torch.Tensor], spec: ConvSpec):
     """A4: W' = W * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps).
-    Returns (weight fp32 contiguous, bias fp32 contiguous) ready for ``m355_set_conv_weights``."""
+    Returns (weight fp32 contiguous, bias fp32 contiguous) ready for ``m355_set_conv_weights``.  A grouped conv's weight
+    (cout, cin / groups, k, k) folds the same way: gamma scales output channels."""
     if spec.rep:   # RepConvN: both branches folded, the 1x1 kernel added at the centre tap of the 3x3 (exact: conv is linear)
         wsum = torch.zeros((spec.cout, spec.cin, 3, 3), dtype=torch.float64)
         bsum = torch.zeros(spec.cout, dtype=torch.float64)

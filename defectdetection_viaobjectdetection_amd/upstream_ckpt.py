@@ -163,8 +163,8 @@ def module_state_dict(module_like) -> "OrderedDict[str, torch.Tensor]":
 
 
 def load_upstream_checkpoint(path: str) -> Dict:
-    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg, YOLOv9c-seg or YOLOv5u
-    detection checkpoint."""
+    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg, YOLOv9c-seg, YOLOv5u or
+    YOLO11 detection checkpoint."""
     from .spec import SCALES, conv_specs, head_prefix, state_dict_keys
     ck = torch.load(path, map_location="cpu", pickle_module=_PickleModule, weights_only=False)
     if not isinstance(ck, dict):
@@ -182,7 +182,12 @@ def load_upstream_checkpoint(path: str) -> Dict:
               "model.24.cv3.0.2.weight" in sd)
     if is_v5u:
         cls0 = sd["model.24.cv3.0.2.weight"]
-    if stem is None or cls0 is None or ("model.22.proto.cv1.conv.weight" not in sd and not is_v5u):
+    # YOLO11 DetectionModel: C2PSA's attention at model.10 and the Detect head at model.23 (a -seg graph has model.23.proto)
+    is_y11 = (stem is not None and "model.10.m.0.attn.qkv.conv.weight" in sd and "model.23.cv3.0.2.weight" in sd and
+              "model.23.proto.cv1.conv.weight" not in sd)
+    if is_y11:
+        cls0 = sd["model.23.cv3.0.2.weight"]
+    if stem is None or cls0 is None or ("model.22.proto.cv1.conv.weight" not in sd and not is_v5u and not is_y11):
         kind = getattr(type(model), "_upstream", type(model).__name__)
         raise ValueError(f"{path}: not a YOLOv8-seg graph ({kind}); yolov8{{n,s,m,l,x}}-seg, yolov9c-seg and yolov5{{n,s,m}}u "
                          "are implemented (SURVEY.md next row N4 lists yolo11)")
@@ -191,10 +196,14 @@ def load_upstream_checkpoint(path: str) -> Dict:
         width = {16: "5n", 32: "5s", 48: "5m"}.get(int(stem.shape[0]))
         if width is None:
             raise ValueError(f"{path}: YOLOv5u stem width {int(stem.shape[0])}: only the n, s and m scales (16 / 32 / 48) are built")
+    elif is_y11:
+        width = {16: "11n", 32: "11s", 64: "11m"}.get(int(stem.shape[0]))
+        if width is None:
+            raise ValueError(f"{path}: YOLO11 stem width {int(stem.shape[0])}: only the n, s and m scales (16 / 32 / 64) are built")
     elif is_v9c:
         from .spec import V9C
         width = V9C
-    if width is None or (width not in SCALES and not is_v9c and not is_v5u):
+    if width is None or (width not in SCALES and not is_v9c and not is_v5u and not is_y11):
         raise ValueError(f"{path}: stem width {int(stem.shape[0])} does not belong to a YOLOv8 scale")
     nc = int(cls0.shape[0])
     keys = state_dict_keys(width, nc)

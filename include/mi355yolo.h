@@ -41,9 +41,10 @@ typedef enum {
 /* Model description: replaces `YOLO("yolov8{n,s,m,l,x}-seg.yaml")` graph construction
  * (yolo_seg_train.py:7).  nc = number of classes (data-seg.yaml:4-5 -> 1).
  * scale selects the graph: 'n','s','m','l','x' = yolov8{scale}-seg; 'c' = yolov9c-seg; ('5' << 8) | 'n','s','m' = YOLOv5u
- * {n,s,m} (detection: box-only head, no prototypes or mask coefficients).  Any other high byte is M355_ERR_INVALID. */
+ * {n,s,m}; ('1' << 8) | 'n','s','m' = YOLO11{n,s,m} (both detection: box-only head, no prototypes or mask coefficients).
+ * Any other high byte, or a scale letter its family does not build, is M355_ERR_INVALID (checked before the device is). */
 typedef struct {
-  int scale;      /* low byte: 'n','s','m','l','x','c'; high byte: 0 (segmentation families) or '5' (YOLOv5u) */
+  int scale;      /* low byte: 'n','s','m','l','x','c'; high byte: 0 (segmentation families), '5' (YOLOv5u) or '1' (YOLO11) */
   int nc;         /* classes */
   int in_h, in_w; /* network input size, multiples of 32 (640x640 headline) */
   int max_batch;  /* workspace is sized for this many images */
@@ -57,7 +58,9 @@ typedef struct {
   int k, stride;   /* kernel size (1,2,3; 6 for the YOLOv5u stem model.0), stride */
   int has_bn;      /* 1: Conv2d(bias=False)+BN+SiLU (fold BN before m355_set_conv_weights) */
   int transposed;  /* 1: ConvTranspose2d(k=2,s=2,bias) -- weight layout (cin,cout,2,2) */
-  int act;         /* 1: SiLU epilogue */
+  int act;         /* 1: SiLU epilogue (0: none -- the YOLO11 attention's qkv / proj / pe and ffn.1) */
+  int groups;      /* Conv2d groups: 1, or cin for a depthwise conv (YOLO11 DWConv and attn.pe), whose weight layout for
+                      m355_set_conv_weights is (cout, cin/groups, k, k) = (C, 1, 3, 3) */
 } m355_conv_info;
 
 /* Version / build info string (static storage). */
@@ -238,6 +241,19 @@ int m355_stem_fwd(const void* d_in_u8, int B, int H, int W, const float* h_w, co
  * positive, W a positive multiple of 16.  Every argument is checked before any HIP call (-1 = M355_ERR_INVALID).   [sync] */
 int m355_stem6_fwd(const void* d_x_u8_nhwc, int B, int H, int W, const float* h_w, const float* h_bias, int C0,
                    void* d_y_f16_nhwc, void* stream);
+/* YOLO11 depthwise 3x3 / s1 / p1 conv (dwconv3x3.hip) on fp16 NHWC channel slices: x (B,H,W,ldx) -> y (B,H,W,ldy), channels
+ * [0, C) of each (the pointers are the slices' first channels), y = act(dwconv(x; w) + b); h_w fp32 (C,1,3,3) BN folded, h_b
+ * (C), act 0 or 1 (SiLU).  C a positive multiple of 8; ldx, ldy multiples of 8 and >= C; x and y 16-byte aligned; B, H, W
+ * >= 1.  Every argument is checked before any HIP call (-1 = M355_ERR_INVALID).                                  [sync] */
+int m355_dwconv3x3_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int C, int ldx, const float* h_w, const float* h_b,
+                       int act, void* d_y_f16_nhwc, int ldy, void* stream);
+/* YOLO11 C2PSA attention core (psa_attn.hip): qkv fp16 NHWC (B,H,W,heads*128), head h's channels [q 32 | k 32 | v 64] at
+ * 128 h -> y fp16 NHWC (B,H,W,heads*64): y[., 64 h + c] = sum_j v[c,j] softmax_j(q_i . k_j / sqrt(32)) + pe(v), pe = the
+ * depthwise 3x3 conv h_pe_w fp32 (heads*64,1,3,3) + h_pe_b (BN folded, no activation) over v as (B, heads*64, H, W).
+ * key_dim must be 32 and head_dim 64 (else M355_ERR_INVALID); heads 1..64, B 1..65535, H, W >= 1, H*W <= 2^24; qkv
+ * 16-byte and y 8-byte aligned.  Every argument is checked before any HIP call.                              [sync] */
+int m355_psa_attn_fwd(const void* d_qkv_f16_nhwc, int B, int H, int W, int heads, int key_dim, int head_dim,
+                      const float* h_pe_w, const float* h_pe_b, void* d_y_f16_nhwc, void* stream);
 /* SPPF pooling: x fp16 NHWC (B,H,W,C) -> y (B,H,W,3C) = [mp5(x), mp5(mp5(x)), mp5^3(x)]. */
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
 /* Nearest 2x upsample, fp16 NHWC (B,H,W,C) -> (B,2H,2W,C). */

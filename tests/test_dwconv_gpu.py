@@ -1,0 +1,83 @@
+"""The YOLO11 depthwise 3x3 kernel (dwconv3x3.hip) through m355_dwconv3x3_fwd on guard-banded fp16 NHWC channel slices.
+
+Each output element is checked against an fp64 reference on the SAME fp16 operands (x, and the weights rounded to fp16 as the
+host packs them; the bias stays fp32):
+    |err| <= 2^-10 |ref| + 2^-12 S,   S = sum over the 9 taps of |w x|.
+Derivation: fp16 x fp16 products are exact in fp32; nine fp32 fmas and the bias add cost at most 10 * 2^-24 (S + |b|) -- far
+below 2^-12 S for any |b| <= S 2^10 (|b| <= 0.5 here, S ~ 1); SiLU (Lipschitz <= 1.1, exp2 / rcp within 2 ulp) adds < 2^-20 |ref|;
+the one rounding to fp16 adds <= 2^-11 |ref| (2^-25 absolute below the fp16 normal range, inside the S term).  So 2^-10 |ref|
+carries a factor 2 of margin over the rounding, and 2^-12 S a factor ~400 over the fp32 sums.  Every element outside the output
+slice -- other channels of the buffer and guard bands before and after it -- must keep its NaN sentinel."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 4096   # fp16 elements of NaN before and after the output buffer
+
+
+def _ref(x16, w16, b, act):
+    """x16 (B,H,W,C) fp16 values, w16 (C,1,3,3) fp16 values, b (C) fp32 -> (ref, S) fp64."""
+    x = torch.from_numpy(x16.astype(np.float64)).permute(0, 3, 1, 2)
+    w = torch.from_numpy(w16.astype(np.float64))
+    z = torch.nn.functional.conv2d(x, w, torch.from_numpy(b.astype(np.float64)), padding=1, groups=x.shape[1])
+    s = torch.nn.functional.conv2d(x.abs(), w.abs(), None, padding=1, groups=x.shape[1])
+    if act:
+        z = z * torch.sigmoid(z)
+    return z.permute(0, 2, 3, 1).numpy(), s.permute(0, 2, 3, 1).numpy()
+
+
+CASES = [  # C, H, W, ldx, xoff, ldy, yoff, act, B
+    (8, 20, 20, 8, 0, 8, 0, 1, 2),
+    (8, 12, 20, 24, 16, 16, 8, 0, 3),
+    (64, 80, 80, 64, 0, 64, 0, 1, 2),
+    (64, 20, 20, 192, 64, 128, 64, 0, 2),
+    (80, 80, 80, 80, 0, 80, 0, 1, 1),
+    (80, 12, 20, 144, 64, 160, 80, 1, 2),
+    (128, 20, 20, 128, 0, 128, 0, 0, 3),
+    (128, 80, 80, 384, 256, 256, 128, 1, 1),
+    (256, 20, 20, 256, 0, 256, 0, 1, 2),
+    (256, 12, 20, 512, 256, 264, 8, 0, 2),
+]
+
+
+@pytest.mark.parametrize("C,H,W,ldx,xoff,ldy,yoff,act,B", CASES)
+def test_dwconv3x3_slices_elementwise(C, H, W, ldx, xoff, ldy, yoff, act, B, cuda_device):
+    from defectdetection_viaobjectdetection_amd import _capi
+    rng = np.random.default_rng(C * 1000 + H * 10 + W + act)
+    xfull = (rng.standard_normal((B, H, W, ldx)) * 1.5).astype(np.float16)
+    # a hot border: large values on the first / last rows and columns catch a wrong padding or a wrapped neighbour
+    xfull[:, 0] *= 4
+    xfull[:, -1] *= 4
+    xfull[:, :, 0] *= 4
+    xfull[:, :, -1] *= 4
+    w = (rng.uniform(-1, 1, (C, 1, 3, 3)) / 3).astype(np.float32)
+    b = rng.uniform(-0.5, 0.5, C).astype(np.float32)
+    w16 = w.astype(np.float16)
+    ref, S = _ref(xfull[..., xoff:xoff + C], w16, b, act)
+
+    xd = torch.from_numpy(xfull).to(cuda_device)
+    n_out = B * H * W * ldy
+    yd = torch.full((n_out + 2 * GUARD,), float("nan"), dtype=torch.float16, device=cuda_device)
+    wt, bt = torch.from_numpy(w), torch.from_numpy(b)
+    rc = _capi.lib.m355_dwconv3x3_fwd(ctypes.c_void_p(xd.data_ptr() + 2 * xoff), B, H, W, C, ldx, ctypes.c_void_p(wt.data_ptr()),
+                                      ctypes.c_void_p(bt.data_ptr()), act, ctypes.c_void_p(yd.data_ptr() + 2 * (GUARD + yoff)),
+                                      ldy, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, _capi.lib.m355_last_error(None)
+    torch.cuda.synchronize()
+    y = yd.cpu().numpy()
+    assert np.isnan(y[:GUARD]).all() and np.isnan(y[GUARD + n_out:]).all(), "write outside the buffer"
+    yb = y[GUARD:GUARD + n_out].reshape(B, H, W, ldy)
+    mask = np.zeros(ldy, bool)
+    mask[yoff:yoff + C] = True
+    assert np.isnan(yb[..., ~mask]).all(), "write outside the channel slice"
+    got = yb[..., mask].astype(np.float64)
+    err = np.abs(got - ref)
+    bound = 2.0 ** -10 * np.abs(ref) + 2.0 ** -12 * S
+    ratio = float((err / bound).max())
+    print(f"dwconv C={C} {H}x{W} ldx={ldx}+{xoff} ldy={ldy}+{yoff} act={act} B={B}: max err {err.max():.2e}, "
+          f"worst err / bound {ratio:.3f}")
+    assert np.isfinite(got).all() and ratio <= 1.0

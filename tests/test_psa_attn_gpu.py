@@ -1,0 +1,123 @@
+"""The YOLO11 C2PSA attention kernel (psa_attn.hip) through m355_psa_attn_fwd, against fp64 on the same fp16 q / k / v and
+fp16-rounded pe weights.
+
+Bounds (set from the kernel's rounding points before the first run):
+  * the scores are fp32 sums of 32 exact fp16 products, exponentiated with exp2 in fp32: relative error of a probability
+    ~ 2^-18 here (|q . k| / sqrt(32) <= ~40, 32 * 2^-24 relative per sum);
+  * P is rounded to fp16 before P V: each p_ij carries <= 2^-11 relative error (2^-25 absolute below the fp16 normal range), so
+    |err(o_ic)| <= 2^-11 A_ic + 2^-25 sum_j |v_cj| / l_i, A_ic = sum_j p_ij |v_cj| / l_i (the normaliser l is summed from the
+    fp32 P);
+  * pe: nine fp32 fmas on exact products, <= 10 * 2^-24 S_pe, S_pe = sum |w v| over the taps;
+  * one rounding of o + pe to fp16: <= 2^-11 |ref|.
+  Element-wise:  |err| <= 2^-10 |ref| + 2^-10 A + 2^-12 S_pe + 2^-14 max_j |v_cj|   (each term >= 2x its derivation);
+  and rel-L2 <= 2e-3 over the whole output.
+The rescale branch of the online softmax (every key tile raises a row's maximum) only runs with data built for it (guide §5.4
+rule 26): logits that grow across the key tiles, with the maximum in the last, partial tile; the opposite order (maximum in the
+first tile) keeps alpha = 1.  The pe term is checked on its own with q = k = 0 (uniform attention) and v != 0."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 2048
+
+
+def _reference(qkv16, heads, H, W, pe_w16, pe_b):
+    """fp64 on the given fp16 values.  qkv16 (B, N, heads*128) -> (out (B, N, heads*64), A, S_pe, vmax)."""
+    B, N, _ = qkv16.shape
+    t = torch.from_numpy(qkv16.astype(np.float64)).view(B, N, heads, 128)
+    q, k, v = t[..., :32], t[..., 32:64], t[..., 64:]                     # (B, N, h, d)
+    s = torch.einsum("bihd,bjhd->bhij", q, k) * 32 ** -0.5
+    p = torch.softmax(s, dim=-1)                                            # (B, h, N, N)
+    o = torch.einsum("bhij,bjhc->bihc", p, v)
+    a = torch.einsum("bhij,bjhc->bihc", p, v.abs())
+    vmax = v.abs().amax(dim=1, keepdim=True).expand_as(v)
+    C = heads * 64
+    vimg = v.reshape(B, H, W, C).permute(0, 3, 1, 2)
+    w = torch.from_numpy(pe_w16.astype(np.float64))
+    pe = torch.nn.functional.conv2d(vimg, w, torch.from_numpy(pe_b.astype(np.float64)), padding=1, groups=C)
+    spe = torch.nn.functional.conv2d(vimg.abs(), w.abs(), None, padding=1, groups=C)
+    pe = pe.permute(0, 2, 3, 1).reshape(B, N, C)
+    spe = spe.permute(0, 2, 3, 1).reshape(B, N, C)
+    return (o.reshape(B, N, C) + pe).numpy(), a.reshape(B, N, C).numpy(), spe.numpy(), vmax.reshape(B, N, C).numpy()
+
+
+def _run(qkv16, B, H, W, heads, pe_w, pe_b, dev):
+    from defectdetection_viaobjectdetection_amd import _capi
+    C = heads * 64
+    qd = torch.from_numpy(qkv16).to(dev).contiguous()
+    n_out = B * H * W * C
+    yd = torch.full((n_out + 2 * GUARD,), float("nan"), dtype=torch.float16, device=dev)
+    wt, bt = torch.from_numpy(pe_w), torch.from_numpy(pe_b)
+    rc = _capi.lib.m355_psa_attn_fwd(ctypes.c_void_p(qd.data_ptr()), B, H, W, heads, 32, 64, ctypes.c_void_p(wt.data_ptr()),
+                                     ctypes.c_void_p(bt.data_ptr()), ctypes.c_void_p(yd.data_ptr() + 2 * GUARD),
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, _capi.lib.m355_last_error(None)
+    torch.cuda.synchronize()
+    y = yd.cpu().numpy()
+    assert np.isnan(y[:GUARD]).all() and np.isnan(y[GUARD + n_out:]).all(), "write outside the output"
+    return y[GUARD:GUARD + n_out].reshape(B, H * W, C).astype(np.float64)
+
+
+def _check(got, ref, A, S, vmax, tag):
+    err = np.abs(got - ref)
+    bound = 2.0 ** -10 * np.abs(ref) + 2.0 ** -10 * A + 2.0 ** -12 * S + 2.0 ** -14 * vmax
+    ratio = float((err / bound).max())
+    rel = float(np.linalg.norm(got - ref) / (np.linalg.norm(ref) + 1e-30))
+    print(f"psa_attn {tag}: rel-L2 {rel:.2e}, max err {err.max():.2e}, worst err / bound {ratio:.3f}")
+    assert np.isfinite(got).all() and ratio <= 1.0 and rel <= 2e-3
+
+
+def _weights(rng, C):
+    return (rng.uniform(-1, 1, (C, 1, 3, 3)) / 3).astype(np.float32), rng.uniform(-0.3, 0.3, C).astype(np.float32)
+
+
+@pytest.mark.parametrize("heads", [2, 4])
+@pytest.mark.parametrize("H,W", [(8, 12), (10, 10), (20, 20), (32, 32)])
+def test_psa_attn_random(heads, H, W, cuda_device):
+    rng = np.random.default_rng(heads * 100 + H * W)
+    B, N, C = 2, H * W, heads * 64
+    qkv = (rng.standard_normal((B, N, 2 * C)) * 1.2).astype(np.float16)
+    pe_w, pe_b = _weights(rng, C)
+    ref, A, S, vm = _reference(qkv, heads, H, W, pe_w.astype(np.float16), pe_b)
+    _check(_run(qkv, B, H, W, heads, pe_w, pe_b, cuda_device), ref, A, S, vm, f"random h={heads} N={N}")
+
+
+@pytest.mark.parametrize("grow", [True, False])
+@pytest.mark.parametrize("H,W", [(8, 12), (20, 20), (32, 32)])
+def test_psa_attn_rescale_stress(grow, H, W, cuda_device):
+    """Logits rising with the key index: every 64-key tile moves each row's maximum (the rescale runs at every tile) and the
+    maximum lies in the last tile -- partial at N = 96.  grow = False: the maximum is in the first tile, alpha stays 1."""
+    heads, B = 2, 1
+    N, C = H * W, heads * 64
+    rng = np.random.default_rng(N + grow)
+    qkv = np.zeros((B, N, 2 * C), np.float32)
+    ramp = np.linspace(0.0, 1.0, N) if grow else np.linspace(1.0, 0.0, N)
+    for h in range(heads):
+        qkv[:, :, 128 * h:128 * h + 32] = rng.uniform(0.8, 1.2, (B, N, 32))                  # q > 0
+        qkv[:, :, 128 * h + 32:128 * h + 64] = (1.2 * ramp)[None, :, None] * rng.uniform(0.98, 1.02, (B, N, 32))
+        qkv[:, :, 128 * h + 64:128 * h + 128] = rng.standard_normal((B, N, 64))
+    qkv = qkv.astype(np.float16)   # scores span ~0 .. 7.5: exp range e^7.5 across the row, rising tile by tile
+    pe_w, pe_b = _weights(rng, C)
+    ref, A, S, vm = _reference(qkv, heads, H, W, pe_w.astype(np.float16), pe_b)
+    _check(_run(qkv, B, H, W, heads, pe_w, pe_b, cuda_device), ref, A, S, vm, f"{'rising' if grow else 'falling'} N={N}")
+
+
+@pytest.mark.parametrize("H,W", [(8, 12), (20, 20)])
+def test_psa_attn_uniform_attention_exposes_pe(H, W, cuda_device):
+    """q = k = 0: every row attends uniformly, o = mean_j v_j, so the check isolates pe(v) (v != 0) and its borders."""
+    heads, B = 4, 2
+    N, C = H * W, heads * 64
+    rng = np.random.default_rng(7 + N)
+    qkv = np.zeros((B, N, 2 * C), np.float16)
+    for h in range(heads):
+        qkv[:, :, 128 * h + 64:128 * h + 128] = (rng.standard_normal((B, N, 64)) * 2).astype(np.float16)
+    pe_w, pe_b = _weights(rng, C)
+    ref, A, S, vm = _reference(qkv, heads, H, W, pe_w.astype(np.float16), pe_b)
+    got = _run(qkv, B, H, W, heads, pe_w, pe_b, cuda_device)
+    mean_v = qkv.astype(np.float64).reshape(B, N, heads, 128)[..., 64:].mean(axis=1).reshape(B, 1, C)
+    assert float(np.abs(ref - mean_v).max()) > 0.5      # the pe term is not negligible in this case
+    _check(got, ref, A, S, vm, f"uniform N={N}")
