@@ -246,11 +246,23 @@ int launch_adown_pool(const half_t* x, long x_bstride, int ldx, half_t* a, long 
                       int ldm, int B, int H, int W, int C, hipStream_t s);
 int launch_head_decode(const float* raw, int B, int in_h, int in_w, int nc, int nm, float* preds,
                        hipStream_t s);
+// agnostic != 0: no class offset.  class_mask: device bitmask of nc bits (bit c of word c / 32; nc <= 1024) -- an anchor is a
+// candidate only if its argmax class is in the set; NULL = every class.
 int launch_nms(const float* preds, int B, int A, int nc, int nm, float conf, float iou, int max_det,
-               float* dets, int* counts, void* workspace, size_t workspace_bytes, hipStream_t s);
+               float* dets, int* counts, void* workspace, size_t workspace_bytes, hipStream_t s, int agnostic = 0,
+               const uint32_t* class_mask = nullptr);
 size_t nms_workspace_bytes(int B, int A);
 int launch_proto_masks(const float* dets, const int* counts, const half_t* protos, int B, int max_det,
                        int nm, int mh, int mw, int in_h, int in_w, uint8_t* masks, hipStream_t s);
+// Native-resolution masks (proto_masks_native.hip, upstream process_mask_native) for images [0, B) of one launch group:
+// h_orig_hw int32 (B,2) and h_offsets int64 (B+1) are HOST arrays (image b's masks are the bytes [h_offsets[b],
+// h_offsets[b+1]) of out, one h0*w0 plane per detection slot); boxes f32 (B,max_det,4) in original pixels.  Host-checked
+// arguments: see m355_proto_masks_native.  Returns 0 or a negative / HIP error code.
+int launch_proto_masks_native(const float* dets, const int* counts, const half_t* protos, int B, int max_det, int mh, int mw,
+                              const int* h_orig_hw, const float* boxes, const int64_t* h_offsets, uint8_t* out,
+                              hipStream_t s);
+// The prototype-grid crop of process_mask_native for one image (rows [*top, *top + *ch), cols [*left, *left + *cw)).
+void native_mask_crop(int mh, int mw, int h0, int w0, int* top, int* left, int* ch, int* cw);
 
 // weight gradient (conv_wgrad.hip): dw fp32 [Cout][k*k*Cin] (KRSC).  Split-K partial slabs go to the caller's workspace
 // (conv_wgrad_workspace_bytes) and are added in a fixed order: bitwise reproducible.  -3: workspace missing / too small.

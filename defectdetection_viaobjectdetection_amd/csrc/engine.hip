@@ -2269,6 +2269,29 @@ int m355_postprocess(m355_engine* e, const float* d_preds, const void* d_protos,
   return M355_OK;
 }
 
+int m355_postprocess_ex(m355_engine* e, const float* d_preds, const void* d_protos, int B, float conf, float iou,
+                        int max_det, int agnostic, const uint32_t* d_class_mask, float* d_dets, int* d_counts,
+                        uint8_t* d_masks, void* stream) {
+  if (!e) return M355_ERR_INVALID;
+  if (!d_preds || !d_dets || !d_counts) return e->fail(M355_ERR_INVALID, "null device pointer");
+  if (B < 1 || B > e->desc.max_batch) return e->fail(M355_ERR_INVALID, "batch must be in [1, max_batch]");
+  if (max_det < 1 || max_det > 1024) return e->fail(M355_ERR_INVALID, "max_det must be in [1, 1024]");
+  if (agnostic != 0 && agnostic != 1) return e->fail(M355_ERR_INVALID, "agnostic must be 0 or 1");
+  if (d_class_mask && e->nc > 1024) return e->fail(M355_ERR_INVALID, "a class set covers at most 1024 classes");
+  if (d_masks && e->nm == 0) return e->fail(M355_ERR_INVALID, "a detection engine has no masks: pass d_masks = NULL");
+  if (d_masks && !d_protos) return e->fail(M355_ERR_INVALID, "d_protos is null");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launch_nms(d_preds, B, e->A, e->nc, e->nm, conf, iou, max_det, d_dets, d_counts, e->nms_ws,
+                      e->nms_ws_bytes, s, agnostic, d_class_mask);
+  if (rc != 0) return e->fail(M355_ERR_HIP, "nms launch failed: " + std::to_string(rc));
+  if (d_masks) {
+    rc = launch_proto_masks(d_dets, d_counts, (const half_t*)d_protos, B, max_det, e->nm, e->proto_h, e->proto_w,
+                            e->desc.in_h, e->desc.in_w, d_masks, s);
+    if (rc != 0) return e->fail(M355_ERR_HIP, "mask launch failed: " + std::to_string(rc));
+  }
+  return M355_OK;
+}
+
 // ------------------------------- per-op entry points (unit parity) -------------------------------
 
 static int set_err(int code, const std::string& m) {
@@ -2929,6 +2952,37 @@ int m355_nms(const float* d_preds, int B, int A, int nc, int nm, float conf, flo
   if (rc != 0) return set_err(M355_ERR_HIP, "nms launch failed: " + std::to_string(rc));
   if (se != hipSuccess) return set_err(M355_ERR_HIP, std::string("nms kernel: ") + hipGetErrorString(se));
   return M355_OK;
+}
+
+int m355_nms_ex(const float* d_preds, int B, int A, int nc, int nm, float conf, float iou, int max_det, int agnostic,
+                const uint32_t* d_class_mask, float* d_dets, int* d_counts, void* stream) {
+  if (!d_preds || !d_dets || !d_counts) return set_err(M355_ERR_INVALID, "null pointer");
+  if (B < 1 || A < 1 || nc < 1 || nm < 0) return set_err(M355_ERR_INVALID, "non-positive shape");
+  if (max_det < 1 || max_det > 1024) return set_err(M355_ERR_INVALID, "max_det must be in [1, 1024]");
+  if (agnostic != 0 && agnostic != 1) return set_err(M355_ERR_INVALID, "agnostic must be 0 or 1");
+  if (d_class_mask && nc > 1024) return set_err(M355_ERR_INVALID, "a class set covers at most 1024 classes");
+  void* ws = nullptr;
+  const size_t wsb = nms_workspace_bytes(B, A);
+  HIP_TRYG(hipMalloc(&ws, wsb));
+  const int rc = launch_nms(d_preds, B, A, nc, nm, conf, iou, max_det, d_dets, d_counts, ws, wsb, (hipStream_t)stream,
+                            agnostic, d_class_mask);
+  hipError_t se = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(ws);
+  if (rc != 0) return set_err(M355_ERR_HIP, "nms launch failed: " + std::to_string(rc));
+  if (se != hipSuccess) return set_err(M355_ERR_HIP, std::string("nms kernel: ") + hipGetErrorString(se));
+  return M355_OK;
+}
+
+int m355_proto_masks_native(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det, int mh,
+                            int mw, const int32_t* h_orig_hw, const float* d_boxes, const int64_t* h_offsets,
+                            uint8_t* d_out, void* stream) {
+  if (!d_dets || !d_counts || !d_protos || !d_boxes || !h_orig_hw || !h_offsets)
+    return set_err(M355_ERR_INVALID, "null pointer");
+  const int rc = launch_proto_masks_native(d_dets, d_counts, (const half_t*)d_protos, B, max_det, mh, mw, h_orig_hw,
+                                           d_boxes, h_offsets, d_out, (hipStream_t)stream);
+  if (rc == -1)
+    return set_err(M355_ERR_INVALID, "proto_masks_native: bad argument (shape, max_det, offset table, alignment or null output)");
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "native mask launch failed: " + std::to_string(rc));
 }
 
 int m355_proto_masks(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det, int mh,

@@ -14,6 +14,7 @@ namespace {
 constexpr int NMS_THREADS = 1024;
 constexpr int MAX_KEEP = 1024;      // upper bound for max_det
 constexpr float MAX_WH = 7680.0f;   // class offset (non-agnostic NMS)
+constexpr int MAX_MASK_WORDS = 32;  // class set of nms_kernel: up to 1024 classes
 
 struct Box { float x1, y1, x2, y2; };
 
@@ -28,8 +29,10 @@ __device__ __forceinline__ float iou_f32(const Box& a, const Box& b) {
 }
 
 // One 1024-thread block per image.
-//  1. candidates: conf = max_c score > thr; key = (conf bits << 32) | (0xFFFFFFFF - anchor)  -> sorting
-//     keys descending gives confidence descending, ties by lower anchor index first (oracle order).
+//  1. candidates: conf = max_c score > thr (and, with a class set, the argmax class in it: upstream filters on the argmax
+//     after the conf test and never re-picks an allowed class that is not the argmax);
+//     key = (conf bits << 32) | (0xFFFFFFFF - anchor)  -> sorting keys descending gives confidence descending, ties by
+//     lower anchor index first (oracle order).
 //  2. bitonic sort of the keys in LDS (n padded to a power of two; <= 16384 keys = 128 KB) or, for
 //     larger anchor counts, in the global workspace.
 //  3. wave 0 runs greedy NMS over 64-candidate chunks: each lane owns one candidate, tests it against
@@ -37,7 +40,7 @@ __device__ __forceinline__ float iou_f32(const Box& a, const Box& b) {
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, int A, int nc, int nm, float conf_thr,
                                                           float iou_thr, int max_det, float* dets, int* counts,
                                                           unsigned long long* gkeys, int keys_in_lds,
-                                                          int npad_max) {
+                                                          int npad_max, int agnostic, const uint32_t* class_mask) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // layout: [kept boxes MAX_KEEP*16][kept idx MAX_KEEP*4][misc 16][keys ...]
   Box* kbox = (Box*)smem;
@@ -53,13 +56,23 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, in
   const int wd = 4 + nc + nm;
   const float* pb = preds + (long)b * A * wd;
 
+  __shared__ uint32_t cset[MAX_MASK_WORDS];   // class set (class_mask != NULL): nc <= 32 * MAX_MASK_WORDS, checked by the launcher
   if (tid == 0) misc[0] = 0;
+  if (class_mask && tid < MAX_MASK_WORDS) cset[tid] = tid < (nc + 31) / 32 ? class_mask[tid] : 0u;
   __syncthreads();
   for (int a = tid; a < A; a += NMS_THREADS) {
     const float* p = pb + (long)a * wd + 4;
     float best = p[0];
     for (int c = 1; c < nc; ++c) best = fmaxf(best, p[c]);
-    if (best > conf_thr) {
+    bool in_set = true;
+    if (class_mask) {   // the argmax exactly as the emit step below finds it (first maximum)
+      int cls = 0;
+      float bs = p[0];
+      for (int c = 1; c < nc; ++c)
+        if (p[c] > bs) { bs = p[c]; cls = c; }
+      in_set = (cset[cls >> 5] >> (cls & 31)) & 1u;
+    }
+    if (best > conf_thr && in_set) {
       const int slot = atomicAdd(&misc[0], 1);
       const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)a);
       if (slot < keys_in_lds) lkeys[slot] = key;
@@ -108,7 +121,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, in
         float best = p[4];
         for (int cc = 1; cc < nc; ++cc)
           if (p[4 + cc] > best) { best = p[4 + cc]; cls = cc; }
-        const float off = (float)cls * MAX_WH;
+        const float off = agnostic ? 0.f : (float)cls * MAX_WH;
         bx.x1 = (cx - hw) + off; bx.y1 = (cy - hh) + off; bx.x2 = (cx + hw) + off; bx.y2 = (cy + hh) + off;
       }
       bool alive = valid;
@@ -345,8 +358,10 @@ size_t nms_workspace_bytes(int B, int A) {
 }
 
 int launch_nms(const float* preds, int B, int A, int nc, int nm, float conf, float iou, int max_det, float* dets,
-               int* counts, void* workspace, size_t workspace_bytes, hipStream_t s) {
+               int* counts, void* workspace, size_t workspace_bytes, hipStream_t s, int agnostic,
+               const uint32_t* class_mask) {
   if (max_det > MAX_KEEP || max_det < 1) return -1;
+  if (class_mask && (nc < 1 || nc > 32 * MAX_MASK_WORDS)) return -1;
   int npad = 1;
   while (npad < A) npad <<= 1;
   const size_t base = MAX_KEEP * 20 + 16;
@@ -368,7 +383,8 @@ int launch_nms(const float* preds, int B, int A, int nc, int nm, float conf, flo
     attr_set = true;
   }
   hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(NMS_THREADS), lds, s, preds, A, nc, nm, conf, iou, max_det, dets,
-                     counts, have_ws ? (unsigned long long*)workspace : nullptr, lds_keys, npad);
+                     counts, have_ws ? (unsigned long long*)workspace : nullptr, lds_keys, npad, agnostic ? 1 : 0,
+                     class_mask);
   return (int)hipGetLastError();
 }
 

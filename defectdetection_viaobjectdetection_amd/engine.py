@@ -7,12 +7,14 @@ arithmetic is in the HIP kernels behind the C-ABI, this file only owns buffers a
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _capi
 from ._capi import ConvInfo, ModelDesc, OpInfo, check, lib
+from .preprocess import scale_boxes_to_original
 from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_detect, is_v5u, is_y11
 
 
@@ -133,11 +135,16 @@ class SegEngine:
         return out
 
     def postprocess(self, preds: torch.Tensor, protos: Optional[torch.Tensor], conf: float = 0.25,
-                    iou: float = 0.7, max_det: int = 300, masks: bool = True, multi_label: bool = False, max_nms: int = 30000):
+                    iou: float = 0.7, max_det: int = 300, masks: bool = True, multi_label: bool = False, max_nms: int = 30000,
+                    agnostic: bool = False, classes=None):
         """Batched NMS + mask assembly.  Returns dets f32 (B,max_det,6+nm), counts i32 (B),
         masks u8 (B,max_det,H,W) or None (always None for a detection graph).  Only rows < counts[b] are defined.
-        ``multi_label`` (upstream's validator mode, nc > 1): every (anchor, class) pair above ``conf`` is a candidate."""
+        ``multi_label`` (upstream's validator mode, nc > 1): every (anchor, class) pair above ``conf`` is a candidate.
+        ``agnostic``: class-agnostic NMS.  ``classes`` (an int or a sequence of them, upstream's predict argument): keep only
+        anchors whose argmax class is one of them (ids outside [0, nc) match nothing; an empty sequence keeps nothing)."""
         masks = masks and self.nm > 0
+        if multi_label and (agnostic or classes is not None):
+            raise ValueError("agnostic / classes are options of the predict NMS; the multi-label validator NMS does not take them")
         if multi_label and self.nc > 1:
             return self._postprocess_multilabel(preds, protos, conf, iou, max_det, masks, max_nms)
         B = preds.shape[0]
@@ -146,9 +153,47 @@ class SegEngine:
         m = None
         if masks:
             m = torch.empty((B, max_det, self.imgsz[0], self.imgsz[1]), dtype=torch.uint8, device=preds.device)
-        check(lib.m355_postprocess(self._h, _ptr(preds), _ptr(protos), B, conf, iou, max_det, _ptr(dets),
-                                   _ptr(counts), _ptr(m), _stream()), self._h)
+        if not agnostic and classes is None:
+            check(lib.m355_postprocess(self._h, _ptr(preds), _ptr(protos), B, conf, iou, max_det, _ptr(dets),
+                                       _ptr(counts), _ptr(m), _stream()), self._h)
+        else:
+            cmask = class_mask(classes, self.nc, preds.device)
+            check(lib.m355_postprocess_ex(self._h, _ptr(preds), _ptr(protos), B, conf, iou, max_det, int(bool(agnostic)),
+                                          _ptr(cmask), _ptr(dets), _ptr(counts), _ptr(m), _stream()), self._h)
         return dets, counts, m
+
+    def postprocess_native(self, preds: torch.Tensor, protos: torch.Tensor, orig_shapes: Sequence[Tuple[int, int]],
+                           conf: float = 0.25, iou: float = 0.7, max_det: int = 300, agnostic: bool = False, classes=None):
+        """NMS, then every detection's mask at its image's ORIGINAL resolution (upstream ``process_mask_native``, what
+        predict(retina_masks=True) returns).  ``orig_shapes``: (h0, w0) of each image, letterboxed to this engine's imgsz.
+        Returns (dets f32 (B,max_det,38) on the device, counts (list of int), boxes (per image f32 ndarray (n,4) in original
+        pixels: ``scale_boxes_to_original`` of the rows, the boxes Results reports and the masks are cropped to), masks (per
+        image uint8 (n,h0,w0) device tensors, views of one buffer of sum n*h0*w0 bytes allocated once the counts are known))."""
+        if self.nm == 0:
+            raise ValueError("a detection engine has no masks")
+        B = preds.shape[0]
+        shapes = [(int(h), int(w)) for h, w in orig_shapes]
+        if len(shapes) != B:
+            raise ValueError(f"{len(shapes)} original shapes for a batch of {B}")
+        dets, counts, _ = self.postprocess(preds, protos, conf, iou, max_det, masks=False, agnostic=agnostic, classes=classes)
+        counts_h = counts.cpu().tolist()
+        rows = dets[..., :4].cpu().numpy()
+        boxes = np.zeros((B, max_det, 4), np.float32)
+        out_boxes = []
+        for b, n in enumerate(counts_h):
+            bx = scale_boxes_to_original(rows[b, :n], self.imgsz, shapes[b])
+            boxes[b, :n] = bx
+            out_boxes.append(bx)
+        offsets = np.zeros(B + 1, np.int64)
+        offsets[1:] = np.cumsum([n * h * w for n, (h, w) in zip(counts_h, shapes)])
+        hw = np.ascontiguousarray(np.asarray(shapes, np.int32).reshape(B, 2))
+        buf = torch.empty((int(offsets[-1]),), dtype=torch.uint8, device=preds.device)
+        d_boxes = torch.from_numpy(boxes).to(preds.device)
+        check(lib.m355_proto_masks_native(_ptr(dets), _ptr(counts), _ptr(protos), B, max_det, self.proto_hw[0],
+                                          self.proto_hw[1], hw.ctypes.data_as(C.c_void_p), _ptr(d_boxes),
+                                          offsets.ctypes.data_as(C.c_void_p), _ptr(buf) if buf.numel() else None, _stream()))
+        masks = [buf[int(offsets[b]):int(offsets[b + 1])].view(counts_h[b], *shapes[b]) for b in range(B)]
+        return dets, counts_h, out_boxes, masks
 
     def _postprocess_multilabel(self, preds, protos, conf, iou, max_det, masks, max_nms):
         """upstream's ``non_max_suppression(multi_label=True)``: class offsets make the classes independent, so it is one
@@ -214,6 +259,21 @@ class SegEngine:
             self.close()
         except Exception:
             pass
+
+
+def class_mask(classes, nc: int, device) -> Optional[torch.Tensor]:
+    """Device bitmask (ceil(nc/32) words, bit c % 32 of word c // 32) of a ``classes`` argument: None (every class), an int
+    or a sequence of ints.  Ids outside [0, nc) set no bit."""
+    if classes is None:
+        return None
+    ids = [classes] if isinstance(classes, (int, np.integer)) or (torch.is_tensor(classes) and classes.dim() == 0) \
+        else list(classes)
+    words = np.zeros((nc + 31) // 32, np.uint32)
+    for c in ids:
+        c = int(c)
+        if 0 <= c < nc:
+            words[c >> 5] |= np.uint32(1 << (c & 31))
+    return torch.from_numpy(words.view(np.int32)).to(device)
 
 
 def version() -> str:

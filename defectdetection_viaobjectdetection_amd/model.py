@@ -197,11 +197,14 @@ class YOLO:
     # ------------------------------------------------------------------ inference
     def predict(self, source=None, save: bool = False, imgsz=None, conf: float = 0.25, iou: float = 0.7,
                 max_det: int = 300, device=0, verbose: bool = True, retina_masks: bool = False,
-                project: Optional[str] = None, name: Optional[str] = None, batch: int = 32, **kwargs) -> List[Results]:
+                project: Optional[str] = None, name: Optional[str] = None, batch: int = 32, classes=None,
+                agnostic_nms: bool = False, **kwargs) -> List[Results]:
+        """``retina_masks=True`` (segmentation models): masks at each image's original resolution (upstream
+        ``process_mask_native``); a detection model accepts it and has no masks.  ``classes`` (int or sequence): keep only
+        detections whose class is one of them.  ``agnostic_nms``: class-agnostic NMS."""
         if source is None:
             raise ValueError("source is required")
-        if retina_masks:
-            raise NotImplementedError("retina_masks=True is not implemented")
+        retina = bool(retina_masks) and self.task == "segment"
         dev = int(device[0] if isinstance(device, (list, tuple)) else device)
         if imgsz is None:
             imgsz = self.train_args.get("imgsz", 640)  # D7: a checkpoint keeps its training size
@@ -231,17 +234,29 @@ class YOLO:
                 preds, protos = eng.forward(x)
                 torch.cuda.synchronize()
                 t2 = time.perf_counter()
-                dets, counts, masks = eng.postprocess(preds, protos, conf, iou, max_det, masks=True)
-                counts_h = counts.cpu().tolist()
+                if retina:
+                    dets, counts_h, boxes_o, masks = eng.postprocess_native(
+                        preds, protos, [im.shape[:2] for im in imgs[i0:i0 + len(chunk)]], conf, iou, max_det,
+                        agnostic=agnostic_nms, classes=classes)
+                    torch.cuda.synchronize()
+                else:
+                    dets, counts, masks = eng.postprocess(preds, protos, conf, iou, max_det, masks=True,
+                                                          agnostic=agnostic_nms, classes=classes)
+                    counts_h = counts.cpu().tolist()
                 t3 = time.perf_counter()
             for j, n in enumerate(counts_h):
                 d = dets[j, :n, :6].cpu().numpy()
                 orig = imgs[i0 + j]
-                d[:, :4] = scale_boxes_to_original(d[:, :4], net_shape, orig.shape[:2])
-                m = masks[j, :n].cpu() if masks is not None else None
                 speed = {"preprocess": t_pre, "inference": (t2 - t1) * 1e3 / len(chunk),
                          "postprocess": (t3 - t2) * 1e3 / len(chunk)}
-                r = Results(orig, paths[i0 + j], self.names, torch.from_numpy(d), m, speed, net_shape)
+                if retina:
+                    # masks at the original resolution: Results sees a frame equal to the image (gain 1, pad 0)
+                    d[:, :4] = boxes_o[j]
+                    r = Results(orig, paths[i0 + j], self.names, torch.from_numpy(d), masks[j].cpu(), speed, orig.shape[:2])
+                else:
+                    d[:, :4] = scale_boxes_to_original(d[:, :4], net_shape, orig.shape[:2])
+                    m = masks[j, :n].cpu() if masks is not None else None
+                    r = Results(orig, paths[i0 + j], self.names, torch.from_numpy(d), m, speed, net_shape)
                 if save_dir:
                     r.save_dir = save_dir
                     r.save(os.path.join(save_dir, os.path.splitext(os.path.basename(paths[i0 + j]))[0] + ".jpg"))

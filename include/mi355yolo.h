@@ -130,6 +130,18 @@ int m355_set_keep_raw(m355_engine* e, int keep);
  *            engine, else M355_ERR_INVALID) */
 int m355_postprocess(m355_engine* e, const float* d_preds, const void* d_protos, int batch, float conf,
                      float iou, int max_det, float* d_dets, int* d_counts, uint8_t* d_masks, void* stream);
+/* m355_postprocess with upstream's agnostic / classes options of predict().
+ *   agnostic      0: class-aware NMS (class offset cls * 7680, as m355_postprocess); 1: class-agnostic (offset 0)
+ *   d_class_mask  NULL: every class.  Else a DEVICE bitmask of nc bits (bit c % 32 of word c / 32, ceil(nc / 32) words):
+ *                 an anchor is a candidate only if its max score is above conf AND its argmax class is in the set (an
+ *                 allowed class that is not the argmax is never picked instead; an empty set gives no detections).
+ * d_dets / d_counts / d_masks as m355_postprocess (d_masks may be NULL).  agnostic = 0 with d_class_mask = NULL gives rows
+ * and counts bit-identical to m355_postprocess.  M355_ERR_INVALID, before any HIP call: a NULL required pointer, batch
+ * outside [1, max_batch], max_det outside [1, 1024], agnostic not 0 / 1, a class mask with nc > 1024, masks of a
+ * detection engine or without d_protos. */
+int m355_postprocess_ex(m355_engine* e, const float* d_preds, const void* d_protos, int batch, float conf, float iou,
+                        int max_det, int agnostic, const uint32_t* d_class_mask, float* d_dets, int* d_counts,
+                        uint8_t* d_masks, void* stream);
 
 /* ---- Environment switches ----------------------------------------------------------------------------------------------------
  * The library is configured by m355_model_desc and the arguments of each call.  The M355_* environment variables below are
@@ -263,6 +275,24 @@ int m355_head_decode(const float* d_raw, int B, int in_h, int in_w, int nc, floa
 /* Batched NMS only. preds (B,A,4+nc+nm). */
 int m355_nms(const float* d_preds, int B, int A, int nc, int nm, float conf, float iou, int max_det,
              float* d_dets, int* d_counts, void* stream);
+/* m355_nms with the agnostic / class-set options of m355_postprocess_ex (same meaning).  M355_ERR_INVALID, before any HIP
+ * call: a NULL pointer, B, A or nc < 1, nm < 0, max_det outside [1, 1024], agnostic not 0 / 1, a class mask with
+ * nc > 1024.                                                                                                         [sync] */
+int m355_nms_ex(const float* d_preds, int B, int A, int nc, int nm, float conf, float iou, int max_det, int agnostic,
+                const uint32_t* d_class_mask, float* d_dets, int* d_counts, void* stream);
+/* Native-resolution masks (upstream process_mask_native, predict(retina_masks=True)), one launch per
+ * 32 images.  d_dets (B,max_det,38) and d_counts (B) as m355_nms writes them; d_protos fp16 (B,mh,mw,32), 16-byte aligned;
+ * h_orig_hw HOST int32 (B,2) original (h0, w0) per image; d_boxes f32 (B,max_det,4) x1,y1,x2,y2 in original pixels (the
+ * boxes the caller reports); h_offsets HOST int64 (B+1), non-decreasing from >= 0: image b's masks are the bytes
+ * [h_offsets[b], h_offsets[b+1]) of d_out, one uint8 {0,1} plane (h0,w0) per detection slot, so that span must hold a whole
+ * number of planes, at most max_det.  Slots at or past counts[b] are written as zeros; d_out must hold h_offsets[B] bytes
+ * (it may be NULL when h_offsets[B] == 0).  The prototype grid is cropped to the letterboxed image, the fp32 logits
+ * interpolated bilinearly (align_corners = false) to (h0, w0), zeroed outside the box (x1 <= col < x2, y1 <= row < y2)
+ * and thresholded at > 0.  M355_ERR_INVALID, before any HIP call: a NULL required pointer, B < 1, max_det outside
+ * [1, 1024], mh or mw outside [1, 512], h0 or w0 outside [1, 32768], a crop of no cells, a bad offset table. */
+int m355_proto_masks_native(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det, int mh,
+                            int mw, const int32_t* h_orig_hw, const float* d_boxes, const int64_t* h_offsets,
+                            uint8_t* d_out, void* stream);
 /* Mask assembly only: dets (B,max_det,6+32), counts (B), protos fp16 (B,mh,mw,32)
  * -> masks uint8 (B,max_det,in_h,in_w). */
 int m355_proto_masks(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det,
