@@ -105,6 +105,8 @@ bool conv_forced_tile_extent(int tile, int cout, int* bch, int* bpx);
 // 3x3 stride-1 halo-tile kernel (conv3x3_halo.hip)
 bool conv3x3_halo_ok(const ConvArgs& a);
 int launch_conv3x3_halo(const ConvArgs& a, int variant, hipStream_t s);  // variant 0 auto, 1: 16x16 px / 8 waves, 2: 8x16 px / 4 waves, 3: wide
+// the kernel variant 0 runs on a call conv3x3_halo_ok takes: TILE_M32, TILE_HALOWIDE or TILE_HALO (M355_NO_WIDE / M355_NO_M32 as given)
+int conv3x3_halo_pick(const ConvArgs& a, bool no_wide, bool no_m32);
 // 128 ch x 16x16 px, K depth 32 per step (conv3x3_wide.hip)
 bool conv3x3_wide_ok(const ConvArgs& a);
 int launch_conv3x3_wide(const ConvArgs& a, hipStream_t s);

@@ -367,6 +367,17 @@ bool conv3x3_halo_ok(const ConvArgs& a) {
   return covered * 10 <= (long)a.Hi * a.Wi * 13;
 }
 
+// The automatic choice of launch_conv3x3_halo for a call conv3x3_halo_ok takes: TILE_M32, TILE_HALOWIDE or TILE_HALO.
+// By shape (measured at batch 32, tools/conv3_sweep.py): the wide kernel where its 16x16-pixel tiles fit (80x80 and
+// larger maps, Cout >= 128: equal to the 32x32x16 kernel there); the 32x32x16 kernel on the smaller maps (128 -> 128 at
+// 40x40: 25.8 -> 21.7 us, 256 -> 224: 79.7 -> 68.8 us, 64 -> 64: 10.0 -> 8.7 us); the 8-row halo kernel for 64-channel
+// layers on large maps (24.6 us against 26.0)
+int conv3x3_halo_pick(const ConvArgs& a, bool no_wide, bool no_m32) {
+  const bool wide = !no_wide && conv3x3_wide_ok(a);
+  if (!no_m32 && !wide && conv3x3_m32_ok(a) && (a.Cout > 64 || a.Hi * a.Wi <= 1600)) return TILE_M32;
+  return wide ? TILE_HALOWIDE : TILE_HALO;
+}
+
 // variant: 0 = auto, 1 = 8 waves / 16x16 px, 2 = 4 waves / 8x16 px
 int launch_conv3x3_halo(const ConvArgs& a0, int variant, hipStream_t s) {
   ConvArgs a = a0;
@@ -374,14 +385,12 @@ int launch_conv3x3_halo(const ConvArgs& a0, int variant, hipStream_t s) {
   if (variant == TILE_SLAB - TILE_HALO) return launch_conv3x3_slab(a, s);
   if (!conv3x3_halo_ok(a)) return -1;
   if (variant >= TILE_M32 - TILE_HALO && variant <= TILE_M32_64x8 - TILE_HALO) return launch_conv3x3_m32(a, variant - (TILE_M32 - TILE_HALO), s);
-  // by shape (measured at batch 32, tools/conv3_sweep.py): the wide kernel where its 16x16-pixel tiles fit (80x80 and
-  // larger maps, Cout >= 128: equal to the 32x32x16 kernel there); the 32x32x16 kernel on the smaller maps (128 -> 128 at
-  // 40x40: 25.8 -> 21.7 us, 256 -> 224: 79.7 -> 68.8 us, 64 -> 64: 10.0 -> 8.7 us); the 8-row halo kernel for 64-channel
-  // layers on large maps (24.6 us against 26.0)
-  if (variant == 0 && !knobs().no_m32 && conv3x3_m32_ok(a) && !(conv3x3_wide_ok(a) && !knobs().no_wide) &&
-      (a.Cout > 64 || a.Hi * a.Wi <= 1600))
-    return launch_conv3x3_m32(a, 0, s);
-  if (variant == 3 || (variant == 0 && conv3x3_wide_ok(a) && !knobs().no_wide)) return launch_conv3x3_wide(a, s);
+  if (variant == 0) {
+    const int pick = conv3x3_halo_pick(a, knobs().no_wide, knobs().no_m32);
+    if (pick == TILE_M32) return launch_conv3x3_m32(a, 0, s);
+    if (pick == TILE_HALOWIDE) variant = 3;
+  }
+  if (variant == 3) return launch_conv3x3_wide(a, s);
   if (variant >= 5) return -1;   // ids 21-24 were the lean halo template (measured equal to the K-64 kernels below; removed in round 3)
   if (variant == 0) {
     variant = knobs().halo_variant;  // measured: the 4-wave variant (two blocks per CU) wins on every layer

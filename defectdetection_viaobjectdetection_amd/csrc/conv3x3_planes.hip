@@ -639,8 +639,11 @@ template <class C>
 long planes_cost(const PlanesArgs& a, PlanesGeom* g) {
   if (!planes_geometry<C>(a, g)) return -1;
   if (C::WC == 4 && a.Cout % 128) return -1;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  static const int cus = [] {   // read once, as planes_launch does
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n;
+  }();
   const long rounds = (g->ntiles + cus - 1) / cus;
   return rounds * g->NP * ((long)C::NPB2 * 18 * 33 + (long)((g->npieces + C::NW - 1) / C::NW) * 120 + 700);
 }

@@ -41,6 +41,19 @@ struct ConvLayer {
 
 enum OpKind { OP_STEM, OP_CONV, OP_CONVT, OP_PHASE, OP_POOL, OP_UP, OP_DECODE, OP_ADOWN, OP_C2F32, OP_PAIR, OP_DWCONV, OP_PSA_ATTN };
 
+// The kernel of an OP_CONV / OP_CONVT / OP_PHASE launch, chosen once at plan time (plan_route)
+enum Route {
+  R_IGEMM,    // im2col implicit GEMM (conv_igemm.hip) with channel tile Op::tile
+  R_HALO,     // 3x3 stride 1: halo / wide / m32 kernel as conv3x3_halo_pick chooses (conv3x3_halo.hip)
+  R_C32,      // 3x3 32 -> 32 (conv3x3_c32.hip)
+  R_SLAB,     // 3x3 on narrow maps (conv3x3_small.hip)
+  R_W1,       // 1x1, weights in registers (conv1x1_wreg.hip)
+  R_PLANES,   // 3x3 row-slab kernel in single-conv mode (conv3x3_planes.hip)
+  R_S2C32,    // 3x3/s2 (32 -> 64) + 1x1 (64 -> 64) on the patch kernel (conv3x3_s2c32.hip)
+  R_S2C64,    // 3x3/s2 (64 -> 128) + 1x1 (128 -> 128), weights in registers (conv3x3_s2c64.hip)
+  R_PROTOR,   // OP_PHASE + proto.cv3, weights in registers (proto_phase_wreg.hip)
+};
+
 struct Op {
   OpKind kind;
   int conv = -1;       // physical conv index (phys_)
@@ -61,12 +74,10 @@ struct Op {
   double flops = 0;       // algorithmic FLOPs per image (2*MACs; 0 for non-conv ops)
   double bytes = 0;       // algorithmic activation bytes per image (in + out + residual)
   double wbytes = 0;      // weight bytes (read once per launch)
-  int tile = -1;
+  Route route = R_IGEMM;
+  int tile = -1;          // im2col tile id: the launch of R_IGEMM, the run-time fallback of R_S2C32 / R_S2C64 / R_PROTOR
   int decode = 0;         // head output conv that also decodes its rows into the prediction tensor (no OP_DECODE launch)
-  int s2c32 = 0;          // conv 3x3/s2 (32 -> 64) + 1x1 (64 -> 64) on the dedicated patch kernel (conv3x3_s2c32.hip)
-  int s2c64 = 0;          // conv 3x3/s2 (64 -> 128) + 1x1 (128 -> 128) on the weights-in-registers kernel (conv3x3_s2c64.hip)
   int headtail = 0;       // head output conv of a level that can run as conv + decode in one launch (head_tail.hip) when the raw maps are not kept
-  int protor = 0;         // OP_PHASE + proto.cv3 on the weights-in-registers kernel (proto_phase_wreg.hip)
   int stemfuse = -1;      // >= 0: index of the stem op this launch also computes (conv_stem_s2c32.hip); that op is then skipped
   bool fused_away = false;
   // stream lanes (plan_lanes): lane 0 is the caller's stream, lanes >= 1 are engine-owned side streams
@@ -1241,12 +1252,188 @@ int alloc_all(m355_engine* e) {
   return 0;
 }
 
-// Fill the measurement metadata of every op and fix the conv tile choice (algorithmic
-// FLOPs = 2*MACs; algorithmic bytes = every activation read once + written once, weights once).
-void annotate_ops(m355_engine* e) {
+// ---- launch arguments of an op over images [b0, b0 + B): one builder per argument struct, shared by the plan (B = max_batch,
+// b0 = 0, no caller buffers yet) and the forward
+ConvArgs conv_args(const m355_engine* e, const Op& op, int B, int b0, float* preds, void* protos) {
+  const PhysConv& p = e->phys[op.conv];
+  const Tensor& ti = e->tensors[op.in.t];
+  ConvArgs a{};
+  a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C; a.x = ti.p + op.in.off + b0 * a.x_bstride;
+  a.Hi = ti.H; a.Wi = ti.W; a.Cin = p.cin;
+  a.w = p.w; a.Kpad = p.Kpad; a.bias = p.bias; a.wf = p.wf; a.zero = e->zero; a.act = p.act;
+  if (op.kind == OP_CONV) {
+    a.ksize = p.k; a.stride = p.stride; a.pad = p.k / 2;
+    a.Ho = (ti.H + 2 * a.pad - p.k) / p.stride + 1;
+    a.Wo = (ti.W + 2 * a.pad - p.k) / p.stride + 1;
+    a.Cout = p.cout;
+  } else {   // OP_CONVT: one 1x1 GEMM onto 4 cout virtual channels; OP_PHASE: four 2x2 phase convs (compose_proto_phases)
+    a.ksize = op.kind == OP_PHASE ? 2 : 1; a.stride = 1; a.pad = 0; a.phase = op.kind == OP_PHASE;
+    a.Ho = ti.H; a.Wo = ti.W; a.Cout = 4 * p.cout; a.convt_co = p.cout;
+  }
+  if (op.out_ext == 1) {   // raw head rows (external outputs are never in the sub-batched segment: b0 = 0)
+    const int rw = 64 + e->nc + e->nm;
+    a.y = e->raw + (long)op.level_off * rw + op.raw_off;
+    a.y_bstride = (long)e->A * rw; a.ldy = rw; a.out_f32 = 1;
+  } else if (op.out_ext == 2) {
+    a.y = protos; a.y_bstride = (long)e->proto_h * e->proto_w * e->nm; a.ldy = e->nm;
+  } else {
+    const Tensor& to = e->tensors[op.out.t];
+    a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.y = to.p + op.out.off + b0 * a.y_bstride;
+  }
+  if (op.in2.t >= 0) {   // Upsample + Concat read through
+    const Tensor& t2 = e->tensors[op.in2.t];
+    a.x2_bstride = (long)t2.H * t2.W * t2.C; a.ldx2 = t2.C; a.csplit = op.in2.c; a.x2 = t2.p + op.in2.off + b0 * a.x2_bstride;
+  }
+  if (op.res.t >= 0) {
+    const Tensor& tr = e->tensors[op.res.t];
+    a.r_bstride = (long)tr.H * tr.W * tr.C; a.ldr = tr.C; a.res = tr.p + op.res.off + b0 * a.r_bstride;
+  }
+  a.M = B * a.Ho * a.Wo;
+  if (op.decode) {
+    a.dec_preds = preds; a.dec_A = e->A; a.dec_level_off = op.level_off; a.dec_nc = e->nc; a.dec_nm = e->nm;
+    a.dec_keep_raw = e->keep_raw; a.dec_stride = (float)(e->desc.in_h / a.Ho);
+  }
+  if (p.l3 >= 0) { a.w2 = p.w2; a.bias2 = p.bias2; a.cout2 = p.cout2; a.wf2 = p.wf2; }   // the 1x1 conv in this launch's epilogue
+  return a;
+}
+
+// row-slab kernels (conv3x3_planes.hip): OP_PAIR, or one OP_CONV in single-conv mode (its conv in the second slot)
+PlanesArgs planes_args(const m355_engine* e, const Op& op, int B, int b0) {
+  const PhysConv& pa = e->phys[op.conv];
+  const PhysConv& pb = e->phys[op.kind == OP_PAIR ? op.conv2 : op.conv];
+  const Tensor& ti = e->tensors[op.in.t];
+  const Tensor& to = e->tensors[op.out.t];
+  PlanesArgs a{};
+  a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C; a.x = ti.p + op.in.off + b0 * a.x_bstride;
+  a.H = ti.H; a.W = ti.W; a.B = B; a.Cin = pa.cin; a.Cout = pb.cout; a.act = pb.act; a.stride = pb.stride;
+  if (op.kind == OP_PAIR) { a.wfa = pa.wf; a.cblocks_a = (pa.cout + 63) / 64 * 2; a.ba = pa.bias; }
+  a.wfb = pb.wf; a.cblocks_b = (pb.cout + 63) / 64 * 2; a.bb = pb.bias;
+  a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.y = to.p + op.out.off + b0 * a.y_bstride;
+  if (op.res.t >= 0) {   // (a Bottleneck pair's shortcut is its input slice)
+    const Tensor& tr = e->tensors[op.res.t];
+    a.r_bstride = (long)tr.H * tr.W * tr.C; a.ldr = tr.C; a.res = tr.p + op.res.off + b0 * a.r_bstride;
+  }
+  return a;
+}
+
+StemArgs stem_args(const m355_engine* e, const Op& op, int B, int b0, const void* in) {
+  const PhysConv& p = e->phys[op.conv];
+  const Tensor& to = e->tensors[op.out.t];
+  StemArgs a{};
+  a.x = (const uint8_t*)in + (long)b0 * op.Hi * op.Wi * 3; a.B = B; a.H = op.Hi; a.W = op.Wi;
+  a.w16 = (const half_t*)p.stem_w; a.bias = p.bias;
+  a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.Cout = p.cout;
+  a.y = to.p + op.out.off + b0 * a.y_bstride;
+  return a;
+}
+
+// (a head level runs on head_tail.hip over whole batches only: b0 = 0)
+HeadTailArgs head_tail_args(const m355_engine* e, const Op& op, int B, float* preds) {
+  const PhysConv& p = e->phys[op.conv];
+  const Tensor& ti = e->tensors[op.in.t];
+  HeadTailArgs a{};
+  a.x = ti.p; a.ldx = ti.C; a.M = (long)B * ti.H * ti.W; a.HW = ti.H * ti.W; a.W = ti.W;
+  a.stride = (float)(e->desc.in_h / ti.H);
+  a.A = e->A; a.level_off = op.level_off; a.nc = e->nc; a.nm = e->nm;
+  a.wf = p.wf; a.bias = p.bias; a.preds = preds;
+  return a;
+}
+
+// A head level's block-diagonal 1x1 in the layout head_tail.hip takes: box 64 <- 64, class nc <- 128, coefficient 32 <- 32
+bool head_tail_layout(const m355_engine* e, const PhysConv& p) {
+  return p.diag && p.logical.size() == 3 && p.cin == 224 && p.cout == 64 + e->nc + e->nm && e->nm == 32 && e->nc <= 32 &&
+         e->convs[p.logical[0]].cin == 64 && e->convs[p.logical[1]].cin == 128;
+}
+
+// Which kernel an OP_CONV / OP_CONVT / OP_PHASE launch runs (op.route, op.tile), from its shapes at max_batch (`a` = its
+// conv_args) and the M355_* switches; and whether a head level is eligible for head_tail.hip.
+void plan_route(m355_engine* e, Op& op, const ConvArgs& a) {
+  PhysConv& p = e->phys[op.conv];
+  const Tensor& ti = e->tensors[op.in.t];
+  if (op.kind == OP_PHASE) {
+    op.tile = p.cout % 128 == 0 ? TILE_128x128 : TILE_64x128;
+    if (p.l3 >= 0 && p.cin == 128 && p.cout == 128 && p.cout2 == 32 && ti.H % 8 == 0 && ti.W % 16 == 0 && !getenv("M355_NO_PROTOR"))
+      op.route = R_PROTOR;
+    return;
+  }
+  const bool conv = op.kind == OP_CONV;
+  op.tile = conv_pick_tile(a.Cout, a.M);
+  if (a.ksize == 1 && op.tile == TILE_128x128 && getenv("M355_K1_TILE")) op.tile = atoi(getenv("M355_K1_TILE"));
+  if (op.decode) op.tile = TILE_128x128;   // the whole 64 + nc + nm row of a pixel in one channel tile
+  if (conv && conv3x3_halo_ok(a) && !getenv("M355_NO_HALO")) op.route = R_HALO;
+  const bool m32 = op.route == R_HALO && conv3x3_halo_pick(a, getenv("M355_NO_WIDE"), getenv("M355_NO_M32")) == TILE_M32;
+  if (conv && conv3x3_c32_ok(a) && !getenv("M355_NO_C32")) op.route = R_C32;
+  // 1x1 with K <= 512 and Cout a multiple of 128: weights in registers (conv1x1_wreg.hip)
+  if (conv && op.out_ext == 0 && p.l3 < 0 && !p.diag && op.res.t < 0 && !op.decode && (op.in2.t < 0 || !getenv("M355_NO_W1_SPLIT")) &&
+      conv1x1_wreg_ok(a) && !getenv("M355_NO_W1"))
+    op.route = R_W1;
+  if (conv && op.route != R_HALO && op.route != R_C32 && conv3x3_slab_ok(a) && !getenv("M355_NO_SLAB")) op.route = R_SLAB;
+  // row-slab kernel in single-conv mode (conv3x3_planes.hip) for what the slab kernel took (the 20 x 20 level): one block per CU
+  // owns a slab x 64 channels with its weights streamed to registers -- 21 us against 34 on 256 -> 256 at batch 32
+  // ... and for the stride-2 3x3 convs that were on the im2col kernel (model.5 / 7 / 16 / 19 of the s scale: 177 us at batch 32)
+  const bool planes_s2 = p.k == 3 && p.stride == 2 && op.res.t < 0 && op.in2.t < 0 && !getenv("M355_NO_PLANES_S2");
+  // ... and for the 64 -> 64 conv of the 40 x 40 level (model.22.cv2.1.1: 9 us against 14 on the 32x32x16 halo kernel)
+  const bool planes_m64 = m32 && a.Cout <= 64 && op.res.t < 0 && op.in2.t < 0 && !getenv("M355_NO_PLANES_M64");
+  if (conv && (op.route == R_SLAB || planes_s2 || planes_m64) && op.out_ext == 0 && p.l3 < 0 && !p.diag && !getenv("M355_NO_PLANES")) {
+    PlanesArgs pa = planes_args(e, op, e->desc.max_batch, 0);
+    pa.wfb = (const half_t*)1;   // placeholder: the fragments are packed after planning, and only for the ops planned here
+    if (conv3x3_planes_ok(pa)) {
+      op.route = R_PLANES;
+      p.planes = 1;
+    }
+  }
+  if (conv && op.out_ext == 1 && !op.decode && head_tail_layout(e, p) && ti.C == 224 && op.in.off == 0 && op.raw_off == 0 &&
+      a.Ho * a.Wo >= 32 && !getenv("M355_NO_HEADTAIL")) {
+    op.headtail = 1;   // (the route stays im2col: which path runs depends on keep_raw at forward time)
+    ++e->headtail_n;
+  }
+  if (conv && p.l3 >= 0 && p.k == 3 && p.stride == 2 && p.cin == 32 && p.cout == 64 && p.cout2 == 64 && a.Ho % 8 == 0 &&
+      a.Wo % 16 == 0 && !getenv("M355_NO_S2C32"))
+    op.route = R_S2C32;
+  if (conv && p.l3 >= 0 && p.k == 3 && p.stride == 2 && p.cin == 64 && p.cout == 128 && p.cout2 == 128 && a.Ho % 8 == 0 &&
+      a.Wo % 8 == 0 && !getenv("M355_NO_S2C64"))
+    op.route = R_S2C64;
+}
+
+// The op table's kernel label of a conv launch, from its route and shapes (`a` = its conv_args at max_batch)
+void conv_label(const m355_engine* e, Op& op, const ConvArgs& a) {
   static const char* tile_names[] = {"128x128", "64x128", "32x256", "64x256"};
+  const PhysConv& p = e->phys[op.conv];
+  char* k = op.kernel;
+  const size_t n = sizeof(op.kernel);
+  const char* ch = a.Cout > 64 ? "128ch" : "64ch";
+  switch (op.route) {
+    case R_IGEMM:
+      if (op.kind == OP_PHASE) snprintf(k, n, "conv_igemm<%s,k2,phase%s>", tile_names[op.tile], p.l3 >= 0 ? "+1x1" : "");
+      else snprintf(k, n, "conv_igemm<%s,k%d%s>", tile_names[op.tile], a.ksize, p.l3 >= 0 ? "+1x1" : op.decode ? "+decode" : "");
+      break;
+    case R_HALO: {
+      const int pick = conv3x3_halo_pick(a, getenv("M355_NO_WIDE"), getenv("M355_NO_M32"));
+      if (pick == TILE_HALOWIDE) snprintf(k, n, "conv3x3_wide<128ch,16x16px>");
+      else if (pick == TILE_M32) snprintf(k, n, "conv3x3_m32<%s,8x16px>", ch);
+      else snprintf(k, n, "conv3x3_halo<%s>", ch);
+      break;
+    }
+    case R_C32: snprintf(k, n, "conv3x3_c32<32ch,16x16px>"); break;
+    case R_SLAB: snprintf(k, n, "conv3x3_slab<64ch,rows>"); break;
+    case R_W1: snprintf(k, n, "conv1x1_wreg<K%d,%dch>", p.cin, a.Cout % 256 == 0 ? 256 : 128); break;
+    case R_PLANES: snprintf(k, n, p.stride == 2 ? "conv3x3_planes<64ch,rows,s2>" : "conv3x3_planes<64ch,rows>"); break;
+    case R_S2C32: snprintf(k, n, "conv3x3_s2c32<8x16px>+1x1"); break;
+    case R_S2C64: snprintf(k, n, "conv3x3_s2c64<8x8px>+1x1"); break;
+    case R_PROTOR: snprintf(k, n, "proto_phase_wreg<8x16px>"); break;
+  }
+}
+
+// Fill the measurement metadata of every op and plan its kernel (algorithmic FLOPs = 2*MACs; algorithmic
+// bytes = every activation read once + written once, weights once).
+void annotate_ops(m355_engine* e) {
   for (Op& op : e->ops) {
     if (op.conv >= 0) snprintf(op.layer, sizeof(op.layer), "%s", e->convs[e->phys[op.conv].logical[0]].name);
+    if (op.kind == OP_CONV || op.kind == OP_CONVT || op.kind == OP_PHASE) {
+      const ConvArgs a = conv_args(e, op, e->desc.max_batch, 0, nullptr, nullptr);
+      plan_route(e, op, a);
+      conv_label(e, op, a);
+    }
     switch (op.kind) {
       case OP_STEM: {
         const PhysConv& p = e->phys[op.conv];
@@ -1266,106 +1453,16 @@ void annotate_ops(m355_engine* e) {
       case OP_CONVT: {
         const PhysConv& p = e->phys[op.conv];
         const Tensor& ti = e->tensors[op.in.t];
-        int Ho, Wo, cout_v = p.cout, k = p.k;
+        int Ho, Wo, cout_v = p.cout;
         if (op.kind == OP_CONVT) {
-          Ho = ti.H; Wo = ti.W; cout_v = 4 * p.cout; k = 1;
+          Ho = ti.H; Wo = ti.W; cout_v = 4 * p.cout;
           op.flops = 2.0 * Ho * Wo * p.cin * cout_v;
         } else {
           Ho = (ti.H + 2 * (p.k / 2) - p.k) / p.stride + 1;
           Wo = (ti.W + 2 * (p.k / 2) - p.k) / p.stride + 1;
           op.flops = 2.0 * Ho * Wo * p.macs_px;
         }
-        op.tile = conv_pick_tile(cout_v, e->desc.max_batch * Ho * Wo);
-        if (k == 1 && op.tile == TILE_128x128 && getenv("M355_K1_TILE")) op.tile = atoi(getenv("M355_K1_TILE"));
-        if (op.decode) op.tile = TILE_128x128;   // the whole 64 + nc + nm row of a pixel in one channel tile
-        bool wide = false, m32 = false;
-        {
-          ConvArgs probe{};
-          probe.ksize = p.k; probe.stride = p.stride; probe.pad = p.k / 2; probe.out_f32 = (op.out_ext == 1);
-          probe.convt_co = (op.kind == OP_CONVT) ? p.cout : 0;
-          probe.Cin = p.cin; probe.Cout = cout_v; probe.Hi = ti.H; probe.Wi = ti.W; probe.Ho = Ho; probe.Wo = Wo;
-          probe.ldx = 8; probe.ldy = 8;
-          if (op.kind == OP_CONV && conv3x3_halo_ok(probe) && !getenv("M355_NO_HALO")) op.tile = TILE_HALO;
-          wide = op.tile == TILE_HALO && conv3x3_wide_ok(probe) && !getenv("M355_NO_WIDE");
-          probe.Kpad = p.Kpad;
-          probe.M = e->desc.max_batch * Ho * Wo; probe.x_bstride = (long)ti.H * ti.W * ti.C; probe.ldx = ti.C;
-          // the same rule launch_conv3x3_halo applies (conv3x3_halo.hip): 32x32x16 kernel on the maps the wide tiles do not fit
-          m32 = op.tile == TILE_HALO && !wide && !getenv("M355_NO_M32") && conv3x3_m32_ok(probe) && (cout_v > 64 || ti.H * ti.W <= 1600);
-          probe.ldx = 8;
-          if (op.kind == OP_CONV && conv3x3_c32_ok(probe) && !getenv("M355_NO_C32")) op.tile = TILE_C32;
-          {
-            ConvArgs pr2 = probe;
-            pr2.ldx = ti.C; pr2.ldy = 8; pr2.Kpad = p.Kpad; pr2.M = e->desc.max_batch * Ho * Wo; pr2.x_bstride = (long)ti.H * ti.W * ti.C;
-            // 1x1 with K <= 512 and Cout a multiple of 128: weights in registers (conv1x1_wreg.hip)
-            if (op.kind == OP_CONV && op.out_ext == 0 && p.l3 < 0 && !p.diag && op.res.t < 0 && !op.decode &&
-                (op.in2.t < 0 || !getenv("M355_NO_W1_SPLIT"))) {
-              ConvArgs pr3 = pr2;
-              const Tensor& to2 = e->tensors[op.out.t];
-              pr3.ldy = to2.C; pr3.y_bstride = (long)to2.H * to2.W * to2.C;
-              if (op.in2.t >= 0) {   // Upsample + Concat read through (model.15.cv1 of the s scale: 384 -> 128)
-                const Tensor& t2 = e->tensors[op.in2.t];
-                pr3.x2 = t2.p + op.in2.off; pr3.x2_bstride = (long)t2.H * t2.W * t2.C; pr3.ldx2 = t2.C; pr3.csplit = op.in2.c;
-              }
-              if (conv1x1_wreg_ok(pr3) && !getenv("M355_NO_W1")) op.tile = TILE_W1;
-            }
-          }
-          if (op.kind == OP_CONV && op.tile != TILE_HALO && op.tile != TILE_C32 && conv3x3_slab_ok(probe) && !getenv("M355_NO_SLAB"))
-            op.tile = TILE_SLAB;
-        }
-        // row-slab kernel in single-conv mode (conv3x3_planes.hip) for what the slab kernel took (the 20 x 20 level): one block per CU
-        // owns a slab x 64 channels with its weights streamed to registers -- 21 us against 34 on 256 -> 256 at batch 32
-        // ... and for the stride-2 3x3 convs that were on the im2col kernel (model.5 / 7 / 16 / 19 of the s scale: 177 us at batch 32)
-        const bool planes_s2 = p.k == 3 && p.stride == 2 && op.res.t < 0 && op.in2.t < 0 && !op.s2c32 && !op.s2c64 && !getenv("M355_NO_PLANES_S2");
-        // ... and for the 64 -> 64 conv of the 40 x 40 level (model.22.cv2.1.1: 9 us against 14 on the 32x32x16 halo kernel)
-        const bool planes_m64 = m32 && cout_v <= 64 && op.res.t < 0 && op.in2.t < 0 && !getenv("M355_NO_PLANES_M64");
-        if (op.kind == OP_CONV && (op.tile == TILE_SLAB || planes_s2 || planes_m64) && op.out_ext == 0 && p.l3 < 0 && !p.diag && !getenv("M355_NO_PLANES")) {
-          const Tensor& to2 = e->tensors[op.out.t];
-          PlanesArgs pa{};
-          pa.x = ti.p; pa.y = to2.p; pa.wfb = (const half_t*)1; pa.bb = (const float*)1;   // (shape check only)
-          pa.x_bstride = (long)ti.H * ti.W * ti.C; pa.ldx = ti.C; pa.H = ti.H; pa.W = ti.W; pa.B = e->desc.max_batch; pa.Cin = p.cin; pa.Cout = p.cout;
-          pa.cblocks_b = (p.cout + 63) / 64 * 2; pa.ldy = to2.C; pa.act = p.act; pa.stride = p.stride;
-          if (conv3x3_planes_ok(pa)) {
-            op.tile = TILE_PLANES;
-            e->phys[op.conv].planes = 1;
-          }
-        }
-        if (op.tile == TILE_PLANES)
-          snprintf(op.kernel, sizeof(op.kernel), p.stride == 2 ? "conv3x3_planes<64ch,rows,s2>" : "conv3x3_planes<64ch,rows>");
-        else if (op.tile == TILE_W1)
-          snprintf(op.kernel, sizeof(op.kernel), "conv1x1_wreg<K%d,%dch>", p.cin, cout_v % 256 == 0 ? 256 : 128);
-        else if (op.tile == TILE_C32)
-          snprintf(op.kernel, sizeof(op.kernel), "conv3x3_c32<32ch,16x16px>");
-        else if (op.tile == TILE_SLAB)
-          snprintf(op.kernel, sizeof(op.kernel), "conv3x3_slab<64ch,rows>");
-        else if (wide)
-          snprintf(op.kernel, sizeof(op.kernel), "conv3x3_wide<128ch,16x16px>");
-        else if (m32)
-          snprintf(op.kernel, sizeof(op.kernel), "conv3x3_m32<%s,8x16px>", cout_v > 64 ? "128ch" : "64ch");
-        else if (op.tile == TILE_HALO)
-          snprintf(op.kernel, sizeof(op.kernel), "conv3x3_halo<%s>", cout_v > 64 ? "128ch" : "64ch");
-        else
-          snprintf(op.kernel, sizeof(op.kernel), "conv_igemm<%s,k%d>", tile_names[op.tile], k);
-        if (op.decode) {
-          snprintf(op.kernel, sizeof(op.kernel), "conv_igemm<128x128,k1+decode>");
-        }
-        if (op.kind == OP_CONV && op.out_ext == 1 && !op.decode && p.diag && p.logical.size() == 3 && p.cin == 224 && ti.C == 224 &&
-            op.in.off == 0 && p.cout == 64 + e->nc + e->nm && e->nm == 32 && e->nc <= 32 && e->convs[p.logical[0]].cin == 64 &&
-            e->convs[p.logical[1]].cin == 128 && op.raw_off == 0 && Ho * Wo >= 32 && !getenv("M355_NO_HEADTAIL")) {
-          op.headtail = 1;   // (the kernel name of the op table stays the im2col one: which path runs depends on keep_raw at forward time)
-          ++e->headtail_n;
-        }
         if (op.kind == OP_CONV && p.l3 >= 0) {   // + the 1x1 conv in the epilogue
-          snprintf(op.kernel, sizeof(op.kernel), "conv_igemm<%s,k%d+1x1>", tile_names[op.tile], k);
-          if (p.k == 3 && p.stride == 2 && p.cin == 32 && p.cout == 64 && p.cout2 == 64 && Ho % 8 == 0 && Wo % 16 == 0 &&
-              !getenv("M355_NO_S2C32")) {
-            op.s2c32 = 1;
-            snprintf(op.kernel, sizeof(op.kernel), "conv3x3_s2c32<8x16px>+1x1");
-          }
-          if (p.k == 3 && p.stride == 2 && p.cin == 64 && p.cout == 128 && p.cout2 == 128 && Ho % 8 == 0 && Wo % 8 == 0 &&
-              !getenv("M355_NO_S2C64")) {
-            op.s2c64 = 1;
-            snprintf(op.kernel, sizeof(op.kernel), "conv3x3_s2c64<8x8px>+1x1");
-          }
           snprintf(op.layer, sizeof(op.layer), "%s+%s", e->convs[p.logical[0]].name, e->convs[p.l3].name);
           op.flops += 2.0 * Ho * Wo * (double)p.cout * p.cout2;
         }
@@ -1381,19 +1478,9 @@ void annotate_ops(m355_engine* e) {
       case OP_PHASE: {
         const PhysConv& p = e->phys[op.conv];
         const Tensor& ti = e->tensors[op.in.t];
-        op.tile = p.cout % 128 == 0 ? TILE_128x128 : TILE_64x128;
-        snprintf(op.kernel, sizeof(op.kernel), "conv_igemm<%s,k2,phase>", tile_names[op.tile]);
-        snprintf(op.layer, sizeof(op.layer), "model.22.proto.upsample+cv2");
+        snprintf(op.layer, sizeof(op.layer), p.l3 >= 0 ? "model.22.proto.upsample+cv2+cv3" : "model.22.proto.upsample+cv2");
         op.flops = 2.0 * ti.H * ti.W * p.macs_px;
         op.bytes = (double)ti.H * ti.W * p.cin * 2 + (double)4 * ti.H * ti.W * (p.l3 >= 0 ? p.cout2 : p.cout) * 2;
-        if (p.l3 >= 0) {
-          snprintf(op.kernel, sizeof(op.kernel), "conv_igemm<128x128,k2,phase+1x1>");
-          snprintf(op.layer, sizeof(op.layer), "model.22.proto.upsample+cv2+cv3");
-          if (p.cin == 128 && p.cout == 128 && p.cout2 == 32 && ti.H % 8 == 0 && ti.W % 16 == 0 && !getenv("M355_NO_PROTOR")) {
-            op.protor = 1;
-            snprintf(op.kernel, sizeof(op.kernel), "proto_phase_wreg<8x16px>");
-          }
-        }
         op.wbytes = (double)p.cout_pad * p.Kpad * 2;
         break;
       }
@@ -1471,7 +1558,7 @@ void annotate_ops(m355_engine* e) {
   for (size_t i = 0; i + 1 < e->ops.size(); ++i) {
     Op& st = e->ops[i];
     Op& nx = e->ops[i + 1];
-    if (st.kind != OP_STEM || e->phys[st.conv].k != 3 || !nx.s2c32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || getenv("M355_NO_STEMFUSE")) continue;
+    if (st.kind != OP_STEM || e->phys[st.conv].k != 3 || nx.route != R_S2C32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || getenv("M355_NO_STEMFUSE")) continue;
     bool other = false;
     for (size_t j = i + 2; j < e->ops.size(); ++j)
       if (e->ops[j].in.t == st.out.t || e->ops[j].res.t == st.out.t || e->ops[j].in2.t == st.out.t) other = true;
@@ -1517,25 +1604,44 @@ std::vector<half_t> frag_pack(const half_t* rows, int Kpad, const std::vector<st
     }
   return out;
 }
-// the fragment lists of the kernels, by conv shape (empty = none of them takes this conv)
-std::vector<std::pair<int, int>> frag_list(int k, int cin, int cout) {
+// [32-row channel block][16-deep K slice] over rows x K: the fragment list of every weights-in-registers kernel but
+// head_tail.hip's.  With rows = K = 4 n it is also proto_phase_wreg.hip's [phase][channel block][slice] of the composed phases.
+std::vector<std::pair<int, int>> frag_grid(int rows, int K) {
   std::vector<std::pair<int, int>> f;
-  // (64 -> 64 and 128 -> 128 3x3 convs had lists for conv3x3_c64r / conv3x3_c128r: measured no gain in round 3, deleted in round 4;
-  // such a conv gets fragments only when a row-slab launch uses it -- PhysConv::planes, planes_frag_pack)
-  if (k == 3 && cin == 64 && cout == 128) {              // conv3x3_s2c64: [channel block m][36 slices]
-    for (int m = 0; m < 4; ++m)
-      for (int s = 0; s < 36; ++s) f.push_back({32 * m, 16 * s});
-  } else if (k == 3 && cin == 32 && cout == 64) {               // conv_stem_c2 (model.1): [channel block][18 slices], operand row order
-    for (int m = 0; m < 2; ++m)
-      for (int s = 0; s < 18; ++s) f.push_back({32 * m, 16 * s});
-  } else if (k == 3 && cin == 32 && cout == 32) {               // c2f_c32: 18 slices
-    for (int s = 0; s < 18; ++s) f.push_back({0, 16 * s});
-  } else if (k == 1 && (cin == 128 || cin == 192 || cin == 256 || cin == 384 || cin == 512) && cout % 128 == 0 && cout <= 512) {
-    for (int cb = 0; cb < cout / 32; ++cb)                       // conv1x1_wreg: [channel block][K / 16 slices]
-      for (int s = 0; s < cin / 16; ++s) f.push_back({32 * cb, 16 * s});
-  }
+  for (int r = 0; r < rows; r += 32)
+    for (int k = 0; k < K; k += 16) f.push_back({r, k});
   return f;
 }
+
+// the fragment lists of the kernels, by conv shape (empty = none of them takes this conv)
+std::vector<std::pair<int, int>> frag_list(int k, int cin, int cout) {
+  // (64 -> 64 and 128 -> 128 3x3 convs had lists for conv3x3_c64r / conv3x3_c128r: measured no gain in round 3, deleted in round 4;
+  // such a conv gets fragments only when a row-slab launch uses it -- PhysConv::planes, planes_frag_pack)
+  const bool taken = (k == 3 && cin == 64 && cout == 128) ||                   // conv3x3_s2c64
+                     (k == 3 && cin == 32 && (cout == 64 || cout == 32)) ||    // conv_stem_c2 (model.1, operand row order), c2f_c32
+                     (k == 1 && (cin == 128 || cin == 192 || cin == 256 || cin == 384 || cin == 512) && cout % 128 == 0 && cout <= 512);   // conv1x1_wreg
+  return taken ? frag_grid(cout, k * k * cin) : std::vector<std::pair<int, int>>();
+}
+
+// head_tail.hip: the 18 fragments of a head level's block-diagonal matrix (head_tail_layout) -- box rows 0-63 over K 0-63, class
+// rows from 64 over K 64-191 (the rows behind them are coefficient rows: zero there), coefficient rows from 64 + nc over K 192-223
+std::vector<std::pair<int, int>> head_level_frags(int nc) {
+  std::vector<std::pair<int, int>> f = frag_grid(64, 64);
+  for (int sl = 0; sl < 8; ++sl) f.push_back({64, 64 + 16 * sl});
+  for (int sl = 0; sl < 2; ++sl) f.push_back({64 + nc, 192 + 16 * sl});
+  return f;
+}
+
+// device copy of a fragment-ordered weight list (allocated on first use)
+hipError_t put_frags(half_t** dst, const std::vector<half_t>& fp) {
+  const size_t bytes = fp.size() * sizeof(half_t);
+  const hipError_t st = *dst ? hipSuccess : hipMalloc((void**)dst, bytes);
+  return st != hipSuccess ? st : hipMemcpy(*dst, fp.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// the 1x1 conv in the epilogue of the kernels that hold it in registers: proto.cv3 (32 x 128, proto_phase_wreg.hip), and the
+// C2f cv1 after a stride-2 conv (64 x 64 on conv_stem_c2, 128 x 128 on conv3x3_s2c64)
+std::vector<std::pair<int, int>> epilogue_frags(int cout2, int k) { return frag_grid(cout2, k); }
 
 // ConvTranspose2d(2x2, s2, bias) followed by Conv3x3 (no activation between them) as four 2x2 phase convs over the low-resolution input
 // (see build_segment_head): fp16 rows [4 n (padded to cout_pad)][Kpad], K = (a * 2 + b) * n + cin, and the [9 border classes][n] bias table.
@@ -1711,29 +1817,10 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
     for (size_t i = 0; i < r2.size(); ++i) r2[i] = (half_t)w[i];
     HIP_TRY(e, hipMemcpy(p.w2, r2.data(), r2.size() * sizeof(half_t), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(p.bias2, bias, p.cout2 * sizeof(float), hipMemcpyHostToDevice));
-    if (p.composed && p.cout2 == 32 && p.cout == 128) {   // proto.cv3 as eight MFMA fragments (proto_phase_wreg.hip)
-      std::vector<std::pair<int, int>> fl;
-      for (int s = 0; s < 8; ++s) fl.push_back({0, 16 * s});
-      const auto fp = frag_pack(r2.data(), p.cout, fl, false);
-      if (!p.wf2) HIP_TRY(e, hipMalloc((void**)&p.wf2, fp.size() * sizeof(half_t)));
-      HIP_TRY(e, hipMemcpy(p.wf2, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    }
-    if (!p.composed && p.k == 3 && p.stride == 2 && p.cin == 32 && p.cout == 64 && p.cout2 == 64) {   // conv_stem_c2: [channel block][4 slices]
-      std::vector<std::pair<int, int>> fl;
-      for (int m = 0; m < 2; ++m)
-        for (int s = 0; s < 4; ++s) fl.push_back({32 * m, 16 * s});
-      const auto fp = frag_pack(r2.data(), p.cout, fl, false);
-      if (!p.wf2) HIP_TRY(e, hipMalloc((void**)&p.wf2, fp.size() * sizeof(half_t)));
-      HIP_TRY(e, hipMemcpy(p.wf2, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    }
-    if (!p.composed && p.k == 3 && p.stride == 2 && p.cin == 64 && p.cout == 128 && p.cout2 == 128) {   // conv3x3_s2c64: [m][8 slices]
-      std::vector<std::pair<int, int>> fl;
-      for (int m = 0; m < 4; ++m)
-        for (int s = 0; s < 8; ++s) fl.push_back({32 * m, 16 * s});
-      const auto fp = frag_pack(r2.data(), p.cout, fl, false);
-      if (!p.wf2) HIP_TRY(e, hipMalloc((void**)&p.wf2, fp.size() * sizeof(half_t)));
-      HIP_TRY(e, hipMemcpy(p.wf2, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    }
+    const bool wreg = p.composed ? (p.cout2 == 32 && p.cout == 128)   // proto_phase_wreg.hip
+                                 : (p.k == 3 && p.stride == 2 && ((p.cin == 32 && p.cout == 64 && p.cout2 == 64) ||      // conv_stem_c2
+                                                                  (p.cin == 64 && p.cout == 128 && p.cout2 == 128)));   // conv3x3_s2c64
+    if (wreg) HIP_TRY(e, put_frags(&p.wf2, frag_pack(r2.data(), p.cout, epilogue_frags(p.cout2, p.cout), false)));
     e->conv_loaded[idx] = true;
     return M355_OK;
   }
@@ -1753,15 +1840,7 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
     compose_proto_phases(n, p.h_wt.data(), p.h_bt.data(), p.h_w3.data(), p.h_b3.data(), p.cout_pad, p.Kpad, rows, btab);
     HIP_TRY(e, hipMemcpy(p.w, rows.data(), rows.size() * sizeof(half_t), hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(p.bias, btab.data(), btab.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (n == 128) {   // fragment-ordered copy [phase][channel block][32 slices] for proto_phase_wreg.hip
-      std::vector<std::pair<int, int>> fl;
-      for (int q = 0; q < 4; ++q)
-        for (int mb = 0; mb < 4; ++mb)
-          for (int s = 0; s < 32; ++s) fl.push_back({q * 128 + 32 * mb, 16 * s});
-      const auto fp = frag_pack(rows.data(), p.Kpad, fl, false);
-      if (!p.wf) HIP_TRY(e, hipMalloc((void**)&p.wf, fp.size() * sizeof(half_t)));
-      HIP_TRY(e, hipMemcpy(p.wf, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-    }
+    if (n == 128) HIP_TRY(e, put_frags(&p.wf, frag_pack(rows.data(), p.Kpad, frag_grid(4 * n, 4 * n), false)));   // proto_phase_wreg.hip
     return M355_OK;
   }
   if (p.groups > 1) {   // depthwise 3x3 (dwconv3x3.hip, psa_attn.hip's pe): (C,1,3,3) -> [9][C] fp16
@@ -1799,27 +1878,14 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
     HIP_TRY(e, hipMemcpy(p.w + (size_t)row0 * p.Kpad, rows.data(), rows.size() * sizeof(half_t),
                          hipMemcpyHostToDevice));
     HIP_TRY(e, hipMemcpy(p.bias + row0, bias, ci.cout * sizeof(float), hipMemcpyHostToDevice));
-    if (p.diag && p.logical.size() == 3 && p.cin == 224 && p.cout == 64 + e->nc + e->nm && e->nm == 32 && e->nc <= 32 &&
-        e->convs[p.logical[0]].cin == 64 && e->convs[p.logical[1]].cin == 128) {
-      // head level (head_tail.hip): once its three convs are here, the 18 MFMA fragments of the block-diagonal matrix --
-      // box rows 0-63 over K 0-63, class rows from 64 over K 64-191 (the rows behind them are coefficient rows: zero there),
-      // coefficient rows from 64 + nc over K 192-223
+    if (head_tail_layout(e, p)) {   // head level (head_tail.hip): the fragments, once its three convs are here
       bool all = true;
       for (int li : p.logical) all = all && (li == idx || e->conv_loaded[li]);
-      if (all) {
-        const int rows_pad = conv_cout_pad(p.cout);
+      const int rows_pad = conv_cout_pad(p.cout);
+      if (all && 64 + e->nc + 32 <= rows_pad) {
         std::vector<half_t> full((size_t)rows_pad * p.Kpad);
         HIP_TRY(e, hipMemcpy(full.data(), p.w, full.size() * sizeof(half_t), hipMemcpyDeviceToHost));
-        std::vector<std::pair<int, int>> fl;
-        for (int blk = 0; blk < 2; ++blk)
-          for (int sl = 0; sl < 4; ++sl) fl.push_back({32 * blk, 16 * sl});
-        for (int sl = 0; sl < 8; ++sl) fl.push_back({64, 64 + 16 * sl});
-        for (int sl = 0; sl < 2; ++sl) fl.push_back({64 + e->nc, 192 + 16 * sl});
-        if (64 + e->nc + 32 <= rows_pad) {
-          const auto fp = frag_pack(full.data(), p.Kpad, fl, false);
-          if (!p.wf) HIP_TRY(e, hipMalloc((void**)&p.wf, fp.size() * sizeof(half_t)));
-          HIP_TRY(e, hipMemcpy(p.wf, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-        }
+        HIP_TRY(e, put_frags(&p.wf, frag_pack(full.data(), p.Kpad, head_level_frags(e->nc), false)));
       }
     }
     if (p.planes && ci.k == 3 && p.cin % 32 == 0 && !p.diag && p.l3 < 0) {   // K-loop fragment order of the row-slab kernels, channel blocks padded with zero rows
@@ -1829,22 +1895,14 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
         const int cbl = (p.cout + 63) / 64 * 2;
         std::vector<half_t> padded((size_t)cbl * 32 * p.Kpad, (half_t)0.f);
         HIP_TRY(e, hipMemcpy(padded.data(), p.w, (size_t)p.cout * p.Kpad * sizeof(half_t), hipMemcpyDeviceToHost));
-        const auto fp = planes_frag_pack(padded.data(), p.Kpad, p.cin, cbl);
-        if (!p.wf) HIP_TRY(e, hipMalloc((void**)&p.wf, fp.size() * sizeof(half_t)));
-        HIP_TRY(e, hipMemcpy(p.wf, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
+        HIP_TRY(e, put_frags(&p.wf, planes_frag_pack(padded.data(), p.Kpad, p.cin, cbl)));
       }
     } else if ((p.logical.size() == 1 || (p.l3 >= 0 && !p.composed && idx == p.logical[0])) && !p.diag && row0 == 0) {   // fragment-ordered copies for the weights-in-registers kernels
       const auto fl = frag_list(ci.k, ci.cin, ci.cout);
       if (!fl.empty()) {
         const bool stem_pair = ci.k == 3 && ci.cin == 32 && ci.cout == 64;   // its accumulators feed the 1x1's MFMAs directly
-        const auto fp = frag_pack(rows.data(), p.Kpad, fl, stem_pair);
-        if (!p.wf) HIP_TRY(e, hipMalloc((void**)&p.wf, fp.size() * sizeof(half_t)));
-        HIP_TRY(e, hipMemcpy(p.wf, fp.data(), fp.size() * sizeof(half_t), hipMemcpyHostToDevice));
-        if (ci.k == 3 && ci.cin == 32 && !stem_pair) {
-          const auto fo = frag_pack(rows.data(), p.Kpad, fl, true);
-          if (!p.wf2) HIP_TRY(e, hipMalloc((void**)&p.wf2, fo.size() * sizeof(half_t)));
-          HIP_TRY(e, hipMemcpy(p.wf2, fo.data(), fo.size() * sizeof(half_t), hipMemcpyHostToDevice));
-        }
+        HIP_TRY(e, put_frags(&p.wf, frag_pack(rows.data(), p.Kpad, fl, stem_pair)));
+        if (ci.k == 3 && ci.cin == 32 && !stem_pair) HIP_TRY(e, put_frags(&p.wf2, frag_pack(rows.data(), p.Kpad, fl, true)));
       }
     }
   }
@@ -1859,7 +1917,6 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
   for (size_t i = 0; i < e->conv_loaded.size(); ++i)
     if (!e->conv_loaded[i]) return e->fail(M355_ERR_STATE, std::string("weights not set for ") + e->convs[i].name);
   hipStream_t s_main = (hipStream_t)stream;
-  const int rw = 64 + e->nc + e->nm;
   // head levels as conv + decode launches (head_tail.hip): all three or none.  The kernel's 31-bit byte-offset bound is reached by the
   // stride-8 level first (batch >= 749 at 640 x 640); a per-level choice would leave the decode launch to overwrite the rows
   // the other two levels had already written with whatever the raw buffer holds.
@@ -1868,12 +1925,8 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
     bool all = true;
     for (const Op& op : e->ops) {
       if (!op.headtail) continue;
-      const PhysConv& p = e->phys[op.conv];
-      const Tensor& ti = e->tensors[op.in.t];
-      HeadTailArgs ha{};
-      ha.x = ti.p; ha.ldx = ti.C; ha.M = (long)B * ti.H * ti.W; ha.HW = ti.H * ti.W; ha.W = ti.W;
-      ha.nc = e->nc; ha.nm = e->nm; ha.wf = p.wf; ha.bias = p.bias; ha.preds = d_preds;
-      if (!p.wf || !head_tail_ok(ha) || (e->headtail_maxm > 0 && ha.M > e->headtail_maxm)) all = false;
+      const HeadTailArgs ha = head_tail_args(e, op, B, d_preds);
+      if (!ha.wf || !head_tail_ok(ha) || (e->headtail_maxm > 0 && ha.M > e->headtail_maxm)) all = false;
     }
     e->headtail_active = all;
   }
@@ -1900,8 +1953,8 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
     switch (op.kind) {
       case OP_STEM: {
         const PhysConv& p = e->phys[op.conv];
-        const Tensor& to = e->tensors[op.out.t];
         if (p.k == 6) {
+          const Tensor& to = e->tensors[op.out.t];
           Stem6Args a{};
           a.x = (const uint8_t*)d_in + (long)b0 * op.Hi * op.Wi * 3; a.B = Bq; a.H = op.Hi; a.W = op.Wi;
           a.w = p.w; a.bias = p.bias; a.C0 = p.cout;
@@ -1910,108 +1963,20 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
           rc = launch_stem6(a, s);
           break;
         }
-        StemArgs a{};
-        a.x = (const uint8_t*)d_in + (long)b0 * op.Hi * op.Wi * 3; a.B = Bq; a.H = op.Hi; a.W = op.Wi;
-        a.w16 = (const half_t*)p.stem_w; a.bias = p.bias;
-        a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.Cout = p.cout;
-        a.y = to.p + op.out.off + b0 * a.y_bstride;
-        rc = launch_stem(a, s);
-        break;
-      }
-      case OP_PHASE: {
-        const PhysConv& p = e->phys[op.conv];
-        const Tensor& ti = e->tensors[op.in.t];
-        ConvArgs a{};
-        a.x = ti.p + op.in.off; a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C;
-        a.Hi = ti.H; a.Wi = ti.W; a.Cin = p.cin;
-        a.w = p.w; a.Kpad = p.Kpad; a.bias = p.bias; a.zero = e->zero; a.act = p.act;
-        a.ksize = 2; a.stride = 1; a.pad = 0; a.phase = 1;
-        a.Ho = ti.H; a.Wo = ti.W; a.Cout = 4 * p.cout; a.convt_co = p.cout;
-        if (p.l3 >= 0) {
-          a.y = d_protos; a.y_bstride = (long)e->proto_h * e->proto_w * e->nm; a.ldy = e->nm;
-          a.w2 = p.w2; a.bias2 = p.bias2; a.cout2 = p.cout2;
-        } else {
-          const Tensor& to = e->tensors[op.out.t];
-          a.y = to.p + op.out.off; a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C;
-        }
-        a.M = Bq * a.Ho * a.Wo;
-        a.wf = p.wf; a.wf2 = p.wf2;
-        if (b0) a.x += b0 * a.x_bstride;
-        rc = (op.protor && proto_phase_wreg_ok(a)) ? launch_proto_phase_wreg(a, s) : launch_conv_igemm(a, op.tile, s);
+        rc = launch_stem(stem_args(e, op, Bq, b0, d_in), s);
         break;
       }
       case OP_CONV:
-      case OP_CONVT: {
-        const PhysConv& p = e->phys[op.conv];
-        const Tensor& ti = e->tensors[op.in.t];
-        ConvArgs a{};
-        a.x = ti.p + op.in.off; a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C;
-        a.Hi = ti.H; a.Wi = ti.W; a.Cin = p.cin;
-        a.w = p.w; a.Kpad = p.Kpad; a.bias = p.bias; a.wf = p.wf;
-        a.zero = e->zero;
-        a.act = p.act;
-        if (op.kind == OP_CONVT) {
-          const Tensor& to = e->tensors[op.out.t];
-          a.ksize = 1; a.stride = 1; a.pad = 0;
-          a.Ho = ti.H; a.Wo = ti.W; a.Cout = 4 * p.cout; a.convt_co = p.cout;
-          a.y = to.p + op.out.off; a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C;
-        } else {
-          a.ksize = p.k; a.stride = p.stride; a.pad = p.k / 2;
-          a.Ho = (ti.H + 2 * a.pad - p.k) / p.stride + 1;
-          a.Wo = (ti.W + 2 * a.pad - p.k) / p.stride + 1;
-          a.Cout = p.cout;
-          if (op.out_ext == 0) {
-            const Tensor& to = e->tensors[op.out.t];
-            a.y = to.p + op.out.off; a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C;
-          } else if (op.out_ext == 1) {
-            a.y = e->raw + (long)op.level_off * rw + op.raw_off;
-            a.y_bstride = (long)e->A * rw; a.ldy = rw; a.out_f32 = 1;
-          } else {
-            a.y = d_protos; a.y_bstride = (long)e->proto_h * e->proto_w * e->nm; a.ldy = e->nm;
-          }
-        }
-        if (op.in2.t >= 0) {
-          const Tensor& t2 = e->tensors[op.in2.t];
-          a.x2 = t2.p + op.in2.off; a.x2_bstride = (long)t2.H * t2.W * t2.C; a.ldx2 = t2.C; a.csplit = op.in2.c;
-        }
-        if (op.res.t >= 0) {
-          const Tensor& tr = e->tensors[op.res.t];
-          a.res = tr.p + op.res.off; a.r_bstride = (long)tr.H * tr.W * tr.C; a.ldr = tr.C;
-        }
-        a.M = Bq * a.Ho * a.Wo;
-        if (b0) {   // sub-batch: every operand starts b0 images in (external outputs never are in the sub-batched segment)
-          a.x += b0 * a.x_bstride;
-          if (op.out_ext == 0) a.y = (half_t*)a.y + b0 * a.y_bstride;
-          if (a.x2) a.x2 += b0 * a.x2_bstride;
-          if (a.res) a.res += b0 * a.r_bstride;
-        }
-        if (op.decode) {
-          a.dec_preds = d_preds; a.dec_A = e->A; a.dec_level_off = op.level_off; a.dec_nc = e->nc; a.dec_nm = e->nm;
-          a.dec_keep_raw = e->keep_raw; a.dec_stride = (float)(e->desc.in_h / a.Ho);
-        }
-        if (op.kind == OP_CONV && e->phys[op.conv].l3 >= 0) {   // following 1x1 conv in this launch's epilogue
-          const PhysConv& pf = e->phys[op.conv];
-          a.w2 = pf.w2; a.bias2 = pf.bias2; a.cout2 = pf.cout2; a.wf2 = pf.wf2;
-        }
+      case OP_CONVT:
+      case OP_PHASE: {
         if (op.headtail && e->headtail_active && !b0) {   // conv + decode of this level in one launch
-          HeadTailArgs ha{};
-          ha.x = ti.p; ha.ldx = ti.C; ha.M = (long)Bq * ti.H * ti.W; ha.HW = ti.H * ti.W; ha.W = ti.W;
-          ha.stride = (float)(e->desc.in_h / ti.H);
-          ha.A = e->A; ha.level_off = op.level_off; ha.nc = e->nc; ha.nm = e->nm;
-          ha.wf = p.wf; ha.bias = p.bias; ha.preds = d_preds;
-          rc = launch_head_tail(ha, s);   // (eligibility was checked for all three levels at the top of this forward)
+          rc = launch_head_tail(head_tail_args(e, op, Bq, d_preds), s);   // (eligibility was checked for all three levels at the top of this forward)
           break;
         }
-        a.tileq = knobs().static_tiles ? nullptr : e->tileq + 4 * oi;
+        ConvArgs a = conv_args(e, op, Bq, b0, d_preds, d_protos);
+        if (op.kind != OP_PHASE) a.tileq = knobs().static_tiles ? nullptr : e->tileq + 4 * oi;
         if (op.stemfuse >= 0) {
-          const Op& so = e->ops[op.stemfuse];
-          const PhysConv& sp = e->phys[so.conv];
-          const Tensor& sto = e->tensors[so.out.t];
-          StemArgs sa{};
-          sa.x = (const uint8_t*)d_in + (long)b0 * so.Hi * so.Wi * 3; sa.B = Bq; sa.H = so.Hi; sa.W = so.Wi;
-          sa.w16 = (const half_t*)sp.stem_w; sa.bias = sp.bias;
-          sa.y_bstride = (long)sto.H * sto.W * sto.C; sa.ldy = sto.C; sa.Cout = sp.cout;
-          sa.y = sto.p + so.out.off + b0 * sa.y_bstride;
+          const StemArgs sa = stem_args(e, e->ops[op.stemfuse], Bq, b0, d_in);
           const bool stem2 = getenv("M355_NO_STEM2") == nullptr;  // two-team form (conv_stem_c2.hip, the default); read per launch: tests toggle it
           if (stem2 && stem_s2c32_v2_ok(a, sa)) {
             rc = launch_stem_s2c32_v2(a, sa, s);
@@ -2024,22 +1989,25 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
           rc = launch_stem(sa, s);            // not eligible after all (shape): the two launches
           if (rc != 0) break;
         }
-        if (op.tile == TILE_PLANES) {
-          PlanesArgs pa{};
-          pa.x = a.x; pa.x_bstride = a.x_bstride; pa.ldx = a.ldx; pa.H = a.Hi; pa.W = a.Wi; pa.B = Bq; pa.Cin = p.cin; pa.Cout = p.cout;
-          pa.wfb = p.wf; pa.cblocks_b = (p.cout + 63) / 64 * 2; pa.bb = p.bias; pa.act = p.act; pa.stride = p.stride;
-          pa.y = (half_t*)a.y; pa.y_bstride = a.y_bstride; pa.ldy = a.ldy;
-          pa.res = a.res; pa.r_bstride = a.r_bstride; pa.ldr = a.ldr;
-          rc = (p.wf && conv3x3_planes_ok(pa)) ? launch_conv3x3_planes(pa, s) : (p.stride == 1 ? (conv3x3_slab_ok(a) ? launch_conv3x3_slab(a, s) : launch_conv3x3_halo(a, 0, s)) : launch_conv_igemm(a, TILE_AUTO, s));
-          break;
+        // the fused and specialised routes fall back to the kernels they replaced where THIS call's shape is not eligible
+        // (e.g. a pixel count that is not a multiple of the kernel's tile although max_batch's was)
+        switch (op.route) {
+          case R_IGEMM: rc = launch_conv_igemm(a, op.tile, s); break;
+          case R_HALO: rc = launch_conv3x3_halo(a, 0, s); break;
+          case R_C32: rc = launch_conv3x3_c32(a, s); break;
+          case R_SLAB: rc = launch_conv3x3_slab(a, s); break;
+          case R_W1: rc = conv1x1_wreg_ok(a) ? launch_conv1x1_wreg(a, s) : launch_conv_igemm(a, TILE_AUTO, s); break;
+          case R_PLANES: {
+            const PlanesArgs pa = planes_args(e, op, Bq, b0);
+            rc = (pa.wfb && conv3x3_planes_ok(pa)) ? launch_conv3x3_planes(pa, s)
+                 : a.stride == 2 ? launch_conv_igemm(a, TILE_AUTO, s)
+                 : conv3x3_slab_ok(a) ? launch_conv3x3_slab(a, s) : launch_conv3x3_halo(a, 0, s);
+            break;
+          }
+          case R_S2C32: rc = conv_s2c32_cv1_ok(a) ? launch_conv_s2c32_cv1(a, s) : launch_conv_igemm(a, op.tile, s); break;
+          case R_S2C64: rc = conv_s2c64_cv1_ok(a) ? launch_conv_s2c64_cv1(a, s) : launch_conv_igemm(a, op.tile, s); break;
+          case R_PROTOR: rc = proto_phase_wreg_ok(a) ? launch_proto_phase_wreg(a, s) : launch_conv_igemm(a, op.tile, s); break;
         }
-        rc = (op.s2c32 && conv_s2c32_cv1_ok(a)) ? launch_conv_s2c32_cv1(a, s)
-             : (op.s2c64 && conv_s2c64_cv1_ok(a)) ? launch_conv_s2c64_cv1(a, s)
-             : (op.tile == TILE_HALO) ? launch_conv3x3_halo(a, 0, s)
-             // (the pixel count of THIS call may not be a multiple of the kernel's tile although max_batch's was: im2col then)
-             : (op.tile == TILE_W1) ? (conv1x1_wreg_ok(a) ? launch_conv1x1_wreg(a, s) : launch_conv_igemm(a, TILE_AUTO, s))
-             : (op.tile == TILE_C32 ? launch_conv3x3_c32(a, s)
-                                    : (op.tile == TILE_SLAB ? launch_conv3x3_slab(a, s) : launch_conv_igemm(a, op.tile, s)));
         break;
       }
       case OP_C2F32: {
@@ -2058,36 +2026,20 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
         break;
       }
       case OP_PAIR: {
-        const Tensor& ti = e->tensors[op.in.t];
-        const Tensor& to = e->tensors[op.out.t];
-        const PhysConv &pa = e->phys[op.conv], &pb = e->phys[op.conv2];
-        PlanesArgs a{};
-        a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C; a.H = ti.H; a.W = ti.W; a.B = Bq; a.Cin = pa.cin; a.Cout = pb.cout;
-        a.x = ti.p + op.in.off + b0 * a.x_bstride;
-        a.wfa = pa.wf; a.wfb = pb.wf; a.cblocks_a = (pa.cout + 63) / 64 * 2; a.cblocks_b = (pb.cout + 63) / 64 * 2;
-        a.ba = pa.bias; a.bb = pb.bias; a.act = 1; a.stride = 1;
-        a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C;
-        a.y = to.p + op.out.off + b0 * a.y_bstride;
-        if (op.shortcut) { a.res = a.x; a.r_bstride = a.x_bstride; a.ldr = a.ldx; }
+        const PlanesArgs a = planes_args(e, op, Bq, b0);
         if (bneck_pair_ok(a)) {
           rc = launch_bneck_pair(a, s);
           break;
         }
         // two launches through the hidden tensor (a batch whose buffers exceed the kernel's 31-bit offsets)
-        const Tensor& tt = e->tensors[op.out2.t];
         for (int half = 0; half < 2 && rc == 0; ++half) {
-          const PhysConv& p = half ? pb : pa;
-          ConvArgs c{};
-          const Tensor& ci_ = half ? tt : ti;
-          const Tensor& co_ = half ? to : tt;
-          const int ioff = half ? op.out2.off : op.in.off, ooff = half ? op.out.off : op.out2.off;
-          c.x = ci_.p + ioff; c.x_bstride = (long)ci_.H * ci_.W * ci_.C; c.ldx = ci_.C;
-          c.Hi = ti.H; c.Wi = ti.W; c.Cin = p.cin; c.w = p.w; c.Kpad = p.Kpad; c.bias = p.bias; c.zero = e->zero; c.act = 1;
-          c.ksize = 3; c.stride = 1; c.pad = 1; c.Ho = ti.H; c.Wo = ti.W; c.Cout = p.cout;
-          c.y = co_.p + ooff; c.y_bstride = (long)co_.H * co_.W * co_.C; c.ldy = co_.C;
-          c.M = Bq * c.Ho * c.Wo;
-          c.x += b0 * c.x_bstride; c.y = (half_t*)c.y + b0 * c.y_bstride;
-          if (half && op.shortcut) { c.res = a.x; c.r_bstride = a.x_bstride; c.ldr = a.ldx; }
+          Op h{};
+          h.kind = OP_CONV;
+          h.conv = half ? op.conv2 : op.conv;
+          h.in = half ? op.out2 : op.in;
+          h.out = half ? op.out : op.out2;
+          if (half) h.res = op.res;
+          const ConvArgs c = conv_args(e, h, Bq, b0, nullptr, nullptr);
           rc = conv3x3_halo_ok(c) ? launch_conv3x3_halo(c, 0, s) : launch_conv_igemm(c, TILE_AUTO, s);
         }
         break;
@@ -2545,8 +2497,8 @@ int m355_bneck_pair_fwd(const void* d_x, int B, int H, int W, int C, int ldx, co
   return M355_OK;
 }
 
-// ---- per-op parity entries of the round-3 fused launches (each: host weights packed exactly as m355_set_conv_weights packs them,
-// one launch, stream synchronised) ---------------------------------------------------------------------------------------------
+// ---- per-op parity entries of the round-3 fused launches (each: host weights packed as m355_set_conv_weights packs them, through
+// the same fragment lists, one launch, stream synchronised) ---------------------------------------------------------------------
 }  // extern "C" (C++ helpers follow)
 namespace {
 struct DevBuf {   // device allocations of one entry call, freed on scope exit
@@ -2590,14 +2542,11 @@ int m355_s2c64_cv1_fwd(const void* d_x, int B, int H, int W, const float* h_w3, 
   std::vector<half_t> rows((size_t)conv_cout_pad(128) * kp, (half_t)0.f);
   pack_conv_rows(h_w3, 128, 64, 3, kp, 0, rows);
   const std::vector<half_t> r2 = to_half_vec(h_w1, (size_t)128 * 128);
-  std::vector<std::pair<int, int>> fl2;
-  for (int m = 0; m < 4; ++m)
-    for (int sl = 0; sl < 8; ++sl) fl2.push_back({32 * m, 16 * sl});
   DevBuf d;
   ConvArgs a{};
   a.x = (const half_t*)d_x; a.x_bstride = (long)H * W * 64; a.ldx = 64; a.Hi = H; a.Wi = W; a.Cin = 64;
   a.w = d.put(rows); a.Kpad = kp; a.wf = d.put(frag_pack(rows.data(), kp, frag_list(3, 64, 128), false));
-  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 128, fl2, false));
+  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 128, epilogue_frags(128, 128), false));
   std::vector<float> b3(conv_cout_pad(128), 0.f), b1(128);
   for (int i = 0; i < 128; ++i) { b3[i] = h_b3[i]; b1[i] = h_b1[i]; }
   a.bias = d.put(b3); a.bias2 = d.put(b1); a.cout2 = 128; a.zero = (const half_t*)d.raw(256);
@@ -2620,9 +2569,6 @@ int m355_stem_s2c32_cv1_fwd(const void* d_in_u8, int B, int H, int W, const floa
   std::vector<half_t> rows((size_t)conv_cout_pad(64) * kp, (half_t)0.f);
   pack_conv_rows(h_w1, 64, 32, 3, kp, 0, rows);
   const std::vector<half_t> r2 = to_half_vec(h_w2, (size_t)64 * 64);
-  std::vector<std::pair<int, int>> fl2;
-  for (int m = 0; m < 2; ++m)
-    for (int sl = 0; sl < 4; ++sl) fl2.push_back({32 * m, 16 * sl});
   DevBuf d;
   StemArgs st{};
   st.x = (const uint8_t*)d_in_u8; st.B = B; st.H = H; st.W = W; st.w16 = d.put(sw);
@@ -2631,7 +2577,7 @@ int m355_stem_s2c32_cv1_fwd(const void* d_in_u8, int B, int H, int W, const floa
   ConvArgs a{};
   a.x = st.y; a.x_bstride = st.y_bstride; a.ldx = 32; a.Hi = H / 2; a.Wi = W / 2; a.Cin = 32;
   a.w = d.put(rows); a.Kpad = kp; a.wf = d.put(frag_pack(rows.data(), kp, frag_list(3, 32, 64), true));
-  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 64, fl2, false));
+  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 64, epilogue_frags(64, 64), false));
   std::vector<float> b1(conv_cout_pad(64), 0.f);
   for (int i = 0; i < 64; ++i) b1[i] = h_b1[i];
   a.bias = d.put(b1); a.bias2 = d.put(std::vector<float>(h_b2, h_b2 + 64)); a.cout2 = 64; a.zero = (const half_t*)d.raw(256);
@@ -2652,17 +2598,12 @@ int m355_proto_phase_fwd(const void* d_x, int B, int H, int W, const float* h_wt
   std::vector<half_t> rows;
   std::vector<float> btab;
   compose_proto_phases(n, h_wt, h_bt, h_w3, h_b3, cp, kp, rows, btab);
-  std::vector<std::pair<int, int>> fl, fl2;
-  for (int q = 0; q < 4; ++q)
-    for (int mb = 0; mb < 4; ++mb)
-      for (int sl = 0; sl < 32; ++sl) fl.push_back({q * 128 + 32 * mb, 16 * sl});
-  for (int sl = 0; sl < 8; ++sl) fl2.push_back({0, 16 * sl});
   const std::vector<half_t> r2 = to_half_vec(h_wc, (size_t)32 * 128);
   DevBuf d;
   ConvArgs a{};
   a.x = (const half_t*)d_x; a.x_bstride = (long)H * W * n; a.ldx = n; a.Hi = H; a.Wi = W; a.Cin = n;
-  a.w = d.put(rows); a.Kpad = kp; a.bias = d.put(btab); a.wf = d.put(frag_pack(rows.data(), kp, fl, false));
-  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 128, fl2, false)); a.bias2 = d.put(std::vector<float>(h_bc, h_bc + 32)); a.cout2 = 32;
+  a.w = d.put(rows); a.Kpad = kp; a.bias = d.put(btab); a.wf = d.put(frag_pack(rows.data(), kp, frag_grid(4 * n, 4 * n), false));
+  a.w2 = d.put(r2); a.wf2 = d.put(frag_pack(r2.data(), 128, epilogue_frags(32, 128), false)); a.bias2 = d.put(std::vector<float>(h_bc, h_bc + 32)); a.cout2 = 32;
   a.zero = (const half_t*)d.raw(256); a.act = 1; a.ksize = 2; a.stride = 1; a.pad = 0; a.phase = 1;
   a.Ho = H; a.Wo = W; a.Cout = 4 * n; a.convt_co = n; a.w_rows = cp;
   a.y = d_y; a.y_bstride = (long)4 * H * W * 32; a.ldy = 32; a.M = B * H * W;
@@ -2679,11 +2620,6 @@ int m355_head_tail_fwd(const void* d_x, int B, int H, int W, int nc, float strid
   pack_conv_rows(h_w2, 64, 64, 1, kp, 0, rows, 0);           // box rows over K 0 .. 63
   pack_conv_rows(h_w3, nc, 128, 1, kp, 64, rows, 64);        // class rows over K 64 .. 191
   pack_conv_rows(h_w4, 32, 32, 1, kp, 64 + nc, rows, 192);   // coefficient rows over K 192 .. 223
-  std::vector<std::pair<int, int>> fl;
-  for (int blk = 0; blk < 2; ++blk)
-    for (int sl = 0; sl < 4; ++sl) fl.push_back({32 * blk, 16 * sl});
-  for (int sl = 0; sl < 8; ++sl) fl.push_back({64, 64 + 16 * sl});
-  for (int sl = 0; sl < 2; ++sl) fl.push_back({64 + nc, 192 + 16 * sl});
   if (64 + nc + 32 > rows_pad) return set_err(M355_ERR_INVALID, "row padding");
   std::vector<float> bias(rows_pad, 0.f);
   for (int i = 0; i < 64; ++i) bias[i] = h_b2[i];
@@ -2693,7 +2629,7 @@ int m355_head_tail_fwd(const void* d_x, int B, int H, int W, int nc, float strid
   HeadTailArgs ha{};
   ha.x = (const half_t*)d_x; ha.ldx = 224; ha.M = (long)B * H * W; ha.HW = H * W; ha.W = W; ha.stride = stride;
   ha.A = A; ha.level_off = level_off; ha.nc = nc; ha.nm = 32;
-  ha.wf = d.put(frag_pack(rows.data(), kp, fl, false)); ha.bias = d.put(bias); ha.preds = d_preds;
+  ha.wf = d.put(frag_pack(rows.data(), kp, head_level_frags(nc), false)); ha.bias = d.put(bias); ha.preds = d_preds;
   if (!ha.wf || !ha.bias) return set_err(M355_ERR_HIP, "allocation failed");
   return finish_entry(head_tail_ok(ha) ? launch_head_tail(ha, s) : -1, s, "head_tail");
 }
