@@ -171,7 +171,7 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s);
 
 // Row-slab 3x3 kernels (conv3x3_planes.hip): a whole Bottleneck -- y = [x +] act(conv3x3(act(conv3x3(x, wa) + ba), wb) + bb), hidden
 // tensor in LDS -- or one 3x3 conv y = act(conv3x3(x, wb) + bb) [+ res].  Weights as MFMA A fragments in K-loop order
-// (planes_frag_pack in engine.hip): fragment ((cb * NP + p) * 9 + tap) * 2 + s = rows 32 cb .. + 31 (plain row permutation),
+// (planes_frag_pack in weight_pack.hip): fragment ((cb * NP + p) * 9 + tap) * 2 + s = rows 32 cb .. + 31 (plain row permutation),
 // K = tap * Cin + 32 p + 16 s .. + 15; 1 KiB each, lane-linear.
 struct PlanesArgs {
   const half_t* x; long x_bstride; int ldx;      // NHWC fp16 input slice (Cin channels)

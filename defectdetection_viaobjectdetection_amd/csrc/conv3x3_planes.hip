@@ -30,7 +30,7 @@
 // each (accumulators: 16 x NPB VGPRs).  K loop: PHASE = one input plane (32 channels) = 9 taps x 2 MFMA slices of K = 16 for every
 // pixel block of the wave, pixel-block-major (the 18 MFMAs of a block back to back on one accumulator).
 //   * WEIGHTS never touch LDS: the host packs them as MFMA A fragments in K-loop order [channel block][plane][tap][slice] (1 KiB
-//     each, lane-linear: planes_frag_pack in engine.hip) and a wave loads the 18 fragments of the NEXT phase straight into its A
+//     each, lane-linear: planes_frag_pack in weight_pack.hip) and a wave loads the 18 fragments of the NEXT phase straight into its A
 //     registers through a per-phase buffer descriptor, each right after its last use in the current phase; they are L2 hits for all
 //     blocks but the first.  No weight stage, no weight barrier, no ds_read for the A operand.
 //   * B fragments (activations) come from the plane by ds_read_b128 through a register FIFO of FQ = 9 slots, FD = 8 reads in flight.

@@ -7,14 +7,14 @@ activations, fp32 accumulation.  ``yolov8_seg_oracle.SegmentationModel`` is the 
 (what upstream's CPU path computes); this module takes such a model and applies the storage format AT THE POINTS
 WHERE THE ENGINE STORES -- nothing else changes, every sum is still PyTorch-CPU fp32:
 
-  * Conv+BN: BN folded in fp64, rounded to fp32, then to fp16 (``spec.fold_bn`` + ``engine.hip:pack_conv_rows``);
+  * Conv+BN: BN folded in fp64, rounded to fp32, then to fp16 (``spec.fold_bn`` + ``weight_pack.hip:pack_conv_rows``);
     bias stays fp32; ``y = fp16(silu(conv(x, w16) + b))``;
   * Bottleneck with shortcut: ``fp16(x + silu(...))`` -- ONE rounding after the residual add (conv epilogue);
   * stem: integer pixels x fp16 weights, ``* (1/255) + bias`` in fp32 (``misc_kernels.hip:stem_rows_kernel``);
   * head output convs (``cv{2,3,4}.{l}.2``): fp16 weights, fp32 bias, fp32 output (raw head map);
   * Proto: ConvTranspose2d(2x2, s2, bias) -> Conv3x3 composed on the host in fp64 into four 2x2 phase
     convolutions over the low-resolution tensor with a 3x3 border-class bias table, composed weights rounded to
-    fp16 (``engine.hip:m355_set_conv_weights``, composed branch); no rounding at the ConvTranspose output;
+    fp16 (``weight_pack.hip:compose_proto_phases``); no rounding at the ConvTranspose output;
   * max-pool, nearest upsample, concat: exact.
 
 Two uses (tests/test_engine_gpu.py, tests/test_keepset_gpu.py):
@@ -47,7 +47,7 @@ def _h(x: torch.Tensor) -> torch.Tensor:
 
 
 def _compose_proto(wt, bt, w3, b3):
-    """Weff[q] (n, n, 2, 2) per phase q = py * 2 + px, and the (3, 3, n) bias table -- engine.hip composed branch."""
+    """Weff[q] (n, n, 2, 2) per phase q = py * 2 + px, and the (3, 3, n) bias table -- weight_pack.hip:compose_proto_phases."""
     n = w3.shape[0]
     wt, w3, bt, b3 = wt.double(), w3.double(), bt.double(), b3.double()
     weff = torch.zeros(4, n, n, 2, 2, dtype=torch.float64)

@@ -2,7 +2,7 @@
 m355_conv_launch, m355_wgrad_launch, m355_bn_train_fwd_launch and m355_bn_train_bwd_launch on channel slices of larger NHWC
 buffers, against fp32/fp64 references on the same fp16 operands (tests/launch_ref.py).
 
-Every conv case names the kernel route it is meant to reach (the `_ok` predicate it satisfies in engine.hip's m355_conv_launch)
+Every conv case names the kernel route it is meant to reach (the `_ok` predicate it satisfies in op_entries.hip's m355_conv_launch)
 and checks: rc 0; the slice per element within 2^-10 |ref| + c S (c = min(2^-13, 1 / 2K)) and rel-L2 <= 1e-3; every element
 outside the output slice still the sentinel NaN, bit for bit (guard bands before / after the allocation, other channels, the
 image-stride gap)."""
