@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -534,8 +535,8 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s) {
   const int step = grid >> 3;                         // linear tile stride of a block's walk inside its XCD group
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
   // diagnostic: M355_C2F_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
-  static const int prio = getenv("M355_C2F_NOPRIO") ? 0 : 1;
-  static const char* st_path = getenv("M355_C2F_STAMPS");
+  const int prio = proc_switches().c2f_noprio ? 0 : 1;
+  const char* st_path = proc_switches().c2f_stamps;
   static unsigned long long* d_st = nullptr;
   if (st_path && !d_st) {
     if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;

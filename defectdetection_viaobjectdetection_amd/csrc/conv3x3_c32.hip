@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -187,11 +188,7 @@ bool conv3x3_c32_ok(const ConvArgs& a) {
   if (a.Cin != 32 || a.Cout != 32 || a.ldx % 8 || a.ldy % 8 || a.Kpad < 288) return false;
   if (a.Ho != a.Hi || a.Wo != a.Wi) return false;
   const long covered = (long)((a.Hi + TH - 1) / TH) * TH * ((a.Wi + TS - 1) / TS) * TS;
-  // covered / real pixels allowed, in tenths (M355_C32_WASTE): 3.0 since round 3 (was 1.3) -- the 32 -> 32 convs of the
-  // smaller head levels (40 x 40: 1.44, 20 x 20: 2.56) are latency-bound launches of a few MFLOP per CU, where empty tile area
-  // costs less than the im2col kernel's prologue: 16.5 -> 8.6 us and 16.3 -> 7.8 us at batch 32
-  static const int waste = getenv("M355_C32_WASTE") ? atoi(getenv("M355_C32_WASTE")) : 30;
-  return covered * 10 <= (long)a.Hi * a.Wi * waste;
+  return covered * 10 <= (long)a.Hi * a.Wi * proc_switches().c32_waste;   // covered / real pixels allowed, in tenths
 }
 
 int launch_conv3x3_c32(const ConvArgs& a, hipStream_t s) {
@@ -206,8 +203,7 @@ int launch_conv3x3_c32(const ConvArgs& a, hipStream_t s) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       return -2;
-    const char* ev = getenv("M355_C32_SLOTS");
-    slots = ev ? atoi(ev) : 2 * cus;
+    slots = proc_switches().c32_slots >= 0 ? proc_switches().c32_slots : 2 * cus;
     if (slots < 8) slots = 8;
     slots &= ~7;   // the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks more than one tile
   }

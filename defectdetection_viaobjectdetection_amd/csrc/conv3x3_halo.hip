@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -381,19 +382,19 @@ int conv3x3_halo_pick(const ConvArgs& a, bool no_wide, bool no_m32) {
 // variant: 0 = auto, 1 = 8 waves / 16x16 px, 2 = 4 waves / 8x16 px
 int launch_conv3x3_halo(const ConvArgs& a0, int variant, hipStream_t s) {
   ConvArgs a = a0;
-  if (knobs().no_fast_epi) a.dbg |= 256;
+  if (proc_switches().no_fast_epi) a.dbg |= 256;
   if (variant == TILE_SLAB - TILE_HALO) return launch_conv3x3_slab(a, s);
   if (!conv3x3_halo_ok(a)) return -1;
   if (variant >= TILE_M32 - TILE_HALO && variant <= TILE_M32_64x8 - TILE_HALO) return launch_conv3x3_m32(a, variant - (TILE_M32 - TILE_HALO), s);
   if (variant == 0) {
-    const int pick = conv3x3_halo_pick(a, knobs().no_wide, knobs().no_m32);
+    const int pick = conv3x3_halo_pick(a, proc_switches().no_wide, proc_switches().no_m32);
     if (pick == TILE_M32) return launch_conv3x3_m32(a, 0, s);
     if (pick == TILE_HALOWIDE) variant = 3;
   }
   if (variant == 3) return launch_conv3x3_wide(a, s);
   if (variant >= 5) return -1;   // ids 21-24 were the lean halo template (measured equal to the K-64 kernels below; removed in round 3)
   if (variant == 0) {
-    variant = knobs().halo_variant;  // measured: the 4-wave variant (two blocks per CU) wins on every layer
+    variant = proc_switches().halo_variant;  // measured: the 4-wave variant (two blocks per CU) wins on every layer
     if (variant != 1 && variant != 2) variant = 2;
   }
   if (variant == 1) {

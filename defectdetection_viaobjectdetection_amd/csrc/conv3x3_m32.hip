@@ -45,6 +45,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -420,8 +421,7 @@ int launch_m32(const ConvArgs& a, hipStream_t s) {
       int per_cu = (160 * 1024) / (i ? LDS2 : LDS1);
       if (per_cu > 2) per_cu = 2;   // two waves per SIMD: the register budget of __launch_bounds__(256, 2)
       if (per_cu < 1) per_cu = 1;
-      const char* ev = getenv("M355_M32_SLOTS");
-      slots[i] = ev ? atoi(ev) : per_cu * cus;
+      slots[i] = proc_switches().m32_slots >= 0 ? proc_switches().m32_slots : per_cu * cus;
       if (slots[i] < 8) slots[i] = 8;
       slots[i] &= ~7;               // the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     }

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -324,11 +325,9 @@ int launch_conv_s2c32_cv1(const ConvArgs& a, hipStream_t s) {
     if (slots < 8) slots = 8;
   }
   const int grid = ntiles <= slots ? ntiles : slots;
-  static const int dbg = getenv("M355_S2C32_DBG") ? atoi(getenv("M355_S2C32_DBG")) : 0;
-  // diagnostic: per-wave section cycles.  M355_S2C32_STAMPS=<file>: the LAST launch, written after a stream sync [sync];
-  // M355_S2C32_RING=<n> with it: the last n launches into a device ring, no sync, written at process exit.
-  static const char* st_path = getenv("M355_S2C32_STAMPS");
-  static const int ring = getenv("M355_S2C32_RING") ? atoi(getenv("M355_S2C32_RING")) : 0;
+  // diagnostic (M355_S2C32_STAMPS, M355_S2C32_RING): per-wave section cycles of the last launch, or of the last `ring` launches
+  static const int dbg = proc_switches().s2c32_dbg, ring = proc_switches().s2c32_ring;
+  static const char* st_path = proc_switches().s2c32_stamps;
   static unsigned long long* d_st = nullptr;
   static long launches = 0;
   static size_t per_launch = 0;

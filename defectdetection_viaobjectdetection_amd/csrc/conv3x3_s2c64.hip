@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -360,9 +361,8 @@ int launch_conv_s2c64_cv1(const ConvArgs& a, hipStream_t s) {
   const int grid = ntiles <= slots ? ntiles : slots;
   const int step = grid >> 3;                          // tiles between two visits of a block (it walks only when grid = slots, % 8 == 0)
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
-  static const int prio = getenv("M355_S2C64_PRIO") ? atoi(getenv("M355_S2C64_PRIO")) : 0;   // experiment: s_setprio(1) around the K loop
-  // diagnostic: M355_S2C64_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
-  static const char* st_path = getenv("M355_S2C64_STAMPS");
+  const int prio = proc_switches().s2c64_prio;
+  const char* st_path = proc_switches().s2c64_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
   static unsigned long long* d_st = nullptr;
   if (st_path && !d_st) {
     if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;

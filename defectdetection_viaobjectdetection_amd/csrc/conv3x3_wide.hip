@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -391,17 +392,12 @@ int launch_conv3x3_wide(const ConvArgs& a, hipStream_t s) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       return -2;
-    const char* ev = getenv("M355_WIDE_SLOTS");
-    slots = ev ? atoi(ev) : 2 * cus;
+    slots = proc_switches().wide_slots >= 0 ? proc_switches().wide_slots : 2 * cus;
     if (slots < 8) slots = 8;
     slots &= ~7;   // the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks more than one tile
   }
   const int grid = ntiles <= slots ? ntiles : slots;
-  static int stagger = -1;
-  if (stagger < 0) {
-    const char* ev = getenv("M355_WIDE_STAGGER");
-    stagger = ev ? atoi(ev) : 0;
-  }
+  const int stagger = proc_switches().wide_stagger >= 0 ? proc_switches().wide_stagger : 0;
   hipLaunchKernelGGL(conv3x3_wide_kernel, dim3(grid), dim3(256), LDS_BYTES, s, a, tiles_x, tiles_y, a.Cin / 32, ntiles,
                      ntiles > grid ? stagger : 0);
   return (int)hipGetLastError();

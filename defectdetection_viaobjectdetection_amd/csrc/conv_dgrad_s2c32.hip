@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -130,8 +131,7 @@ __global__ __launch_bounds__(256) void dgrad_s2c32_kernel(const half_t* dz, long
 }  // namespace
 
 bool dgrad_s2c32_ok(const ConvArgs& a) {
-  static const bool off = getenv("M355_NO_DGRAD_S2C32") != nullptr;
-  return !off && a.phase == 2 && a.ksize == 2 && a.convt_co == 32 && a.Cin == 64 && a.Cout == 128 && !a.res && !a.act && !a.out_f32 &&
+  return !proc_switches().no_dgrad_s2c32 && a.phase == 2 && a.ksize == 2 && a.convt_co == 32 && a.Cin == 64 && a.Cout == 128 && !a.res && !a.act && !a.out_f32 &&
          a.Kpad >= 256 && a.Kpad % 8 == 0 && a.ldx % 8 == 0 && a.ldy % 8 == 0 && a.Wo % DG_PX == 0 && a.Hi == a.Ho && a.Wi == a.Wo &&
          a.M % ((long)a.Ho * a.Wo) == 0;
 }

@@ -29,6 +29,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 
@@ -840,7 +841,7 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
   // 3-10 % from the persistent walk once they have more tiles than resident blocks (tools/conv1_sweep.py: 39.2 -> 34.2,
   // 47.4 -> 43.6, 21.1 -> 19.7 us), inside the network nothing (model.4.cv2 46.9 -> 47.8, model.15.cv2 37.9 -> 39.6 us):
   // still one tile per block for them
-  if ((a.dbg & 64) || (a.ksize == 1 && BCH <= 64 && !knobs().no_persist)) {
+  if ((a.dbg & 64) || (a.ksize == 1 && BCH <= 64 && !proc_switches().no_persist)) {
     int per_cu = (160 * 1024) / LDS;
     if (per_cu > 2) per_cu = 2;
     if (grid_x > g_num_cus * per_cu) grid_x = g_num_cus * per_cu;
@@ -851,7 +852,7 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
   int lds_bytes = LDS;
   {
     const int nb = a.convt_co > 0 ? a.convt_co : tiles_ch * BCH;
-    const bool plain = !a.w2 && !a.dec_preds && !a.phase && !a.out_f32 && MT >= 2 && !knobs().no_bias_lds;
+    const bool plain = !a.w2 && !a.dec_preds && !a.phase && !a.out_f32 && MT >= 2 && !proc_switches().no_bias_lds;
     if (plain && nb * 4 <= 8192 && (a.w_rows == 0 || nb <= a.w_rows)) {
       aa.bias_lds = nb;
       lds_bytes += nb * 4;
@@ -884,31 +885,13 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-const Knobs& knobs() {
-  static const Knobs k = [] {
-    Knobs v{};
-    v.no_fast_epi = getenv("M355_NO_FAST_EPI") != nullptr;
-    v.no_wide = getenv("M355_NO_WIDE") != nullptr;
-    v.no_m32 = getenv("M355_NO_M32") != nullptr;
-    v.no_bias_lds = getenv("M355_NO_BIAS_LDS") != nullptr;
-    v.static_tiles = getenv("M355_STATIC_TILES") != nullptr;   // persistent kernels: static tile walk instead of the queue
-    v.no_persist = getenv("M355_NO_PERSIST") != nullptr;
-    v.stem_gather = getenv("M355_STEM_GATHER") != nullptr;
-    v.persist = getenv("M355_PERSIST") ? atoi(getenv("M355_PERSIST")) : 0;
-    v.halo_variant = getenv("M355_HALO_VARIANT") ? atoi(getenv("M355_HALO_VARIANT")) : 2;
-    v.smallm = getenv("M355_SMALLM") ? atoi(getenv("M355_SMALLM")) : 300;
-    return v;
-  }();
-  return k;
-}
-
 int conv_cout_pad(int cout) { return (cout + 127) / 128 * 128; }
 int conv_kpad(int cin, int ksize) { return (cin * ksize * ksize + BK - 1) / BK * BK; }
 
 int conv_pick_tile(int cout, long M) {
   // small pixel counts (20x20 maps at batch 32): a 128x128 grid leaves most CUs with <= 1 block; halve the
   // channel tile to double the number of blocks
-  const long thr = knobs().smallm;  // measured sweep 0/300/600/1000 on MI355X: 300 is best
+  const long thr = proc_switches().smallm;  // measured sweep 0/300/600/1000 on MI355X: 300 is best
   if (cout > 64 && M * ((cout + 127) / 128) / 128 < thr) return TILE_64x128;
   if (cout > 64) return TILE_128x128;
   if (cout > 32) return TILE_64x128;
@@ -941,8 +924,8 @@ bool conv_forced_tile_extent(int tile, int cout, int* bch, int* bpx) {
 
 int launch_conv_igemm(const ConvArgs& a0, int force_tile, hipStream_t s) {
   ConvArgs a = a0;
-  if (knobs().no_fast_epi) a.dbg |= 256;
-  if ((knobs().persist & (a.ksize == 1 ? 1 : 2)) && a.phase != 3) a.dbg |= 64;
+  if (proc_switches().no_fast_epi) a.dbg |= 256;
+  if ((proc_switches().persist & (a.ksize == 1 ? 1 : 2)) && a.phase != 3) a.dbg |= 64;
   if (a.ksize < 1 || a.ksize > 3) return -1;
   if (a.ksize == 2 && !a.phase && (a.stride != 2 || a.pad != 0 || a.tmode)) return -1;  // the ConvT-dgrad form ...
   if (a.ksize == 2 && a.phase == 1 && (a.stride != 1 || a.tmode || a.out_f32 || a.convt_co <= 0 || a.convt_co % 64)) return -1;  // ... or a phase conv

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -360,7 +361,7 @@ int launch_stem_s2c32_v2(const ConvArgs& a, const StemArgs& st, hipStream_t s) {
     if (slots < 8) slots = 8;
   }
   const int grid = ntiles <= slots ? ntiles : slots;
-  static const int nxb_env = getenv("M355_STEM2_NXB") ? atoi(getenv("M355_STEM2_NXB")) : 7;
+  const int nxb_env = proc_switches().stem2_nxb;
   const int nxb = nxb_env < 5 ? 5 : (nxb_env > 9 ? 9 : nxb_env);   // stem blocks per wave of team X (of 9; the rest go to team Y)
   hipLaunchKernelGGL(stem_s2c32_cv1_v2_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, st, tiles_x, tiles_y, ntiles, nxb);
   return (int)hipGetLastError();

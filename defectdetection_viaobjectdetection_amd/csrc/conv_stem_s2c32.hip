@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -312,8 +313,7 @@ __global__ __launch_bounds__(512, 2) void stem_s2c32_cv1_kernel(const ConvArgs a
 
 // a: the model.1 + model.2.cv1 launch of conv3x3_s2c32.hip (its x is ignored); st: the stem launch (its y is ignored).
 bool stem_s2c32_ok(const ConvArgs& a, const StemArgs& st) {
-  static const bool off = getenv("M355_NO_STEMFUSE") != nullptr;
-  if (off || !conv_s2c32_cv1_ok(a)) return false;
+  if (proc_switches().no_stemfuse || !conv_s2c32_cv1_ok(a)) return false;
   if (st.Cout != 32 || st.H != 2 * a.Hi || st.W != 2 * a.Wi || (st.W * 3) % 16 || !st.w16 || !st.bias) return false;
   return (long)st.B * st.H * st.W * 3 < (1L << 31) && st.B == a.M / (a.Ho * a.Wo);
 }

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 
@@ -366,8 +367,7 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(const half_t* dz, long 
 }
 
 bool wgrad_stem_ok(int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int ksize, int stride, int pad, int lddz, int ldx, long x_bstride) {
-  static const bool off = getenv("M355_NO_WGRAD_STEM") != nullptr;
-  return !off && ksize == 3 && stride == 2 && pad == 1 && Cin == 8 && ldx == 8 && x_bstride == (long)Hi * Wi * 8 && Cout >= 8 && Cout <= 64 &&
+  return !proc_switches().no_wgrad_stem && ksize == 3 && stride == 2 && pad == 1 && Cin == 8 && ldx == 8 && x_bstride == (long)Hi * Wi * 8 && Cout >= 8 && Cout <= 64 &&
          Cout % 8 == 0 && lddz >= Cout && Hi == 2 * Ho && Wi == 2 * Wo && Wo % SW_PX == 0;
 }
 
@@ -513,8 +513,7 @@ __global__ __launch_bounds__(256) void wgrad_s2c32_kernel(const half_t* dz, long
 
 constexpr int W2_SLABS = 512;   // partial slabs (= blocks) the workspace is sized for
 bool wgrad_s2c32_ok(int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int ksize, int stride, int pad, int lddz, int ldx) {
-  static const bool off = getenv("M355_NO_WGRAD_S2C32") != nullptr;
-  return !off && ksize == 3 && stride == 2 && pad == 1 && Cin == 32 && Cout == 64 && ldx >= 32 && lddz >= 64 && Hi == 2 * Ho && Wi == 2 * Wo &&
+  return !proc_switches().no_wgrad_s2c32 && ksize == 3 && stride == 2 && pad == 1 && Cin == 32 && Cout == 64 && ldx >= 32 && lddz >= 64 && Hi == 2 * Ho && Wi == 2 * Wo &&
          Wo >= W2_PX;
 }
 
@@ -523,7 +522,7 @@ void wgrad_plan(int M, int Cout, int N, int* splitk, int* steps_per_split) {
   const int steps_total = (M + KST - 1) / KST;
   // every block writes one 64 KB partial tile: the slab traffic of a layer is (blocks x 64 KB), so no more blocks than
   // fill three quarters of the chip once (256 CUs x 2 resident blocks); M355_WGRAD_BLOCKS overrides for tuning
-  static const int target = getenv("M355_WGRAD_BLOCKS") ? atoi(getenv("M355_WGRAD_BLOCKS")) : 384;   // measured (s-seg b64 @640 step): 256 -> 49.0 ms, 384 -> 46.1, 512 -> 47.7, 1024 -> 49.3
+  const int target = proc_switches().wgrad_blocks;
   int sk = (target + tiles - 1) / tiles;
   if (sk > steps_total) sk = steps_total;
   if (sk < 1) sk = 1;
@@ -570,8 +569,7 @@ int launch_conv_wgrad(const half_t* dz, long dz_bstride, int lddz, const half_t*
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
     }
     const long chunks = (long)B * Ho * ((Wo + W2_PX - 1) / W2_PX);
-    static const int per_cu_x2 = getenv("M355_W2_BLOCKS_X2") ? atoi(getenv("M355_W2_BLOCKS_X2")) : 4;   // blocks per CU x 2 (tuning)
-    long nb = (long)per_cu_x2 * cus / 2;                     // two blocks per CU (registers), one slab each
+    long nb = (long)proc_switches().w2_blocks_x2 * cus / 2;                     // two blocks per CU (registers), one slab each
     if (nb > W2_SLABS) nb = W2_SLABS;
     if (nb > chunks) nb = chunks;
     const long fit = (long)(ws_bytes / ((size_t)64 * 288 * sizeof(float)));

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 
@@ -221,7 +222,8 @@ Plan3 plan3(int B, int H, int W, int Cin, int Cout) {
   Plan3 p{};
   p.nco = Cout > 32 ? 2 : 1;
   p.nci = Cin > 32 ? 2 : 1;
-  static const int shrink = getenv("M355_WGRAD3_SHRINK") ? atoi(getenv("M355_WGRAD3_SHRINK")) : 0;   // experiments: 1 halve ci, 2 halve co, 3 both when the layer is one tile
+  const ProcSwitches& ps = proc_switches();
+  const int shrink = ps.wgrad3_shrink;   // experiments on a layer of one tile
   if (Cout <= 64 && Cin <= 64) {
     if (shrink & 1) p.nci = 1;
     if (shrink & 2) p.nco = 1;
@@ -233,9 +235,8 @@ Plan3 plan3(int B, int H, int W, int Cin, int Cout) {
   p.tiles_sp = B * p.tiles_x * p.tiles_y;
   // Splits: about two blocks per CU, at least 8 spatial tiles per block (its prologue and its 9 x 32 x 32 x 4-byte-per-wave
   // store amortise), and no more slab bytes than ~96 MB per layer (every slab is written once and read once by the reduction).
-  static const int target = getenv("M355_WGRAD3_BLOCKS") ? atoi(getenv("M355_WGRAD3_BLOCKS")) : 512;
-  static const int min_tiles = getenv("M355_WGRAD3_MINTILES") ? atoi(getenv("M355_WGRAD3_MINTILES")) : 8;
-  static const long slab_cap = (getenv("M355_WGRAD3_SLABMB") ? atol(getenv("M355_WGRAD3_SLABMB")) : 96) << 20;
+  const int target = ps.wgrad3_blocks, min_tiles = ps.wgrad3_mintiles;
+  const long slab_cap = ps.wgrad3_slabmb << 20;
   int sk = (target + p.co_tiles * p.ci_tiles - 1) / (p.co_tiles * p.ci_tiles);
   if (sk > p.tiles_sp / min_tiles) sk = p.tiles_sp / min_tiles;
   const long dw_bytes = (long)Cout * 9 * Cin * 4;
@@ -269,8 +270,7 @@ int launch3(const Wgrad3Args& a, int blocks, hipStream_t s) {
 
 // Eligibility: 3x3 / stride 1 / pad 1, at least two tile columns (a 20-pixel-wide map would compute 32), 32-bit offsets.
 bool conv_wgrad3_ok(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int lddz, int ldx) {
-  static const bool off = getenv("M355_NO_WGRAD3") != nullptr;
-  if (off || ksize != 3 || stride != 1 || pad != 1 || Cin % 8 || Cout % 8 || lddz % 8 || ldx % 8) return false;
+  if (proc_switches().no_wgrad3 || ksize != 3 || stride != 1 || pad != 1 || Cin % 8 || Cout % 8 || lddz % 8 || ldx % 8) return false;
   if (W < 2 * TW || (long)H * W * (lddz > ldx ? lddz : ldx) >= (1L << 30)) return false;
   const int waste_num = ((W + TW - 1) / TW) * TW * (((H + TH - 1) / TH) * TH);
   return waste_num * 4 <= H * W * 5;   // at most 25 % of the tile area outside the map

@@ -14,6 +14,7 @@
 
 #include "../../include/mi355yolo.h"
 #include "common.h"
+#include "switches.h"
 #include "weight_pack.h"
 
 using namespace m355;
@@ -116,6 +117,7 @@ struct PhysConv {
 
 struct m355_engine {
   m355_model_desc desc{};
+  PlanSwitches sw{};         // the M355_* switches of graph construction and planning, as read at create
   std::string err;
   std::vector<Tensor> tensors;
   std::vector<m355_conv_info> convs;   // logical convs (canonical order)
@@ -148,7 +150,6 @@ struct m355_engine {
   bool decode_fused = false;
   int headtail_n = 0;        // head levels eligible for head_tail.hip (3: the decode launch is skipped when the raw maps are not kept)
   bool headtail_active = false;   // decided per forward, for ALL three levels or none: every level passes head_tail_ok for this batch
-  long headtail_maxm = 0;    // testing only (M355_HEADTAIL_MAXM at create): a level with more pixels than this counts as ineligible
   int keep_raw = 1;
   // profiling: HIP events around every op launch, recorded on the caller's stream (single lane while profiling)
   bool profiling = false;
@@ -277,7 +278,7 @@ struct Builder {
     // checked here for the largest batch the engine takes: s scale at 640 x 640 from 437 images on keeps the three-launch form)
     const long c2f_px = (long)e->desc.max_batch * H * W;
     const bool c2f_addr_ok = c2f_px * (2 + n) * c * 2 < (1L << 31) && c2f_px * e->tensors[out.t].C < (1L << 31);
-    if (c == 32 && n == 1 && H % 8 == 0 && W % 16 == 0 && out.c == 64 && c2f_addr_ok && !getenv("M355_NO_C2F32")) {
+    if (c == 32 && n == 1 && H % 8 == 0 && W % 16 == 0 && out.c == 64 && c2f_addr_ok && !e->sw.no_c2f32) {
       // the whole block body in one launch (c2f_c32.hip): t and y2 never reach HBM, no tensor for either
       const int la = logical(name + ".m.0.cv1", c, c, 3, 1, 1, 0, 1), lb = logical(name + ".m.0.cv2", c, c, 3, 1, 1, 0, 1);
       const int lc = logical(name + ".cv2", 3 * c, out.c, 1, 1, 1, 0, 1);
@@ -292,7 +293,7 @@ struct Builder {
     for (int j = 0; j < n; ++j) {
       const int tmp = tensor(H, W, c);
       const Slice src{cat, (1 + j) * c, c};
-      if (bneck_pair_shape_ok(c, H, W) && !getenv("M355_NO_PAIR")) {
+      if (bneck_pair_shape_ok(c, H, W) && !e->sw.no_pair) {
         // the whole Bottleneck in one launch, hidden tensor in LDS (conv3x3_planes.hip); `tmp` only serves the two-launch
         // fallback of a call the kernel's 31-bit buffer offsets cannot address
         const std::string mn = name + ".m." + std::to_string(j);
@@ -363,10 +364,7 @@ int build_segment_head(m355_engine* e, Builder& b, const int feats[3], const int
     e->ops.push_back(op);
   };
   const int HW[3][2] = {{H3, W3}, {H4, W4}, {H5, W5}};
-  // stream lane of Proto and of the three head levels (plan_lanes): measured best on MI355X at batch 32
-  int lane_plan[4] = {1, 2, 2, 0};
-  if (const char* lp = getenv("M355_LANE_PLAN"))
-    for (int i = 0; i < 4 && lp[i] >= '0' && lp[i] <= '3'; ++i) lane_plan[i] = lp[i] - '0';
+  const int* lane_plan = e->sw.lane_plan;   // stream lane of Proto and of the three head levels (plan_lanes)
   for (int l = 0; l < 3; ++l) {
     const size_t lvl_first = e->ops.size();
     const int hcat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3 + hc4);
@@ -393,8 +391,8 @@ int build_segment_head(m355_engine* e, Builder& b, const int feats[3], const int
   }
   const size_t proto_first = e->ops.size();
   {
-    const bool fuse2 = !getenv("M355_NO_PROTOFUSE") && npr % 64 == 0;   // a channel tile (64 or 128) must lie inside one phase
-    const bool fuse3 = fuse2 && npr == 128 && nm == 32 && !getenv("M355_NO_PROTOFUSE3");
+    const bool fuse2 = !e->sw.no_protofuse && npr % 64 == 0;   // a channel tile (64 or 128) must lie inside one phase
+    const bool fuse3 = fuse2 && npr == 128 && nm == 32 && !e->sw.no_protofuse3;
     const int pr1 = b.tensor(H3, W3, npr);
     add_conv_op({l_p1}, Slice{feats[0], 0, fch[0]}, Slice{pr1, 0, npr}, 0, 0, 0);
     if (!fuse2) {
@@ -539,7 +537,7 @@ int build_graph_v9c(m355_engine* e) {
     e->ops.push_back(op);
     b.conv("model.9.cv5", Slice{sp, 0, 1024}, x9, 1, 1);
   }
-  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  const bool upfuse = !e->sw.no_upfuse;
   auto up = [&](Slice src, Slice dst) {
     if (upfuse) return;
     Op op{};
@@ -693,7 +691,7 @@ int build_graph_v5u(m355_engine* e) {
   }
   b.conv("model.10", Slice{t9, 0, c1024}, x10, 1, 1);
   // 11/12 and 15/16: Upsample + Concat read through by the next C3's cv2 || cv1 (M355_NO_UPFUSE: materialised by upsample2x)
-  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  const bool upfuse = !e->sw.no_upfuse;
   auto up = [&](Slice src, Slice dst) {
     if (upfuse) return;
     Op op{};
@@ -914,7 +912,7 @@ int build_graph_y11(m355_engine* e) {
   }
   build_c2psa(e, b, "model.10", Slice{t9, 0, c1024}, x10);
   // 11/12 and 14/15: Upsample + Concat read through by the next C3k2's cv1 (M355_NO_UPFUSE: materialised by upsample2x)
-  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  const bool upfuse = !e->sw.no_upfuse;
   auto up = [&](Slice src, Slice dst) {
     if (upfuse) return;
     Op op{};
@@ -1011,7 +1009,7 @@ int build_graph(m355_engine* e) {
   // 10/11: Upsample(x9) + Concat with x6.  By default nothing is copied: model.12.cv1 (1x1) reads channels
   // [0, c1024) through its gather from the half-resolution x9 (upsample read-through, conv_igemm.hip); with
   // M355_NO_UPFUSE the upsample kernel materialises them in cat11 instead.
-  const bool upfuse = !getenv("M355_NO_UPFUSE");
+  const bool upfuse = !e->sw.no_upfuse;
   if (!upfuse) {
     Op op{};
     op.kind = OP_UP;
@@ -1046,7 +1044,7 @@ int build_graph(m355_engine* e) {
 // im2col channel tile holds (64 or 128) on both sides: the 1x1 runs in the conv kernel's epilogue through LDS and the
 // conv's own output never goes to HBM (model.1 -> model.2.cv1 and model.3 -> model.4.cv1 for the s scale).
 void fuse_conv_cv1(m355_engine* e) {
-  if (getenv("M355_NO_CVFUSE")) return;
+  if (e->sw.no_cvfuse) return;
   for (size_t i = 0; i < e->ops.size(); ++i) {
     Op& oi = e->ops[i];
     if (oi.kind != OP_CONV || oi.out_ext != 0 || oi.res.t >= 0 || oi.in2.t >= 0) continue;
@@ -1087,9 +1085,7 @@ void fuse_conv_cv1(m355_engine* e) {
 // tile holds a whole row and 64 raw + 64 decoded rows fit the LDS stages.  All three levels or none: OP_DECODE is then
 // not launched at all.
 void fuse_decode(m355_engine* e) {
-  // measured at batch 32: 179 us for the three launches against 93 + 39 us separately, -1 % end to end (two serial 64-pixel
-  // passes with four barriers each behind every tile): opt-in
-  if (!getenv("M355_DECFUSE")) return;
+  if (!e->sw.decfuse) return;   // opt-in (M355_DECFUSE)
   const int wi = 64 + e->nc + e->nm, wo = 4 + e->nc + e->nm;
   if (wi > 128 || (wi + wo) * 64 * 4 > 65536) return;
   int n = 0;
@@ -1122,9 +1118,8 @@ std::vector<int> op_producers(const m355_engine* e, int i) {
 // convs on the caller's lane whose output map is at least 1/8 of the input.  M355_SUBBATCH = images per pass (default 0: off),
 // M355_SUBBATCH_OPS = number of leading ops.
 void plan_sub_batches(m355_engine* e) {
-  const char* sb = getenv("M355_SUBBATCH");
-  e->sub_batch = sb ? atoi(sb) : 0;   // measured at batch 32 with two engines in flight: 8 -> -5 %, 16 -> -2 %: off by default
-  if (e->sub_batch <= 0 || getenv("M355_NO_SUBBATCH")) { e->sub_batch = 0; return; }
+  e->sub_batch = e->sw.subbatch;
+  if (e->sub_batch <= 0 || e->sw.no_subbatch) { e->sub_batch = 0; return; }
   int n = 0;
   for (const Op& op : e->ops) {
     if ((op.kind != OP_STEM && op.kind != OP_CONV && op.kind != OP_C2F32 && op.kind != OP_PAIR) || op.lane != 0 || op.record || !op.wait_ops.empty() || op.out_ext != 0) break;
@@ -1132,8 +1127,7 @@ void plan_sub_batches(m355_engine* e) {
     if (to.H * 8 < e->desc.in_h) break;
     ++n;
   }
-  if (const char* so = getenv("M355_SUBBATCH_OPS")) n = std::min(n, atoi(so));
-  e->sub_ops = n;
+  e->sub_ops = std::min(n, e->sw.subbatch_ops);
 }
 
 // Stream lanes.  The builder tags the ops of Proto and of the stride-8 head level with lane 1; everything else is
@@ -1141,7 +1135,7 @@ void plan_sub_batches(m355_engine* e) {
 // host enqueues it as early as the data allows (lane order is kept, so the result is still a topological order).
 // (2) Cross-lane dependencies become event waits; the last op of every side lane is joined into the caller's stream.
 int plan_lanes(m355_engine* e) {
-  if (getenv("M355_NO_LANES")) {
+  if (e->sw.no_lanes) {
     for (Op& op : e->ops) op.lane = 0;
     return 0;
   }
@@ -1349,33 +1343,35 @@ bool head_tail_layout(const m355_engine* e, const PhysConv& p) {
 // Which kernel an OP_CONV / OP_CONVT / OP_PHASE launch runs (op.route, op.tile), from its shapes at max_batch (`a` = its
 // conv_args) and the M355_* switches; and whether a head level is eligible for head_tail.hip.
 void plan_route(m355_engine* e, Op& op, const ConvArgs& a) {
+  const PlanSwitches& sw = e->sw;
   PhysConv& p = e->phys[op.conv];
   const Tensor& ti = e->tensors[op.in.t];
   if (op.kind == OP_PHASE) {
     op.tile = p.cout % 128 == 0 ? TILE_128x128 : TILE_64x128;
-    if (p.l3 >= 0 && p.cin == 128 && p.cout == 128 && p.cout2 == 32 && ti.H % 8 == 0 && ti.W % 16 == 0 && !getenv("M355_NO_PROTOR"))
+    if (p.l3 >= 0 && p.cin == 128 && p.cout == 128 && p.cout2 == 32 && ti.H % 8 == 0 && ti.W % 16 == 0 && !sw.no_protor)
       op.route = R_PROTOR;
     return;
   }
   const bool conv = op.kind == OP_CONV;
   op.tile = conv_pick_tile(a.Cout, a.M);
-  if (a.ksize == 1 && op.tile == TILE_128x128 && getenv("M355_K1_TILE")) op.tile = atoi(getenv("M355_K1_TILE"));
+  if (a.ksize == 1 && op.tile == TILE_128x128 && sw.k1_tile >= 0) op.tile = sw.k1_tile;
   if (op.decode) op.tile = TILE_128x128;   // the whole 64 + nc + nm row of a pixel in one channel tile
-  if (conv && conv3x3_halo_ok(a) && !getenv("M355_NO_HALO")) op.route = R_HALO;
-  const bool m32 = op.route == R_HALO && conv3x3_halo_pick(a, getenv("M355_NO_WIDE"), getenv("M355_NO_M32")) == TILE_M32;
-  if (conv && conv3x3_c32_ok(a) && !getenv("M355_NO_C32")) op.route = R_C32;
+  if (conv && conv3x3_halo_ok(a) && !sw.no_halo) op.route = R_HALO;
+  // (M355_NO_WIDE / M355_NO_M32 as launch_conv3x3_halo takes them, so that this, the label and the launch cannot disagree)
+  const bool m32 = op.route == R_HALO && conv3x3_halo_pick(a, proc_switches().no_wide, proc_switches().no_m32) == TILE_M32;
+  if (conv && conv3x3_c32_ok(a) && !sw.no_c32) op.route = R_C32;
   // 1x1 with K <= 512 and Cout a multiple of 128: weights in registers (conv1x1_wreg.hip)
-  if (conv && op.out_ext == 0 && p.l3 < 0 && !p.diag && op.res.t < 0 && !op.decode && (op.in2.t < 0 || !getenv("M355_NO_W1_SPLIT")) &&
-      conv1x1_wreg_ok(a) && !getenv("M355_NO_W1"))
+  if (conv && op.out_ext == 0 && p.l3 < 0 && !p.diag && op.res.t < 0 && !op.decode && (op.in2.t < 0 || !sw.no_w1_split) &&
+      conv1x1_wreg_ok(a) && !sw.no_w1)
     op.route = R_W1;
-  if (conv && op.route != R_HALO && op.route != R_C32 && conv3x3_slab_ok(a) && !getenv("M355_NO_SLAB")) op.route = R_SLAB;
+  if (conv && op.route != R_HALO && op.route != R_C32 && conv3x3_slab_ok(a) && !sw.no_slab) op.route = R_SLAB;
   // row-slab kernel in single-conv mode (conv3x3_planes.hip) for what the slab kernel took (the 20 x 20 level): one block per CU
   // owns a slab x 64 channels with its weights streamed to registers -- 21 us against 34 on 256 -> 256 at batch 32
   // ... and for the stride-2 3x3 convs that were on the im2col kernel (model.5 / 7 / 16 / 19 of the s scale: 177 us at batch 32)
-  const bool planes_s2 = p.k == 3 && p.stride == 2 && op.res.t < 0 && op.in2.t < 0 && !getenv("M355_NO_PLANES_S2");
+  const bool planes_s2 = p.k == 3 && p.stride == 2 && op.res.t < 0 && op.in2.t < 0 && !sw.no_planes_s2;
   // ... and for the 64 -> 64 conv of the 40 x 40 level (model.22.cv2.1.1: 9 us against 14 on the 32x32x16 halo kernel)
-  const bool planes_m64 = m32 && a.Cout <= 64 && op.res.t < 0 && op.in2.t < 0 && !getenv("M355_NO_PLANES_M64");
-  if (conv && (op.route == R_SLAB || planes_s2 || planes_m64) && op.out_ext == 0 && p.l3 < 0 && !p.diag && !getenv("M355_NO_PLANES")) {
+  const bool planes_m64 = m32 && a.Cout <= 64 && op.res.t < 0 && op.in2.t < 0 && !sw.no_planes_m64;
+  if (conv && (op.route == R_SLAB || planes_s2 || planes_m64) && op.out_ext == 0 && p.l3 < 0 && !p.diag && !sw.no_planes) {
     PlanesArgs pa = planes_args(e, op, e->desc.max_batch, 0);
     pa.wfb = (const half_t*)1;   // placeholder: the fragments are packed after planning, and only for the ops planned here
     if (conv3x3_planes_ok(pa)) {
@@ -1384,15 +1380,15 @@ void plan_route(m355_engine* e, Op& op, const ConvArgs& a) {
     }
   }
   if (conv && op.out_ext == 1 && !op.decode && head_tail_layout(e, p) && ti.C == 224 && op.in.off == 0 && op.raw_off == 0 &&
-      a.Ho * a.Wo >= 32 && !getenv("M355_NO_HEADTAIL")) {
+      a.Ho * a.Wo >= 32 && !sw.no_headtail) {
     op.headtail = 1;   // (the route stays im2col: which path runs depends on keep_raw at forward time)
     ++e->headtail_n;
   }
   if (conv && p.l3 >= 0 && p.k == 3 && p.stride == 2 && p.cin == 32 && p.cout == 64 && p.cout2 == 64 && a.Ho % 8 == 0 &&
-      a.Wo % 16 == 0 && !getenv("M355_NO_S2C32"))
+      a.Wo % 16 == 0 && !sw.no_s2c32)
     op.route = R_S2C32;
   if (conv && p.l3 >= 0 && p.k == 3 && p.stride == 2 && p.cin == 64 && p.cout == 128 && p.cout2 == 128 && a.Ho % 8 == 0 &&
-      a.Wo % 8 == 0 && !getenv("M355_NO_S2C64"))
+      a.Wo % 8 == 0 && !sw.no_s2c64)
     op.route = R_S2C64;
 }
 
@@ -1409,7 +1405,7 @@ void conv_label(const m355_engine* e, Op& op, const ConvArgs& a) {
       else snprintf(k, n, "conv_igemm<%s,k%d%s>", tile_names[op.tile], a.ksize, p.l3 >= 0 ? "+1x1" : op.decode ? "+decode" : "");
       break;
     case R_HALO: {
-      const int pick = conv3x3_halo_pick(a, getenv("M355_NO_WIDE"), getenv("M355_NO_M32"));
+      const int pick = conv3x3_halo_pick(a, proc_switches().no_wide, proc_switches().no_m32);
       if (pick == TILE_HALOWIDE) snprintf(k, n, "conv3x3_wide<128ch,16x16px>");
       else if (pick == TILE_M32) snprintf(k, n, "conv3x3_m32<%s,8x16px>", ch);
       else snprintf(k, n, "conv3x3_halo<%s>", ch);
@@ -1559,7 +1555,7 @@ void annotate_ops(m355_engine* e) {
   for (size_t i = 0; i + 1 < e->ops.size(); ++i) {
     Op& st = e->ops[i];
     Op& nx = e->ops[i + 1];
-    if (st.kind != OP_STEM || e->phys[st.conv].k != 3 || nx.route != R_S2C32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || getenv("M355_NO_STEMFUSE")) continue;
+    if (st.kind != OP_STEM || e->phys[st.conv].k != 3 || nx.route != R_S2C32 || nx.in.t != st.out.t || st.lane != nx.lane || st.record || e->sw.no_stemfuse) continue;
     bool other = false;
     for (size_t j = i + 2; j < e->ops.size(); ++j)
       if (e->ops[j].in.t == st.out.t || e->ops[j].res.t == st.out.t || e->ops[j].in2.t == st.out.t) other = true;
@@ -1623,7 +1619,7 @@ int m355_create(const m355_model_desc* desc, m355_engine** out) {
   }
   m355_engine* e = new m355_engine();
   e->desc = *desc;
-  if (const char* mm = getenv("M355_HEADTAIL_MAXM")) e->headtail_maxm = atol(mm);   // testing: force a head level ineligible
+  e->sw = read_plan_switches();
   int rc = build_graph(e);
   if (rc == 0) fuse_conv_cv1(e);
   if (rc == 0) fuse_decode(e);
@@ -1791,7 +1787,7 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
     for (const Op& op : e->ops) {
       if (!op.headtail) continue;
       const HeadTailArgs ha = head_tail_args(e, op, B, d_preds);
-      if (!ha.wf || !head_tail_ok(ha) || (e->headtail_maxm > 0 && ha.M > e->headtail_maxm)) all = false;
+      if (!ha.wf || !head_tail_ok(ha) || (e->sw.headtail_maxm > 0 && ha.M > e->sw.headtail_maxm)) all = false;
     }
     e->headtail_active = all;
   }
@@ -1839,10 +1835,10 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
           break;
         }
         ConvArgs a = conv_args(e, op, Bq, b0, d_preds, d_protos);
-        if (op.kind != OP_PHASE) a.tileq = knobs().static_tiles ? nullptr : e->tileq + 4 * oi;
+        if (op.kind != OP_PHASE) a.tileq = proc_switches().static_tiles ? nullptr : e->tileq + 4 * oi;
         if (op.stemfuse >= 0) {
           const StemArgs sa = stem_args(e, e->ops[op.stemfuse], Bq, b0, d_in);
-          const bool stem2 = getenv("M355_NO_STEM2") == nullptr;  // two-team form (conv_stem_c2.hip, the default); read per launch: tests toggle it
+          const bool stem2 = !live_no_stem2();  // two-team form (conv_stem_c2.hip, the default); read per launch: tests toggle it
           if (stem2 && stem_s2c32_v2_ok(a, sa)) {
             rc = launch_stem_s2c32_v2(a, sa, s);
             break;

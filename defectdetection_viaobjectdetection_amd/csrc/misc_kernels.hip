@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -421,7 +422,7 @@ static int launch_stem_rows(const StemArgs& a, hipStream_t s) {
 }
 
 int launch_stem(const StemArgs& a, hipStream_t s) {
-  if ((a.W * 3) % 16 == 0 && a.W % 2 == 0 && a.H % 2 == 0 && 3 * (a.W * 3 + 32) <= 64 * 1024 && !knobs().stem_gather) {
+  if ((a.W * 3) % 16 == 0 && a.W % 2 == 0 && a.H % 2 == 0 && 3 * (a.W * 3 + 32) <= 64 * 1024 && !proc_switches().stem_gather) {
     switch (a.Cout) {
       case 16: return launch_stem_rows<16>(a, s);
       case 32: return launch_stem_rows<32>(a, s);
@@ -451,7 +452,7 @@ int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y
   if (C % 8 || ldx % 8 || ldy % 8) return -1;
   // widest channel chunk per block that still leaves >= 256 blocks (one per CU) and fits the LDS; planes of at most 256 * SPPF_ME
   // elements take the form with per-thread element ownership
-  static const int min_blocks = getenv("M355_SPPF_MINBLOCKS") ? atoi(getenv("M355_SPPF_MINBLOCKS")) : 256;
+  const int min_blocks = proc_switches().sppf_minblocks;
   int cg = 4;
   while (cg > 1 && ((C / 8) % cg != 0 || (long)B * (C / (8 * cg)) < min_blocks || (size_t)3 * H * W * 16 * cg > 160 * 1024 ||
                     H * W * cg > SPPF_NT * SPPF_ME))

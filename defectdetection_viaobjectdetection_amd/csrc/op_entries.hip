@@ -10,6 +10,7 @@
 
 #include "../../include/mi355yolo.h"
 #include "common.h"
+#include "switches.h"
 #include "weight_pack.h"
 
 using namespace m355;
@@ -62,7 +63,7 @@ int finish_entry(int rc, hipStream_t s, const char* what) {
 //   M355_STAMPS=<file>   the kernel's stamps go to a zeroed buffer of `words` uint64, written to <file> by dump();
 //   M355_BNECK_REPS=<n>  after a launch that succeeded, n more back to back; their mean time goes to stderr.
 struct SlabDiag {
-  const char* path = getenv("M355_STAMPS");
+  const char* path = live_stamps_path();
   size_t words = 0;
   unsigned long long* stamps = nullptr;   // nullptr when M355_STAMPS is unset
   bool alloc(DevBuf& d, size_t n) {       // false: the stamp buffer could not be allocated
@@ -72,19 +73,17 @@ struct SlabDiag {
   }
   template <class Launch>
   int reps(int rc, hipStream_t s, const char* what, Launch launch) const {
-    if (const char* reps = getenv("M355_BNECK_REPS")) {
-      const int n = atoi(reps);
-      hipEvent_t e0, e1;
-      if (rc == 0 && n > 0 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-        (void)hipEventRecord(e0, s);
-        for (int i = 0; i < n && rc == 0; ++i) rc = launch();
-        (void)hipEventRecord(e1, s);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        fprintf(stderr, "%s: %.2f us per launch (%d launches)\n", what, ms * 1e3f / n, n);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-      }
+    const int n = live_bneck_reps();
+    hipEvent_t e0, e1;
+    if (rc == 0 && n > 0 && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+      (void)hipEventRecord(e0, s);
+      for (int i = 0; i < n && rc == 0; ++i) rc = launch();
+      (void)hipEventRecord(e1, s);
+      (void)hipEventSynchronize(e1);
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, e0, e1);
+      fprintf(stderr, "%s: %.2f us per launch (%d launches)\n", what, ms * 1e3f / n, n);
+      (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
     return rc;
   }
@@ -363,7 +362,7 @@ int m355_conv2d_dgrad(const void* d_dy, int B, int H, int W, int cin, const floa
   // stride 2 on even maps: four 2x2 phase convs over dY (conv_igemm.hip, phase == 2) -- rows [phase][ci], columns [(ty, tx)][co];
   // dX row 2i takes tap kh = 1 from dY row i, row 2i + 1 takes kh = 2 from row i and kh = 0 from row i + 1 (columns alike)
   // (which phase form, if any, launch_conv_igemm can tile: dgrad_phase_form; the masked gather otherwise)
-  const int form = stride == 2 && k == 3 && H == 2 * Ho && W == 2 * Wo && !getenv("M355_NO_DGRAD_PHASES") ? dgrad_phase_form(cin, cout, false) : 0;
+  const int form = stride == 2 && k == 3 && H == 2 * Ho && W == 2 * Wo && !live_no_dgrad_phases() ? dgrad_phase_form(cin, cout, false) : 0;
   const bool phases = form != 0;
   const int cout_pad = conv_cout_pad(phases ? 4 * cin : cin);
   const int Kpad = phases ? conv_kpad(cout, 2) : conv_kpad(cout, k);
@@ -633,8 +632,8 @@ int m355_conv_launch(const m355_conv_args* c, void* stream) {
   int rc;
   // 1x1 convs of the training step (forward and input gradients) on conv1x1_wreg.hip where it applies (the weights are gathered
   // from the packed rows: the per-step re-pack writes no fragment-ordered copy): 27.4-27.5 -> 27.2-27.3 ms per s-seg b64 step on one box
-  static const bool train_w1 = getenv("M355_NO_TRAIN_W1") == nullptr;
-  static const bool train_c32 = getenv("M355_NO_TRAIN_C32") == nullptr;   // 32 -> 32 3x3 layers on conv3x3_c32.hip: a further -0.1 ms
+  const bool train_w1 = !proc_switches().no_train_w1;
+  const bool train_c32 = !proc_switches().no_train_c32;   // 32 -> 32 3x3 layers on conv3x3_c32.hip: a further -0.1 ms
   if (a.phase == 2 && dgrad_s2c32_ok(a))
     rc = launch_dgrad_s2c32(a, (hipStream_t)stream);
   else if (!a.tmode && conv3x3_halo_ok(a))

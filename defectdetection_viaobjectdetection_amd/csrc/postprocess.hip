@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -392,8 +393,7 @@ int launch_proto_masks(const float* dets, const int* counts, const half_t* proto
                        int mh, int mw, int in_h, int in_w, uint8_t* masks, hipStream_t s) {
   if (nm != 32) return -1;
   if (in_h % mh || in_w % mw || in_w / mw != 4 || in_h / mh != 4 || in_w % 16) return -1;
-  static const int dbg = getenv("M355_MASK_DBG") ? atoi(getenv("M355_MASK_DBG")) : 0;   // timing ablations: 1 zero fill only, 2 no stores
-  static const int shape = getenv("M355_MASK_TILE") ? atoi(getenv("M355_MASK_TILE")) : 0;   // 1: the 16 x 16-cell tile (experiments)
+  const int dbg = proc_switches().mask_dbg, shape = proc_switches().mask_tile;   // timing ablations / the 16 x 16-cell tile
   if (shape == 1) {
     const int tiles = ((mw + 15) / 16) * ((mh + 15) / 16);
     hipLaunchKernelGGL((proto_masks_kernel<32, 16, 16>), dim3(tiles, B), dim3(256), 0, s, dets, counts, protos, max_det, mh, mw,

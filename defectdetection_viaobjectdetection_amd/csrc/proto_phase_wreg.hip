@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace m355 {
 namespace {
@@ -352,9 +353,8 @@ int launch_proto_phase_wreg(const ConvArgs& a, hipStream_t s) {
   int grid = 4 * ntiles <= slots ? 4 * ntiles : slots;  // a multiple of 4: every phase gets the same number of blocks
   const int step = grid >> 2;                          // tiles between two visits of a block (= blocks per phase)
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
-  static const int prio = getenv("M355_PROTOR_PRIO") ? atoi(getenv("M355_PROTOR_PRIO")) : 0;   // experiment: s_setprio(1) around the K loop
-  // diagnostic: M355_PROTOR_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
-  static const char* st_path = getenv("M355_PROTOR_STAMPS");
+  const int prio = proc_switches().protor_prio;
+  const char* st_path = proc_switches().protor_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
   static unsigned long long* d_st = nullptr;
   if (st_path && !d_st) {
     if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;
