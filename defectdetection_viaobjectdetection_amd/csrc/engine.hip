@@ -1,9 +1,7 @@
-// libmi355yolo.so engine: YOLOv8-seg layer plan, weight upload (layouts: weight_pack.hip), workspace and the engine's C-ABI
-// (include/mi355yolo.h; the per-op entries are in op_entries.hip).  Host-side C++; all arithmetic is in the HIP kernels here.
-//
-// Graph (upstream yolov8-seg.yaml as exercised by
-// BscanBased/yolo8_seg_predict.py:5-8): every Concat is physical-zero-copy -- producers write their
-// output at a channel offset of the consumer's NHWC buffer; C2f's split/concat is one buffer.
+// libmi355yolo.so engine: how a built graph runs.  The passes over the graph that graph.hip builds (conv + cv1 and decode fusion,
+// stream lanes, sub-batches), allocation of the workspace, the kernel choice of every op (plan_route), weight upload (layouts:
+// weight_pack.hip), m355_forward and the engine's C-ABI (include/mi355yolo.h; the per-op entries are in op_entries.hip).
+// Host-side C++: this file has no kernel, all arithmetic is in the HIP kernel files it launches.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,6 +12,7 @@
 
 #include "../../include/mi355yolo.h"
 #include "common.h"
+#include "engine_types.h"
 #include "switches.h"
 #include "weight_pack.h"
 
@@ -22,1023 +21,6 @@ using namespace m355;
 thread_local std::string m355::g_err;
 
 namespace {
-
-struct Tensor {
-  int H = 0, W = 0, C = 0;
-  half_t* p = nullptr;  // (max_batch, H, W, C) fp16 NHWC
-};
-
-struct Slice {  // channel slice of a tensor
-  int t = -1, off = 0, c = 0;
-};
-
-struct ConvLayer {
-  m355_conv_info info{};
-  int Kpad = 0, cout_pad = 0;
-  half_t* w = nullptr;  // packed [cout_pad][Kpad]
-  float* bias = nullptr;
-  bool loaded = false;
-  // fused group: logical convs that were merged into this physical conv (head first-layer fusion)
-};
-
-enum OpKind { OP_STEM, OP_CONV, OP_CONVT, OP_PHASE, OP_POOL, OP_UP, OP_DECODE, OP_ADOWN, OP_C2F32, OP_PAIR, OP_DWCONV, OP_PSA_ATTN };
-
-// The kernel of an OP_CONV / OP_CONVT / OP_PHASE launch, chosen once at plan time (plan_route)
-enum Route {
-  R_IGEMM,    // im2col implicit GEMM (conv_igemm.hip) with channel tile Op::tile
-  R_HALO,     // 3x3 stride 1: halo / wide / m32 kernel as conv3x3_halo_pick chooses (conv3x3_halo.hip)
-  R_C32,      // 3x3 32 -> 32 (conv3x3_c32.hip)
-  R_SLAB,     // 3x3 on narrow maps (conv3x3_small.hip)
-  R_W1,       // 1x1, weights in registers (conv1x1_wreg.hip)
-  R_PLANES,   // 3x3 row-slab kernel in single-conv mode (conv3x3_planes.hip)
-  R_S2C32,    // 3x3/s2 (32 -> 64) + 1x1 (64 -> 64) on the patch kernel (conv3x3_s2c32.hip)
-  R_S2C64,    // 3x3/s2 (64 -> 128) + 1x1 (128 -> 128), weights in registers (conv3x3_s2c64.hip)
-  R_PROTOR,   // OP_PHASE + proto.cv3, weights in registers (proto_phase_wreg.hip)
-};
-
-struct Op {
-  OpKind kind;
-  int conv = -1;       // physical conv index (phys_)
-  int conv2 = -1, conv3 = -1;   // OP_C2F32: Bottleneck.cv2 and C2f.cv2 (conv = Bottleneck.cv1); `in` = the [y0, y1] slice C2f.cv1 wrote
-                                // OP_PAIR: conv = Bottleneck.cv1, conv2 = Bottleneck.cv2 in one launch (conv3x3_planes.hip); out2 = the hidden tensor of the two-launch fallback
-  int shortcut = 0;
-  int heads = 0;       // OP_PSA_ATTN: attention heads (conv = the attn.pe depthwise conv, in = the qkv tensor)
-  Slice in, out, res;  // tensor slices
-  Slice in2;           // upsample read-through: channels [0, in2.c) of `in` come from this half-resolution slice
-  Slice out2;          // OP_ADOWN: second output (max-pooled half); `out` is the average-pooled half
-  int out_ext = 0;     // 0: internal tensor; 1: raw head buffer (fp32, anchor offset); 2: protos (caller)
-  int raw_off = 0;     // channel offset in raw buffer
-  int level_off = 0;   // anchor offset of the level in the raw buffer
-  int Hi = 0, Wi = 0;
-  // measurement metadata (per image)
-  char kernel[48] = {0};  // kernel family label, e.g. "conv_igemm<128x128,k3>"
-  char layer[64] = {0};   // first logical layer name
-  double flops = 0;       // algorithmic FLOPs per image (2*MACs; 0 for non-conv ops)
-  double bytes = 0;       // algorithmic activation bytes per image (in + out + residual)
-  double wbytes = 0;      // weight bytes (read once per launch)
-  Route route = R_IGEMM;
-  int tile = -1;          // im2col tile id: the launch of R_IGEMM, the run-time fallback of R_S2C32 / R_S2C64 / R_PROTOR
-  int decode = 0;         // head output conv that also decodes its rows into the prediction tensor (no OP_DECODE launch)
-  int headtail = 0;       // head output conv of a level that can run as conv + decode in one launch (head_tail.hip) when the raw maps are not kept
-  int stemfuse = -1;      // >= 0: index of the stem op this launch also computes (conv_stem_s2c32.hip); that op is then skipped
-  bool fused_away = false;
-  // stream lanes (plan_lanes): lane 0 is the caller's stream, lanes >= 1 are engine-owned side streams
-  int lane = 0;
-  std::vector<int> wait_ops;   // ops on OTHER lanes whose completion event this op's stream waits for before the launch
-  bool record = false;         // an op on another lane (or the end-of-forward join) waits for this op
-};
-
-// A physical conv = what one kernel launch computes.  Usually one logical conv; the three first-layer
-// head convs of a level (cv2/cv3/cv4 .0) share their input and are fused into one launch.
-struct PhysConv {
-  std::vector<int> logical;  // indices into convs_
-  int cin = 0, cout = 0, k = 1, stride = 1, act = 1, transposed = 0;
-  int groups = 1;            // > 1: depthwise 3x3 (groups = cin = cout): w = [9][cout] fp16 (pack_dw3x3_weights), bias [cout]
-  int composed = 0;          // 1: ConvTranspose(2x2,s2) -> Conv(3x3) composed into four 2x2 phase convs (proto)
-  int l3 = -1;               // composed + this logical 1x1 conv (proto.cv3) applied in the same kernel's epilogue
-  half_t* w2 = nullptr;      // its weights, fp16 [cout2][cin] in logical order, and bias
-  float* bias2 = nullptr;
-  int cout2 = 0;
-  std::vector<float> h_wt, h_bt, h_w3, h_b3;   // host copies of the two logical convs until both are set
-  int diag = 0;              // 1: block-diagonal fusion of 1x1 convs with different inputs (cin = sum of theirs)
-  double macs_px = 0;        // algorithmic MACs per output pixel (diag: sum over the blocks, not cin * cout)
-  int Kpad = 0, cout_pad = 0;
-  half_t* w = nullptr;
-  float* bias = nullptr;
-  float* stem_w = nullptr;  // stem only: [27][cout] fp32
-  // fragment-ordered copies of `w` for the weights-in-registers kernels (frag_pack below): wf = plain row order (conv1x1_wreg,
-  // conv3x3_s2c64, c2f_c32's first conv, the row-slab kernels), wf2 = operand row order (c2f_c32's second conv); nullptr = not built
-  half_t* wf = nullptr;
-  half_t* wf2 = nullptr;
-  int planes = 0;            // wf = the K-loop fragment order of the row-slab 3x3 kernels (planes_frag_pack)
-};
-
-}  // namespace
-
-struct m355_engine {
-  m355_model_desc desc{};
-  PlanSwitches sw{};         // the M355_* switches of graph construction and planning, as read at create
-  std::string err;
-  std::vector<Tensor> tensors;
-  std::vector<m355_conv_info> convs;   // logical convs (canonical order)
-  std::vector<bool> conv_loaded;
-  std::vector<int> conv_phys;          // logical -> physical
-  std::vector<int> conv_phys_off;      // output-channel offset inside the physical conv
-  std::vector<int> conv_phys_koff;     // input-channel (K) offset inside the physical conv (block-diagonal fusion)
-  std::vector<PhysConv> phys;
-  std::vector<Op> ops;
-  int nc = 1, nm = 32, A = 0, n3 = 0, n4 = 0, n5 = 0;
-  int proto_h = 0, proto_w = 0;
-  float* raw = nullptr;      // (max_batch, A, 64+nc+nm) fp32
-  half_t* zero = nullptr;    // zero page
-  int* tileq = nullptr;      // tile queues of the persistent kernels, 4 ints per op (ConvArgs.tileq)
-  void* nms_ws = nullptr;
-  size_t nms_ws_bytes = 0;
-  size_t ws_bytes = 0;
-  double macs = 0;           // conv MACs per image
-  int feat_in = -1;
-  // stream lanes: independent branches of the graph (Proto + the stride-8 head level vs the rest of the neck and the
-  // other head levels) are launched on two streams so that the tails / partial waves of one fill the other's gaps
-  int nlanes = 1;
-  std::vector<hipStream_t> side;      // lanes 1 .. nlanes-1
-  std::vector<hipEvent_t> op_done;    // one per op with record == true (else nullptr)
-  std::vector<int> lane_last;         // last op of every lane (joined into the caller's stream at the end of a forward)
-  // sub-batches: the leading large-map ops run over `sub_batch` images at a time, so that a tensor (26-52 MB instead of
-  // 105-210 MB at batch 32) is still in the 256 MiB Infinity Cache when its consumer reads it
-  int sub_batch = 0, sub_ops = 0;
-  // head output convs decode in their epilogue (all three levels, else none); the raw maps are then written only on request
-  bool decode_fused = false;
-  int headtail_n = 0;        // head levels eligible for head_tail.hip (3: the decode launch is skipped when the raw maps are not kept)
-  bool headtail_active = false;   // decided per forward, for ALL three levels or none: every level passes head_tail_ok for this batch
-  int keep_raw = 1;
-  // profiling: HIP events around every op launch, recorded on the caller's stream (single lane while profiling)
-  bool profiling = false;
-  std::vector<hipEvent_t> ev_pool;   // 2 events per op per recorded forward
-  size_t ev_used = 0;
-  std::vector<int> ev_op;    // op index of every recorded event pair (ops fused into a neighbour record none)
-  std::vector<double> op_ms;         // accumulated per-op milliseconds
-  std::vector<long> op_cnt;
-
-  int fail(int code, const std::string& m) {
-    err = m;
-    g_err = m;
-    return code;
-  }
-};
-
-namespace {
-
-#define HIP_TRY(e, call)                                                                            \
-  do {                                                                                              \
-    hipError_t _st = (call);                                                                        \
-    if (_st != hipSuccess)                                                                          \
-      return (e)->fail(M355_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st));           \
-  } while (0)
-
-int make_divisible(double x, int d) { return (int)ceil(x / d) * d; }
-
-struct Builder {
-  m355_engine* e;
-  double depth, width;
-  int maxc;
-  int ch(int c) const { return make_divisible(std::min(c, maxc) * width, 8); }
-  int rep(int n) const { return n > 1 ? std::max((int)lround(n * depth), 1) : n; }
-
-  int tensor(int H, int W, int C) {
-    Tensor t;
-    t.H = H; t.W = W; t.C = C;
-    e->tensors.push_back(t);
-    return (int)e->tensors.size() - 1;
-  }
-  int logical(const std::string& name, int cin, int cout, int k, int s, int has_bn, int transposed, int act, int groups = 1) {
-    m355_conv_info ci{};
-    snprintf(ci.name, sizeof(ci.name), "%s", name.c_str());
-    ci.cin = cin; ci.cout = cout; ci.k = k; ci.stride = s; ci.has_bn = has_bn; ci.transposed = transposed;
-    ci.act = act; ci.groups = groups;
-    e->convs.push_back(ci);
-    e->conv_loaded.push_back(false);
-    e->conv_phys.push_back(-1);
-    e->conv_phys_off.push_back(0);
-    e->conv_phys_koff.push_back(0);
-    return (int)e->convs.size() - 1;
-  }
-  int phys_from(const std::vector<int>& logicals) {
-    PhysConv p;
-    p.logical = logicals;
-    const m355_conv_info& c0 = e->convs[logicals[0]];
-    p.cin = c0.cin; p.k = c0.k; p.stride = c0.stride; p.act = c0.act; p.transposed = c0.transposed; p.groups = c0.groups;
-    int off = 0;
-    for (int li : logicals) {
-      e->conv_phys[li] = (int)e->phys.size();
-      e->conv_phys_off[li] = off;
-      off += e->convs[li].cout;
-    }
-    p.cout = off;
-    p.macs_px = (double)(p.cin / p.groups) * p.cout * p.k * p.k;
-    e->phys.push_back(p);
-    return (int)e->phys.size() - 1;
-  }
-  // 1x1 convs with DIFFERENT inputs that sit side by side in one tensor, fused into one launch with a
-  // block-diagonal weight matrix: rows = all outputs, K = all inputs, zeros off the diagonal blocks.
-  int phys_diag(const std::vector<int>& logicals) {
-    PhysConv p;
-    p.logical = logicals;
-    const m355_conv_info& c0 = e->convs[logicals[0]];
-    p.k = 1; p.stride = 1; p.act = c0.act; p.transposed = 0; p.diag = 1;
-    int off = 0, koff = 0;
-    for (int li : logicals) {
-      e->conv_phys[li] = (int)e->phys.size();
-      e->conv_phys_off[li] = off;
-      e->conv_phys_koff[li] = koff;
-      off += e->convs[li].cout;
-      koff += e->convs[li].cin;
-      p.macs_px += (double)e->convs[li].cin * e->convs[li].cout;
-    }
-    p.cout = off;
-    p.cin = koff;
-    e->phys.push_back(p);
-    return (int)e->phys.size() - 1;
-  }
-  void add_macs(const Op& op, const PhysConv& p) {
-    const Tensor& ti = e->tensors[op.in.t];
-    if (op.kind == OP_CONVT) {
-      e->macs += (double)(2 * ti.H) * (2 * ti.W) * p.cin * p.cout;
-    } else {
-      const int Ho = (ti.H + 2 * (p.k / 2) - p.k) / p.stride + 1, Wo = (ti.W + 2 * (p.k / 2) - p.k) / p.stride + 1;
-      e->macs += (double)Ho * Wo * p.macs_px;
-    }
-  }
-  // Conv(+BN+SiLU) from slice `in` to slice `out`
-  void conv(const std::string& name, Slice in, Slice out, int k, int s, Slice res = Slice(), Slice in2 = Slice()) {
-    const int li = logical(name, in.c, out.c, k, s, 1, 0, 1);
-    Op op{};
-    op.kind = OP_CONV;
-    op.conv = phys_from({li});
-    op.in = in; op.out = out; op.res = res; op.in2 = in2;
-    add_macs(op, e->phys[op.conv]);
-    e->ops.push_back(op);
-  }
-  // one launch of an existing physical conv (logicals created by the caller, e.g. C3's cv2 || cv1 pair)
-  void conv_phys(int phys, Slice in, Slice out, Slice res = Slice(), Slice in2 = Slice()) {
-    Op op{};
-    op.kind = OP_CONV;
-    op.conv = phys;
-    op.in = in; op.out = out; op.res = res; op.in2 = in2;
-    add_macs(op, e->phys[op.conv]);
-    e->ops.push_back(op);
-  }
-  // C2f: in -> out
-  void c2f(const std::string& name, Slice in, Slice out, int n, bool shortcut, Slice up_src = Slice()) {
-    const Tensor& ti = e->tensors[in.t];
-    const int H = ti.H, W = ti.W;
-    const int c = out.c / 2;
-    const int cat = tensor(H, W, (2 + n) * c);
-    conv(name + ".cv1", in, Slice{cat, 0, 2 * c}, 1, 1, Slice(), up_src);
-    // (the launch has no run-time fallback -- t and y2 have no tensors -- so the kernel's 31-bit offset bounds (c2f_c32_ok) are
-    // checked here for the largest batch the engine takes: s scale at 640 x 640 from 437 images on keeps the three-launch form)
-    const long c2f_px = (long)e->desc.max_batch * H * W;
-    const bool c2f_addr_ok = c2f_px * (2 + n) * c * 2 < (1L << 31) && c2f_px * e->tensors[out.t].C < (1L << 31);
-    if (c == 32 && n == 1 && H % 8 == 0 && W % 16 == 0 && out.c == 64 && c2f_addr_ok && !e->sw.no_c2f32) {
-      // the whole block body in one launch (c2f_c32.hip): t and y2 never reach HBM, no tensor for either
-      const int la = logical(name + ".m.0.cv1", c, c, 3, 1, 1, 0, 1), lb = logical(name + ".m.0.cv2", c, c, 3, 1, 1, 0, 1);
-      const int lc = logical(name + ".cv2", 3 * c, out.c, 1, 1, 1, 0, 1);
-      Op op{};
-      op.kind = OP_C2F32;
-      op.conv = phys_from({la}); op.conv2 = phys_from({lb}); op.conv3 = phys_from({lc});
-      op.in = Slice{cat, 0, 2 * c}; op.out = out; op.shortcut = shortcut ? 1 : 0;
-      e->macs += (double)H * W * (2.0 * 9 * c * c + 3.0 * c * out.c);
-      e->ops.push_back(op);
-      return;
-    }
-    for (int j = 0; j < n; ++j) {
-      const int tmp = tensor(H, W, c);
-      const Slice src{cat, (1 + j) * c, c};
-      if (bneck_pair_shape_ok(c, H, W) && !e->sw.no_pair) {
-        // the whole Bottleneck in one launch, hidden tensor in LDS (conv3x3_planes.hip); `tmp` only serves the two-launch
-        // fallback of a call the kernel's 31-bit buffer offsets cannot address
-        const std::string mn = name + ".m." + std::to_string(j);
-        const int la = logical(mn + ".cv1", c, c, 3, 1, 1, 0, 1), lb = logical(mn + ".cv2", c, c, 3, 1, 1, 0, 1);
-        Op op{};
-        op.kind = OP_PAIR;
-        op.conv = phys_from({la}); op.conv2 = phys_from({lb});
-        e->phys[op.conv].planes = e->phys[op.conv2].planes = 1;
-        op.in = src; op.out = Slice{cat, (2 + j) * c, c}; op.out2 = Slice{tmp, 0, c};
-        op.shortcut = shortcut ? 1 : 0;
-        if (shortcut) op.res = src;
-        e->macs += (double)H * W * 2.0 * 9 * c * c;
-        e->ops.push_back(op);
-        continue;
-      }
-      conv(name + ".m." + std::to_string(j) + ".cv1", src, Slice{tmp, 0, c}, 3, 1);
-      conv(name + ".m." + std::to_string(j) + ".cv2", Slice{tmp, 0, c}, Slice{cat, (2 + j) * c, c}, 3, 1,
-           shortcut ? src : Slice());
-    }
-    conv(name + ".cv2", Slice{cat, 0, (2 + n) * c}, out, 1, 1);
-  }
-};
-
-// model.22 = Segment(nc, 32, npr) on the three feature tensors `feats` (channels fch): Detect branches, coefficient branch,
-// Proto, decode.  Shared by the yolov8-seg and yolov9c-seg graphs.
-int build_segment_head(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const int npr) {
-  const int nc = e->nc, nm = e->nm;
-  const int H3 = e->tensors[feats[0]].H, W3 = e->tensors[feats[0]].W, H4 = e->tensors[feats[1]].H, W4 = e->tensors[feats[1]].W,
-            H5 = e->tensors[feats[2]].H, W5 = e->tensors[feats[2]].W, H2 = 2 * H3, W2 = 2 * W3;
-  const int hc2 = std::max(std::max(16, fch[0] / 4), 64);
-  const int hc3 = std::max(fch[0], std::min(nc, 100));
-  const int hc4 = std::max(fch[0] / 4, nm);
-  e->n3 = H3 * W3; e->n4 = H4 * W4; e->n5 = H5 * W5;
-  e->A = e->n3 + e->n4 + e->n5;
-  const int lvl_off[3] = {0, e->n3, e->n3 + e->n4};
-  // canonical logical order follows the upstream state dict: cv2.{l}.{0,1,2}, cv3.{l}.*, proto.*, cv4.{l}.*.
-  // Physical fusion: cv2.l.0 + cv3.l.0 + cv4.l.0 share their input -> one launch with cout = hc2+hc3+hc4.
-  int l_cv2[3][3], l_cv3[3][3], l_cv4[3][3];
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = "model.22.cv2." + std::to_string(l);
-    l_cv2[l][0] = b.logical(p + ".0", fch[l], hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][1] = b.logical(p + ".1", hc2, hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][2] = b.logical(p + ".2", hc2, 64, 1, 1, 0, 0, 0);
-  }
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = "model.22.cv3." + std::to_string(l);
-    l_cv3[l][0] = b.logical(p + ".0", fch[l], hc3, 3, 1, 1, 0, 1);
-    l_cv3[l][1] = b.logical(p + ".1", hc3, hc3, 3, 1, 1, 0, 1);
-    l_cv3[l][2] = b.logical(p + ".2", hc3, nc, 1, 1, 0, 0, 0);
-  }
-  const int l_p1 = b.logical("model.22.proto.cv1", fch[0], npr, 3, 1, 1, 0, 1);
-  const int l_pu = b.logical("model.22.proto.upsample", npr, npr, 2, 2, 0, 1, 0);
-  const int l_p2 = b.logical("model.22.proto.cv2", npr, npr, 3, 1, 1, 0, 1);
-  const int l_p3 = b.logical("model.22.proto.cv3", npr, nm, 1, 1, 1, 0, 1);
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = "model.22.cv4." + std::to_string(l);
-    l_cv4[l][0] = b.logical(p + ".0", fch[l], hc4, 3, 1, 1, 0, 1);
-    l_cv4[l][1] = b.logical(p + ".1", hc4, hc4, 3, 1, 1, 0, 1);
-    l_cv4[l][2] = b.logical(p + ".2", hc4, nm, 1, 1, 0, 0, 0);
-  }
-  auto add_conv_op = [&](const std::vector<int>& logicals, Slice in, Slice out, int out_ext, int raw_off,
-                         int level_off, OpKind kind = OP_CONV) {
-    Op op{};
-    op.kind = kind;
-    op.conv = b.phys_from(logicals);
-    op.in = in; op.out = out; op.out_ext = out_ext; op.raw_off = raw_off; op.level_off = level_off;
-    b.add_macs(op, e->phys[op.conv]);
-    e->ops.push_back(op);
-  };
-  const int HW[3][2] = {{H3, W3}, {H4, W4}, {H5, W5}};
-  const int* lane_plan = e->sw.lane_plan;   // stream lane of Proto and of the three head levels (plan_lanes)
-  for (int l = 0; l < 3; ++l) {
-    const size_t lvl_first = e->ops.size();
-    const int hcat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3 + hc4);
-    const Slice f{feats[l], 0, fch[l]};
-    add_conv_op({l_cv2[l][0], l_cv3[l][0], l_cv4[l][0]}, f, Slice{hcat, 0, hc2 + hc3 + hc4}, 0, 0, 0);
-    // the three second convs write side by side into one tensor, so that the three 1x1 output convs (64 box bins,
-    // nc classes, nm mask coefficients: different inputs) run as ONE launch with a block-diagonal weight matrix and
-    // write a whole row of the raw head map
-    const int ucat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3 + hc4);
-    add_conv_op({l_cv2[l][1]}, Slice{hcat, 0, hc2}, Slice{ucat, 0, hc2}, 0, 0, 0);
-    add_conv_op({l_cv3[l][1]}, Slice{hcat, hc2, hc3}, Slice{ucat, hc2, hc3}, 0, 0, 0);
-    add_conv_op({l_cv4[l][1]}, Slice{hcat, hc2 + hc3, hc4}, Slice{ucat, hc2 + hc3, hc4}, 0, 0, 0);
-    {
-      Op op{};
-      op.kind = OP_CONV;
-      op.conv = b.phys_diag({l_cv2[l][2], l_cv3[l][2], l_cv4[l][2]});
-      op.in = Slice{ucat, 0, hc2 + hc3 + hc4};
-      op.out = Slice{-1, 0, 64 + nc + nm};
-      op.out_ext = 1; op.raw_off = 0; op.level_off = lvl_off[l];
-      b.add_macs(op, e->phys[op.conv]);
-      e->ops.push_back(op);
-    }
-    for (size_t i = lvl_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[1 + l];
-  }
-  const size_t proto_first = e->ops.size();
-  {
-    const bool fuse2 = !e->sw.no_protofuse && npr % 64 == 0;   // a channel tile (64 or 128) must lie inside one phase
-    const bool fuse3 = fuse2 && npr == 128 && nm == 32 && !e->sw.no_protofuse3;
-    const int pr1 = b.tensor(H3, W3, npr);
-    add_conv_op({l_p1}, Slice{feats[0], 0, fch[0]}, Slice{pr1, 0, npr}, 0, 0, 0);
-    if (!fuse2) {
-      const int pr2 = b.tensor(H2, W2, npr), pr3 = b.tensor(H2, W2, npr);
-      add_conv_op({l_pu}, Slice{pr1, 0, npr}, Slice{pr2, 0, npr}, 0, 0, 0, OP_CONVT);
-      add_conv_op({l_p2}, Slice{pr2, 0, npr}, Slice{pr3, 0, npr}, 0, 0, 0);
-      add_conv_op({l_p3}, Slice{pr3, 0, npr}, Slice{-1, 0, nm}, 2, 0, 0);
-    } else {
-      // ConvTranspose2d(2x2, s2, bias) has no activation, so upsample -> cv2's 3x3 conv is ONE linear map of the
-      // 80x80 tensor: per output phase (py, px) a 2x2 convolution with composed weights (host, fp64).  4 taps instead
-      // of 1 + 9 per output pixel, and the 160x160x128 intermediate (0.42 GB of HBM traffic at batch 32) is gone.
-      // With 128 prototype channels a 128 x 128 tile holds every channel of its pixels, so proto.cv3 (1x1, 128 -> 32)
-      // runs in the same kernel's epilogue and the 160x160x128 tensor is never written at all.
-      Op op{};
-      op.kind = OP_PHASE;
-      PhysConv p;
-      p.logical = {l_pu, l_p2};
-      p.cin = npr; p.cout = npr; p.k = 2; p.stride = 1; p.act = 1; p.composed = 1;
-      p.macs_px = 4.0 * (4.0 * npr) * npr;      // per LOW-resolution pixel: 4 phases x 4 taps x npr x npr
-      if (fuse3) {
-        p.logical.push_back(l_p3);
-        p.l3 = l_p3;
-        p.cout2 = nm;
-        p.macs_px += 4.0 * npr * nm;
-        e->conv_phys[l_p3] = (int)e->phys.size();
-      }
-      e->conv_phys[l_pu] = e->conv_phys[l_p2] = (int)e->phys.size();
-      e->phys.push_back(p);
-      op.conv = (int)e->phys.size() - 1;
-      op.in = Slice{pr1, 0, npr};
-      // the model's nominal MACs (upstream counts ConvT + 3x3 (+ 1x1)) stay in the whole-net figure
-      e->macs += (double)(2 * H3) * (2 * W3) * npr * npr + (double)(2 * H3) * (2 * W3) * npr * npr * 9;
-      if (fuse3) {
-        op.out = Slice{-1, 0, nm};
-        op.out_ext = 2;
-        e->macs += (double)(2 * H3) * (2 * W3) * npr * nm;
-        e->ops.push_back(op);
-      } else {
-        const int pr3 = b.tensor(H2, W2, npr);
-        op.out = Slice{pr3, 0, npr};
-        e->ops.push_back(op);
-        add_conv_op({l_p3}, Slice{pr3, 0, npr}, Slice{-1, 0, nm}, 2, 0, 0);
-      }
-    }
-  }
-  for (size_t i = proto_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[0];
-  {
-    Op op{};
-    op.kind = OP_DECODE;
-    e->ops.push_back(op);
-  }
-  e->proto_h = H2; e->proto_w = W2;
-  return 0;
-}
-
-// yolov9c-seg (SURVEY next row N4: the architecture /root/reference/BscanBased/yolo_seg_train.py:7 names).  GELAN blocks on
-// the same conv kernels: RepNCSPELAN4 = 1x1 -> two (RepCSP -> 3x3) stages -> 1x1 over the zero-copy concat of all four
-// parts; RepCSP = two 1x1 branches, one RepBottleneck (RepConvN arrives from the host as ONE merged 3x3 conv), 1x1;
-// ADown = one pooling kernel (2x2 average, then 3x3 / s2 max on the second channel half) + a 3x3 / s2 and a 1x1 conv
-// writing the two halves of the output; SPPELAN = SPPF's serial pooling between two 1x1 convs.
-// Block structure and names: oracle/yolov9c_seg_oracle.py (exact published parameter counts), spec.py conv_specs_v9c.
-struct V9cBuilder {
-  m355_engine* e;
-  Builder& b;
-  // RepCSP(c1 -> c2) from slice `in` to slice `out`
-  void repcsp(const std::string& name, Slice in, Slice out) {
-    const Tensor& ti = e->tensors[in.t];
-    const int c_ = out.c / 2;
-    const int tmp = b.tensor(ti.H, ti.W, c_), mid = b.tensor(ti.H, ti.W, c_), cat = b.tensor(ti.H, ti.W, 2 * c_);
-    b.conv(name + ".cv1", in, Slice{tmp, 0, c_}, 1, 1);
-    b.conv(name + ".m.0.cv1", Slice{tmp, 0, c_}, Slice{mid, 0, c_}, 3, 1);                        // RepConvN, merged
-    b.conv(name + ".m.0.cv2", Slice{mid, 0, c_}, Slice{cat, 0, c_}, 3, 1, Slice{tmp, 0, c_});     // + shortcut
-    b.conv(name + ".cv2", in, Slice{cat, c_, c_}, 1, 1);
-    b.conv(name + ".cv3", Slice{cat, 0, 2 * c_}, out, 1, 1);
-  }
-  void elan(const std::string& name, Slice in, Slice out, int c3, int c4, Slice up_src = Slice()) {
-    const Tensor& ti = e->tensors[in.t];
-    const int cat = b.tensor(ti.H, ti.W, c3 + 2 * c4);
-    b.conv(name + ".cv1", in, Slice{cat, 0, c3}, 1, 1, Slice(), up_src);
-    const int r1 = b.tensor(ti.H, ti.W, c4), r2 = b.tensor(ti.H, ti.W, c4);
-    repcsp(name + ".cv2.0", Slice{cat, c3 / 2, c3 / 2}, Slice{r1, 0, c4});
-    b.conv(name + ".cv2.1", Slice{r1, 0, c4}, Slice{cat, c3, c4}, 3, 1);
-    repcsp(name + ".cv3.0", Slice{cat, c3, c4}, Slice{r2, 0, c4});
-    b.conv(name + ".cv3.1", Slice{r2, 0, c4}, Slice{cat, c3 + c4, c4}, 3, 1);
-    b.conv(name + ".cv4", Slice{cat, 0, c3 + 2 * c4}, out, 1, 1);
-  }
-  void adown(const std::string& name, Slice in, Slice out) {
-    const Tensor& ti = e->tensors[in.t];
-    const int ch = in.c / 2, co = out.c / 2;
-    const int ta = b.tensor(ti.H - 1, ti.W - 1, ch), tm = b.tensor(ti.H / 2, ti.W / 2, ch);
-    Op op{};
-    op.kind = OP_ADOWN;
-    op.in = in; op.out = Slice{ta, 0, ch}; op.out2 = Slice{tm, 0, ch};
-    e->ops.push_back(op);
-    b.conv(name + ".cv1", Slice{ta, 0, ch}, Slice{out.t, out.off, co}, 3, 2);
-    b.conv(name + ".cv2", Slice{tm, 0, ch}, Slice{out.t, out.off + co, co}, 1, 1);
-  }
-};
-
-int build_graph_v9c(m355_engine* e) {
-  const m355_model_desc& d = e->desc;
-  Builder b{e, 1.0, 1.0, 1024};
-  V9cBuilder v{e, b};
-  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 64 || d.in_w < 64)
-    return e->fail(M355_ERR_INVALID, "in_h/in_w must be multiples of 32, at least 64");
-  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
-  e->nc = d.nc; e->nm = 32;
-  const int H = d.in_h, W = d.in_w;
-  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16, H5 = H / 32, W5 = W / 32;
-  // zero-copy concat buffers: cat11 = [up(x9), x6], cat14 = [up(x12), x4], cat17 = [x16, x12], cat20 = [x19, x9]
-  const int cat11 = b.tensor(H4, W4, 512 + 512), cat14 = b.tensor(H3, W3, 512 + 512);
-  const int cat17 = b.tensor(H4, W4, 256 + 512), cat20 = b.tensor(H5, W5, 512 + 512);
-  const Slice x4{cat14, 512, 512}, x6{cat11, 512, 512}, x9{cat20, 512, 512}, x12{cat17, 256, 512};
-  const int t0 = b.tensor(H1, W1, 64);
-  {
-    const int li = b.logical("model.0", 3, 64, 3, 2, 1, 0, 1);
-    Op op{};
-    op.kind = OP_STEM;
-    op.conv = b.phys_from({li});
-    op.out = Slice{t0, 0, 64};
-    op.Hi = H; op.Wi = W;
-    e->macs += (double)H1 * W1 * 64 * 27;
-    e->ops.push_back(op);
-  }
-  const int t1 = b.tensor(H2, W2, 128), t2 = b.tensor(H2, W2, 256), t3 = b.tensor(H3, W3, 256), t5 = b.tensor(H4, W4, 512),
-            t7 = b.tensor(H5, W5, 512), t8 = b.tensor(H5, W5, 512);
-  b.conv("model.1", Slice{t0, 0, 64}, Slice{t1, 0, 128}, 3, 2);
-  v.elan("model.2", Slice{t1, 0, 128}, Slice{t2, 0, 256}, 128, 64);
-  v.adown("model.3", Slice{t2, 0, 256}, Slice{t3, 0, 256});
-  v.elan("model.4", Slice{t3, 0, 256}, x4, 256, 128);
-  v.adown("model.5", x4, Slice{t5, 0, 512});
-  v.elan("model.6", Slice{t5, 0, 512}, x6, 512, 256);
-  v.adown("model.7", x6, Slice{t7, 0, 512});
-  v.elan("model.8", Slice{t7, 0, 512}, Slice{t8, 0, 512}, 512, 256);
-  {
-    const int sp = b.tensor(H5, W5, 4 * 256);                  // SPPELAN: cv1 -> three serial 5x5 max pools -> cv5
-    b.conv("model.9.cv1", Slice{t8, 0, 512}, Slice{sp, 0, 256}, 1, 1);
-    Op op{};
-    op.kind = OP_POOL;
-    op.in = Slice{sp, 0, 256};
-    op.out = Slice{sp, 256, 3 * 256};
-    e->ops.push_back(op);
-    b.conv("model.9.cv5", Slice{sp, 0, 1024}, x9, 1, 1);
-  }
-  const bool upfuse = !e->sw.no_upfuse;
-  auto up = [&](Slice src, Slice dst) {
-    if (upfuse) return;
-    Op op{};
-    op.kind = OP_UP;
-    op.in = src; op.out = dst;
-    e->ops.push_back(op);
-  };
-  up(x9, Slice{cat11, 0, 512});
-  v.elan("model.12", Slice{cat11, 0, 1024}, x12, 512, 256, upfuse ? x9 : Slice());
-  up(x12, Slice{cat14, 0, 512});
-  const int t15 = b.tensor(H3, W3, 256), t18 = b.tensor(H4, W4, 512), t21 = b.tensor(H5, W5, 512);
-  v.elan("model.15", Slice{cat14, 0, 1024}, Slice{t15, 0, 256}, 256, 128, upfuse ? x12 : Slice());
-  v.adown("model.16", Slice{t15, 0, 256}, Slice{cat17, 0, 256});
-  v.elan("model.18", Slice{cat17, 0, 768}, Slice{t18, 0, 512}, 512, 256);
-  v.adown("model.19", Slice{t18, 0, 512}, Slice{cat20, 0, 512});
-  v.elan("model.21", Slice{cat20, 0, 1024}, Slice{t21, 0, 512}, 512, 256);
-  const int feats[3] = {t15, t18, t21};
-  const int fch[3] = {256, 512, 512};
-  return build_segment_head(e, b, feats, fch, 256);
-}
-
-// model.24 = Detect(nc) of YOLOv5u (box-only, nm = 0): per level the two first 3x3 convs (cv2.l.0, cv3.l.0) share their input
-// and run as one launch, the two second convs write side by side, and the two 1x1 output convs run as one block-diagonal launch
-// writing whole raw rows of 64 + nc.  The decode launch turns them into prediction rows of 4 + nc.
-int build_detect_head(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const std::string& pre) {
-  const int nc = e->nc;
-  const int hc2 = std::max(std::max(16, fch[0] / 4), 64);
-  const int hc3 = std::max(fch[0], std::min(nc, 100));
-  int HW[3][2];
-  for (int l = 0; l < 3; ++l) { HW[l][0] = e->tensors[feats[l]].H; HW[l][1] = e->tensors[feats[l]].W; }
-  e->n3 = HW[0][0] * HW[0][1]; e->n4 = HW[1][0] * HW[1][1]; e->n5 = HW[2][0] * HW[2][1];
-  e->A = e->n3 + e->n4 + e->n5;
-  const int lvl_off[3] = {0, e->n3, e->n3 + e->n4};
-  int l_cv2[3][3], l_cv3[3][3];
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = pre + ".cv2." + std::to_string(l);
-    l_cv2[l][0] = b.logical(p + ".0", fch[l], hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][1] = b.logical(p + ".1", hc2, hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][2] = b.logical(p + ".2", hc2, 64, 1, 1, 0, 0, 0);
-  }
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = pre + ".cv3." + std::to_string(l);
-    l_cv3[l][0] = b.logical(p + ".0", fch[l], hc3, 3, 1, 1, 0, 1);
-    l_cv3[l][1] = b.logical(p + ".1", hc3, hc3, 3, 1, 1, 0, 1);
-    l_cv3[l][2] = b.logical(p + ".2", hc3, nc, 1, 1, 0, 0, 0);
-  }
-  const int lane_plan[3] = {1, 1, 0};   // the stride-8 and stride-16 levels beside the stride-32 level on the caller's stream
-  for (int l = 0; l < 3; ++l) {
-    const size_t lvl_first = e->ops.size();
-    const int hcat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3), ucat = b.tensor(HW[l][0], HW[l][1], hc2 + hc3);
-    b.conv_phys(b.phys_from({l_cv2[l][0], l_cv3[l][0]}), Slice{feats[l], 0, fch[l]}, Slice{hcat, 0, hc2 + hc3});
-    b.conv_phys(b.phys_from({l_cv2[l][1]}), Slice{hcat, 0, hc2}, Slice{ucat, 0, hc2});
-    b.conv_phys(b.phys_from({l_cv3[l][1]}), Slice{hcat, hc2, hc3}, Slice{ucat, hc2, hc3});
-    Op op{};
-    op.kind = OP_CONV;
-    op.conv = b.phys_diag({l_cv2[l][2], l_cv3[l][2]});
-    op.in = Slice{ucat, 0, hc2 + hc3};
-    op.out = Slice{-1, 0, 64 + nc};
-    op.out_ext = 1; op.raw_off = 0; op.level_off = lvl_off[l];
-    b.add_macs(op, e->phys[op.conv]);
-    e->ops.push_back(op);
-    for (size_t i = lvl_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[l];
-  }
-  Op op{};
-  op.kind = OP_DECODE;
-  e->ops.push_back(op);
-  e->proto_h = e->proto_w = 0;
-  return 0;
-}
-
-// C3(c1 -> c2, n, shortcut) of YOLOv5u in ONE buffer X = [m out | cv2 out | cv1 out] (3 c_ channels, c_ = c2 / 2): cv2 || cv1
-// are one 1x1 launch into X[c_, 3 c_); the Bottleneck chain (1x1 then 3x3, + input when shortcut) reads X[2 c_:] and leaves its
-// result in X[:c_] (ping-pong tensors in between for n > 1: a residual never aliases its own output); cv3 reads X[:2 c_], which is
-// upstream's cat(m(cv1 x), cv2 x) without a copy.
-void build_c3(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out, int n, bool shortcut, Slice up_src = Slice()) {
-  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c_ = out.c / 2;
-  const int X = b.tensor(H, W, 3 * c_);
-  const int l1 = b.logical(name + ".cv1", in.c, c_, 1, 1, 1, 0, 1);
-  const int l2 = b.logical(name + ".cv2", in.c, c_, 1, 1, 1, 0, 1);
-  const int l3 = b.logical(name + ".cv3", 2 * c_, out.c, 1, 1, 1, 0, 1);
-  b.conv_phys(b.phys_from({l2, l1}), in, Slice{X, c_, 2 * c_}, Slice(), up_src);
-  const int tmp = b.tensor(H, W, c_);
-  int pp[2] = {-1, -1};
-  if (n > 1) { pp[0] = b.tensor(H, W, c_); pp[1] = n > 2 ? b.tensor(H, W, c_) : -1; }
-  Slice src{X, 2 * c_, c_};
-  for (int j = 0; j < n; ++j) {
-    const std::string mn = name + ".m." + std::to_string(j);
-    const int la = b.logical(mn + ".cv1", c_, c_, 1, 1, 1, 0, 1), lb = b.logical(mn + ".cv2", c_, c_, 3, 1, 1, 0, 1);
-    const Slice dst = j == n - 1 ? Slice{X, 0, c_} : Slice{pp[j & 1], 0, c_};
-    b.conv_phys(b.phys_from({la}), src, Slice{tmp, 0, c_});
-    b.conv_phys(b.phys_from({lb}), Slice{tmp, 0, c_}, dst, shortcut ? src : Slice());
-    src = dst;
-  }
-  b.conv_phys(b.phys_from({l3}), Slice{X, 0, 2 * c_}, out);
-}
-
-// YOLOv5u (/root/reference/BscanBased/yolo5s_retrain.py:6 loads yolov5su.pt; upstream cfg/models/v5/yolov5.yaml with
-// the anchor-free Detect head).  model.0 is the 6x6 / s2 / p2 stem (conv_stem6_s2.hip); every other conv goes through the planner's
-// usual kernel rules.  Names and canonical order: spec.py conv_specs_v5u; block structure: tests/yolov5u_det_ref.py.
-int build_graph_v5u(m355_engine* e) {
-  const m355_model_desc& d = e->desc;
-  Builder b{e, 0, 0, 1024};
-  switch (d.scale & 0xff) {
-    case 'n': b.depth = 0.33; b.width = 0.25; break;
-    case 's': b.depth = 0.33; b.width = 0.50; break;
-    case 'm': b.depth = 0.67; b.width = 0.75; break;
-    default: return e->fail(M355_ERR_INVALID, "YOLOv5u scale must be n, s or m (l and x are not built)");
-  }
-  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 64 || d.in_w < 64)
-    return e->fail(M355_ERR_INVALID, "in_h/in_w must be multiples of 32, at least 64");
-  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
-  e->nc = d.nc; e->nm = 0;
-  const int c64 = b.ch(64), c128 = b.ch(128), c256 = b.ch(256), c512 = b.ch(512), c1024 = b.ch(1024);
-  const int H = d.in_h, W = d.in_w;
-  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16, H5 = H / 32, W5 = W / 32;
-  // zero-copy concat buffers: cat12 = [up(x10), x6], cat16 = [up(x14), x4], cat19 = [x18, x14], cat22 = [x21, x10]
-  const int cat12 = b.tensor(H4, W4, 2 * c512), cat16 = b.tensor(H3, W3, 2 * c256);
-  const int cat19 = b.tensor(H4, W4, 2 * c256), cat22 = b.tensor(H5, W5, 2 * c512);
-  const Slice x4{cat16, c256, c256}, x6{cat12, c512, c512}, x10{cat22, c512, c512}, x14{cat19, c256, c256};
-  const int t0 = b.tensor(H1, W1, c64);
-  {
-    const int li = b.logical("model.0", 3, c64, 6, 2, 1, 0, 1);
-    Op op{};
-    op.kind = OP_STEM;
-    op.conv = b.phys_from({li});
-    op.out = Slice{t0, 0, c64};
-    op.Hi = H; op.Wi = W;
-    e->macs += (double)H1 * W1 * c64 * 108;
-    e->ops.push_back(op);
-  }
-  const int t1 = b.tensor(H2, W2, c128), t2 = b.tensor(H2, W2, c128), t3 = b.tensor(H3, W3, c256), t5 = b.tensor(H4, W4, c512),
-            t7 = b.tensor(H5, W5, c1024), t8 = b.tensor(H5, W5, c1024), t9 = b.tensor(H5, W5, c1024);
-  b.conv("model.1", Slice{t0, 0, c64}, Slice{t1, 0, c128}, 3, 2);
-  build_c3(e, b, "model.2", Slice{t1, 0, c128}, Slice{t2, 0, c128}, b.rep(3), true);
-  b.conv("model.3", Slice{t2, 0, c128}, Slice{t3, 0, c256}, 3, 2);
-  build_c3(e, b, "model.4", Slice{t3, 0, c256}, x4, b.rep(6), true);
-  b.conv("model.5", x4, Slice{t5, 0, c512}, 3, 2);
-  build_c3(e, b, "model.6", Slice{t5, 0, c512}, x6, b.rep(9), true);
-  b.conv("model.7", x6, Slice{t7, 0, c1024}, 3, 2);
-  build_c3(e, b, "model.8", Slice{t7, 0, c1024}, Slice{t8, 0, c1024}, b.rep(3), true);
-  {
-    const int c_ = c1024 / 2;
-    const int sp = b.tensor(H5, W5, 4 * c_);                   // SPPF: cv1 -> three serial 5x5 max pools -> cv2
-    b.conv("model.9.cv1", Slice{t8, 0, c1024}, Slice{sp, 0, c_}, 1, 1);
-    Op op{};
-    op.kind = OP_POOL;
-    op.in = Slice{sp, 0, c_};
-    op.out = Slice{sp, c_, 3 * c_};
-    e->ops.push_back(op);
-    b.conv("model.9.cv2", Slice{sp, 0, 4 * c_}, Slice{t9, 0, c1024}, 1, 1);
-  }
-  b.conv("model.10", Slice{t9, 0, c1024}, x10, 1, 1);
-  // 11/12 and 15/16: Upsample + Concat read through by the next C3's cv2 || cv1 (M355_NO_UPFUSE: materialised by upsample2x)
-  const bool upfuse = !e->sw.no_upfuse;
-  auto up = [&](Slice src, Slice dst) {
-    if (upfuse) return;
-    Op op{};
-    op.kind = OP_UP;
-    op.in = src; op.out = dst;
-    e->ops.push_back(op);
-  };
-  const int t13 = b.tensor(H4, W4, c512), t17 = b.tensor(H3, W3, c256), t20 = b.tensor(H4, W4, c512), t23 = b.tensor(H5, W5, c1024);
-  up(x10, Slice{cat12, 0, c512});
-  build_c3(e, b, "model.13", Slice{cat12, 0, 2 * c512}, Slice{t13, 0, c512}, b.rep(3), false, upfuse ? x10 : Slice());
-  b.conv("model.14", Slice{t13, 0, c512}, x14, 1, 1);
-  up(x14, Slice{cat16, 0, c256});
-  build_c3(e, b, "model.17", Slice{cat16, 0, 2 * c256}, Slice{t17, 0, c256}, b.rep(3), false, upfuse ? x14 : Slice());
-  b.conv("model.18", Slice{t17, 0, c256}, Slice{cat19, 0, c256}, 3, 2);
-  build_c3(e, b, "model.20", Slice{cat19, 0, 2 * c256}, Slice{t20, 0, c512}, b.rep(3), false);
-  b.conv("model.21", Slice{t20, 0, c512}, Slice{cat22, 0, c512}, 3, 2);
-  build_c3(e, b, "model.23", Slice{cat22, 0, 2 * c512}, Slice{t23, 0, c1024}, b.rep(3), false);
-  const int feats[3] = {t17, t20, t23};
-  const int fch[3] = {c256, c512, c1024};
-  return build_detect_head(e, b, feats, fch, "model.24");
-}
-
-// One depthwise 3x3 launch (dwconv3x3.hip) of the logical conv li: in -> out, both channel slices
-void dwconv_op(m355_engine* e, Builder& b, int li, Slice in, Slice out) {
-  Op op{};
-  op.kind = OP_DWCONV;
-  op.conv = b.phys_from({li});
-  op.in = in; op.out = out;
-  b.add_macs(op, e->phys[op.conv]);
-  e->ops.push_back(op);
-}
-
-// model.23 = Detect(nc) of YOLO11 (box-only, nm = 0).  Box branch as YOLOv8's; the class branch is DWConv 3x3 -> 1x1 ->
-// DWConv 3x3 -> 1x1 (cv3.l.0.0 .. cv3.l.1.1), so cv2.l.0 no longer shares its launch with the class branch's first conv.  The
-// two second stages write side by side and the two output 1x1 convs run as one block-diagonal launch writing raw rows of
-// 64 + nc, as in build_detect_head.
-int build_detect_head_y11(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const std::string& pre) {
-  const int nc = e->nc;
-  const int hc2 = std::max(std::max(16, fch[0] / 4), 64);
-  const int hc3 = std::max(fch[0], std::min(nc, 100));
-  if (hc3 % 8)
-    return e->fail(M355_ERR_INVALID, "YOLO11: the class branch width max(P3 channels, min(nc, 100)) must be a multiple of 8 "
-                                     "(the depthwise kernel's 16-byte channel groups): n scale with nc in 65..100 not a multiple of 8");
-  int HW[3][2];
-  for (int l = 0; l < 3; ++l) { HW[l][0] = e->tensors[feats[l]].H; HW[l][1] = e->tensors[feats[l]].W; }
-  e->n3 = HW[0][0] * HW[0][1]; e->n4 = HW[1][0] * HW[1][1]; e->n5 = HW[2][0] * HW[2][1];
-  e->A = e->n3 + e->n4 + e->n5;
-  const int lvl_off[3] = {0, e->n3, e->n3 + e->n4};
-  int l_cv2[3][3], l_cv3[3][5];
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = pre + ".cv2." + std::to_string(l);
-    l_cv2[l][0] = b.logical(p + ".0", fch[l], hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][1] = b.logical(p + ".1", hc2, hc2, 3, 1, 1, 0, 1);
-    l_cv2[l][2] = b.logical(p + ".2", hc2, 64, 1, 1, 0, 0, 0);
-  }
-  for (int l = 0; l < 3; ++l) {
-    const std::string p = pre + ".cv3." + std::to_string(l);
-    l_cv3[l][0] = b.logical(p + ".0.0", fch[l], fch[l], 3, 1, 1, 0, 1, fch[l]);
-    l_cv3[l][1] = b.logical(p + ".0.1", fch[l], hc3, 1, 1, 1, 0, 1);
-    l_cv3[l][2] = b.logical(p + ".1.0", hc3, hc3, 3, 1, 1, 0, 1, hc3);
-    l_cv3[l][3] = b.logical(p + ".1.1", hc3, hc3, 1, 1, 1, 0, 1);
-    l_cv3[l][4] = b.logical(p + ".2", hc3, nc, 1, 1, 0, 0, 0);
-  }
-  const int lane_plan[3] = {1, 1, 0};   // as build_detect_head
-  for (int l = 0; l < 3; ++l) {
-    const size_t lvl_first = e->ops.size();
-    const int H = HW[l][0], W = HW[l][1];
-    const int hb = b.tensor(H, W, hc2), ucat = b.tensor(H, W, hc2 + hc3);
-    const int d0 = b.tensor(H, W, fch[l]), e0 = b.tensor(H, W, hc3), d1 = b.tensor(H, W, hc3);
-    b.conv_phys(b.phys_from({l_cv2[l][0]}), Slice{feats[l], 0, fch[l]}, Slice{hb, 0, hc2});
-    b.conv_phys(b.phys_from({l_cv2[l][1]}), Slice{hb, 0, hc2}, Slice{ucat, 0, hc2});
-    dwconv_op(e, b, l_cv3[l][0], Slice{feats[l], 0, fch[l]}, Slice{d0, 0, fch[l]});
-    b.conv_phys(b.phys_from({l_cv3[l][1]}), Slice{d0, 0, fch[l]}, Slice{e0, 0, hc3});
-    dwconv_op(e, b, l_cv3[l][2], Slice{e0, 0, hc3}, Slice{d1, 0, hc3});
-    b.conv_phys(b.phys_from({l_cv3[l][3]}), Slice{d1, 0, hc3}, Slice{ucat, hc2, hc3});
-    Op op{};
-    op.kind = OP_CONV;
-    op.conv = b.phys_diag({l_cv2[l][2], l_cv3[l][4]});
-    op.in = Slice{ucat, 0, hc2 + hc3};
-    op.out = Slice{-1, 0, 64 + nc};
-    op.out_ext = 1; op.raw_off = 0; op.level_off = lvl_off[l];
-    b.add_macs(op, e->phys[op.conv]);
-    e->ops.push_back(op);
-    for (size_t i = lvl_first; i < e->ops.size(); ++i) e->ops[i].lane = lane_plan[l];
-  }
-  Op op{};
-  op.kind = OP_DECODE;
-  e->ops.push_back(op);
-  e->proto_h = e->proto_w = 0;
-  return 0;
-}
-
-// C3k2(c1 -> c2, c3k, e) of YOLO11 (shortcut on) in ONE buffer X = [cv1 out (2c) | m.0 out (c)], c = int(c2 e): C2f's
-// zero-copy layout, cv2 reads X whole.  m.0 = Bottleneck(c, c, e=0.5): 3x3 c -> c/2, 3x3 c/2 -> c + its input; or, with c3k,
-// C3k(c, c, n=2) in a buffer Y = [m out | cv2 out | cv1 out] (c/2 each) as build_c3, with two 3x3 -> 3x3 Bottlenecks.
-void build_c3k2(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out, bool c3k, double ew, Slice up_src = Slice()) {
-  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c = (int)(out.c * ew);
-  const int X = b.tensor(H, W, 3 * c);
-  const int l1 = b.logical(name + ".cv1", in.c, 2 * c, 1, 1, 1, 0, 1);
-  const int l2 = b.logical(name + ".cv2", 3 * c, out.c, 1, 1, 1, 0, 1);
-  b.conv_phys(b.phys_from({l1}), in, Slice{X, 0, 2 * c}, Slice(), up_src);
-  const Slice src{X, c, c}, dst{X, 2 * c, c};
-  const std::string mn = name + ".m.0";
-  if (!c3k) {
-    const int h = c / 2;
-    const int la = b.logical(mn + ".cv1", c, h, 3, 1, 1, 0, 1), lb = b.logical(mn + ".cv2", h, c, 3, 1, 1, 0, 1);
-    const int tmp = b.tensor(H, W, h);
-    b.conv_phys(b.phys_from({la}), src, Slice{tmp, 0, h});
-    b.conv_phys(b.phys_from({lb}), Slice{tmp, 0, h}, dst, src);
-  } else {
-    const int c_ = c / 2;
-    const int k1 = b.logical(mn + ".cv1", c, c_, 1, 1, 1, 0, 1), k2 = b.logical(mn + ".cv2", c, c_, 1, 1, 1, 0, 1);
-    const int k3 = b.logical(mn + ".cv3", 2 * c_, c, 1, 1, 1, 0, 1);
-    int la[2], lb[2];
-    for (int j = 0; j < 2; ++j) {
-      la[j] = b.logical(mn + ".m." + std::to_string(j) + ".cv1", c_, c_, 3, 1, 1, 0, 1);
-      lb[j] = b.logical(mn + ".m." + std::to_string(j) + ".cv2", c_, c_, 3, 1, 1, 0, 1);
-    }
-    const int Y = b.tensor(H, W, 3 * c_), tmp = b.tensor(H, W, c_), mid = b.tensor(H, W, c_);
-    b.conv_phys(b.phys_from({k2, k1}), src, Slice{Y, c_, 2 * c_});
-    b.conv_phys(b.phys_from({la[0]}), Slice{Y, 2 * c_, c_}, Slice{tmp, 0, c_});
-    b.conv_phys(b.phys_from({lb[0]}), Slice{tmp, 0, c_}, Slice{mid, 0, c_}, Slice{Y, 2 * c_, c_});
-    b.conv_phys(b.phys_from({la[1]}), Slice{mid, 0, c_}, Slice{tmp, 0, c_});
-    b.conv_phys(b.phys_from({lb[1]}), Slice{tmp, 0, c_}, Slice{Y, 0, c_}, Slice{mid, 0, c_});
-    b.conv_phys(b.phys_from({k3}), Slice{Y, 0, 2 * c_}, dst);
-  }
-  b.conv_phys(b.phys_from({l2}), Slice{X, 0, 3 * c}, out);
-}
-
-// C2PSA(c1) of YOLO11 with one PSABlock, c = c1 / 2, heads = c / 64.  X = [a | b] is cv1's output; the block's result b2
-// overwrites b in place (b's last readers, qkv and proj's residual, run before), so cv2 reads X = cat(a, b2) without a copy.
-//   qkv (1x1, BN, no act) -> QKV;  OP_PSA_ATTN: O = attention + pe(v) (psa_attn.hip);  proj (1x1, no act) + b -> B1;
-//   ffn.0 (1x1 + SiLU) -> F;  ffn.1 (1x1, no act) + B1 -> X[c:];  cv2 -> out.  The two residuals are epilogue adds.
-void build_c2psa(m355_engine* e, Builder& b, const std::string& name, Slice in, Slice out) {
-  const int H = e->tensors[in.t].H, W = e->tensors[in.t].W, c1 = in.c, c = c1 / 2;
-  const std::string pre = name + ".m.0.";
-  const int l_cv1 = b.logical(name + ".cv1", c1, 2 * c, 1, 1, 1, 0, 1), l_cv2 = b.logical(name + ".cv2", 2 * c, c1, 1, 1, 1, 0, 1);
-  const int l_qkv = b.logical(pre + "attn.qkv", c, 2 * c, 1, 1, 1, 0, 0);
-  const int l_proj = b.logical(pre + "attn.proj", c, c, 1, 1, 1, 0, 0);
-  const int l_pe = b.logical(pre + "attn.pe", c, c, 3, 1, 1, 0, 0, c);
-  const int l_f0 = b.logical(pre + "ffn.0", c, 2 * c, 1, 1, 1, 0, 1);
-  const int l_f1 = b.logical(pre + "ffn.1", 2 * c, c, 1, 1, 1, 0, 0);
-  const int X = b.tensor(H, W, 2 * c), QKV = b.tensor(H, W, 2 * c), O = b.tensor(H, W, c), B1 = b.tensor(H, W, c), F = b.tensor(H, W, 2 * c);
-  b.conv_phys(b.phys_from({l_cv1}), in, Slice{X, 0, 2 * c});
-  b.conv_phys(b.phys_from({l_qkv}), Slice{X, c, c}, Slice{QKV, 0, 2 * c});
-  {
-    Op op{};
-    op.kind = OP_PSA_ATTN;
-    op.conv = b.phys_from({l_pe});
-    op.heads = c / 64;
-    op.in = Slice{QKV, 0, 2 * c};
-    op.out = Slice{O, 0, c};
-    b.add_macs(op, e->phys[op.conv]);   // the pe conv; the two attention products are in the op table's FLOPs
-    e->ops.push_back(op);
-  }
-  b.conv_phys(b.phys_from({l_proj}), Slice{O, 0, c}, Slice{B1, 0, c}, Slice{X, c, c});
-  b.conv_phys(b.phys_from({l_f0}), Slice{B1, 0, c}, Slice{F, 0, 2 * c});
-  b.conv_phys(b.phys_from({l_f1}), Slice{F, 0, 2 * c}, Slice{X, c, c}, Slice{B1, 0, c});
-  b.conv_phys(b.phys_from({l_cv2}), Slice{X, 0, 2 * c}, out);
-}
-
-// YOLO11 (BscanBased/yolo/yolo_bbox_retrain.py trains yolo11n; upstream cfg/models/11/yolo11.yaml, Detect at
-// model.23).  Depth 0.5: every repeated block has n = 1.  Names and canonical order: spec.py conv_specs_y11; block structure:
-// tests/yolo11_det_ref.py.  The stem and every plain conv go through the planner's usual rules; the depthwise convs run on
-// dwconv3x3.hip and the attention core on psa_attn.hip.
-int build_graph_y11(m355_engine* e) {
-  const m355_model_desc& d = e->desc;
-  Builder b{e, 0.5, 0, 1024};
-  bool c3k_all = false;    // upstream parse_model: every C3k2 of the m (l, x) scale uses C3k
-  switch (d.scale & 0xff) {
-    case 'n': b.width = 0.25; break;
-    case 's': b.width = 0.50; break;
-    case 'm': b.width = 1.00; b.maxc = 512; c3k_all = true; break;
-    default: return e->fail(M355_ERR_INVALID, "YOLO11 scale must be n, s or m (l and x are not built)");
-  }
-  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 64 || d.in_w < 64)
-    return e->fail(M355_ERR_INVALID, "in_h/in_w must be multiples of 32, at least 64");
-  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
-  e->nc = d.nc; e->nm = 0;
-  const int c64 = b.ch(64), c128 = b.ch(128), c256 = b.ch(256), c512 = b.ch(512), c1024 = b.ch(1024);
-  const int H = d.in_h, W = d.in_w;
-  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16, H5 = H / 32, W5 = W / 32;
-  // zero-copy concat buffers: cat12 = [up(x10), x6], cat15 = [up(x13), x4], cat18 = [x17, x13], cat21 = [x20, x10]
-  const int cat12 = b.tensor(H4, W4, c1024 + c512), cat15 = b.tensor(H3, W3, c512 + c512);
-  const int cat18 = b.tensor(H4, W4, c256 + c512), cat21 = b.tensor(H5, W5, c512 + c1024);
-  const Slice x4{cat15, c512, c512}, x6{cat12, c1024, c512}, x10{cat21, c512, c1024}, x13{cat18, c256, c512};
-  const int t0 = b.tensor(H1, W1, c64);
-  {
-    const int li = b.logical("model.0", 3, c64, 3, 2, 1, 0, 1);
-    Op op{};
-    op.kind = OP_STEM;
-    op.conv = b.phys_from({li});
-    op.out = Slice{t0, 0, c64};
-    op.Hi = H; op.Wi = W;
-    e->macs += (double)H1 * W1 * c64 * 27;
-    e->ops.push_back(op);
-  }
-  const int t1 = b.tensor(H2, W2, c128), t2 = b.tensor(H2, W2, c256), t3 = b.tensor(H3, W3, c256), t5 = b.tensor(H4, W4, c512),
-            t7 = b.tensor(H5, W5, c1024), t8 = b.tensor(H5, W5, c1024), t9 = b.tensor(H5, W5, c1024);
-  b.conv("model.1", Slice{t0, 0, c64}, Slice{t1, 0, c128}, 3, 2);
-  build_c3k2(e, b, "model.2", Slice{t1, 0, c128}, Slice{t2, 0, c256}, c3k_all, 0.25);
-  b.conv("model.3", Slice{t2, 0, c256}, Slice{t3, 0, c256}, 3, 2);
-  build_c3k2(e, b, "model.4", Slice{t3, 0, c256}, x4, c3k_all, 0.25);
-  b.conv("model.5", x4, Slice{t5, 0, c512}, 3, 2);
-  build_c3k2(e, b, "model.6", Slice{t5, 0, c512}, x6, true, 0.5);
-  b.conv("model.7", x6, Slice{t7, 0, c1024}, 3, 2);
-  build_c3k2(e, b, "model.8", Slice{t7, 0, c1024}, Slice{t8, 0, c1024}, true, 0.5);
-  {
-    const int c_ = c1024 / 2;
-    const int sp = b.tensor(H5, W5, 4 * c_);                   // SPPF: cv1 -> three serial 5x5 max pools -> cv2
-    b.conv("model.9.cv1", Slice{t8, 0, c1024}, Slice{sp, 0, c_}, 1, 1);
-    Op op{};
-    op.kind = OP_POOL;
-    op.in = Slice{sp, 0, c_};
-    op.out = Slice{sp, c_, 3 * c_};
-    e->ops.push_back(op);
-    b.conv("model.9.cv2", Slice{sp, 0, 4 * c_}, Slice{t9, 0, c1024}, 1, 1);
-  }
-  build_c2psa(e, b, "model.10", Slice{t9, 0, c1024}, x10);
-  // 11/12 and 14/15: Upsample + Concat read through by the next C3k2's cv1 (M355_NO_UPFUSE: materialised by upsample2x)
-  const bool upfuse = !e->sw.no_upfuse;
-  auto up = [&](Slice src, Slice dst) {
-    if (upfuse) return;
-    Op op{};
-    op.kind = OP_UP;
-    op.in = src; op.out = dst;
-    e->ops.push_back(op);
-  };
-  const int t16 = b.tensor(H3, W3, c256), t19 = b.tensor(H4, W4, c512), t22 = b.tensor(H5, W5, c1024);
-  up(x10, Slice{cat12, 0, c1024});
-  build_c3k2(e, b, "model.13", Slice{cat12, 0, c1024 + c512}, x13, c3k_all, 0.5, upfuse ? x10 : Slice());
-  up(x13, Slice{cat15, 0, c512});
-  build_c3k2(e, b, "model.16", Slice{cat15, 0, c512 + c512}, Slice{t16, 0, c256}, c3k_all, 0.5, upfuse ? x13 : Slice());
-  b.conv("model.17", Slice{t16, 0, c256}, Slice{cat18, 0, c256}, 3, 2);
-  build_c3k2(e, b, "model.19", Slice{cat18, 0, c256 + c512}, Slice{t19, 0, c512}, c3k_all, 0.5);
-  b.conv("model.20", Slice{t19, 0, c512}, Slice{cat21, 0, c512}, 3, 2);
-  build_c3k2(e, b, "model.22", Slice{cat21, 0, c512 + c1024}, Slice{t22, 0, c1024}, true, 0.5);
-  const int feats[3] = {t16, t19, t22};
-  const int fch[3] = {c256, c512, c1024};
-  return build_detect_head_y11(e, b, feats, fch, "model.23");
-}
-
-int build_graph(m355_engine* e) {
-  const m355_model_desc& d = e->desc;
-  if ((d.scale >> 8) == '5') return build_graph_v5u(e);
-  if ((d.scale >> 8) == '1') return build_graph_y11(e);
-  if ((d.scale >> 8) != 0) return e->fail(M355_ERR_INVALID, "unknown model family in the high byte of m355_model_desc.scale");
-  if (d.scale == 'c') return build_graph_v9c(e);
-  Builder b{e, 0, 0, 0};
-  switch (d.scale) {
-    case 'n': b.depth = 0.33; b.width = 0.25; b.maxc = 1024; break;
-    case 's': b.depth = 0.33; b.width = 0.50; b.maxc = 1024; break;
-    case 'm': b.depth = 0.67; b.width = 0.75; b.maxc = 768; break;
-    case 'l': b.depth = 1.00; b.width = 1.00; b.maxc = 512; break;
-    case 'x': b.depth = 1.00; b.width = 1.25; b.maxc = 512; break;
-    default: return e->fail(M355_ERR_INVALID, "scale must be one of n,s,m,l,x (yolov8-seg) or c (yolov9c-seg)");
-  }
-  if (d.in_h % 32 || d.in_w % 32 || d.in_h < 32 || d.in_w < 32)
-    return e->fail(M355_ERR_INVALID, "in_h/in_w must be positive multiples of 32");
-  if (d.nc < 1 || d.max_batch < 1) return e->fail(M355_ERR_INVALID, "nc and max_batch must be >= 1");
-  const int nc = d.nc, nm = 32;
-  e->nc = nc; e->nm = nm;
-  const int c64 = b.ch(64), c128 = b.ch(128), c256 = b.ch(256), c512 = b.ch(512), c1024 = b.ch(1024);
-  const int H = d.in_h, W = d.in_w;
-  const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16,
-            H5 = H / 32, W5 = W / 32;
-  if (c64 != 16 && c64 != 32 && c64 != 48 && c64 != 64 && c64 != 80)
-    return e->fail(M355_ERR_INVALID, "unsupported stem width");
-
-  // concat buffers (zero-copy): cat11=[up(x9), x6] cat14=[up(x12), x4] cat17=[x16, x12] cat20=[x19, x9]
-  const int cat11 = b.tensor(H4, W4, c1024 + c512);
-  const int cat14 = b.tensor(H3, W3, c512 + c256);
-  const int cat17 = b.tensor(H4, W4, c256 + c512);
-  const int cat20 = b.tensor(H5, W5, c512 + c1024);
-  const Slice x4{cat14, c512, c256}, x6{cat11, c1024, c512}, x9{cat20, c512, c1024}, x12{cat17, c256, c512};
-
-  // 0: stem
-  const int t0 = b.tensor(H1, W1, c64);
-  {
-    const int li = b.logical("model.0", 3, c64, 3, 2, 1, 0, 1);
-    Op op{};
-    op.kind = OP_STEM;
-    op.conv = b.phys_from({li});
-    op.out = Slice{t0, 0, c64};
-    op.Hi = H; op.Wi = W;
-    e->macs += (double)H1 * W1 * c64 * 27;
-    e->ops.push_back(op);
-  }
-  const int t1 = b.tensor(H2, W2, c128);
-  b.conv("model.1", Slice{t0, 0, c64}, Slice{t1, 0, c128}, 3, 2);
-  const int t2 = b.tensor(H2, W2, c128);
-  b.c2f("model.2", Slice{t1, 0, c128}, Slice{t2, 0, c128}, b.rep(3), true);
-  const int t3 = b.tensor(H3, W3, c256);
-  b.conv("model.3", Slice{t2, 0, c128}, Slice{t3, 0, c256}, 3, 2);
-  b.c2f("model.4", Slice{t3, 0, c256}, x4, b.rep(6), true);
-  const int t5 = b.tensor(H4, W4, c512);
-  b.conv("model.5", x4, Slice{t5, 0, c512}, 3, 2);
-  b.c2f("model.6", Slice{t5, 0, c512}, x6, b.rep(6), true);
-  const int t7 = b.tensor(H5, W5, c1024);
-  b.conv("model.7", x6, Slice{t7, 0, c1024}, 3, 2);
-  const int t8 = b.tensor(H5, W5, c1024);
-  b.c2f("model.8", Slice{t7, 0, c1024}, Slice{t8, 0, c1024}, b.rep(3), true);
-  // 9: SPPF
-  {
-    const int c_ = c1024 / 2;
-    const int sp = b.tensor(H5, W5, 4 * c_);
-    b.conv("model.9.cv1", Slice{t8, 0, c1024}, Slice{sp, 0, c_}, 1, 1);
-    Op op{};
-    op.kind = OP_POOL;
-    op.in = Slice{sp, 0, c_};
-    op.out = Slice{sp, c_, 3 * c_};
-    e->ops.push_back(op);
-    b.conv("model.9.cv2", Slice{sp, 0, 4 * c_}, x9, 1, 1);
-  }
-  // 10/11: Upsample(x9) + Concat with x6.  By default nothing is copied: model.12.cv1 (1x1) reads channels
-  // [0, c1024) through its gather from the half-resolution x9 (upsample read-through, conv_igemm.hip); with
-  // M355_NO_UPFUSE the upsample kernel materialises them in cat11 instead.
-  const bool upfuse = !e->sw.no_upfuse;
-  if (!upfuse) {
-    Op op{};
-    op.kind = OP_UP;
-    op.in = x9;
-    op.out = Slice{cat11, 0, c1024};
-    e->ops.push_back(op);
-  }
-  b.c2f("model.12", Slice{cat11, 0, c1024 + c512}, x12, b.rep(3), false, upfuse ? x9 : Slice());
-  if (!upfuse) {
-    Op op{};
-    op.kind = OP_UP;
-    op.in = x12;
-    op.out = Slice{cat14, 0, c512};
-    e->ops.push_back(op);
-  }
-  const int t15 = b.tensor(H3, W3, c256);
-  b.c2f("model.15", Slice{cat14, 0, c512 + c256}, Slice{t15, 0, c256}, b.rep(3), false, upfuse ? x12 : Slice());
-  b.conv("model.16", Slice{t15, 0, c256}, Slice{cat17, 0, c256}, 3, 2);
-  const int t18 = b.tensor(H4, W4, c512);
-  b.c2f("model.18", Slice{cat17, 0, c256 + c512}, Slice{t18, 0, c512}, b.rep(3), false);
-  b.conv("model.19", Slice{t18, 0, c512}, Slice{cat20, 0, c512}, 3, 2);
-  const int t21 = b.tensor(H5, W5, c1024);
-  b.c2f("model.21", Slice{cat20, 0, c512 + c1024}, Slice{t21, 0, c1024}, b.rep(3), false);
-
-  // 22: Segment head
-  const int feats[3] = {t15, t18, t21};
-  const int fch[3] = {c256, c512, c1024};
-  return build_segment_head(e, b, feats, fch, b.ch(256));
-}
 
 // A stride-2 backbone conv whose ONLY consumer is the 1x1 cv1 of the following C2f, with as many channels as one
 // im2col channel tile holds (64 or 128) on both sides: the 1x1 runs in the conv kernel's epilogue through LDS and the

@@ -2,7 +2,7 @@
 // -- as a persistent kernel with the WEIGHTS IN REGISTERS (gfx950, v_mfma_f32_32x32x16_f16).
 //
 // Replaces: upstream's Proto.upsample / Proto.cv2 / Proto.cv3 (nn.modules.block.Proto), reached through
-// /root/reference/BscanBased/yolo8_seg_predict.py:8.  The algebra is the engine's composed form (engine.hip, DESIGN.md
+// /root/reference/BscanBased/yolo8_seg_predict.py:8.  The algebra is the engine's composed form (graph.hip, DESIGN.md
 // section 4): the transposed convolution has no activation, so upsample -> 3x3 is, per output phase (py, px), a 2x2
 // convolution over the LOW-resolution map with host-composed weights [4 phases][128][(a, b, cin)] and a bias table by
 // border class of the output pixel.

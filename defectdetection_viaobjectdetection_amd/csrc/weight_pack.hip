@@ -94,7 +94,7 @@ FragList head_level_frags(int nc) {
 FragList epilogue_frags(int cout2, int k) { return frag_grid(cout2, k); }
 
 // ConvTranspose2d(2x2, s2, bias) followed by Conv3x3 (no activation between them) as four 2x2 phase convs over the low-resolution input
-// (see build_segment_head in engine.hip): fp16 rows [4 n (padded to cout_pad)][Kpad], K = (a * 2 + b) * n + cin, and the [9 border classes][n] bias table.
+// (see build_segment_head in graph.hip): fp16 rows [4 n (padded to cout_pad)][Kpad], K = (a * 2 + b) * n + cin, and the [9 border classes][n] bias table.
 void compose_proto_phases(int n, const float* wtp, const float* btp, const float* w3p, const float* b3p, int cout_pad, int Kpad,
                           std::vector<half_t>& rows, std::vector<float>& btab) {
     // Weff[q][co][(a*2+b)*n + ci] = sum over the (kh, kw) of phase q = py*2+px that fall on low-res offset (a, b):

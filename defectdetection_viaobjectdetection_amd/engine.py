@@ -70,7 +70,7 @@ class SegEngine:
     @staticmethod
     def proto_is_composed(scale: str) -> bool:
         """True when the engine runs Proto's ConvTranspose + 3x3 conv as four composed 2x2 phase convolutions
-        (engine.hip build_graph: prototype width a multiple of 64 and M355_NO_PROTOFUSE unset)."""
+        (graph.hip build_segment_head: prototype width a multiple of 64 and M355_NO_PROTOFUSE unset)."""
         import math
         import os
         from .spec import SCALES

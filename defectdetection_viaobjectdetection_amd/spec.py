@@ -174,18 +174,23 @@ def conv_specs_v5u(scale: str, nc: int = 1) -> List[ConvSpec]:
     return out
 
 
+def _branch_specs(out: List[ConvSpec], pre: str, fch, hc: int, cout: int) -> None:
+    """One head branch over the three levels: {pre}.{l}.0 and .1 (3x3 Conv+BN+SiLU, fch[l] -> hc -> hc), .2 (plain 1x1 with bias)."""
+    for l in range(3):
+        out.append(ConvSpec(f"{pre}.{l}.0", fch[l], hc, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.{l}.1", hc, hc, 3, 1, True))
+        out.append(ConvSpec(f"{pre}.{l}.2", hc, cout, 1, 1, False))
+
+
+def _box_specs(out: List[ConvSpec], fch, pre: str) -> None:
+    """The box branch cv2.{l}.{0,1,2} that every head has (4 * REG_MAX distribution bins per anchor)."""
+    _branch_specs(out, f"{pre}.cv2", fch, max(16, fch[0] // 4, REG_MAX * 4), 4 * REG_MAX)
+
+
 def _detect_specs(out: List[ConvSpec], nc: int, fch, pre: str) -> None:
     """Detect head (box-only, no mask coefficients): cv2.{l}.{0,1,2} box branches, cv3.{l}.{0,1,2} class branches."""
-    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
-    hc3 = max(fch[0], min(nc, 100))
-    for l in range(3):
-        out.append(ConvSpec(f"{pre}.cv2.{l}.0", fch[l], hc2, 3, 1, True))
-        out.append(ConvSpec(f"{pre}.cv2.{l}.1", hc2, hc2, 3, 1, True))
-        out.append(ConvSpec(f"{pre}.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
-    for l in range(3):
-        out.append(ConvSpec(f"{pre}.cv3.{l}.0", fch[l], hc3, 3, 1, True))
-        out.append(ConvSpec(f"{pre}.cv3.{l}.1", hc3, hc3, 3, 1, True))
-        out.append(ConvSpec(f"{pre}.cv3.{l}.2", hc3, nc, 1, 1, False))
+    _box_specs(out, fch, pre)
+    _branch_specs(out, f"{pre}.cv3", fch, max(fch[0], min(nc, 100)), nc)
 
 
 def conv_specs_y11(scale: str, nc: int = 1) -> List[ConvSpec]:
@@ -251,12 +256,8 @@ def conv_specs_y11(scale: str, nc: int = 1) -> List[ConvSpec]:
     conv("model.20", c512, c512, 3, 2)
     c3k2("model.22", c512 + c1024, c1024, True)
     fch = (c256, c512, c1024)
-    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
     hc3 = max(fch[0], min(nc, 100))
-    for l in range(3):
-        conv(f"model.23.cv2.{l}.0", fch[l], hc2, 3, 1)
-        conv(f"model.23.cv2.{l}.1", hc2, hc2, 3, 1)
-        out.append(ConvSpec(f"model.23.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
+    _box_specs(out, fch, "model.23")
     for l in range(3):
         conv(f"model.23.cv3.{l}.0.0", fch[l], fch[l], 3, 1, groups=fch[l])
         conv(f"model.23.cv3.{l}.0.1", fch[l], hc3, 1, 1)
@@ -289,28 +290,14 @@ def y11_gflops(scale: str, nc: int = 80, imgsz: int = 640) -> float:
 
 def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
     """model.22 = Segment: the box / class / coefficient branches per level and Proto (A9/A10), upstream state-dict order."""
-    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
-    hc3 = max(fch[0], min(nc, 100))
-    hc4 = max(fch[0] // 4, NM)
-
     def conv(name, cin, cout, k, s):
         out.append(ConvSpec(name, cin, cout, k, s, True))
-    for l in range(3):
-        conv(f"model.22.cv2.{l}.0", fch[l], hc2, 3, 1)
-        conv(f"model.22.cv2.{l}.1", hc2, hc2, 3, 1)
-        out.append(ConvSpec(f"model.22.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
-    for l in range(3):
-        conv(f"model.22.cv3.{l}.0", fch[l], hc3, 3, 1)
-        conv(f"model.22.cv3.{l}.1", hc3, hc3, 3, 1)
-        out.append(ConvSpec(f"model.22.cv3.{l}.2", hc3, nc, 1, 1, False))
+    _detect_specs(out, nc, fch, "model.22")
     conv("model.22.proto.cv1", fch[0], npr, 3, 1)
     out.append(ConvSpec("model.22.proto.upsample", npr, npr, 2, 2, False, True))
     conv("model.22.proto.cv2", npr, npr, 3, 1)
     conv("model.22.proto.cv3", npr, NM, 1, 1)
-    for l in range(3):
-        conv(f"model.22.cv4.{l}.0", fch[l], hc4, 3, 1)
-        conv(f"model.22.cv4.{l}.1", hc4, hc4, 3, 1)
-        out.append(ConvSpec(f"model.22.cv4.{l}.2", hc4, NM, 1, 1, False))
+    _branch_specs(out, "model.22.cv4", fch, max(fch[0] // 4, NM), NM)
 
 
 def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
@@ -356,27 +343,7 @@ def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
     c2f("model.18", c256 + c512, c512, rep(3))
     conv("model.19", c512, c512, 3, 2)
     c2f("model.21", c512 + c1024, c1024, rep(3))
-    fch = (c256, c512, c1024)
-    hc2 = max(16, fch[0] // 4, REG_MAX * 4)
-    hc3 = max(fch[0], min(nc, 100))
-    hc4 = max(fch[0] // 4, NM)
-    npr = ch(256)
-    for l in range(3):
-        conv(f"model.22.cv2.{l}.0", fch[l], hc2, 3, 1)
-        conv(f"model.22.cv2.{l}.1", hc2, hc2, 3, 1)
-        out.append(ConvSpec(f"model.22.cv2.{l}.2", hc2, 4 * REG_MAX, 1, 1, False))
-    for l in range(3):
-        conv(f"model.22.cv3.{l}.0", fch[l], hc3, 3, 1)
-        conv(f"model.22.cv3.{l}.1", hc3, hc3, 3, 1)
-        out.append(ConvSpec(f"model.22.cv3.{l}.2", hc3, nc, 1, 1, False))
-    conv("model.22.proto.cv1", fch[0], npr, 3, 1)
-    out.append(ConvSpec("model.22.proto.upsample", npr, npr, 2, 2, False, True))
-    conv("model.22.proto.cv2", npr, npr, 3, 1)
-    conv("model.22.proto.cv3", npr, NM, 1, 1)
-    for l in range(3):
-        conv(f"model.22.cv4.{l}.0", fch[l], hc4, 3, 1)
-        conv(f"model.22.cv4.{l}.1", hc4, hc4, 3, 1)
-        out.append(ConvSpec(f"model.22.cv4.{l}.2", hc4, NM, 1, 1, False))
+    _segment_specs(out, nc, (c256, c512, c1024), ch(256))
     return out
 
 
