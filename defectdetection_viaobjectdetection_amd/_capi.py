@@ -58,6 +58,12 @@ class WgradLaunchArgs(C.Structure):
                 ("ws_bytes", C.c_int64)]
 
 
+class LetterboxImage(C.Structure):
+    """m355_letterbox_image (include/mi355yolo.h)."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("uh", C.c_int32), ("uw", C.c_int32),
+                ("top", C.c_int32), ("left", C.c_int32)]
+
+
 # symbol -> (restype, argtypes); every entry of include/mi355yolo.h
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -151,6 +157,7 @@ SIGNATURES = {
     "m355_postprocess_ex": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "m355_nms_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),
     "m355_proto_masks_native": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "m355_letterbox_u8": (C.c_int, [_P, C.POINTER(LetterboxImage), C.c_int, C.c_int, C.c_int, _P, _P]),
 }
 
 

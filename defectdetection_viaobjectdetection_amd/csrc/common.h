@@ -315,6 +315,10 @@ int launch_sgd_step(float* p, const float* g, float* buf, float* ema, const unsi
                     float lr_bias, float momentum, int nesterov, float wd, float grad_mul, float ema_d, hipStream_t s);
 int launch_grad_sumsq(const float* g, long n, float* out, hipStream_t s);   // out: grad_sumsq_workspace_floats() floats
 size_t grad_sumsq_workspace_floats();
+// LetterBox of n raw BGR images into the uint8 NHWC RGB input batch (letterbox.hip): src = the ragged device buffer of the
+// sources, table = HOST array of n m355_letterbox_image (include/mi355yolo.h), out (n, net_h, net_w, 3).  Every argument is
+// checked on the host first: -1 = refused (see m355_letterbox_u8), 0 = launched, else a HIP error code.
+int launch_letterbox_u8(const uint8_t* src, const void* table, int n, int net_h, int net_w, uint8_t* out, hipStream_t s);
 // mosaic + affine + HSV + flip gather (augment.hip); params: device array of B m355_aug_params
 int launch_augment(const uint8_t* cache, const void* params, uint8_t* out, int B, int H, int W, hipStream_t s);
 int launch_bn_silu_train_bwd(const half_t* z, const half_t* dy, long npix, int ldz, int lddy, int C, const float* mean,

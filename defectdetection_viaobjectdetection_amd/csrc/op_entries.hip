@@ -599,6 +599,15 @@ int m355_proto_masks_native(const float* d_dets, const int* d_counts, const void
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "native mask launch failed: " + std::to_string(rc));
 }
 
+int m355_letterbox_u8(const uint8_t* d_src, const m355_letterbox_image* h_table, int n, int net_h, int net_w,
+                      uint8_t* d_out, void* stream) {
+  if (!d_src || !h_table || !d_out) return set_err(M355_ERR_INVALID, "letterbox: null pointer");
+  const int rc = launch_letterbox_u8(d_src, h_table, n, net_h, net_w, d_out, (hipStream_t)stream);
+  if (rc == -1)
+    return set_err(M355_ERR_INVALID, "letterbox: bad argument (n, net shape, output alignment, image or window size, offset table)");
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "letterbox launch failed: " + std::to_string(rc));
+}
+
 int m355_proto_masks(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det, int mh,
                      int mw, int in_h, int in_w, uint8_t* d_masks, void* stream) {
   if (!d_dets || !d_counts || !d_protos || !d_masks) return set_err(M355_ERR_INVALID, "null pointer");

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import ConvInfo, ModelDesc, OpInfo, check, lib
+from ._capi import ConvInfo, LetterboxImage, ModelDesc, OpInfo, check, lib
 from .preprocess import scale_boxes_to_original
 from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_detect, is_v5u, is_y11
 
@@ -66,6 +66,10 @@ class SegEngine:
         self.workspace_bytes = lib.m355_workspace_bytes(self._h)
         self.specs: List[ConvSpec] = conv_specs(scale, nc)
         self._check_graph()
+        self._lb_host: Optional[torch.Tensor] = None     # pinned staging of letterbox(): the raw sources, one after the other
+        self._lb_dev: Optional[torch.Tensor] = None      # its device copy
+        self._lb_copied: Optional[torch.cuda.Event] = None   # the last upload has left the staging buffer
+        self._lb_done: Optional[torch.cuda.Event] = None     # the last kernel has read the device copy
 
     @staticmethod
     def proto_is_composed(scale: str) -> bool:
@@ -111,6 +115,45 @@ class SegEngine:
                 check(lib.m355_set_conv_weights(self._h, i, _ptr(w), _ptr(b)), self._h)
 
     # ------------------------------------------------------------------ forward / postprocess
+    def letterbox(self, images: Sequence[np.ndarray], plan) -> torch.Tensor:
+        """LetterBox on the device.  images: uint8 (h, w, 3) BGR arrays of any sizes; plan: what
+        ``preprocess.letterbox_plan`` returned for their shapes (any net shape, not only this engine's).  Returns the uint8
+        (n, net_h, net_w, 3) RGB batch ``forward`` takes, bit-identical to ``preprocess.letterbox`` of each image with the
+        channels reversed.  The sources are packed into one pinned staging buffer and uploaded with one copy; staging and
+        device buffer are kept and grown.  Asynchronous on the current stream; the images are only read."""
+        table, (net_h, net_w) = plan
+        n = len(images)
+        if n < 1 or len(table) != n:
+            raise ValueError(f"{n} images for a plan of {len(table)}")
+        rows = (LetterboxImage * n)()
+        srcs, total = [], 0
+        for i, (im, (h, w, uh, uw, top, left)) in enumerate(zip(images, np.asarray(table).tolist())):
+            if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.shape != (h, w, 3):
+                raise ValueError(f"image {i}: expected a uint8 ndarray of shape {(h, w, 3)}")
+            rows[i] = LetterboxImage(total, h, w, uh, uw, top, left)
+            srcs.append(im)
+            total += im.size
+        with torch.cuda.device(self.device):
+            if self._lb_host is None or self._lb_host.numel() < total:
+                cap = (total + (1 << 22) - 1) >> 22 << 22
+                if self._lb_done is not None:
+                    self._lb_done.synchronize()          # nothing in flight reads the buffers that are let go
+                self._lb_host = torch.empty((cap,), dtype=torch.uint8, pin_memory=True)
+                self._lb_dev = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+                self._lb_copied, self._lb_done = torch.cuda.Event(), torch.cuda.Event()
+            else:
+                self._lb_copied.synchronize()            # the previous upload has read the staging buffer
+                torch.cuda.current_stream().wait_event(self._lb_done)
+            host = self._lb_host.numpy()
+            for r, im in zip(rows, srcs):
+                np.copyto(host[r.offset:r.offset + im.size].reshape(im.shape), im)
+            self._lb_dev[:total].copy_(self._lb_host[:total], non_blocking=True)
+            self._lb_copied.record()
+            out = torch.empty((n, net_h, net_w, 3), dtype=torch.uint8, device=self.device)
+            check(lib.m355_letterbox_u8(_ptr(self._lb_dev), rows, n, net_h, net_w, _ptr(out), _stream()))
+            self._lb_done.record()
+        return out
+
     def forward(self, images_u8_nhwc: torch.Tensor):
         """images: uint8 (B,H,W,3) on this device.  Returns preds f32 (B,A,4+nc+nm), protos f16 (B,h,w,32) (None when nm = 0)."""
         x = images_u8_nhwc

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .preprocess import expand_sources, letterbox, letterbox_shape, scale_boxes_to_original
+from .preprocess import expand_sources, letterbox, letterbox_plan, scale_boxes_to_original
 from .results import Results
 from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_detect, state_dict_keys
 
@@ -216,9 +216,10 @@ class YOLO:
         # auto=True (min-rectangle) letterbox like upstream's predictor for a single shape; mixed shapes pad to imgsz
         shapes = {im.shape[:2] for im in imgs}
         auto = len(shapes) == 1
-        net_shapes = [letterbox_shape(im.shape[:2], imgsz, auto)[3] for im in imgs]
-        net_shape = net_shapes[0] if auto else imgsz
-        lb = [letterbox(im, imgsz, auto=auto) for im in imgs]
+        table, net_shape = letterbox_plan([im.shape[:2] for im in imgs], imgsz, auto)
+        # the letterbox itself runs on the device (SegEngine.letterbox); M355_HOST_LETTERBOX=1 keeps the numpy one (the reference
+        # the kernel is tested against), for A/B runs
+        lb = [letterbox(im, imgsz, auto=auto) for im in imgs] if os.environ.get("M355_HOST_LETTERBOX") == "1" else None
         results: List[Results] = []
         save_dir = None
         if save:
@@ -226,11 +227,16 @@ class YOLO:
             os.makedirs(save_dir, exist_ok=True)
         t_pre = (time.perf_counter() - t0) * 1e3 / len(imgs)
         for i0 in range(0, len(imgs), batch):
-            chunk = lb[i0:i0 + batch]
+            chunk = imgs[i0:i0 + batch]
             eng = self._engine(net_shape, len(chunk), dev)
             with torch.cuda.device(eng.device):
+                ta = time.perf_counter()
+                if lb is None:
+                    x = eng.letterbox(chunk, (table[i0:i0 + len(chunk)], net_shape))
+                else:
+                    x = torch.from_numpy(np.stack(lb[i0:i0 + len(chunk)])[:, :, :, ::-1].copy()).to(eng.device)  # BGR -> RGB, H2D
+                torch.cuda.synchronize()
                 t1 = time.perf_counter()
-                x = torch.from_numpy(np.stack(chunk)[:, :, :, ::-1].copy()).to(eng.device)  # BGR -> RGB, H2D
                 preds, protos = eng.forward(x)
                 torch.cuda.synchronize()
                 t2 = time.perf_counter()
@@ -242,12 +248,20 @@ class YOLO:
                 else:
                     dets, counts, masks = eng.postprocess(preds, protos, conf, iou, max_det, masks=True,
                                                           agnostic=agnostic_nms, classes=classes)
-                    counts_h = counts.cpu().tolist()
+                    counts_h = None
+                # the chunk's rows (and, where the host has not got them yet, its counts: exact in fp32) in one copy to the host
+                rows_d = dets[:, :, :6].reshape(len(chunk), -1)
+                if counts_h is None:
+                    rows_d = torch.cat((rows_d, counts.to(torch.float32)[:, None]), 1)
+                rows_h = rows_d.cpu().numpy()
+                if counts_h is None:
+                    counts_h = rows_h[:, -1].astype(np.int64).tolist()
+                rows_h = rows_h[:, :max_det * 6].reshape(len(chunk), max_det, 6)
                 t3 = time.perf_counter()
             for j, n in enumerate(counts_h):
-                d = dets[j, :n, :6].cpu().numpy()
+                d = rows_h[j, :n].copy()
                 orig = imgs[i0 + j]
-                speed = {"preprocess": t_pre, "inference": (t2 - t1) * 1e3 / len(chunk),
+                speed = {"preprocess": t_pre + (t1 - ta) * 1e3 / len(chunk), "inference": (t2 - t1) * 1e3 / len(chunk),
                          "postprocess": (t3 - t2) * 1e3 / len(chunk)}
                 if retina:
                     # masks at the original resolution: Results sees a frame equal to the image (gain 1, pad 0)

@@ -114,6 +114,27 @@ def letterbox(img: np.ndarray, imgsz: Tuple[int, int] = (640, 640), auto: bool =
     return out
 
 
+def letterbox_plan(shapes: Sequence[Tuple[int, int]], imgsz: Tuple[int, int], auto: bool, stride: int = 32):
+    """Geometry of a batch for the device letterbox (``SegEngine.letterbox``): returns (table, net_shape), table an int32
+    (n, 6) array of rows (h, w, unpad_h, unpad_w, top, left) taken from ``letterbox_shape`` and net_shape the (height,
+    width) every image of the batch is padded to.  ``auto`` (the min-rectangle pad) needs images that share one frame."""
+    if not len(shapes):
+        raise ValueError("letterbox_plan needs at least one shape")
+    table = np.zeros((len(shapes), 6), np.int32)
+    net_shape = None
+    for i, (h, w) in enumerate(shapes):
+        _, (uh, uw), (top, _, left, _), out = letterbox_shape((int(h), int(w)), imgsz, auto, stride)
+        if uh < 1 or uw < 1:
+            raise ValueError(f"image {i} of shape {(h, w)} resizes to {(uh, uw)} at imgsz {tuple(imgsz)}: nothing to letterbox")
+        if net_shape is None:
+            net_shape = (int(out[0]), int(out[1]))
+        if tuple(out) != net_shape:
+            raise ValueError(f"image {i} of shape {(h, w)} letterboxes to {tuple(out)}, the batch to {net_shape}: "
+                             "mixed shapes need auto=False")
+        table[i] = (h, w, uh, uw, top, left)
+    return table, net_shape
+
+
 def scale_boxes_to_original(boxes_xyxy: np.ndarray, net_shape: Tuple[int, int], orig_shape: Tuple[int, int]) -> np.ndarray:
     """A.3 step 3: letterboxed-pixel boxes -> original-image pixels, clipped."""
     gain = min(net_shape[0] / orig_shape[0], net_shape[1] / orig_shape[1])

@@ -293,6 +293,23 @@ int m355_nms_ex(const float* d_preds, int B, int A, int nc, int nm, float conf, 
 int m355_proto_masks_native(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det, int mh,
                             int mw, const int32_t* h_orig_hw, const float* d_boxes, const int64_t* h_offsets,
                             uint8_t* d_out, void* stream);
+/* LetterBox on the device: n raw decoded images, uint8 BGR (h,w,3), packed one after the
+ * other in the device buffer d_src, become the engine's input batch d_out uint8 (n,net_h,net_w,3) RGB: image i resized to
+ * (uh,uw) lies at rows [top, top+uh), columns [left, left+uw) of its frame, every other byte is 114.  The resize is the
+ * bilinear one of preprocess.resize_linear_u8 (half-pixel centres, clamped taps, round half up), evaluated in the same
+ * IEEE double operations, so the bytes equal the host letterbox's; (h,w) == (uh,uw) is a copy.  h_table is a HOST array.
+ * Asynchronous on `stream`, one launch per 32 images.  M355_ERR_INVALID, before any HIP call: a NULL pointer, n < 1,
+ * net_h or net_w not a positive multiple of 32 (or above 32768), d_out not 16-byte aligned, h, w, uh or uw < 1, h or w
+ * above 32768, a window that leaves the frame, an offset below the end of the previous image (negative, overlapping or
+ * misordered). */
+typedef struct {
+  int64_t offset;            /* byte offset of the image's first pixel in d_src; the image occupies 3*h*w bytes */
+  int32_t h, w;              /* source size */
+  int32_t uh, uw;            /* size after the resize */
+  int32_t top, left;         /* position of the resized image in the frame */
+} m355_letterbox_image;
+int m355_letterbox_u8(const uint8_t* d_src, const m355_letterbox_image* h_table, int n, int net_h, int net_w,
+                      uint8_t* d_out, void* stream);
 /* Mask assembly only: dets (B,max_det,6+32), counts (B), protos fp16 (B,mh,mw,32)
  * -> masks uint8 (B,max_det,in_h,in_w). */
 int m355_proto_masks(const float* d_dets, const int* d_counts, const void* d_protos, int B, int max_det,
