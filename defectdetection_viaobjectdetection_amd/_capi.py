@@ -38,6 +38,28 @@ class AugParams(C.Structure):
                 ("hgain", C.c_float), ("sgain", C.c_float), ("vgain", C.c_float), ("flip", C.c_int32), ("mosaic", C.c_int32)]
 
 
+class AugLayer(C.Structure):
+    """m355_aug_layer (include/mi355yolo.h)."""
+    _fields_ = [("src", C.c_int32 * 4), ("xc", C.c_float), ("yc", C.c_float), ("minv", C.c_float * 9), ("mosaic", C.c_int32),
+                ("poly_first", C.c_int32), ("poly_count", C.c_int32)]
+
+
+class AugExParams(C.Structure):
+    """m355_aug_ex_params (include/mi355yolo.h)."""
+    _fields_ = [("layer", AugLayer * 2), ("n_layers", C.c_int32), ("mix", C.c_float), ("hgain", C.c_float), ("sgain", C.c_float),
+                ("vgain", C.c_float), ("flip", C.c_int32), ("flipud", C.c_int32)]
+
+
+class AugPoly(C.Structure):
+    """m355_aug_poly (include/mi355yolo.h)."""
+    _fields_ = [("vert_first", C.c_int32), ("vert_count", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32)]
+
+
+AUG_MAX_PASTE = 32            # M355_AUG_MAX_PASTE
+AUG_MAX_POLY_VERTS = 1024     # M355_AUG_MAX_POLY_VERTS
+
+
 class ConvLaunchArgs(C.Structure):
     """m355_conv_args (include/mi355yolo.h)."""
     _fields_ = [("x", C.c_void_p), ("x_bstride", C.c_int64), ("ldx", C.c_int32), ("hi", C.c_int32), ("wi", C.c_int32),
@@ -126,6 +148,9 @@ SIGNATURES = {
                                 C.c_float, C.c_float, _P]),
     "m355_grad_sumsq": (C.c_int, [_P, C.c_int64, _P, _P]),
     "m355_augment": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "m355_augment_ex_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "m355_augment_ex": (C.c_int, [_P, C.c_int32, C.POINTER(AugExParams), C.POINTER(AugPoly), C.c_int32, _F, C.c_int32, _P, C.c_int64,
+                                  _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "m355_msda_forward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32,
                                     C.c_int32, C.c_int32, _P, _P]),
     "m355_msda_module_forward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P,

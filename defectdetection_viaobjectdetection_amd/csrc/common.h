@@ -321,6 +321,13 @@ size_t grad_sumsq_workspace_floats();
 int launch_letterbox_u8(const uint8_t* src, const void* table, int n, int net_h, int net_w, uint8_t* out, hipStream_t s);
 // mosaic + affine + HSV + flip gather (augment.hip); params: device array of B m355_aug_params
 int launch_augment(const uint8_t* cache, const void* params, uint8_t* out, int B, int H, int W, hipStream_t s);
+// the same gather with a homography, flipud, a paste list and a second layer (augment_ex.hip): params / polys / verts are HOST
+// arrays (m355_aug_ex_params, m355_aug_poly, x,y float pairs), checked, copied into `work` on the stream and read from there.
+// -1 = refused before any HIP call (see m355_augment_ex), 0 = launched, else a HIP error code.
+size_t augment_ex_workspace_bytes(int B, int n_polys, int n_verts);
+int launch_augment_ex(const uint8_t* cache, int n_images, const void* h_params, const void* h_polys, int n_polys,
+                      const float* h_verts, int n_verts, void* work, long long work_bytes, uint8_t* out, int B, int H, int W,
+                      hipStream_t s);
 int launch_bn_silu_train_bwd(const half_t* z, const half_t* dy, long npix, int ldz, int lddy, int C, const float* mean,
                              const float* invstd, const float* gamma, const float* beta, float* rsum, half_t* dz,
                              int lddz, int act, float* ws, hipStream_t s);

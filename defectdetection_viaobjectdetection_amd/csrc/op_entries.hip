@@ -708,6 +708,19 @@ int m355_augment(const void* d_cache, const m355_aug_params* d_params, void* d_o
   const int rc = m355::launch_augment((const uint8_t*)d_cache, d_params, (uint8_t*)d_out, B, H, W, (hipStream_t)stream);
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "augment launch failed: " + std::to_string(rc));
 }
+size_t m355_augment_ex_workspace_bytes(int32_t B, int32_t n_polys, int32_t n_verts) {
+  return m355::augment_ex_workspace_bytes(B, n_polys, n_verts);
+}
+int m355_augment_ex(const void* d_cache, int32_t n_images, const m355_aug_ex_params* h_params, const m355_aug_poly* h_polys,
+                    int32_t n_polys, const float* h_verts, int32_t n_verts, void* d_work, int64_t work_bytes, void* d_out,
+                    int32_t B, int32_t H, int32_t W, void* stream) {
+  if (!d_cache || !h_params || !d_work || !d_out) return set_err(M355_ERR_INVALID, "augment_ex: null pointer");
+  const int rc = m355::launch_augment_ex((const uint8_t*)d_cache, n_images, h_params, h_polys, n_polys, h_verts, n_verts, d_work,
+                                         work_bytes, (uint8_t*)d_out, B, H, W, (hipStream_t)stream);
+  if (rc == -1)
+    return set_err(M355_ERR_INVALID, "augment_ex: bad argument (shape, n_layers, src index, polygon or vertex range, paste cap, workspace)");
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "augment_ex launch failed: " + std::to_string(rc));
+}
 int m355_msda_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
                       int32_t num_levels, const float* d_loc, const float* d_attn, const int32_t* points_per_level,
                       int32_t Q, int32_t P, int32_t discrete, float* d_out, void* stream) {

@@ -12,8 +12,11 @@ fp16 activations / gradients with a dynamic loss scale play the role of upstream
 path: without a GPU and ``libmi355yolo.so`` this raises.
 
 Augmentation (mosaic, scale / translate affine, HSV, flip) is one GPU gather kernel over the HBM-resident image cache
-(``augment.py`` / ``csrc/augment.hip``).  ``resume=True`` continues from ``weights/last.pt`` (optimizer, EMA, loss scale,
-history); ``patience`` stops early.  Not built: plots.
+(``augment.py`` / ``csrc/augment.hip``).  The options upstream leaves at 0 -- ``degrees``, ``shear``, ``perspective``,
+``flipud``, ``mixup``, ``copy_paste`` -- are accepted under upstream's names and ranges; any of them above 0 moves the batch
+to the second gather kernel (``csrc/augment_ex.hip``), still one launch.  ``resume=True`` continues from ``weights/last.pt``
+(optimizer, EMA, loss scale, history, and every scalar option of the first call); ``patience`` stops early.  Not built: plots,
+``copy_paste_mode="mixup"``, ``erasing``, ``auto_augment``, ``bgr``, ``cutmix``.
 """
 from __future__ import annotations
 
@@ -39,7 +42,8 @@ DEFAULTS = dict(optimizer="auto", lr0=0.01, lrf=0.01, momentum=0.937, weight_dec
                 warmup_momentum=0.8, warmup_bias_lr=0.1, nbs=64, seed=0, fliplr=0.5, val=True, exist_ok=False,
                 box=7.5, cls=0.5, dfl=1.5, conf=0.001, iou=0.7, max_det=300, workers=8, patience=100, amp=True,
                 verbose=True, save=True, bucket_mb=32, augment=True, mosaic=1.0, scale=0.5, translate=0.1, hsv_h=0.015,
-                hsv_s=0.7, hsv_v=0.4, close_mosaic=10)
+                hsv_s=0.7, hsv_v=0.4, close_mosaic=10, degrees=0.0, shear=0.0, perspective=0.0, flipud=0.0, mixup=0.0,
+                copy_paste=0.0)
 EMA_DECAY, EMA_TAU = 0.9999, 2000.0
 GRAD_CLIP = 10.0
 
@@ -230,6 +234,8 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
     if not data:
         raise ValueError("train() needs data=<dataset yaml>")
     a = SimpleNamespace(**{**DEFAULTS, **{k: v for k, v in kwargs.items() if k in DEFAULTS}})
+    from .augment import EX_OPTIONS, check_hyp
+    check_hyp({k: getattr(a, k) for k in EX_OPTIONS})       # upstream's ranges, before any device or file is touched
     devices = _devices(device)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if len(devices) > 1 and world == 1:
@@ -316,7 +322,7 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
     if a.augment:
         from .augment import Augmenter
         augmenter = Augmenter(train_ds, dev, seed=a.seed + 1000 * rank, mosaic=a.mosaic, scale=a.scale, translate=a.translate,
-                              hsv_h=a.hsv_h, hsv_s=a.hsv_s, hsv_v=a.hsv_v, fliplr=a.fliplr)
+                              hsv_h=a.hsv_h, hsv_s=a.hsv_s, hsv_v=a.hsv_v, fliplr=a.fliplr, **{k: getattr(a, k) for k in EX_OPTIONS})
     scaler = LossScaler()
     rng = np.random.default_rng(a.seed + 1000 * rank)
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
@@ -371,7 +377,7 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
                 lr = f * lr0 * lf
                 lr_bias = warmup_bias_lr + f * (lr0 * lf - warmup_bias_lr)
                 mom = a.warmup_momentum + f * (momentum - a.warmup_momentum) if opt_name == "sgd" else momentum
-            if augmenter is not None:     # mosaic / affine / HSV / flip rendered by the GPU kernel from the HBM image cache
+            if augmenter is not None:     # the whole augmentation chain rendered by one GPU kernel from the HBM image cache
                 b = augmenter.batch(idx, mosaic_on=epoch < epochs - a.close_mosaic)
                 imgs = b["img"]
             else:

@@ -485,6 +485,59 @@ typedef struct {
 int m355_augment(const void* d_cache, const m355_aug_params* d_params, void* d_out, int32_t B, int32_t H, int32_t W,
                  void* stream);
 
+/* The rest of upstream's chain -- degrees / shear / perspective (RandomPerspective), flipud (RandomFlip), mixup (MixUp) and
+ * copy_paste (CopyPaste, flip mode) -- on the same image cache, still one launch per batch (csrc/augment_ex.hip, DESIGN.md
+ * section 16).  An output image blends up to two LAYERS; a layer is what m355_aug_params describes, with two differences:
+ *   - minv is a full inverse homography: output pixel (x, y) samples the canvas at
+ *       (m0 x + m1 y + m2, m3 x + m4 y + m5) / (m6 x + m7 y + m8);   m6 = m7 = 0, m8 = 1 is m355_augment's affine;
+ *   - a paste list, polygons [poly_first, poly_first + poly_count) of the table, in canvas coordinates.  Canvas texel
+ *     (cx, cy) is PASTED when the point (cx, cy) is inside any listed polygon, and then reads the mirrored canvas texel
+ *     (Wc - 1 - cx, cy) in place of (cx, cy); Wc = 2W with mosaic, W without.  Each of the four bilinear corners decides for
+ *     itself.  Inside is even-odd over the edges (a, b) of the polygon: an edge is crossed when (a.y > cy) != (b.y > cy) and
+ *     cx lies strictly left of the edge at height cy, evaluated without a division as
+ *       d = b.y - a.y;   d > 0 ? (cx - a.x) * d < (cy - a.y) * (b.x - a.x) : (cx - a.x) * d > (cy - a.y) * (b.x - a.x).
+ *     So a polygon owns its left and top edges and not its right and bottom ones: a point on an edge has one answer.
+ *     [x0, x1] x [y0, y1] is a polygon's inclusive integer bounding box; a texel outside it is never tested, so the box must
+ *     cover the vertices (floor of the minima, ceil of the maxima).
+ * Per output pixel: flip / flipud applied to (x, y), each layer sampled bilinearly (border 114), rgb = mix * layer 0 +
+ * (1 - mix) * layer 1 in fp32 when n_layers == 2, then the HSV gains, round half up and clip as in m355_augment.  The file
+ * is built without FMA contraction: a float32 restatement in the same operation order gives the same bytes.
+ * h_params (B records), h_polys (n_polys) and h_verts (n_verts x,y pairs) are HOST arrays; the entry checks them, copies them
+ * into d_work (a device buffer of at least m355_augment_ex_workspace_bytes() bytes, 16-byte aligned) on `stream` and launches.
+ * The three host arrays must stay valid and unchanged until `stream` has executed the copies this call enqueues (they may be
+ * pageable; synchronise the stream, or record an event after the call and wait for it, before freeing or rewriting them), and
+ * d_work until the kernel has run.
+ * M355_ERR_INVALID, before any HIP call: a NULL pointer (h_polys / h_verts may be NULL when their count is 0); B, H or W < 1,
+ * B > 65535, H or W > 16384; n_images < 1 or a src index outside [0, n_images); n_layers not 1 or 2; n_polys or n_verts < 0;
+ * a layer's polygon range outside [0, n_polys) or longer than M355_AUG_MAX_PASTE; a polygon's vertex range outside
+ * [0, n_verts), empty or longer than M355_AUG_MAX_POLY_VERTS; work_bytes too small or d_work misaligned.  The caller drops
+ * surplus pastes; the cap bounds the work of one output pixel. */
+#define M355_AUG_MAX_PASTE 32          /* polygons in one layer's paste list */
+#define M355_AUG_MAX_POLY_VERTS 1024   /* vertices of one paste polygon */
+typedef struct {
+  int32_t src[4];          /* cache indices, as in m355_aug_params */
+  float xc, yc;            /* mosaic centre on the canvas */
+  float minv[9];           /* inverse homography, row-major */
+  int32_t mosaic;          /* 0: single image src[0] at the canvas origin */
+  int32_t poly_first, poly_count;
+} m355_aug_layer;
+typedef struct {
+  m355_aug_layer layer[2];
+  int32_t n_layers;        /* 1, or 2 for mixup */
+  float mix;               /* weight r of layer 0; layer 1 gets 1 - r */
+  float hgain, sgain, vgain;
+  int32_t flip;            /* 1: output column x reads column W-1-x */
+  int32_t flipud;          /* 1: output row y reads row H-1-y */
+} m355_aug_ex_params;
+typedef struct {
+  int32_t vert_first, vert_count;   /* vertices [vert_first, vert_first + vert_count) of h_verts, canvas coordinates */
+  int32_t x0, y0, x1, y1;           /* inclusive integer bounding box */
+} m355_aug_poly;
+size_t m355_augment_ex_workspace_bytes(int32_t B, int32_t n_polys, int32_t n_verts);
+int m355_augment_ex(const void* d_cache, int32_t n_images, const m355_aug_ex_params* h_params, const m355_aug_poly* h_polys,
+                    int32_t n_polys, const float* h_verts, int32_t n_verts, void* d_work, int64_t work_bytes, void* d_out,
+                    int32_t B, int32_t H, int32_t W, void* stream);
+
 /* ---- D-FINE decoder hot ops (/root/reference/D-Fine/temporal_dfine.py:160-181) ---------------
  * The reference reaches these through transformers' modeling_d_fine.py; each entry point names what it replaces.
  *
