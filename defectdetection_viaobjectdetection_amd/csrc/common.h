@@ -120,6 +120,16 @@ int launch_msda(const float* value, const float* loc, const float* attn, float* 
                 const float* ref = nullptr, float offset_scale = 0.f);
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
                         float reg_scale, int clamp01, hipStream_t s);
+// their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
+// grad_value and the per-head partials of grad_ref.  -1 = refused before any launch, -3 = workspace missing / too small.
+size_t msda_backward_workspace_bytes(int B, int Q, int H, int P);
+int launch_msda_backward(const float* grad_out, const float* value, const float* loc, const float* attn, float* grad_value,
+                         float* grad_loc, float* grad_attn, int B, int S, int H, int D, int Q, int P, int L,
+                         const int* shapes_hw, const int* points_per_level, int discrete, void* work, long long work_bytes,
+                         hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f, float* grad_ref = nullptr);
+int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
+                                 float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
+                                 hipStream_t s);
 // 1x1, K <= 512, Cout % 128 == 0: weights in registers, persistent (conv1x1_wreg.hip)
 bool conv1x1_wreg_ok(const ConvArgs& a);
 int launch_conv1x1_wreg(const ConvArgs& a, hipStream_t s);

@@ -750,6 +750,46 @@ int m355_dfine_decode(const float* d_dist, const float* d_project, const float* 
   if (rc == -1) return set_err(M355_ERR_INVALID, "dfine_decode: null pointer, n < 0, fewer than 2 bins or reg_scale == 0");
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_decode launch failed: " + std::to_string(rc));
 }
+size_t m355_msda_backward_workspace_bytes(int32_t B, int32_t Q, int32_t heads, int32_t P) {
+  return m355::msda_backward_workspace_bytes(B, Q, heads, P);
+}
+static int msda_backward_rc(int rc, const char* what) {
+  if (rc == -1)
+    return set_err(M355_ERR_INVALID, std::string(what) + ": head_dim must be 32, 1..8 levels tiling S, points tiling P, workspace 16-byte aligned");
+  if (rc == -3) return set_err(M355_ERR_INVALID, std::string(what) + ": workspace missing or smaller than m355_msda_backward_workspace_bytes");
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, std::string(what) + " launch failed: " + std::to_string(rc));
+}
+int m355_msda_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                       const int32_t* shapes_hw, int32_t num_levels, const float* d_loc, const float* d_attn,
+                       const int32_t* points_per_level, int32_t Q, int32_t P, int32_t discrete, float* d_grad_value,
+                       float* d_grad_loc, float* d_grad_attn, void* d_work, int64_t work_bytes, void* stream) {
+  if (!d_grad_out || !d_value || !d_loc || !d_attn || !shapes_hw || !points_per_level) return set_err(M355_ERR_INVALID, "null pointer");
+  return msda_backward_rc(m355::launch_msda_backward(d_grad_out, d_value, d_loc, d_attn, d_grad_value, d_grad_loc, d_grad_attn, B, S,
+                                                     heads, head_dim, Q, P, num_levels, shapes_hw, points_per_level, discrete,
+                                                     d_work, work_bytes, (hipStream_t)stream),
+                          "msda backward");
+}
+int m355_msda_module_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                              const int32_t* shapes_hw, int32_t num_levels, const float* d_ref, const float* d_offsets,
+                              const float* d_logits, const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale,
+                              float* d_grad_value, float* d_grad_ref, float* d_grad_offsets, float* d_grad_logits, void* d_work,
+                              int64_t work_bytes, void* stream) {
+  if (!d_grad_out || !d_value || !d_ref || !d_offsets || !d_logits || !shapes_hw || !points_per_level)
+    return set_err(M355_ERR_INVALID, "null pointer");
+  return msda_backward_rc(m355::launch_msda_backward(d_grad_out, d_value, d_offsets, d_logits, d_grad_value, d_grad_offsets,
+                                                     d_grad_logits, B, S, heads, head_dim, Q, P, num_levels, shapes_hw,
+                                                     points_per_level, 0, d_work, work_bytes, (hipStream_t)stream, d_ref,
+                                                     offset_scale, d_grad_ref),
+                          "msda module backward (at most 16 points)");
+}
+int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
+                               float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
+                               int32_t clamp01, void* stream) {
+  const int rc = m355::launch_dfine_decode_backward(d_grad_boxes, d_dist, d_project, d_ref, d_grad_dist, d_grad_ref, (long)n,
+                                                    num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream);
+  if (rc == -1) return set_err(M355_ERR_INVALID, "dfine_decode_backward: null pointer, n < 0, fewer than 2 bins or reg_scale == 0");
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_decode_backward launch failed: " + std::to_string(rc));
+}
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");

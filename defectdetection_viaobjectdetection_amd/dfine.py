@@ -4,7 +4,9 @@ Same names, argument meaning and error behaviour as the functions /root/referenc
 160-181 imports from / reaches through ``transformers.models.d_fine.modeling_d_fine`` (5.15.0):
 ``multi_scale_deformable_attention_v2`` (:150-221), ``weighting_function`` (:1091-1112), ``distance2bbox``
 (:1115-1137), ``DFineIntegral.forward`` (:756-778).  Tensors are CUDA fp32; there is no CPU path (the C-ABI call
-fails loudly without a gfx950 device).  A maintainer binds them with
+fails loudly without a gfx950 device).  The three kernel-backed ops are differentiable (torch.autograd.Function over the
+HIP backward entries, bitwise-reproducible gradients); with nothing to differentiate they take the plain forward path.
+A maintainer binds them with
 ``modeling_d_fine.multi_scale_deformable_attention_v2 = dfine.multi_scale_deformable_attention_v2`` (the attention
 module keeps a reference in ``self.ms_deformable_attn_core``, :244) — see INTEGRATION.md.
 """
@@ -46,13 +48,114 @@ def multi_scale_deformable_attention_v2(value: torch.Tensor, value_spatial_shape
         raise ValueError("spatial shapes do not add up to the value sequence length")
     if sum(num_points_list) != P or len(num_points_list) != len(shapes):
         raise ValueError("num_points_list must have one entry per level and add up to the number of points")
-    value, loc, attn = _f32c(value, "value"), _f32c(loc, "sampling_locations"), _f32c(attention_weights, "attention_weights")
-    out = torch.empty((B, Q, H * D), dtype=torch.float32, device=value.device)
+    if _wants_grad(value, loc, attention_weights):
+        return _MsdaCore.apply(value, loc, attention_weights, shapes, [int(n) for n in num_points_list], method == "discrete")
+    return _msda_forward(_f32c(value, "value"), _f32c(loc, "sampling_locations"), _f32c(attention_weights, "attention_weights"),
+                         shapes, num_points_list, method == "discrete")
+
+
+def _wants_grad(*tensors: torch.Tensor) -> bool:
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _tables(shapes, num_points_list):
     sh = (C.c_int32 * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
     pp = (C.c_int32 * len(shapes))(*[int(n) for n in num_points_list])
-    check(lib.m355_msda_forward(C.c_void_p(value.data_ptr()), B, S, H, D, sh, len(shapes), C.c_void_p(loc.data_ptr()),
-                                C.c_void_p(attn.data_ptr()), pp, Q, P, 1 if method == "discrete" else 0,
-                                C.c_void_p(out.data_ptr()), _stream()))
+    return sh, pp
+
+
+def _msda_forward(value, loc, attn, shapes, num_points_list, discrete: bool) -> torch.Tensor:
+    """contiguous fp32 CUDA tensors -> (B, Q, heads * 32)"""
+    B, S, H, D = value.shape
+    Q, P = loc.shape[1], loc.shape[3]
+    out = torch.empty((B, Q, H * D), dtype=torch.float32, device=value.device)
+    sh, pp = _tables(shapes, num_points_list)
+    check(lib.m355_msda_forward(_ptr(value), B, S, H, D, sh, len(shapes), _ptr(loc), _ptr(attn), pp, Q, P, int(discrete),
+                                _ptr(out), _stream()))
+    return out
+
+
+def _backward_workspace(B, Q, H, P, device) -> torch.Tensor:
+    return torch.empty(int(lib.m355_msda_backward_workspace_bytes(B, Q, H, P)), dtype=torch.uint8, device=device)
+
+
+def _grad_like(need: bool, t: torch.Tensor):
+    return torch.empty_like(t) if need else None
+
+
+def _as_input(g, shape, dtype):
+    return None if g is None else g.reshape(shape).to(dtype)
+
+
+class _MsdaCore(torch.autograd.Function):
+    """multi_scale_deformable_attention_v2 with m355_msda_backward behind it; gradients for value, loc, attn."""
+
+    @staticmethod
+    def forward(ctx, value, loc, attn, shapes, pts, discrete):
+        v, l, a = _f32c(value, "value"), _f32c(loc, "sampling_locations"), _f32c(attn, "attention_weights")
+        ctx.save_for_backward(v, l, a)
+        ctx.meta = (shapes, pts, discrete, [(t.shape, t.dtype) for t in (value, loc, attn)])
+        return _msda_forward(v, l, a, shapes, pts, discrete)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        v, l, a = ctx.saved_tensors
+        shapes, pts, discrete, like = ctx.meta
+        B, S, H, D = v.shape
+        Q, P = l.shape[1], l.shape[3]
+        need = ctx.needs_input_grad
+        gv, gl, ga = _grad_like(need[0], v), _grad_like(need[1], l), _grad_like(need[2], a)
+        work = _backward_workspace(B, Q, H, P, v.device) if need[0] else None
+        sh, pp = _tables(shapes, pts)
+        go = _f32c(grad_out, "grad_output")
+        check(lib.m355_msda_backward(_ptr(go), _ptr(v), B, S, H, D, sh, len(shapes), _ptr(l), _ptr(a), pp, Q, P, int(discrete),
+                                     _ptr(gv), _ptr(gl), _ptr(ga), _ptr(work), work.numel() if work is not None else 0,
+                                     _stream()))
+        return tuple(_as_input(g, *sd) for g, sd in zip((gv, gl, ga), like)) + (None, None, None)
+
+
+class _MsdaModule(torch.autograd.Function):
+    """The fused module kernel with m355_msda_module_backward behind it; gradients for value, ref, offsets, logits."""
+
+    @staticmethod
+    def forward(ctx, value, ref, off, logit, n_heads, shapes, pts, offset_scale):
+        v, r = _f32c(value, "encoder_hidden_states"), _f32c(ref, "reference_points")
+        o, z = _f32c(off, "sampling offsets"), _f32c(logit, "attention logits")
+        ctx.save_for_backward(v, r, o, z)
+        ctx.meta = (n_heads, shapes, pts, offset_scale, [(t.shape, t.dtype) for t in (value, ref, off, logit)])
+        return _module_forward(v, r, o, z, n_heads, shapes, pts, offset_scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        v, r, o, z = ctx.saved_tensors
+        H, shapes, pts, offset_scale, like = ctx.meta
+        B, S, d = v.shape
+        Q, P = r.shape[1], sum(pts)
+        need = ctx.needs_input_grad
+        gv, gr, go_, gz = (_grad_like(n, t) for n, t in zip(need, (v, r, o, z)))
+        work = _backward_workspace(B, Q, H, P, v.device) if need[0] or need[1] else None
+        sh, pp = _tables(shapes, pts)
+        go = _f32c(grad_out, "grad_output")
+        check(lib.m355_msda_module_backward(_ptr(go), _ptr(v), B, S, H, d // H, sh, len(shapes), _ptr(r), _ptr(o), _ptr(z), pp,
+                                            Q, P, float(offset_scale), _ptr(gv), _ptr(gr), _ptr(go_), _ptr(gz), _ptr(work),
+                                            work.numel() if work is not None else 0, _stream()))
+        return tuple(_as_input(g, *sd) for g, sd in zip((gv, gr, go_, gz), like)) + (None, None, None, None)
+
+
+def _module_forward(value, ref, off, logit, n_heads, shapes, pts, offset_scale) -> torch.Tensor:
+    """contiguous fp32 CUDA tensors: value (B, S, d), ref (B, Q, 4), off (B, Q, heads * P * 2), logit (B, Q, heads * P)"""
+    B, S, d = value.shape
+    Q, P = ref.shape[1], sum(pts)
+    out = torch.empty((B, Q, d), dtype=torch.float32, device=value.device)
+    sh, pp = _tables(shapes, pts)
+    check(lib.m355_msda_module_forward(_ptr(value), B, S, n_heads, d // n_heads, sh, len(shapes), _ptr(ref), _ptr(off),
+                                       _ptr(logit), pp, Q, P, float(offset_scale), _ptr(out), _stream()))
     return out
 
 
@@ -73,17 +176,17 @@ def deformable_attention(hidden_states: torch.Tensor, reference_points: torch.Te
     ref = reference_points.reshape(B, Q, -1)
     if ref.shape[-1] != 4:
         raise ValueError(f"Last dim of reference_points must be 4 for the fused form, but get {ref.shape[-1]} instead.")
-    value = _f32c(encoder_hidden_states, "encoder_hidden_states")          # (B, S, heads, D) is a view of (B, S, d)
-    off = _f32c(sampling_offsets(hidden_states), "sampling offsets")       # (B, Q, heads * P * 2)
-    logit = _f32c(attention_weights(hidden_states), "attention logits")    # (B, Q, heads * P)
-    ref = _f32c(ref, "reference_points")
-    out = torch.empty((B, Q, d), dtype=torch.float32, device=value.device)
-    sh = (C.c_int32 * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
-    pp = (C.c_int32 * len(shapes))(*[int(n) for n in num_points_list])
-    check(lib.m355_msda_module_forward(C.c_void_p(value.data_ptr()), B, S, n_heads, D, sh, len(shapes), C.c_void_p(ref.data_ptr()),
-                                       C.c_void_p(off.data_ptr()), C.c_void_p(logit.data_ptr()), pp, Q, P, float(offset_scale),
-                                       C.c_void_p(out.data_ptr()), _stream()))
-    return out
+    pts = [int(n) for n in num_points_list]
+    off = sampling_offsets(hidden_states)          # (B, Q, heads * P * 2)
+    logit = attention_weights(hidden_states)       # (B, Q, heads * P)
+    if off.shape[-1] != n_heads * P * 2 or logit.shape[-1] != n_heads * P or d != n_heads * D:
+        raise ValueError("the linear layers must produce heads * points * 2 offsets and heads * points logits")
+    if _wants_grad(encoder_hidden_states, ref, off, logit):
+        return _MsdaModule.apply(encoder_hidden_states, ref, off, logit, n_heads, shapes, pts, float(offset_scale))
+    # (B, S, heads, D) is a view of (B, S, d)
+    return _module_forward(_f32c(encoder_hidden_states, "encoder_hidden_states"), _f32c(ref, "reference_points"),
+                           _f32c(off, "sampling offsets"), _f32c(logit, "attention logits"), n_heads, shapes, pts,
+                           float(offset_scale))
 
 
 def weighting_function(max_num_bins: int, up: torch.Tensor, reg_scale) -> torch.Tensor:
@@ -107,12 +210,42 @@ def decode_boxes(pred_corners: torch.Tensor, project: torch.Tensor, points: torc
     lead = pred_corners.shape[:-1]
     if pred_corners.shape[-1] != 4 * nb1 or tuple(points.shape) != tuple(lead) + (4,):
         raise ValueError("pred_corners must be (..., 4 * len(project)) and points (..., 4)")
-    d, pr, pt = _f32c(pred_corners, "pred_corners"), _f32c(project, "project"), _f32c(points, "points")
-    out = torch.empty(tuple(lead) + (4,), dtype=torch.float32, device=d.device)
-    n = out.numel() // 4
-    check(lib.m355_dfine_decode(C.c_void_p(d.data_ptr()), C.c_void_p(pr.data_ptr()), C.c_void_p(pt.data_ptr()),
-                                C.c_void_p(out.data_ptr()), n, nb1, float(reg_scale), int(clamp01), _stream()))
+    if torch.is_grad_enabled() and project.requires_grad:
+        raise RuntimeError("decode_boxes treats project (the weighting function W(n)) as a constant: it has no gradient; "
+                           "detach it, or use integral() + distance2bbox() to train reg_scale / up")
+    if _wants_grad(pred_corners, points):
+        return _Decode.apply(pred_corners, project, points, float(reg_scale), bool(clamp01))
+    return _decode_forward(_f32c(pred_corners, "pred_corners"), _f32c(project, "project"), _f32c(points, "points"),
+                           float(reg_scale), bool(clamp01))
+
+
+def _decode_forward(d, pr, pt, reg_scale: float, clamp01: bool) -> torch.Tensor:
+    out = torch.empty(tuple(d.shape[:-1]) + (4,), dtype=torch.float32, device=d.device)
+    check(lib.m355_dfine_decode(_ptr(d), _ptr(pr), _ptr(pt), _ptr(out), out.numel() // 4, pr.numel(), reg_scale, int(clamp01),
+                                _stream()))
     return out
+
+
+class _Decode(torch.autograd.Function):
+    """decode_boxes with m355_dfine_decode_backward behind it; gradients for pred_corners and points."""
+
+    @staticmethod
+    def forward(ctx, pred_corners, project, points, reg_scale, clamp01):
+        d, pr, pt = _f32c(pred_corners, "pred_corners"), _f32c(project, "project"), _f32c(points, "points")
+        ctx.save_for_backward(d, pr, pt)
+        ctx.meta = (reg_scale, clamp01, [(t.shape, t.dtype) for t in (pred_corners, points)])
+        return _decode_forward(d, pr, pt, reg_scale, clamp01)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_boxes):
+        d, pr, pt = ctx.saved_tensors
+        reg_scale, clamp01, like = ctx.meta
+        gd, gp = _grad_like(ctx.needs_input_grad[0], d), _grad_like(ctx.needs_input_grad[2], pt)
+        gb = _f32c(grad_boxes, "grad_output")
+        check(lib.m355_dfine_decode_backward(_ptr(gb), _ptr(d), _ptr(pr), _ptr(pt), _ptr(gd), _ptr(gp), gb.numel() // 4,
+                                             pr.numel(), reg_scale, int(clamp01), _stream()))
+        return _as_input(gd, *like[0]), None, _as_input(gp, *like[1]), None, None
 
 
 def integral(pred_corners: torch.Tensor, project: torch.Tensor) -> torch.Tensor:

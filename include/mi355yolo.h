@@ -567,6 +567,40 @@ int m355_msda_module_forward(const float* d_value, int32_t B, int32_t S, int32_t
 int m355_dfine_decode(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
                       int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream);
 
+/* ---- Backward of the three entries above, for fine-tuning runs that call the ops under loss.backward() --------------
+ * (the reference's D-FINE trainers: D-Fine/temp_dfine_over_improved.py:152-157, 250-272; temporal_dfine.py:175-181).
+ * fp32, same layouts as the forward twins.  No float atomics: every gradient is bitwise reproducible.
+ *
+ * m355_msda_backward = backward of m355_msda_forward.
+ *   grad_out   (B, Q, heads * head_dim); value / loc / attn / shapes_hw / points_per_level / discrete as the forward
+ *   grad_value (B, S, heads, head_dim), grad_loc (B, Q, heads, P, 2), grad_attn (B, Q, heads, P): each may be NULL
+ *              ("not needed": its work is skipped); every element of a non-NULL output is written
+ *   discrete 0: grid_sample backward (bilinear, zeros padding, align_corners=False): corners outside the map contribute
+ *               nothing to any gradient;  1: grad_loc is zeros, the other two go through the one selected pixel
+ *   work       device scratch of m355_msda_backward_workspace_bytes(B, Q, heads, P) bytes, 16-byte aligned; needed when
+ *              grad_value is asked for (one {pixel, weight} entry per (q, point, corner), summed per pixel in that order) */
+size_t m355_msda_backward_workspace_bytes(int32_t B, int32_t Q, int32_t heads, int32_t P);
+int m355_msda_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                       const int32_t* shapes_hw, int32_t num_levels, const float* d_loc, const float* d_attn,
+                       const int32_t* points_per_level, int32_t Q, int32_t P, int32_t discrete, float* d_grad_value,
+                       float* d_grad_loc, float* d_grad_attn, void* d_work, int64_t work_bytes, void* stream);
+/* m355_msda_module_backward = backward of m355_msda_module_forward: the softmax and the sampling locations are recomputed
+ * in the kernel, then the softmax backward over the P points and the chain rule of
+ * location = ref.xy + offset * (1 / points of the level) * ref.wh * offset_scale.
+ *   grad_value as above, grad_ref (B, Q, 4), grad_offsets (B, Q, heads, P, 2), grad_logits (B, Q, heads, P): each may be
+ *   NULL; work as above, needed for grad_value and grad_ref (per-head partials, added in head order); P <= 16. */
+int m355_msda_module_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                              const int32_t* shapes_hw, int32_t num_levels, const float* d_ref, const float* d_offsets,
+                              const float* d_logits, const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale,
+                              float* d_grad_value, float* d_grad_ref, float* d_grad_offsets, float* d_grad_logits, void* d_work,
+                              int64_t work_bytes, void* stream);
+/* m355_dfine_decode_backward = backward of m355_dfine_decode: grad_boxes (n, 4) -> grad_dist (n, 4 * num_bins_plus1)
+ * (softmax-expectation backward per side) and grad_ref (n, 4); either may be NULL.  With clamp01 the gradient passes where
+ * 0 <= box <= 1, as torch.clamp does.  project is a constant (no gradient). */
+int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
+                               float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
+                               int32_t clamp01, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

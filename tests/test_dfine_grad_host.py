@@ -1,0 +1,110 @@
+"""The gradient reference of the D-FINE ops (tests/msda_grad_ref.py) on the CPU: its forward against the golden vectors
+produced by the transformers functions, float64 gradcheck, and the C-ABI surface of the backward entries."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import msda_grad_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = np.load(os.path.join(ROOT, "tests", "golden", "dfine_golden.npz"))
+SHAPES = [tuple(int(v) for v in hw) for hw in G["shapes"]]
+T = lambda k: torch.from_numpy(np.ascontiguousarray(G[k]))  # noqa: E731
+
+
+def _close(y, ref):
+    err = float((y - ref).abs().max())
+    assert err <= 2e-6 * max(1.0, float(ref.abs().max())), err
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("method", ["default", "discrete"])
+def test_helper_msda_matches_golden(tag, method):
+    y = R.msda(T("value"), SHAPES, T(f"loc_{tag}"), T(f"attn_{tag}"), [int(n) for n in G[f"pts_{tag}"]], method)
+    _close(y, T(f"msda_{tag}_{method}"))
+
+
+def test_helper_module_matches_golden():
+    y = R.module(T("value"), SHAPES, T("mod_ref"), T("mod_offsets"), T("mod_logits"), [4, 4, 4], float(G["mod_offset_scale"]))
+    _close(y, T("mod_out"))
+    B, S, H, D = G["value"].shape
+    y = R.deformable_attention(T("mod_hidden"), T("mod_ref"), T("value").reshape(B, S, H * D), SHAPES, T("mod_w_off"),
+                               T("mod_b_off"), T("mod_w_att"), T("mod_b_att"), [4, 4, 4], H, float(G["mod_offset_scale"]))
+    # the linear layers ahead of the kernel: the allowance tests/test_dfine_gpu.py gives the GEMM order
+    assert float((y - T("mod_out")).abs().max()) <= 5e-5 * max(1.0, float(T("mod_out").abs().max()))
+
+
+@pytest.mark.parametrize("clamp, key", [(False, "boxes"), (True, "boxes_clamped")])
+def test_helper_decode_matches_golden(clamp, key):
+    with np.errstate(all="ignore"):
+        y = R.decode_boxes(T("dist"), T("project"), T("points"), 4.0, clamp)
+    ref = T(key)
+    assert torch.equal(torch.isnan(y), torch.isnan(ref)) and torch.equal(torch.isinf(y), torch.isinf(ref))
+    fin = torch.isfinite(ref)
+    _close(y[fin], ref[fin])
+
+
+@pytest.mark.parametrize("method", ["default", "discrete"])
+def test_helper_gradcheck_ragged(method):
+    shapes, pts, value, loc, attn = R.ragged_case(D=4)
+    leaves = [t.double().requires_grad_(True) for t in (value, loc, attn)]
+    f = lambda v, l, a: R.msda(v, shapes, l, a, pts, method)  # noqa: E731
+    assert torch.autograd.gradcheck(f, leaves, eps=1e-6, atol=1e-6, rtol=1e-5)
+
+
+def test_helper_gradcheck_module_and_decode():
+    g = torch.Generator().manual_seed(4)
+    shapes, pts = [(3, 4), (2, 2)], [2, 3]
+    value = torch.randn(2, 16, 2, 4, generator=g).double().requires_grad_(True)
+    ref = (torch.rand(2, 3, 4, generator=g) * 0.5 + 0.2).double().requires_grad_(True)
+    off = torch.randn(2, 3, 2, 5, 2, generator=g).double().requires_grad_(True)
+    logit = torch.randn(2, 3, 2, 5, generator=g).double().requires_grad_(True)
+    assert torch.autograd.gradcheck(lambda v, r, o, z: R.module(v, shapes, r, o, z, pts, 0.5), (value, ref, off, logit),
+                                    eps=1e-6, atol=1e-6, rtol=1e-5)
+    dist = torch.randn(5, 4 * 9, generator=g).double().requires_grad_(True)
+    points = (torch.rand(5, 4, generator=g) * 0.4 + 0.2).double().requires_grad_(True)
+    proj = torch.linspace(-2, 2, 9).double()
+    for clamp in (False, True):
+        assert torch.autograd.gradcheck(lambda d, p: R.decode_boxes(d, proj, p, 4.0, clamp), (dist, points),
+                                        eps=1e-6, atol=1e-6, rtol=1e-5)
+
+
+def test_backward_entries_are_bound():
+    from defectdetection_viaobjectdetection_amd import _capi
+    for name in ("m355_msda_backward", "m355_msda_module_backward", "m355_dfine_decode_backward"):
+        assert name in _capi.SIGNATURES and hasattr(_capi.lib, name)
+
+
+def test_backward_arguments_are_refused_before_any_device_work():
+    """Validation happens on the host before any launch, as for the forward entries: checked here without a GPU."""
+    import ctypes as C
+    from defectdetection_viaobjectdetection_amd import _capi
+    fake = C.c_void_p(0x1000)   # never dereferenced
+    sh, pp = (C.c_int32 * 2)(5, 5), (C.c_int32 * 1)(4)
+    call = lambda **k: _capi.lib.m355_msda_backward(  # noqa: E731
+        fake, fake, 1, k.get("S", 25), 2, k.get("D", 32), sh, 1, fake, fake, pp, 3, k.get("P", 4), 0, k.get("gv", fake), None, None,
+        k.get("work", fake), k.get("bytes", 1 << 20), None)
+    assert call(D=16) == -1 and call(S=24) == -1 and call(P=5) == -1
+    assert call(work=None) == -1 and call(bytes=8) == -1          # grad_value needs the workspace
+    assert b"workspace" in _capi.lib.m355_last_error(None)
+    assert _capi.lib.m355_msda_backward_workspace_bytes(1, 3, 2, 4) >= 1 * 2 * 4 * 3 * 4 * 8
+    assert _capi.lib.m355_msda_module_backward(fake, fake, 1, 25, 2, 32, sh, 1, fake, fake, fake, (C.c_int32 * 1)(17), 3, 17, 0.5,
+                                               None, None, fake, None, None, 0, None) == -1        # more than 16 points
+    assert _capi.lib.m355_dfine_decode_backward(fake, fake, fake, fake, fake, None, 4, 1, 4.0, 0, None) == -1
+    assert _capi.lib.m355_dfine_decode_backward(fake, fake, fake, fake, fake, None, 4, 33, 0.0, 0, None) == -1
+
+
+def test_deformable_attention_refuses_mismatched_linear_layers():
+    """The fused module kernel indexes the two linear outputs as (heads, points, 2) / (heads, points): a layer of another
+    width is refused before anything is launched (the check precedes every device call, so it runs here)."""
+    from defectdetection_viaobjectdetection_amd import dfine
+    hidden, ref, enc = torch.zeros(1, 3, 64), torch.zeros(1, 3, 4), torch.zeros(1, 25, 64)
+    good_o, good_a = torch.nn.Linear(64, 2 * 4 * 2), torch.nn.Linear(64, 2 * 4)
+    for lin_o, lin_a in ((torch.nn.Linear(64, 2 * 4 * 2 - 2), good_a), (good_o, torch.nn.Linear(64, 2 * 4 + 1))):
+        with pytest.raises(ValueError, match="linear layers"):
+            dfine.deformable_attention(hidden, ref, enc, [(5, 5)], lin_o, lin_a, [4], 2, 0.5)
+    with pytest.raises(ValueError, match="linear layers"):                      # d not a multiple of the heads
+        dfine.deformable_attention(torch.zeros(1, 3, 65), ref, torch.zeros(1, 25, 65), [(5, 5)], torch.nn.Linear(65, 16),
+                                   torch.nn.Linear(65, 8), [4], 2, 0.5)

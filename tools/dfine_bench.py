@@ -1,6 +1,8 @@
 """Time the D-FINE deformable-attention core at BASELINE config 5's shape (batch 16 of 640x640: 300 queries, 8 heads,
 80^2 + 40^2 + 20^2 value map, 3 x 4 points): the HIP kernel through the C-ABI, the same transformers function run by
-PyTorch-ROCm on the GPU (grid_sample + permutes), and the numpy oracle on the host (one batch element)."""
+PyTorch-ROCm on the GPU (grid_sample + permutes), and the numpy oracle on the host (one batch element).  Also forward +
+backward of the core with every input requiring grad (a fine-tuning step's view of it): the HIP autograd Function against
+the transformers function under torch autograd, same GPU, same tensors."""
 import os, sys, time, json
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +37,19 @@ try:
     out["max_abs_diff_vs_torch_rocm"] = float((ref - mine).abs().max())
 except Exception as ex:  # transformers missing on the box
     out["torch_rocm_us"] = None; out["note"] = repr(ex)
+# forward + backward, all three inputs require grad; the backward alone = (forward + backward) - forward with a graph
+go = torch.randn(B, Q, H * D, generator=g).cuda()
+leaves = [t.clone().requires_grad_(True) for t in (value, loc, attn)]
+def fwd_bwd(core, *extra):
+    for t in leaves: t.grad = None
+    core(leaves[0], shapes, leaves[1], leaves[2], pts, *extra).backward(go)
+out["hip_fwd_bwd_us"] = round(timeit(lambda: fwd_bwd(dfine.multi_scale_deformable_attention_v2)), 1)
+out["hip_fwd_tracked_us"] = round(timeit(lambda: dfine.multi_scale_deformable_attention_v2(leaves[0], shapes, leaves[1], leaves[2], pts)), 1)
+if out["torch_rocm_us"] is not None:
+    hip_grads = [t.grad.clone() for t in leaves]
+    out["torch_rocm_fwd_bwd_us"] = round(timeit(lambda: fwd_bwd(M.multi_scale_deformable_attention_v2, "default"), 20), 1)
+    # per gradient (value, loc, attn): max |HIP - torch| as a fraction of max |torch| (both fp32; torch's own sums use atomics)
+    out["grad_max_diff_vs_torch_rocm_rel"] = [float((a - b.grad).abs().max() / b.grad.abs().max()) for a, b in zip(hip_grads, leaves)]
 # the whole attention module (two linear layers + softmax + locations + core), random-init weights
 try:
     from transformers.models.d_fine.configuration_d_fine import DFineConfig
