@@ -32,12 +32,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 16, PP = 20;          // output tile, pixel pitch of the y1 patch and of t
 constexpr int Y1_BYTES = 12 * PP * 64;           // 15360: 12 x 20 patch of y1 (halo 2)
@@ -54,26 +54,12 @@ constexpr int WC_OFF = BIAS_OFF + 512;           // Wc in MFMA fragment order: [
 constexpr int STG_OFF = WC_OFF + 12 * 1024;     // output staging: 4 waves x 32 pixels x 128 bytes
 constexpr int LDS_BYTES = STG_OFF + 4 * 4096;    // 148992
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-// MFMA row rho = 8 q + 4 h + i is accumulator register 4 q + i of lane-half h.
-// Plain order: lane-half h's 16 registers are 16 consecutive channels 16 h + r (what a 16-byte NHWC store wants).
-__device__ __forceinline__ int row_plain(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
-// Operand order: register r of lane-half h is channel 16 (r >> 3) + 8 h + (r & 7), so that registers 8 s .. 8 s + 7,
-// converted to fp16, ARE the B fragment (K slice s, k = 16 s + 8 h + j) of the next 32x32x16 MFMA for the same pixels.
-__device__ __forceinline__ int row_operand(int rho) {
-  const int q = rho >> 3, h = (rho >> 2) & 1, i = rho & 3;
-  return 16 * (q >> 1) + 8 * h + 4 * (q & 1) + i;
-}
-
 // SiLU of all 16 accumulators of a lane, STAGED: sixteen multiplies, sixteen v_exp, sixteen adds, sixteen v_rcp, sixteen
 // multiplies -- the same five operations per element as m355_silu (same bits), but every result is used sixteen
 // instructions after it was issued.  Left to itself the compiler interleaves two elements at a time and each
 // transcendental's consumer waits for it: measured 44 cycles per element (89 beside the partner wave's MFMAs) against
-// 28 of issue.
-__device__ __forceinline__ void silu16(float16v& v) {
+// 28 of issue.  (The shared silu16 of device_prims.h has the same stages without the scheduling barriers between them.)
+__device__ __forceinline__ void silu16_c2f(float16v& v) {
 #pragma clang fp contract(off)
   float16v t;
 #pragma unroll
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
 #pragma unroll
           for (int k = 0; k < NB; ++k) {
             const bool in = (unsigned)(ty0[1] - 1 + ti[k]) < (unsigned)H && (unsigned)(tx0[1] - 1 + tj[k]) < (unsigned)W;
-            silu16(acc[k]);
+            silu16_c2f(acc[k]);
             half8 lo = to_half8(acc[k], 0), hi = to_half8(acc[k], 8);
             if (!in) { lo = (half8)(half_t)0.f; hi = lo; }
             if (k == 0 || store1) {
@@ -391,10 +377,10 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
     const int st_p = lane >> 3, st_k = lane & 7;              // read side: pixel 8 i + st_p, chunk st_k
     int out_off = 0;                                          // element offset of this wave's first pixel row pair in y
     auto flush = [&]() __attribute__((always_inline)) {   // lane (pixel, half) holds channels 32 mb + 16 h + (0 .. 15)
-      silu16(o0);
+      silu16_c2f(o0);
       *(half8*)(stg + st_w + (((2 * h) ^ st_sw) << 4)) = to_half8(o0, 0);
       *(half8*)(stg + st_w + (((2 * h + 1) ^ st_sw) << 4)) = to_half8(o0, 8);
-      silu16(o1);
+      silu16_c2f(o1);
       *(half8*)(stg + st_w + (((4 + 2 * h) ^ st_sw) << 4)) = to_half8(o1, 0);
       *(half8*)(stg + st_w + (((5 + 2 * h) ^ st_sw) << 4)) = to_half8(o1, 8);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -473,7 +459,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
         C2F_STAMP(3)   // 1x1 over y0, y1
         // ---- y2 = y1 + SiLU(.) -> fp16 (the rounding point of the unfused path's HBM store): B fragments of slices 4, 5
         half8 y2[2];
-        silu16(acc);
+        silu16_c2f(acc);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
@@ -523,11 +509,9 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s) {
   const int ntiles = a.B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)c2f_c32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)c2f_c32_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     if (slots < 8) slots = 8;
   }
@@ -537,21 +521,10 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s) {
   // diagnostic: M355_C2F_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
   const int prio = proc_switches().c2f_noprio ? 0 : 1;
   const char* st_path = proc_switches().c2f_stamps;
-  static unsigned long long* d_st = nullptr;
-  if (st_path && !d_st) {
-    if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;
-    (void)hipMemset(d_st, 0, (size_t)slots * NWAVES * 64);
-  }
-  hipLaunchKernelGGL(c2f_c32_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, d_st, prio);
-  if (st_path) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -2;
-    const size_t nbytes = (size_t)grid * NWAVES * 64;
-    unsigned long long* hbuf = (unsigned long long*)malloc(nbytes);
-    (void)hipMemcpy(hbuf, d_st, nbytes, hipMemcpyDeviceToHost);
-    FILE* f = fopen(st_path, "wb");
-    if (f) { fwrite(hbuf, 1, nbytes, f); fclose(f); }
-    free(hbuf);
-  }
+  static StampSink sink;
+  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
+  hipLaunchKernelGGL(c2f_c32_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, sink.d, prio);
+  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
   return (int)hipGetLastError();
 }
 

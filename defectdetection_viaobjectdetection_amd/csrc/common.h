@@ -342,91 +342,4 @@ int launch_bn_silu_train_bwd(const half_t* z, const half_t* dy, long npix, int l
                              const float* invstd, const float* gamma, const float* beta, float* rsum, half_t* dz,
                              int lddz, int act, float* ws, hipStream_t s);
 
-
-// ---------------------------------------------------------------------------------------------------------
-// Fast conv epilogue shared by the conv kernels (device code, include from .hip files only).
-// A wave measured 13-15 k cycles in the generic epilogue of a 64 ch x 128 px tile: ~85 instructions per 16-byte
-// store (per-group validity branches with EXEC save / restore, 64-bit address multiplies, an LDS / global bias read
-// with its own wait) at one instruction per 4 cycles per wave.  When the whole wave tile is inside the tensor the
-// addresses are affine (base + nt * ystep + group * 32 channels), the bias sits in 16 registers and the SiLU is
-// packed: ~40 instructions per store, no branch.
-// ---------------------------------------------------------------------------------------------------------
-#ifdef __HIPCC__
-// No FMA contraction in the epilogue arithmetic: the generic and the fast epilogue must give the same bits, so that an
-// image's result does not depend on whether its tile was a full one (batch size / position invariance is tested).
-__device__ __forceinline__ float m355_silu(float v) {
-#pragma clang fp contract(off)
-  const float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-  return v * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-// Round-to-fp16 of an epilogue value.  The value is made opaque first: otherwise the compiler may fuse the last
-// multiply (or the residual add) with the conversion into v_fma_mix*_f16 for SOME elements of SOME template
-// instantiations -- one rounding instead of two, a rare 1-ulp difference that breaks bit-exact tile / batch invariance.
-__device__ __forceinline__ half_t m355_to_half(float v) {
-  asm volatile("" : "+v"(v));
-  return (half_t)v;
-}
-
-// acc[2s][nt] / acc[2s+1][nt] hold channels 8g..8g+3 / 8g+4..8g+7 of group s for pixel nt (see conv_igemm.hip);
-// yp / rp point at (pixel nt = 0, group 0) of this lane; ystep / rstep = elements between consecutive nt.
-template <int MT, int NT, bool ACT, bool RES>
-__device__ __forceinline__ void conv_epilogue_fast(float4v (&acc)[MT][NT], const float4v (&bias)[MT / 2][2], half_t* yp,
-                                                   long ystep, const half_t* rp, long rstep) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-    for (int s = 0; s < MT / 2; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = acc[2 * s][nt][j] + bias[s][0][j];
-        v[4 + j] = acc[2 * s + 1][nt][j] + bias[s][1][j];
-      }
-      if (ACT) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
-      }
-      if (RES) {
-        const half8 rv = *(const half8*)(rp + nt * rstep + s * 32);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += (float)rv[j];
-      }
-      half8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = m355_to_half(v[j]);
-      *(half8*)(yp + nt * ystep + s * 32) = o;
-    }
-  }
-}
-// Same, with one output pointer per pixel tile (ConvTranspose pixel-shuffle stores: not affine in nt), no residual.
-template <int MT, int NT, bool ACT>
-__device__ __forceinline__ void conv_epilogue_fast_ptrs(float4v (&acc)[MT][NT], const float4v (&bias)[MT / 2][2],
-                                                        half_t* const (&yp)[NT]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-    for (int s = 0; s < MT / 2; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = acc[2 * s][nt][j] + bias[s][0][j];
-        v[4 + j] = acc[2 * s + 1][nt][j] + bias[s][1][j];
-      }
-      if (ACT) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
-      }
-      half8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = m355_to_half(v[j]);
-      *(half8*)(yp[nt] + s * 32) = o;
-    }
-  }
-}
-#endif
-
-
 }  // namespace m355

@@ -32,32 +32,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 constexpr int NWAVES = 8;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ int row_plain(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
-
-__device__ __forceinline__ void silu16(float16v& v) {
-#pragma clang fp contract(off)
-  float16v t;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = v[j] * -1.4426950408889634f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_exp2f(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = 1.0f + t[j];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_rcpf(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = v[j] * t[j];
-}
 
 template <int K, int CB, int PB = 2>
 struct W1 {
@@ -307,11 +288,9 @@ int launch_w1(const ConvArgs& a, hipStream_t s) {
   static int slots = 0;
   auto k = conv1x1_wreg_kernel<K, CB, PB, SPLIT>;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)k, C::LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus < 8 ? 8 : cus;
   }
   // a block must not change its channel tile in the middle of a uniform loop more than once and all blocks must agree on

@@ -12,23 +12,16 @@
 //     one wait + barrier per tile;
 //   * four waves, each 32 channels x 4 image rows (MT = 2, NT = 4: 32 fp32 accumulators), two workgroups per CU.
 // LDS rows are 64 B with chunk c of row r in slot c ^ (2 * ((r >> 2) & 1)); patch row pitch 20 pixels (see
-// conv3x3_wide.hip for both).  Epilogue: conv_epilogue_fast (common.h) for interior tiles.
+// conv3x3_wide.hip for both).  Epilogue: conv_epilogue_fast (device_prims.h) for interior tiles.
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
-}
 
 constexpr int TS = 16, TH = 16;
 constexpr int PP = 20, PH = TH + 2;
@@ -198,11 +191,9 @@ int launch_conv3x3_c32(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_c32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)conv3x3_c32_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = proc_switches().c32_slots >= 0 ? proc_switches().c32_slots : 2 * cus;
     if (slots < 8) slots = 8;
     slots &= ~7;   // the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks more than one tile

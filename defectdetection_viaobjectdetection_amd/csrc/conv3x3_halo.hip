@@ -22,17 +22,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ float silu_f(float v) { return m355_silu(v); }
 
 constexpr int TS = 16;            // output tile is TH rows x TS (16) pixels
 constexpr int PW = TS + 2;        // patch width (18)
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) bf0[nt] = *(const half8*)(smem + bcur[nt]);
 
-  // Fast epilogue (common.h) when this wave's rows x 16 columns x 64 channels are all inside the tensor: the bias is
+  // Fast epilogue (device_prims.h) when this wave's rows x 16 columns x 64 channels are all inside the tensor: the bias is
   // fetched here, before the K loop, and waits in registers.
   const bool fast = y0 + wpx * NT + NT <= H && x0 + TS <= W && ch_base + wch * MT * 16 + MT * 16 <= a.Cout && !(a.dbg & (12 | 256));
   float4v bv[MT / 2][2];
@@ -297,7 +292,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       for (int j = 0; j < GW; ++j) v[j] += a.bias[ch0 + j];
       if (a.act && !(a.dbg & 4)) {
 #pragma unroll
-        for (int j = 0; j < GW; ++j) v[j] = silu_f(v[j]);
+        for (int j = 0; j < GW; ++j) v[j] = m355_silu(v[j]);
       }
       if (a.res) {
         const half_t* rp = a.res + (long)b * a.r_bstride + pix * a.ldr + ch0;
@@ -348,8 +343,7 @@ int launch_halo_variant(const ConvArgs& a, hipStream_t s) {
   const int lds = npatch * PGROUPS * 8 * ROWB + ((WCH * WPX == 8) ? 4 : 2) * BCH * ROWB;
   auto k = conv3x3_halo_kernel<MT, NT, WCH, WPX>;
   if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)k, lds)) return e;
   }
   hipLaunchKernelGGL(k, dim3(B * tiles_y * tiles_x * tiles_ch), dim3(WCH * WPX * 64), lds, s, a, tiles_x, tiles_y,
                      nchunks, npatch);

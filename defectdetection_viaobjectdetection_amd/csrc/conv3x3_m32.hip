@@ -45,20 +45,16 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
-
 constexpr int TS = 16;      // tile width in pixels
 constexpr int PP = 18;      // patch pitch (pixels): EVEN, so that a pixel's LDS-row parity is its column parity
 constexpr int ROWB = 128;   // bytes per LDS row
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 
 template <int BCH, int NB>
 struct M32 {
@@ -412,11 +408,9 @@ int launch_m32(const ConvArgs& a, hipStream_t s) {
   static int slots[2] = {0, 0};   // resident blocks for (one, two) patch buffers
   constexpr int LDS1 = C::PATCH_BYTES + 2 * C::WBUF, LDS2 = 2 * C::PATCH_BYTES + 2 * C::WBUF;
   if (!slots[0]) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)k, LDS2)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     for (int i = 0; i < 2; ++i) {
       int per_cu = (160 * 1024) / (i ? LDS2 : LDS1);
       if (per_cu > 2) per_cu = 2;   // two waves per SIMD: the register budget of __launch_bounds__(256, 2)

@@ -45,19 +45,15 @@
 #include <utility>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
-
 constexpr int ROWB = 64;      // bytes per LDS row: 32 channels of one pixel / 32 K values of one weight row
 constexpr int LDS_MAX = 160 * 1024;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 
 struct PlanesGeom {
   int R, nslab, PW;         // output rows per slab, slabs per image, pitch W + 1
@@ -577,12 +573,11 @@ int planes_launch(const PlanesArgs& a, const PlanesGeom& g, hipStream_t s) {
   auto k = a.res ? planes_kernel<C, true> : planes_kernel<C, false>;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)planes_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)planes_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    int e = prepare_kernel((const void*)planes_kernel<C, true>, LDS_MAX);
+    if (!e) e = prepare_kernel((const void*)planes_kernel<C, false>, LDS_MAX);
+    if (e) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     if (slots < 8) slots = 8;
   }
@@ -639,11 +634,7 @@ template <class C>
 long planes_cost(const PlanesArgs& a, PlanesGeom* g) {
   if (!planes_geometry<C>(a, g)) return -1;
   if (C::WC == 4 && a.Cout % 128) return -1;
-  static const int cus = [] {   // read once, as planes_launch does
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n;
-  }();
+  static const int cus = num_cus() > 0 ? num_cus() : 256;   // read once, as planes_launch does
   const long rounds = (g->ntiles + cus - 1) / cus;
   return rounds * g->NP * ((long)C::NPB2 * 18 * 33 + (long)((g->npieces + C::NW - 1) / C::NW) * 120 + 700);
 }

@@ -31,12 +31,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 16;                 // output tile
 constexpr int PR = 2 * TH + 1;                 // 17 patch rows
@@ -50,10 +50,6 @@ constexpr int W1_PITCH = 592, W2_PITCH = 144, Z_PITCH = 144;
 constexpr int W1_OFF = 2 * PATCH_BYTES, W2_OFF = W1_OFF + 64 * W1_PITCH, Z_OFF = W2_OFF + 64 * W2_PITCH;
 constexpr int BIAS_OFF = Z_OFF + 128 * Z_PITCH;    // 64 + 64 fp32 biases
 constexpr int LDS_BYTES = BIAS_OFF + 512 + 16;     // 154128 (the last 16: the published next-tile index)
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
 
 // MFMA row rho of a 32-row block holds logical channel 16 h + 4 q + i (rho = 8 q + 4 h + i): lane-half h's 16
 // accumulator registers are 16 consecutive channels
@@ -316,11 +312,9 @@ int launch_conv_s2c32_cv1(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_s2c32_cv1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)conv_s2c32_cv1_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     if (slots < 8) slots = 8;
   }
@@ -328,37 +322,29 @@ int launch_conv_s2c32_cv1(const ConvArgs& a, hipStream_t s) {
   // diagnostic (M355_S2C32_STAMPS, M355_S2C32_RING): per-wave section cycles of the last launch, or of the last `ring` launches
   static const int dbg = proc_switches().s2c32_dbg, ring = proc_switches().s2c32_ring;
   static const char* st_path = proc_switches().s2c32_stamps;
-  static unsigned long long* d_st = nullptr;
+  static StampSink sink;
   static long launches = 0;
   static size_t per_launch = 0;
   ConvArgs aa = a;
   if (st_path) {
-    if (!d_st) {
+    if (!sink.d) {
       per_launch = (size_t)slots * NWAVES * 8 * 8;
-      if (hipMalloc((void**)&d_st, per_launch * (ring > 0 ? ring : 1)) != hipSuccess) return -2;
-      (void)hipMemset(d_st, 0, per_launch * (ring > 0 ? ring : 1));
+      if (!sink.alloc(per_launch * (ring > 0 ? ring : 1))) return -2;
       if (ring > 0)
         atexit([] {
           (void)hipDeviceSynchronize();
           const size_t n = per_launch * ring;
           unsigned long long* h = (unsigned long long*)malloc(n);
-          (void)hipMemcpy(h, d_st, n, hipMemcpyDeviceToHost);
+          (void)hipMemcpy(h, sink.d, n, hipMemcpyDeviceToHost);
           FILE* f = fopen(st_path, "wb");
           if (f) { fwrite(h, 1, n, f); fclose(f); }
           free(h);
         });
     }
-    aa.stamps = d_st + (ring > 0 ? (launches++ % ring) * (per_launch / 8) : 0);
+    aa.stamps = sink.d + (ring > 0 ? (launches++ % ring) * (per_launch / 8) : 0);
   }
   hipLaunchKernelGGL(conv_s2c32_cv1_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, aa, tiles_x, tiles_y, ntiles, dbg);
-  if (st_path && ring <= 0) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -2;
-    unsigned long long* h = (unsigned long long*)malloc(per_launch);
-    (void)hipMemcpy(h, d_st, per_launch, hipMemcpyDeviceToHost);
-    FILE* f = fopen(st_path, "wb");
-    if (f) { fwrite(h, 8, (size_t)grid * NWAVES * 8, f); fclose(f); }
-    free(h);
-  }
+  if (ring <= 0 && sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
   return (int)hipGetLastError();
 }
 

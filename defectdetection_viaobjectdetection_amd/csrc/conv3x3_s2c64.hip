@@ -28,12 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 8, PQ = 20, PRN = 17, ROWB = 128, NWAVES = 8;
 constexpr int PPIX = PRN * PQ;                       // 340 LDS pixels
@@ -44,31 +44,6 @@ constexpr int STG_OFF = Z_OFF + 2 * 8192;            // output staging: 8 waves 
 constexpr int BIAS_OFF = STG_OFF + NWAVES * 2048;    // 128 + 128 floats
 constexpr int W2_OFF = BIAS_OFF + 1024;              // the 1x1's 4 x 8 fragments (lane-linear: conflict-free reads)
 constexpr int LDS_BYTES = W2_OFF + 32 * 1024;        // 154624
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-__device__ __forceinline__ void silu16(float16v& v) {
-#pragma clang fp contract(off)
-  float16v t;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = v[j] * -1.4426950408889634f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_exp2f(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = 1.0f + t[j];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_rcpf(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = v[j] * t[j];
-}
-
-__device__ __forceinline__ int lane_id() {            // volatile: lane-derived values are rebuilt where they are used, not kept
-  int ln;                                             // live (= spilled) across the K loop; a scratch reload waits on vmcnt(0)
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-  return ln;
-}
 
 __global__ __launch_bounds__(512, 2) void conv3x3_s2c64_cv1_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ntiles, int sx,
                                                                   int sy, int sb, int prio, unsigned long long* stamps) {
@@ -350,11 +325,9 @@ int launch_conv_s2c64_cv1(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_s2c64_cv1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)conv3x3_s2c64_cv1_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;
     if (slots < 8) slots = 8;
   }
@@ -363,21 +336,10 @@ int launch_conv_s2c64_cv1(const ConvArgs& a, hipStream_t s) {
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
   const int prio = proc_switches().s2c64_prio;
   const char* st_path = proc_switches().s2c64_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
-  static unsigned long long* d_st = nullptr;
-  if (st_path && !d_st) {
-    if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;
-    (void)hipMemset(d_st, 0, (size_t)slots * NWAVES * 64);
-  }
-  hipLaunchKernelGGL(conv3x3_s2c64_cv1_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, d_st);
-  if (st_path) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -2;
-    const size_t nbytes = (size_t)grid * NWAVES * 64;
-    unsigned long long* hbuf = (unsigned long long*)malloc(nbytes);
-    (void)hipMemcpy(hbuf, d_st, nbytes, hipMemcpyDeviceToHost);
-    FILE* f = fopen(st_path, "wb");
-    if (f) { fwrite(hbuf, 1, nbytes, f); fclose(f); }
-    free(hbuf);
-  }
+  static StampSink sink;
+  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
+  hipLaunchKernelGGL(conv3x3_s2c64_cv1_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, sink.d);
+  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
   return (int)hipGetLastError();
 }
 

@@ -13,25 +13,11 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 
 namespace m355 {
 namespace {
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ void glds4(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
-}
-
-__device__ __forceinline__ float silu_f(float v) { return m355_silu(v); }
-
-// s_waitcnt immediate (gfx9 encoding): vmcnt(n) lgkmcnt(0), expcnt untouched.  The builtin (unlike inline asm) is
-// visible to the compiler's own wait-count insertion, which then does not re-wait for LDS reads issued before it.
-#define WAITCNT_VM_LGKM0(n) ((((n) & 0xf) | (((n) >> 4) << 14) | (7 << 4)))
 
 constexpr int PP = 28;                // patch row pitch in LDS rows (W + 2 <= 28 used)
 constexpr int ROWB = 64;              // LDS row = 32 halves
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_slab_kernel(const ConvArgs a, 
         }
         if (a.act && !(a.dbg & 4)) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = silu_f(v[j]);
+          for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
         }
         if (a.res) {
           const half8 rv = *(const half8*)(a.res + (long)eb * a.r_bstride + pix * a.ldr + ch0);
@@ -391,17 +377,15 @@ int launch_conv3x3_slab(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * slabs * tiles_ch;
   static int slots = 0;   // resident blocks: two per CU
   if (!slots) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = (2 * cus) & ~7;   // the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     if (slots < 8) slots = 8;
   }
   const int grid = ntiles <= slots ? ntiles : slots;
   static bool attr = false;
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)conv3x3_slab_kernel, LDS_BYTES)) return e;
     attr = true;
   }
   hipLaunchKernelGGL(conv3x3_slab_kernel, dim3(grid), dim3(256), LDS_BYTES, s, a, R, slabs, a.Cin / 32, ntiles);

@@ -19,17 +19,16 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 constexpr int DG_PX = 32;                   // dY pixels per chunk
 constexpr int DG_COLS = DG_PX + 1;          // ... plus the right neighbour
 constexpr int DG_WBYTES = 2 * DG_COLS * 128;   // one wave's image: [row 0/1][33 px][64 ch] fp16
-
-__device__ __forceinline__ int row_plain(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
 
 __global__ __launch_bounds__(256) void dgrad_s2c32_kernel(const half_t* dz, long dz_bs, int lddz, const half_t* wq, int kpad, half_t* dx,
                                                           long dx_bs, int lddx, int B, int Ho, int Wo) {
@@ -140,12 +139,8 @@ int launch_dgrad_s2c32(const ConvArgs& a, hipStream_t s) {
   if (!dgrad_s2c32_ok(a)) return -1;
   const int B = (int)(a.M / ((long)a.Ho * a.Wo));
   const long chunks = (long)B * a.Ho * (a.Wo / DG_PX);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-    if (cus < 1) cus = 1;
-  }
+  const int cus = num_cus();
+  if (cus <= 0) return -2;
   long grid = (long)cus * 2;                               // two blocks per CU: 248 registers per wave, 34 KB of LDS per block
   if (grid * 4 > chunks) grid = (chunks + 3) / 4;
   hipLaunchKernelGGL(dgrad_s2c32_kernel, dim3((unsigned)grid), dim3(256), 4 * DG_WBYTES, s, a.x, a.x_bstride, a.ldx, a.w, a.Kpad, (half_t*)a.y,

@@ -29,27 +29,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 
 namespace {
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-// v * sigmoid(v);  exp2-based, rcp approx (1 ulp) -- far inside fp16 output rounding (shared with the fast epilogue)
-__device__ __forceinline__ float silu_f(float v) { return m355_silu(v); }
-
-// q = n / d, r = n % d for 0 <= n < 2^24 via a float reciprocal estimate + exact integer correction.
-__device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, int& r) {
-  q = (int)((float)n * inv_d);
-  r = n - q * d;
-  if (r < 0) { r += d; --q; }
-  if (r >= d) { r -= d; ++q; }
-}
 
 // MT/NT: 16x16 MFMA tiles per wave along channels / pixels.  WCH/WPX: waves along channels / pixels.
 // EPI selects the special epilogues that only one launch of the network uses, each in an instantiation of its own:
@@ -344,7 +330,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
     int tile_px, tile_ch;
     fast_divmod(tile, tiles_ch, inv_tch, tile_px, tile_ch);
     const int px_base = tile_px * BPX, ch_base = tile_ch * BCH;
-    // Fast epilogue (common.h): the whole tile is inside the tensor and images are contiguous, so the output address
+    // Fast epilogue (device_prims.h): the whole tile is inside the tensor and images are contiguous, so the output address
     // is affine in the pixel index; the bias is fetched before the K loop and waits in registers.
     const bool fast = MT >= 2 && !a.out_f32 && a.convt_co == 0 && px_base + BPX <= a.M && ch_base + BCH <= a.Cout &&
                       a.y_bstride == (long)HoWo * a.ldy && (!a.res || a.r_bstride == (long)HoWo * a.ldr) && !(a.dbg & (32 | 256));
@@ -407,7 +393,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float v0 = acc[2 * sg][nt][j] + b0[j], v1 = acc[2 * sg + 1][nt][j] + b1[j];
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); }
+            if (a.act) { v0 = m355_silu(v0); v1 = m355_silu(v1); }
             o[j] = m355_to_half(v0);
             o[4 + j] = m355_to_half(v1);
           }
@@ -564,7 +550,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float v0 = acc[2 * sg][nt][j] + b0[j], v1 = acc[2 * sg + 1][nt][j] + b1[j];
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); }
+            if (a.act) { v0 = m355_silu(v0); v1 = m355_silu(v1); }
             o[j] = m355_to_half(v0);
             o[4 + j] = m355_to_half(v1);
           }
@@ -611,8 +597,8 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float v0 = acc2[0][nt2][j] + c0[j], v1 = acc2[1][nt2][j] + c1[j];
-          v0 = silu_f(v0);
-          v1 = silu_f(v1);
+          v0 = m355_silu(v0);
+          v1 = m355_silu(v1);
           o[j] = m355_to_half(v0);
           o[4 + j] = m355_to_half(v1);
         }
@@ -661,7 +647,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float v0 = acc[2 * sg][nt][j] + b0[j], v1 = acc[(MT >= 2 ? 2 * sg + 1 : 0)][nt][j] + b1[j];
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); }
+            if (a.act) { v0 = m355_silu(v0); v1 = m355_silu(v1); }
             if (rp) { v0 += (float)rv[j]; v1 += (float)rv[4 + j]; }
             o[j] = m355_to_half(v0);
             o[4 + j] = m355_to_half(v1);
@@ -769,7 +755,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         for (int j = 0; j < GW; ++j) v[j] += bias_fin[cidx + j];
         if (a.act && !(a.dbg & 32)) {
 #pragma unroll
-          for (int j = 0; j < GW; ++j) v[j] = silu_f(v[j]);
+          for (int j = 0; j < GW; ++j) v[j] = m355_silu(v[j]);
         }
         if (a.res) {
           const half_t* rp = a.res + (long)b * a.r_bstride + (long)pix * a.ldr + ch0;
@@ -815,8 +801,6 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
   // every LDS-DMA this wave issued was waited for by the last kstep's vmcnt(0): no DMA can land after exit
 }
 
-int g_num_cus = 0;
-
 template <int MT, int NT, int WCH, int WPX>
 int launch_variant(const ConvArgs& a, hipStream_t s) {
   constexpr int BCH = WCH * MT * 16, BPX = WPX * NT * 16;
@@ -824,12 +808,8 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
   const int tiles_ch = (a.Cout + BCH - 1) / BCH;
   const int tiles_px = (a.M + BPX - 1) / BPX;
   if (!conv_rows_covered(a, BCH)) return -1;   // the tile would fetch weight rows past the caller's buffer
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -2;
-    g_num_cus = prop.multiProcessorCount;
-  }
+  const int cus = num_cus();
+  if (cus <= 0) return -2;
   // One tile per block by default.  A persistent grid (CUs x resident blocks, loader cursor crossing
   // tile boundaries) is supported by the kernel but measured SLOWER on MI355X for every layer of this
   // network (fewer resident waves, epilogue-store drain on the next tile's first vmcnt(0)); it is kept
@@ -844,7 +824,7 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
   if ((a.dbg & 64) || (a.ksize == 1 && BCH <= 64 && !proc_switches().no_persist)) {
     int per_cu = (160 * 1024) / LDS;
     if (per_cu > 2) per_cu = 2;
-    if (grid_x > g_num_cus * per_cu) grid_x = g_num_cus * per_cu;
+    if (grid_x > cus * per_cu) grid_x = cus * per_cu;
   }
   // bias table in LDS: the 1x1 / 3x3 fast-epilogue launches without the fused second conv or the decode (their epilogues
   // reuse the stage memory and read a.bias directly)
@@ -859,7 +839,6 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
     }
   }
   const dim3 grid(grid_x), block(WCH * WPX * 64);
-  hipError_t e;
   auto k1 = conv_igemm_kernel<MT, NT, WCH, WPX, 1>;
   auto k2 = conv_igemm_kernel<MT, NT, WCH, WPX, 2>;
   auto k3 = conv_igemm_kernel<MT, NT, WCH, WPX, 3>;
@@ -876,8 +855,7 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
     if (a.dec_preds || (a.phase && a.w2)) return -1;
   }
   if (lds_bytes > 65536) {
-    e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS + 8192);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)k, LDS + 8192)) return e;
   }
   hipLaunchKernelGGL(k, grid, block, lds_bytes, s, aa);
   return (int)hipGetLastError();

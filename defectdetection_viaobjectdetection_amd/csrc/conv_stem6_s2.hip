@@ -19,6 +19,7 @@
 #include <stdio.h>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace m355 {
 namespace {

@@ -21,12 +21,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 16;                 // output tile (160 x 160 map at 640 x 640)
@@ -46,21 +47,6 @@ constexpr int W2_OFF = W0_OFF + 2048;          // the 1x1's 2 x 4 fragments, lan
 constexpr int LDS_BYTES = W2_OFF + 8192;       // 115 744
 constexpr int NPX = PRR * PCC;                 // 561 patch pixels
 static_assert((NPX + 15) / 16 == 36, "nine blocks of 16 patch pixels per wave of team X");
-
-__device__ __forceinline__ void silu16(float16v& v) {       // the five operations of m355_silu per element, staged: same bits
-#pragma clang fp contract(off)
-  float16v t;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = v[j] * -1.4426950408889634f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_exp2f(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = 1.0f + t[j];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_rcpf(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = v[j] * t[j];
-}
 
 __global__ __launch_bounds__(512, 2) void stem_s2c32_cv1_v2_kernel(const ConvArgs a, const StemArgs st, int tiles_x, int tiles_y, int ntiles,
                                                                   int nxb) {
@@ -352,11 +338,9 @@ int launch_stem_s2c32_v2(const ConvArgs& a, const StemArgs& st, hipStream_t s) {
   const int ntiles = st.B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem_s2c32_cv1_v2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)stem_s2c32_cv1_v2_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;
     if (slots < 8) slots = 8;
   }

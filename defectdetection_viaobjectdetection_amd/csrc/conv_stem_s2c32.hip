@@ -21,12 +21,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 16;                 // output tile (160 x 160 map at 640 x 640)
@@ -324,11 +325,9 @@ int launch_stem_s2c32(const ConvArgs& a, const StemArgs& st, hipStream_t s) {
   const int ntiles = st.B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem_s2c32_cv1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)stem_s2c32_cv1_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~7;
     if (slots < 8) slots = 8;
   }

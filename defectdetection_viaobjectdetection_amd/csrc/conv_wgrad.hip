@@ -21,6 +21,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
@@ -42,19 +44,8 @@ namespace {
 
 typedef short short4v __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-__device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, int& r) {
-  q = (int)((float)n * inv_d);
-  r = n - q * d;
-  if (r < 0) { r += d; --q; }
-  if (r >= d) { r -= d; ++q; }
-}
-
-__device__ __forceinline__ half8 tr_frag(const char* p) {
+// fixed 256-byte LDS rows (conv_wgrad3.hip: tr_frag_rows, row pitch as a template argument)
+__device__ __forceinline__ half8 tr_frag_256(const char* p) {
   // two transposed reads: rows +0..3 and +4..7 (4 rows = 1024 bytes apart) -> 8 k-values of one column
   const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)p);
   const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(p + 1024));
@@ -158,9 +149,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     for (int ks = 0; ks < 2; ++ks) {
       half8 af[4], bf[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = tr_frag(sb + aoff[i] + ks * 32 * ROWB2);
+      for (int i = 0; i < 4; ++i) af[i] = tr_frag_256(sb + aoff[i] + ks * 32 * ROWB2);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) bf[i] = tr_frag(sb + boff[i] + ks * 32 * ROWB2);
+      for (int i = 0; i < 4; ++i) bf[i] = tr_frag_256(sb + boff[i] + ks * 32 * ROWB2);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -234,7 +225,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, floa
 // registers for the whole stream.  D[co][n], n = (tap, ci) = the KRSC column.  The four waves of a block add their tiles in wave
 // order and the block writes ONE partial slab; wgrad_reduce_kernel adds the slabs in block order: bitwise reproducible.
 // ---------------------------------------------------------------------------------------------------------
-typedef float float16v __attribute__((ext_vector_type(16)));
 constexpr int SW_PX = 64;                  // output pixels per chunk
 constexpr int SW_XCOLS = 2 * SW_PX + 1;    // input columns a chunk touches (2 wo0 - 1 .. 2 wo0 + 127)
 constexpr int SW_XPITCH = SW_XCOLS + 1;    // LDS pitch of an input row in pixels (16 bytes each)
@@ -563,11 +553,8 @@ int launch_conv_wgrad(const half_t* dz, long dz_bstride, int lddz, const half_t*
     return (int)hipGetLastError();
   }
   if (wgrad_s2c32_ok(Hi, Wi, Cin, Ho, Wo, Cout, ksize, stride, pad, lddz, ldx) && ws && ws_bytes >= (size_t)64 * 64 * 288 * sizeof(float)) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -2;
-    }
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     const long chunks = (long)B * Ho * ((Wo + W2_PX - 1) / W2_PX);
     long nb = (long)proc_switches().w2_blocks_x2 * cus / 2;                     // two blocks per CU (registers), one slab each
     if (nb > W2_SLABS) nb = W2_SLABS;
@@ -596,8 +583,7 @@ int launch_conv_wgrad(const half_t* dz, long dz_bstride, int lddz, const half_t*
     if (lds < 4 * mb * 32 * 96 * 4) lds = 4 * mb * 32 * 96 * 4;
     auto k = mb == 2 ? wgrad_stem_kernel<2> : wgrad_stem_kernel<1>;
     if (lds > 65536) {
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
+      if (const int e = prepare_kernel((const void*)k, lds)) return e;
     }
     hipLaunchKernelGGL(k, dim3(sk), dim3(256), lds, s, dz, dz_bstride, lddz, x, x_bstride, B, Ho, Wo, Cout, sk > 1 ? ws : dw, sk);
     if (sk > 1) {

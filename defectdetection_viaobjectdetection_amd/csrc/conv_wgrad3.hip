@@ -26,6 +26,8 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
@@ -43,18 +45,12 @@ struct Wgrad3Args {
 namespace {
 
 typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 16, PW = TW + 2;   // output tile, patch width; the patch has TH + 2 = 10 rows = 180 pixels
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
-// 8 consecutive LDS rows (pixels) of one channel: rows +0..3 and +4..7
+// 8 consecutive LDS rows (pixels) of one channel: rows +0..3 and +4..7; ROWB = the row pitch (conv_wgrad.hip: tr_frag_256, fixed)
 template <int ROWB>
-__device__ __forceinline__ half8 tr_frag(const char* p) {
+__device__ __forceinline__ half8 tr_frag_rows(const char* p) {
   const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)p);
   const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(p + 4 * ROWB));
   half8 r;
@@ -165,13 +161,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_kernel(const Wgrad3Args a)
 #pragma unroll
     for (int cc = 0; cc < TH / KS; ++cc) {
       const int c = cc * KS + wk;                       // tile row = K chunk of 16 pixels
-      const half8 af = tr_frag<ROWZ>(zb + c * 16 * ROWZ + zoff);
+      const half8 af = tr_frag_rows<ROWZ>(zb + c * 16 * ROWZ + zoff);
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
           const int base = (c + kh) * PW + kw;
-          const half8 bf = tr_frag<ROWX>(xb + base * ROWX + xoff[base & 3]);
+          const half8 bf = tr_frag_rows<ROWX>(xb + base * ROWX + xoff[base & 3]);
           acc[kh * 3 + kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[kh * 3 + kw], 0, 0, 0);
         }
     }
@@ -257,8 +253,7 @@ int launch3(const Wgrad3Args& a, int blocks, hipStream_t s) {
   if (LDS > 65536) {
     static bool set = false;
     if (!set) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad3_kernel<NCO, NCI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      if (e != hipSuccess) return (int)e;
+      if (const int e = prepare_kernel((const void*)conv_wgrad3_kernel<NCO, NCI>, LDS)) return e;
       set = true;
     }
   }

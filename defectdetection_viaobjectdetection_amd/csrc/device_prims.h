@@ -1,0 +1,155 @@
+// Device primitives shared by the kernel files (gfx950 only).  Include from .hip files only.
+// One definition each: a kernel file whose helper differs keeps it locally under a name that says how.
+#pragma once
+#include "common.h"
+
+namespace m355 {
+
+typedef float float16v __attribute__((ext_vector_type(16)));   // the accumulator of one 32x32 MFMA
+
+// ---- LDS-DMA: 16 (4) bytes per lane straight from memory into LDS, lane-linear at the wave-uniform LDS address
+// buffer form: descriptor + per-lane byte offset voff + wave-uniform byte offset soff (out-of-range lanes read zeros)
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
+}
+// global form (global_load_lds_dwordx4 / _dword): per-lane SOURCE address, no bound
+__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+__device__ __forceinline__ void glds4(const void* gsrc, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
+}
+
+// s_waitcnt immediate (gfx9 encoding): vmcnt(n) lgkmcnt(0), expcnt untouched.  The builtin (unlike inline asm) is
+// visible to the compiler's own wait-count insertion, which then does not re-wait for LDS reads issued before it.
+#define WAITCNT_VM_LGKM0(n) ((((n) & 0xf) | (((n) >> 4) << 14) | (7 << 4)))
+
+__device__ __forceinline__ int lane_id() {            // volatile: lane-derived values are rebuilt where they are used, not kept
+  int ln;                                             // live (= spilled) across the K loop; a scratch reload waits on vmcnt(0)
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+  return ln;
+}
+
+// q = n / d, r = n % d for 0 <= n < 2^24 via a float reciprocal estimate + exact integer correction.
+__device__ __forceinline__ void fast_divmod(int n, int d, float inv_d, int& q, int& r) {
+  q = (int)((float)n * inv_d);
+  r = n - q * d;
+  if (r < 0) { r += d; --q; }
+  if (r >= d) { r -= d; ++q; }
+}
+
+// ---- weight-row order of a 32x32x16 MFMA
+// MFMA row rho = 8 q + 4 h + i is accumulator register 4 q + i of lane-half h.
+// Plain order: lane-half h's 16 registers are 16 consecutive channels 16 h + r (what a 16-byte NHWC store wants).
+__device__ __forceinline__ int row_plain(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
+// Operand order: register r of lane-half h is channel 16 (r >> 3) + 8 h + (r & 7), so that registers 8 s .. 8 s + 7,
+// converted to fp16, ARE the B fragment (K slice s, k = 16 s + 8 h + j) of the next 32x32x16 MFMA for the same pixels.
+__device__ __forceinline__ int row_operand(int rho) {
+  const int q = rho >> 3, h = (rho >> 2) & 1, i = rho & 3;
+  return 16 * (q >> 1) + 8 * h + 4 * (q & 1) + i;
+}
+
+// ---- SiLU and the conv epilogue
+// v * sigmoid(v);  exp2-based, rcp approx (1 ulp) -- far inside fp16 output rounding.
+// No FMA contraction in the epilogue arithmetic: the generic and the fast epilogue must give the same bits, so that an
+// image's result does not depend on whether its tile was a full one (batch size / position invariance is tested).
+__device__ __forceinline__ float m355_silu(float v) {
+#pragma clang fp contract(off)
+  const float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
+  return v * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
+// SiLU of all 16 accumulators of a lane: the five operations of m355_silu per element, staged: same bits
+__device__ __forceinline__ void silu16(float16v& v) {
+#pragma clang fp contract(off)
+  float16v t;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t[j] = v[j] * -1.4426950408889634f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_exp2f(t[j]);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t[j] = 1.0f + t[j];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_rcpf(t[j]);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = v[j] * t[j];
+}
+
+// Round-to-fp16 of an epilogue value.  The value is made opaque first: otherwise the compiler may fuse the last
+// multiply (or the residual add) with the conversion into v_fma_mix*_f16 for SOME elements of SOME template
+// instantiations -- one rounding instead of two, a rare 1-ulp difference that breaks bit-exact tile / batch invariance.
+__device__ __forceinline__ half_t m355_to_half(float v) {
+  asm volatile("" : "+v"(v));
+  return (half_t)v;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Fast conv epilogue shared by the conv kernels.
+// A wave measured 13-15 k cycles in the generic epilogue of a 64 ch x 128 px tile: ~85 instructions per 16-byte
+// store (per-group validity branches with EXEC save / restore, 64-bit address multiplies, an LDS / global bias read
+// with its own wait) at one instruction per 4 cycles per wave.  When the whole wave tile is inside the tensor the
+// addresses are affine (base + nt * ystep + group * 32 channels), the bias sits in 16 registers and the SiLU is
+// packed: ~40 instructions per store, no branch.
+// ---------------------------------------------------------------------------------------------------------
+// acc[2s][nt] / acc[2s+1][nt] hold channels 8g..8g+3 / 8g+4..8g+7 of group s for pixel nt (see conv_igemm.hip);
+// yp / rp point at (pixel nt = 0, group 0) of this lane; ystep / rstep = elements between consecutive nt.
+template <int MT, int NT, bool ACT, bool RES>
+__device__ __forceinline__ void conv_epilogue_fast(float4v (&acc)[MT][NT], const float4v (&bias)[MT / 2][2], half_t* yp,
+                                                   long ystep, const half_t* rp, long rstep) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+    for (int s = 0; s < MT / 2; ++s) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = acc[2 * s][nt][j] + bias[s][0][j];
+        v[4 + j] = acc[2 * s + 1][nt][j] + bias[s][1][j];
+      }
+      if (ACT) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
+      }
+      if (RES) {
+        const half8 rv = *(const half8*)(rp + nt * rstep + s * 32);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += (float)rv[j];
+      }
+      half8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = m355_to_half(v[j]);
+      *(half8*)(yp + nt * ystep + s * 32) = o;
+    }
+  }
+}
+// Same, with one output pointer per pixel tile (ConvTranspose pixel-shuffle stores: not affine in nt), no residual.
+template <int MT, int NT, bool ACT>
+__device__ __forceinline__ void conv_epilogue_fast_ptrs(float4v (&acc)[MT][NT], const float4v (&bias)[MT / 2][2],
+                                                        half_t* const (&yp)[NT]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+    for (int s = 0; s < MT / 2; ++s) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = acc[2 * s][nt][j] + bias[s][0][j];
+        v[4 + j] = acc[2 * s + 1][nt][j] + bias[s][1][j];
+      }
+      if (ACT) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
+      }
+      half8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = m355_to_half(v[j]);
+      *(half8*)(yp[nt] + s * 32) = o;
+    }
+  }
+}
+
+}  // namespace m355

@@ -24,11 +24,11 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 
 namespace m355 {
 namespace {
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TP = 128, ROWB = 448, NWAVES = 8;      // (28 chunks of 16 bytes per pixel row)
 constexpr int TILE_BYTES = TP * ROWB;                // 57344
@@ -40,15 +40,6 @@ constexpr int STG_BLOCK = 32 * WO_MAX * 4 + 256;     // (per pixel block)
 constexpr int BIAS_OFF = STG_OFF + 4 * STG_BLOCK;    // 64 + nc + nm floats
 constexpr int ROWT_OFF = BIAS_OFF + 512;             // 128 row bases (float index into preds, as long)
 constexpr int LDS_BYTES = ROWT_OFF + TP * 8;         // 151 040
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ int lane_id() {
-  int ln;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-  return ln;
-}
 
 // the DFL expectation of one side: head_decode_kernel's loop over the 16 bins, bias added first
 __device__ __forceinline__ float dfl_side(const float16v& acc, const float* bias16) {
@@ -227,11 +218,9 @@ int launch_head_tail(const HeadTailArgs& a, hipStream_t s) {
   const int ntiles = (int)((a.M + TP - 1) / TP);
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)head_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)head_tail_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus > 0 ? cus : 1;
   }
   const int grid = ntiles <= slots ? ntiles : slots;

@@ -16,6 +16,8 @@
 //     backward, so the dense map is written once, already scaled (a stored fp32 map, `* g` and `.half()` were 3 passes).
 // HBM traffic is the prototype map once per kernel plus the gradient map once: ~0.2 GB at batch 64.
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 
 namespace m355 {
 namespace {
@@ -571,8 +573,8 @@ int launch_tal_assign(const float* scores, const float* boxes, const float* anch
   if (lds1 > 150 * 1024 || lds2 > 150 * 1024) return -1;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)tal_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -2;
-    if (hipFuncSetAttribute((const void*)tal_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return -2;
+    if (prepare_kernel((const void*)tal_topk_kernel, 150 * 1024)) return -2;
+    if (prepare_kernel((const void*)tal_resolve_kernel, 150 * 1024)) return -2;
     attr = true;
   }
   hipLaunchKernelGGL(tal_topk_kernel, dim3(G, B), dim3(256), lds1, s, scores, boxes, anchors_px, gt_cls, gt_boxes, gt_valid, A, G, nc, top_idx,

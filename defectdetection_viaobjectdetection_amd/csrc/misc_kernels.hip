@@ -5,12 +5,14 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
 
-__device__ __forceinline__ float silu_f(float v) {
+// m355_silu without its fp-contract pragma: the compiler may fuse the caller's arithmetic into it
+__device__ __forceinline__ float silu_contracted(float v) {
   float e = __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
   return v * __builtin_amdgcn_rcpf(1.0f + e);
 }
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemArgs a) {
       for (int mt = 0; mt < MT; ++mt) {
         half4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (half_t)silu_f(acc[mt][j] * inv255 + bias[mt][j]);
+        for (int j = 0; j < 4; ++j) o[j] = (half_t)silu_contracted(acc[mt][j] * inv255 + bias[mt][j]);
         *(half4*)(yp + mt * 16 + g * 4) = o;
       }
     }
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(256) void stem_rows_kernel(const StemArgs a) {
       for (int mt = 0; mt < MT; ++mt) {
         half4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (half_t)silu_f(acc[mt][j] * inv255 + bias[mt][j]);
+        for (int j = 0; j < 4; ++j) o[j] = (half_t)silu_contracted(acc[mt][j] * inv255 + bias[mt][j]);
         *(half4*)(yp + mt * 16 + g * 4) = o;
       }
     }
@@ -463,8 +465,7 @@ int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y
   auto k = owned ? (cg == 4 ? sppf_pool_kernel<4> : (cg == 2 ? sppf_pool_kernel<2> : sppf_pool_kernel<1>))
                  : (cg == 4 ? sppf_pool_generic_kernel<4> : (cg == 2 ? sppf_pool_generic_kernel<2> : sppf_pool_generic_kernel<1>));
   if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)k, (int)lds)) return e;
   }
   hipLaunchKernelGGL(k, dim3(B * (C / (8 * cg))), dim3(owned ? SPPF_NT : 256), lds, s, x, x_bstride, ldx, y, y_bstride, ldy, H, W, C);
   return (int)hipGetLastError();
@@ -489,8 +490,7 @@ int launch_head_decode(const float* raw, int B, int in_h, int in_w, int nc, int 
   const size_t lds = (size_t)DEC_ANCHORS * ((64 + nc + nm) + (4 + nc + nm)) * sizeof(float);
   if (lds > 160 * 1024) return -1;
   if (lds > 64 * 1024) {  // many classes (nc = 80: 75 KB)
-    hipError_t e = hipFuncSetAttribute((const void*)head_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)head_decode_kernel, (int)lds)) return e;
   }
   hipLaunchKernelGGL(head_decode_kernel, dim3((unsigned)((total + DEC_ANCHORS - 1) / DEC_ANCHORS)), dim3(256), lds, s,
                      raw, total, A, w3, w4, w5, n3, n4, nc, nm, preds);

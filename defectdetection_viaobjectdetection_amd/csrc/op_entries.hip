@@ -10,6 +10,7 @@
 
 #include "../../include/mi355yolo.h"
 #include "common.h"
+#include "launch_util.h"
 #include "switches.h"
 #include "weight_pack.h"
 
@@ -65,11 +66,11 @@ int finish_entry(int rc, hipStream_t s, const char* what) {
 struct SlabDiag {
   const char* path = live_stamps_path();
   size_t words = 0;
-  unsigned long long* stamps = nullptr;   // nullptr when M355_STAMPS is unset
+  StampSink sink;                         // over a buffer of the entry's DevBuf; sink.d stays nullptr when M355_STAMPS is unset
   bool alloc(DevBuf& d, size_t n) {       // false: the stamp buffer could not be allocated
     words = n;
-    if (path) stamps = (unsigned long long*)d.zeroed(n * 8);
-    return !path || stamps;
+    if (path) sink.d = (unsigned long long*)d.zeroed(n * 8);
+    return !path || sink.d;
   }
   template <class Launch>
   int reps(int rc, hipStream_t s, const char* what, Launch launch) const {
@@ -88,11 +89,7 @@ struct SlabDiag {
     return rc;
   }
   void dump(bool ok) const {   // after the stream synchronisation
-    if (!path || !ok) return;
-    std::vector<unsigned long long> h(words);
-    (void)hipMemcpy(h.data(), stamps, words * 8, hipMemcpyDeviceToHost);
-    FILE* f = fopen(path, "wb");
-    if (f) { fwrite(h.data(), 8, words, f); fclose(f); }
+    if (ok) sink.write(path, words * 8);
   }
 };
 
@@ -142,7 +139,7 @@ int conv_op_common(const void* d_x, int B, int H, int W, int cin, const float* h
   }
   a.M = B * a.Ho * a.Wo;
   a.dbg = force_tile >= 0 ? (force_tile >> 8) : 0;
-  a.stamps = diag.stamps;
+  a.stamps = diag.sink.d;
   int rc = 0;
   if (force_tile >= 0 && (force_tile & 0xff) == TILE_PLANES) {   // row-slab kernel (conv3x3_planes.hip), single-conv mode
     PlanesArgs pa{};
@@ -226,7 +223,7 @@ int m355_bneck_pair_fwd(const void* d_x, int B, int H, int W, int C, int ldx, co
   a.ba = db; a.bb = db + rows;
   a.y = (half_t*)d_y; a.y_bstride = (long)H * W * ldy; a.ldy = ldy; a.act = 1; a.stride = 1;
   if (shortcut) { a.res = a.x; a.r_bstride = a.x_bstride; a.ldr = ldx; }
-  a.stamps = diag.stamps;
+  a.stamps = diag.sink.d;
   const bool ok = bneck_pair_ok(a);
   char what[64];
   snprintf(what, sizeof(what), "bneck_pair B=%d %dx%d C=%d", B, H, W, C);

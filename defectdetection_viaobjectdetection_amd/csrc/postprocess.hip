@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
@@ -378,9 +379,7 @@ int launch_nms(const float* preds, int B, int A, int nc, int nm, float conf, flo
   const size_t lds = base + (size_t)lds_keys * 8;
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)nms_kernel, 160 * 1024 - 256)) return e;
     attr_set = true;
   }
   hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(NMS_THREADS), lds, s, preds, A, nc, nm, conf, iou, max_det, dets,

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "launch_util.h"
 
 namespace m355 {
 namespace {
@@ -212,9 +213,7 @@ int launch_proto_masks_native(const float* dets, const int* counts, const half_t
   const size_t lds_max = (size_t)WIN_ROWS * MAX_PROTO * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)proto_masks_native_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_max);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)proto_masks_native_kernel, (int)lds_max)) return e;
     attr_set = true;
   }
   for (int g0 = 0; g0 < B; g0 += MAX_IMGS) {

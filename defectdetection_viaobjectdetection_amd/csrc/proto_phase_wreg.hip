@@ -24,12 +24,12 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "switches.h"
 
 namespace m355 {
 namespace {
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int TH = 8, TW = 16, PP = 17, ROWB = 256, NWAVES = 8;
 constexpr int PROWS = (TH + 1) * PP;                 // 153 patch pixels
@@ -43,26 +43,6 @@ constexpr int BIAS_OFF = W3_OFF + 8 * 1024;          // [9][128] floats + 32 flo
 constexpr int STG_OFF = BIAS_OFF + 9 * 512 + 128;    // output staging: 4 waves x 32 pixels x 64 bytes
 constexpr int TAB_OFF = STG_OFF + 4 * 2048;          // DMA offset table: [39 pieces][64 lanes] ints
 constexpr int LDS_BYTES = TAB_OFF + 39 * 256;        // 143744
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ int row_plain(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
-
-__device__ __forceinline__ void silu16(float16v& v) {
-#pragma clang fp contract(off)
-  float16v t;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = v[j] * -1.4426950408889634f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_exp2f(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = 1.0f + t[j];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) t[j] = __builtin_amdgcn_rcpf(t[j]);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = v[j] * t[j];
-}
 
 __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ntiles, int sx, int sy,
                                                                  int sb, int prio, unsigned long long* stamps) {
@@ -342,11 +322,9 @@ int launch_proto_phase_wreg(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;            // per phase
   static int slots = 0;
   if (!slots) {
-    hipError_t e = hipFuncSetAttribute((const void*)proto_phase_wreg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -2;
+    if (const int e = prepare_kernel((const void*)proto_phase_wreg_kernel, LDS_BYTES)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
     slots = cus & ~3;
     if (slots < 4) slots = 4;
   }
@@ -355,21 +333,10 @@ int launch_proto_phase_wreg(const ConvArgs& a, hipStream_t s) {
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
   const int prio = proc_switches().protor_prio;
   const char* st_path = proc_switches().protor_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
-  static unsigned long long* d_st = nullptr;
-  if (st_path && !d_st) {
-    if (hipMalloc((void**)&d_st, (size_t)slots * NWAVES * 64) != hipSuccess) return -2;
-    (void)hipMemset(d_st, 0, (size_t)slots * NWAVES * 64);
-  }
-  hipLaunchKernelGGL(proto_phase_wreg_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, d_st);
-  if (st_path) {
-    if (hipStreamSynchronize(s) != hipSuccess) return -2;
-    const size_t nbytes = (size_t)grid * NWAVES * 64;
-    unsigned long long* hbuf = (unsigned long long*)malloc(nbytes);
-    (void)hipMemcpy(hbuf, d_st, nbytes, hipMemcpyDeviceToHost);
-    FILE* f = fopen(st_path, "wb");
-    if (f) { fwrite(hbuf, 1, nbytes, f); fclose(f); }
-    free(hbuf);
-  }
+  static StampSink sink;
+  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
+  hipLaunchKernelGGL(proto_phase_wreg_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, sink.d);
+  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
   return (int)hipGetLastError();
 }
 

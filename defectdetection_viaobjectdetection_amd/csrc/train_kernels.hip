@@ -8,6 +8,8 @@
 // ~100 us per launch: one block reading 256 rows is a serial tail; the separate kernel costs what the memset of the
 // atomic version did -- one more stream operation.)
 #include "common.h"
+#include "device_prims.h"
+#include "launch_util.h"
 #include "../../include/mi355yolo.h"
 
 namespace m355 {
@@ -575,8 +577,7 @@ int launch_sppf_pool_bwd(const half_t* a, long a_bs, int lda, const half_t* y, l
   const size_t lds = (size_t)H * W * 8 * (2 + 2 + 4 + 4);
   if (lds > 160 * 1024) return -1;
   if (lds > 65536) {
-    hipError_t e = hipFuncSetAttribute((const void*)sppf_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = prepare_kernel((const void*)sppf_pool_bwd_kernel, (int)lds)) return e;
   }
   hipLaunchKernelGGL(sppf_pool_bwd_kernel, dim3(B * (C / 8)), dim3(256), lds, s, a, a_bs, lda, y, y_bs, ldy, gy, gy_bs, ldgy, ga,
                      ga_bs, ldga, H, W, C, accumulate);
