@@ -115,6 +115,8 @@ SIGNATURES = {
                                   C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "m355_c2f_c32_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "m355_bneck_pair_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "m355_conv3x3_blockdiag_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "m355_planes_diag_pack": (C.c_long, [C.c_int, _P, _P, _P, _P, C.c_long]),
     "m355_s2c64_cv1_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "m355_stem_s2c32_cv1_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "m355_proto_phase_fwd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),

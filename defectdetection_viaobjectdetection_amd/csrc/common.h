@@ -188,12 +188,21 @@ struct PlanesArgs {
   const half_t* res; long r_bstride; int ldr;    // optional residual (the shortcut of a Bottleneck: x itself)
   int act;
   unsigned long long* stamps;                    // diagnostic: 8 uint64 per wave (nullptr in production)
+  // block-diagonal single mode (launch_conv3x3_blockdiag): diag_n convs side by side, conv i = the next diag_cin[i] input channels ->
+  // the next diag_cout[i] output channels (Cin / Cout = their sums; every cout but the last a multiple of 64).  wfb = the convs'
+  // planes_frag_pack_padded lists one after the other (each over its OWN input planes), bb = their biases at their channel offsets,
+  // padded with zeros to a multiple of 64 floats.
+  int diag_n;
+  int diag_cin[4], diag_cout[4];
+  int diag_walk;                                 // 0: the launcher chooses how a block walks the tiles; tests: 1 single tiles, 2 whole slabs
 };
 bool bneck_pair_shape_ok(int C, int H, int W);
 bool bneck_pair_ok(const PlanesArgs& a);
 int launch_bneck_pair(const PlanesArgs& a, hipStream_t s);
 bool conv3x3_planes_ok(const PlanesArgs& a);
 int launch_conv3x3_planes(const PlanesArgs& a, hipStream_t s);
+bool conv3x3_blockdiag_ok(const PlanesArgs& a);
+int launch_conv3x3_blockdiag(const PlanesArgs& a, hipStream_t s);
 
 struct StemArgs {
   const uint8_t* x; int B, H, W;     // uint8 NHWC (B,H,W,3)

@@ -4,7 +4,8 @@
 // Replaces: the Conv+BN+SiLU 3x3 pairs  m.cv1 -> m.cv2  of upstream's C2f Bottleneck (e = 1.0) that
 // BscanBased/yolo8_seg_predict.py:8 reaches through torch.nn.functional.conv2d, two launches and one HBM round trip of the
 // hidden tensor in rounds 1-3 (conv3x3_m32 / conv3x3_halo); in single-conv mode the 3x3 layers of the 20 x 20 level
-// (conv3x3_small.hip's slab kernel).
+// (conv3x3_small.hip's slab kernel); in block-diagonal single mode the second 3x3 stage of a head level -- cv2.l.1, cv3.l.1 and
+// cv4.l.1 over the channel slices of one tensor, three launches before -- with every channel tile on the input planes of its own conv.
 //
 // Why.  Round 3's stamps: a 128 -> 128 layer on a 40 x 40 map at batch 32 keeps the matrix pipe 42 % busy.  conv3x3_m32 runs
 // two blocks per CU that each stream the whole 295 KB weight matrix through LDS for 128 pixels: 32 B/clk/CU of weight
@@ -63,6 +64,12 @@ struct PlanesGeom {
   int tiles_ch;             // single mode: output channel tiles
   int ntiles;
   int off_x, off_s;         // LDS byte offsets: input ring, one spare KiB behind it (reads of never-stored pixel blocks may run past a slot)
+  // block-diagonal single mode (PlanesArgs::diag_n > 0): channel tile t reads the input planes [first, first + count) only and
+  // finds its fragments `wo` phases (18 KiB each) into wfb.  Wave-uniform tables, packed: a nibble / a byte per channel tile.
+  // A block walks UNITS of gsz consecutive tiles (1, or tiles_ch = every channel tile of a slab: the tiles differ in cost).
+  int gsz, nunits;
+  unsigned p0_pk, np_pk;
+  unsigned long long wo_pk;
 };
 
 template <int WC_, int NPB1_, int NPB2_, bool PAIR_, int PPS_, int NW_ = 4, bool S2_ = false>
@@ -243,9 +250,10 @@ __device__ __forceinline__ void planes_phase(PState<C>& st, const float16v& bv, 
 
 struct PTile {
   int b, y0, ch;   // image, first output row, first output channel
+  int p0, np, wo;  // block-diagonal mode: first input plane, input planes, fragment offset in phases
 };
 
-template <class C, bool RES>
+template <class C, bool RES, bool DIAG = false>
 __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const PlanesArgs a, const PlanesGeom g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -263,15 +271,25 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
 
   // XCD-aware persistent walk (as conv3x3_m32.hip): the virtual blocks of one XCD cover a contiguous run of tiles; channel
   // tiles fastest (they share the input slab in L2), then slabs, then images.
-  auto decode = [&](int vb) __attribute__((always_inline)) {
-    const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+  // (block-diagonal mode: vb counts units of gsz tiles, `sub` is the tile inside the unit)
+  auto decode = [&](int vb, int sub) __attribute__((always_inline)) {
+    const int nu = DIAG ? g.nunits : ntiles;
+    const int xcd = vb & 7, q = nu >> 3, r = nu & 7;
+    int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+    if constexpr (DIAG) L = L * g.gsz + sub;
     PTile t;
     const int tch = L % g.tiles_ch;
     const int rest = L / g.tiles_ch;
     t.b = rest / g.nslab;
     t.y0 = (rest - t.b * g.nslab) * R;
     t.ch = tch * 32 * C::WC;
+    if constexpr (DIAG) {
+      t.p0 = (int)(g.p0_pk >> (4 * tch)) & 15;
+      t.np = (int)(g.np_pk >> (4 * tch)) & 15;
+      t.wo = (int)(g.wo_pk >> (8 * tch)) & 255;
+    } else {
+      t.p0 = 0; t.np = g.NP; t.wo = 0;
+    }
     return t;
   };
 
@@ -343,13 +361,24 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
   };
 
   // ---- the block's stream of tiles
-  int vb = blockIdx.x;
-  PTile cur = decode(vb), nxt = cur;
-  bool more = vb + nwg < ntiles;
-  if (more) nxt = decode(vb + nwg);
+  int vb = blockIdx.x, sub = 0;
+  // the tile after (vb, sub) in this block's walk
+  auto has_next = [&]() __attribute__((always_inline)) { return DIAG ? (sub + 1 < g.gsz || vb + nwg < g.nunits) : vb + nwg < ntiles; };
+  auto next_of = [&]() __attribute__((always_inline)) {
+    if constexpr (DIAG) return sub + 1 < g.gsz ? decode(vb, sub + 1) : decode(vb + nwg, 0);
+    else return decode(vb + nwg, 0);
+  };
+  // this wave's fragments of a tile's (second / only) convolution
+  auto wbase_of = [&](const PTile& t) __attribute__((always_inline)) {
+    if constexpr (DIAG) return (const char*)a.wfb + (long)(t.wo + wc * t.np) * pbytes;
+    else return (const char*)a.wfb + (t.ch / 32 + wc) * wblock;
+  };
+  PTile cur = decode(vb, 0), nxt = cur;
+  bool more = has_next();
+  if (more) nxt = next_of();
   const char* const wbase_a = C::PAIR ? (const char*)a.wfa + wc * wblock : nullptr;   // pair: this wave's channel block in the first conv
-  const char* wbase_b = (const char*)a.wfb + (cur.ch / 32 + wc) * wblock;             // second / only conv, this tile
-  const char* wbase_b_next = (const char*)a.wfb + (nxt.ch / 32 + wc) * wblock;        // ... the block's next tile
+  const char* wbase_b = wbase_of(cur);             // second / only conv, this tile
+  const char* wbase_b_next = wbase_of(nxt);        // ... the block's next tile
 
   // ---- prologue: input plane 0 into slot 0, the weight fragments of the first phase
   // (the fragments first: their latency -- a cold L2 for the first blocks of a launch -- covers the piece address arithmetic)
@@ -358,7 +387,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
 #pragma unroll
   for (int m = 0; m < C::PIT; ++m) {
     const int k = wave + C::NW * m;
-    if (k < g.npieces) dma16(st.rs_x, st.pvoff[m], cur.b * img_stride, smem + g.off_x + k * 1024);
+    if (k < g.npieces) dma16(st.rs_x, st.pvoff[m], cur.b * img_stride + (DIAG ? cur.p0 * 64 : 0), smem + g.off_x + k * 1024);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -367,7 +396,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
   const int xslot = g.xrows * ROWB;   // bytes of an input ring slot
   const int iplane = g.irows * ROWB;  // bytes of an intermediate plane
   int xg = 0;                         // input planes consumed so far by this block (ring slot = xg & 1)
-  const int NP = g.NP;                // even
+  int NP = DIAG ? cur.np : g.NP;      // input planes of the tile's (first) convolution
 
   while (true) {
     // =========================== first convolution (pair mode): R + 2 rows of the hidden tensor ===========================
@@ -477,11 +506,11 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
           st.px_dst = st.pnext + wave * 1024;
           if (p + 1 < NP) {
             pieces = true;
-            st.px_soff = cur.b * img_stride + (p + 1) * 64;
+            st.px_soff = cur.b * img_stride + ((DIAG ? cur.p0 : 0) + p + 1) * 64;
           } else if (more) {
             piece_offsets(nxt);
             pieces = true;
-            st.px_soff = nxt.b * img_stride;
+            st.px_soff = nxt.b * img_stride + (DIAG ? nxt.p0 * 64 : 0);
           }
           ++xg;
         }
@@ -490,23 +519,36 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
       };
       setup2(0);
       if (a.stamps) pst[4] = __builtin_amdgcn_s_memtime();
-      planes_phase<C, C::NPB2, true, 0, false>(st, bv2, store2);
-      for (int p = 1; p + 1 < npl; ++p) {
-        setup2(p);
-        if (a.stamps && p < 3) pst[4 + p] = __builtin_amdgcn_s_memtime();
-        planes_phase<C, C::NPB2, false, 0, true>(st, bv2, store2);
+      if constexpr (DIAG) {   // a diagonal block of one input plane: its only phase is the first and the last
+        if (npl == 1) {
+          if (a.stamps) stamp[4] = pst[7] = pst[4];
+          planes_phase<C, C::NPB2, true, RES ? 3 : 2, false>(st, bv2, store2);
+        }
       }
-      setup2(npl - 1);
-      if (a.stamps) stamp[4] = pst[7] = __builtin_amdgcn_s_memtime();
-      planes_phase<C, C::NPB2, false, RES ? 3 : 2, true>(st, bv2, store2);
+      if (!DIAG || npl > 1) {
+        planes_phase<C, C::NPB2, true, 0, false>(st, bv2, store2);
+        for (int p = 1; p + 1 < npl; ++p) {
+          setup2(p);
+          if (a.stamps && p < 3) pst[4 + p] = __builtin_amdgcn_s_memtime();
+          planes_phase<C, C::NPB2, false, 0, true>(st, bv2, store2);
+        }
+        setup2(npl - 1);
+        if (a.stamps) stamp[4] = pst[7] = __builtin_amdgcn_s_memtime();
+        planes_phase<C, C::NPB2, false, RES ? 3 : 2, true>(st, bv2, store2);
+      }
     }
     if (!more) break;
-    vb += nwg;
+    if constexpr (DIAG) {
+      if (++sub == g.gsz) { sub = 0; vb += nwg; }
+      NP = nxt.np;
+    } else {
+      vb += nwg;
+    }
     cur = nxt;
-    more = vb + nwg < ntiles;
-    if (more) nxt = decode(vb + nwg);
+    more = has_next();
+    if (more) nxt = next_of();
     wbase_b = wbase_b_next;
-    wbase_b_next = (const char*)a.wfb + (nxt.ch / 32 + wc) * wblock;
+    wbase_b_next = wbase_of(nxt);
     // this tile's last phase ended without a barrier: the next tile's plane 0 (pieces issued in an earlier phase of this tile by
     // every wave) and its first weight fragments must have landed before anyone reads them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -526,7 +568,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 template <class C>
-bool planes_geometry(const PlanesArgs& a, PlanesGeom* g) {
+bool planes_geometry(const PlanesArgs& a, PlanesGeom* g, bool any_fill = false) {
   constexpr int HALO = C::PAIR ? 2 : 1;
   if (C::S2 && ((a.H | a.W) & 1)) return false;
   const int Ho = C::S2 ? a.H / 2 : a.H, Wo = C::S2 ? a.W / 2 : a.W;
@@ -547,7 +589,7 @@ bool planes_geometry(const PlanesArgs& a, PlanesGeom* g) {
   const int nslab = (Ho + R - 1) / R;
   R = (Ho + nslab - 1) / nslab;                                 // equal slabs
   // the kernel always runs its NPB2 (and NPB1) pixel blocks: refuse geometries that leave them mostly empty
-  if ((long)R * PW * 10 < (long)32 * C::NB2 * 6) return false;
+  if (!any_fill && (long)R * PW * 10 < (long)32 * C::NB2 * 6) return false;
   g->R = R; g->nslab = nslab; g->PW = PW;
   g->irows = 32 * C::NB1;
   g->npieces = (rows_of(R) + 15) / 16;
@@ -557,6 +599,7 @@ bool planes_geometry(const PlanesArgs& a, PlanesGeom* g) {
   g->ntiles = a.B * nslab * g->tiles_ch;
   g->off_x = C::PAIR ? C::WC * g->irows * ROWB : 0;
   g->off_s = g->off_x + 2 * g->xrows * ROWB;
+  g->gsz = 1; g->nunits = g->ntiles; g->p0_pk = g->np_pk = 0; g->wo_pk = 0;
   return g->off_s + 1024 <= LDS_MAX;
 }
 
@@ -646,6 +689,96 @@ bool conv3x3_planes_ok(const PlanesArgs& a) {
   if (a.stride == 2 && a.res) return false;
   PlanesGeom g;
   return a.stride == 2 ? (planes_geometry<S64S2>(a, &g) || (a.Cout % 128 == 0 && planes_geometry<S128S2>(a, &g))) : planes_geometry<S64>(a, &g);
+}
+
+// ---- block-diagonal single mode: diag_n 3x3 convs side by side (the second stage of a head level: 64 -> 64, 128 -> 128, 32 -> 32 over
+// the channels of one 224-channel tensor) as ONE launch.  Channel tile t (64 channels of one conv) runs the K loop over the input
+// planes of its own conv only, in the order of that conv's own conv3x3_planes<64ch,rows> launch: same bits per channel.
+namespace {
+constexpr int DIAG_MAX_TILES = 8;
+
+bool diag_geometry(const PlanesArgs& a, PlanesGeom* g) {
+  if (!planes_common_ok(a) || a.stride != 1 || a.res || a.diag_n < 1 || a.diag_n > 4) return false;
+  int ci = 0, co = 0, tiles = 0, wo = 0;
+  unsigned p0_pk = 0, np_pk = 0;
+  unsigned long long wo_pk = 0;
+  for (int i = 0; i < a.diag_n; ++i) {
+    const int cin = a.diag_cin[i], cout = a.diag_cout[i];
+    if (cin < 32 || cin % 32 || cin / 32 > 15 || cout < 16 || cout % 16) return false;
+    if (i + 1 < a.diag_n && cout % 64) return false;   // only the last conv may end inside a 64-channel tile (its zero rows are never stored)
+    for (int c = 0; c < cout; c += 64) {
+      if (tiles >= DIAG_MAX_TILES || ci / 32 > 15 || wo > 255) return false;
+      p0_pk |= (unsigned)(ci / 32) << (4 * tiles);
+      np_pk |= (unsigned)(cin / 32) << (4 * tiles);
+      wo_pk |= (unsigned long long)wo << (8 * tiles);
+      wo += 2 * (cin / 32);   // two channel blocks of cin / 32 phases each
+      ++tiles;
+    }
+    ci += cin; co += cout;
+  }
+  if (ci != a.Cin || co != a.Cout || a.ldx < a.Cin || a.ldy < a.Cout) return false;
+  if ((long)wo * 18 * 1024 >= (1L << 31)) return false;
+  if (!planes_geometry<S64>(a, g, true) || g->tiles_ch != tiles) return false;
+  g->p0_pk = p0_pk; g->np_pk = np_pk; g->wo_pk = wo_pk;
+  return true;
+}
+
+// The longest walk of a block, in cycles (the planes cost model per phase + the drain and the barrier behind a tile), when the
+// blocks walk units of gsz tiles: the tiles of one slab cost 2 / 4 / 4 / 1 phases on a head level, and a block that walks single
+// tiles always meets the same channel tile when the tile count per XCD is a multiple of tiles_ch.
+long diag_makespan(const PlanesGeom& g, int gsz, int slots) {
+  const int nunits = g.ntiles / gsz, grid = std::min(nunits, slots);
+  const long phase = (long)S64::NPB2 * 18 * 33 + (long)((g.npieces + S64::NW - 1) / S64::NW) * 120 + 700, tile = 1500;
+  long worst = 0;
+  for (int b = 0; b < grid; ++b) {
+    long c = 0;
+    for (int vb = b; vb < nunits; vb += grid) {
+      const int xcd = vb & 7, q = nunits >> 3, r = nunits & 7;
+      const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+      for (int sub = 0; sub < gsz; ++sub) c += tile + phase * ((g.np_pk >> (4 * ((L * gsz + sub) % g.tiles_ch))) & 15);
+    }
+    worst = std::max(worst, c);
+  }
+  return worst;
+}
+}  // namespace
+
+bool conv3x3_blockdiag_ok(const PlanesArgs& a) {
+  PlanesGeom g;
+  return diag_geometry(a, &g);
+}
+
+int launch_conv3x3_blockdiag(const PlanesArgs& a, hipStream_t s) {
+  PlanesGeom g;
+  if (!diag_geometry(a, &g)) return -1;
+  static int slots = 0;
+  if (!slots) {
+    if (const int e = prepare_kernel((const void*)planes_kernel<S64, false, true>, LDS_MAX)) return e;
+    const int cus = num_cus();
+    if (cus <= 0) return -2;
+    slots = std::max(cus & ~7, 8);   // as planes_launch
+  }
+  // the walk: single tiles or whole slabs, whichever ends first; decided once per shape (the forward launches the same few)
+  struct Walk { int B, H, W; unsigned np_pk; int gsz; };
+  thread_local Walk memo[4] = {};
+  thread_local int memo_n = 0;
+  int gsz = a.diag_walk == 1 ? 1 : a.diag_walk == 2 ? g.tiles_ch : 0;
+  for (int i = 0; !gsz && i < memo_n; ++i)
+    if (memo[i].B == a.B && memo[i].H == a.H && memo[i].W == a.W && memo[i].np_pk == g.np_pk) gsz = memo[i].gsz;
+  if (!gsz) {
+    gsz = diag_makespan(g, g.tiles_ch, slots) < diag_makespan(g, 1, slots) ? g.tiles_ch : 1;
+    memo[memo_n % 4] = Walk{a.B, a.H, a.W, g.np_pk, gsz};
+    memo_n = std::min(memo_n + 1, 4);
+  }
+  g.gsz = gsz;
+  g.nunits = g.ntiles / gsz;
+  const int grid = std::min(g.nunits, slots);
+  // every pixel block of a wave is read, also those behind the slab's last row (their results are never stored): the reads of the
+  // last one reach 2 PW + 2 storage indices past the block -- inside the allocation for any fill of the slab
+  const int reach = g.off_x + g.xrows * ROWB + (32 * S64::NB2 + 2 * g.PW + 3) * ROWB;
+  const int lds = std::min(std::max(g.off_s + 1024, (reach + 1023) & ~1023), LDS_MAX);
+  hipLaunchKernelGGL((planes_kernel<S64, false, true>), dim3(grid), dim3(64 * S64::NW), lds, s, a, g);
+  return (int)hipGetLastError();
 }
 
 int launch_conv3x3_planes(const PlanesArgs& a, hipStream_t s) {

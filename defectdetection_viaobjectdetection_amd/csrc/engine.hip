@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -293,6 +294,47 @@ PlanesArgs planes_args(const m355_engine* e, const Op& op, int B, int b0) {
   return a;
 }
 
+// the block-diagonal launch of op `lead` and the op.diag_n - 1 ops behind it (conv3x3_planes.hip, launch_conv3x3_blockdiag)
+PlanesArgs diag_args(const m355_engine* e, size_t lead, int B, int b0) {
+  const Op& op = e->ops[lead];
+  const PhysConv& p = e->phys[op.conv];
+  const Tensor& ti = e->tensors[op.in.t];
+  const Tensor& to = e->tensors[op.out.t];
+  PlanesArgs a{};
+  a.x_bstride = (long)ti.H * ti.W * ti.C; a.ldx = ti.C; a.x = ti.p + op.in.off + b0 * a.x_bstride;
+  a.H = ti.H; a.W = ti.W; a.B = B; a.act = 1; a.stride = 1;
+  a.diag_n = std::min(op.diag_n, 4);
+  for (int i = 0; i < a.diag_n && lead + i < e->ops.size(); ++i) {
+    const PhysConv& q = e->phys[e->ops[lead + i].conv];
+    a.diag_cin[i] = q.cin; a.diag_cout[i] = q.cout;
+    a.Cin += q.cin; a.Cout += q.cout; a.cblocks_b += planes_cblocks(q.cout);
+  }
+  a.wfb = p.wf_diag; a.bb = p.bias_diag;
+  a.y_bstride = (long)to.H * to.W * to.C; a.ldy = to.C; a.y = to.p + op.out.off + b0 * a.y_bstride;
+  return a;
+}
+
+// Can the ops [lead, lead + diag_n) run as one block-diagonal launch?  Plain 3x3 / s1 Conv+SiLU layers on one lane whose input and
+// output slices follow each other in one tensor each, and a shape the kernel takes at max_batch.
+bool head_diag_ok(const m355_engine* e, size_t lead) {
+  const Op& l = e->ops[lead];
+  if (l.diag_n < 2 || l.diag_n > 4 || lead + l.diag_n > e->ops.size()) return false;
+  int in_off = l.in.off, out_off = l.out.off;
+  for (int i = 0; i < l.diag_n; ++i) {
+    const Op& op = e->ops[lead + i];
+    if (op.kind != OP_CONV || op.fused_away || op.stemfuse >= 0) return false;
+    const PhysConv& p = e->phys[op.conv];
+    if (p.k != 3 || p.stride != 1 || !p.act || p.diag || p.l3 >= 0 || p.groups != 1 || p.logical.size() != 1) return false;
+    if (op.res.t >= 0 || op.in2.t >= 0 || op.out_ext != 0 || op.decode || op.lane != l.lane) return false;
+    if (op.in.t != l.in.t || op.out.t != l.out.t || op.in.off != in_off || op.out.off != out_off || op.in.c != p.cin || op.out.c != p.cout) return false;
+    if (i > 0 && (op.record || !op.wait_ops.empty())) return false;
+    in_off += p.cin; out_off += p.cout;
+  }
+  PlanesArgs a = diag_args(e, lead, e->desc.max_batch, 0);
+  a.wfb = (const half_t*)1; a.bb = (const float*)1;   // placeholders: packed when the weights arrive
+  return conv3x3_blockdiag_ok(a);
+}
+
 StemArgs stem_args(const m355_engine* e, const Op& op, int B, int b0, const void* in) {
   const PhysConv& p = e->phys[op.conv];
   const Tensor& to = e->tensors[op.out.t];
@@ -552,6 +594,41 @@ void annotate_ops(m355_engine* e) {
     nx.wbytes += st.wbytes;
     st.flops = st.bytes = st.wbytes = 0;
   }
+  // the second 3x3 stage of the head levels (cv2.l.1 + cv3.l.1 + cv4.l.1) as one block-diagonal row-slab launch per level: every
+  // level the graph marked, or none (the three launches)
+  bool diag_all = !e->sw.no_headdiag && !e->sw.no_planes && e->nm == 32 && e->nc <= 32;   // (the head the kernel was measured on: widths 64 / 128 / 32)
+  size_t diag_groups = 0;
+  for (size_t i = 0; i < e->ops.size(); ++i)
+    if (e->ops[i].diag_n > 0) {
+      ++diag_groups;
+      diag_all = diag_all && head_diag_ok(e, i) && e->ops[i].diag_n == 3 && e->ops[i].in.c == 64 && e->ops[i + 1].in.c == 128 && e->ops[i + 2].in.c == 32;
+    }
+  for (size_t i = 0; diag_all && diag_groups && i < e->ops.size(); ++i) {
+    Op& lead = e->ops[i];
+    if (lead.diag_n <= 0) continue;
+    const Tensor& t = e->tensors[lead.in.t];
+    lead.diag_on = 1;
+    snprintf(lead.kernel, sizeof(lead.kernel), "conv3x3_planes<64ch,rows,diag>");
+    int cin = 0, cout = 0;
+    for (int j = 0; j < lead.diag_n; ++j) {
+      Op& m = e->ops[i + j];
+      PhysConv& p = e->phys[m.conv];
+      p.diag_lead = (int)i;
+      cin += p.cin; cout += p.cout;
+      if (j == 0) continue;
+      // "model.22.cv2.1.1+cv3.1.1+cv4.1.1": the members' names without the module prefix
+      const char* nm = e->convs[p.logical[0]].name;
+      const char* d1 = strchr(nm, '.');
+      const char* d2 = d1 ? strchr(d1 + 1, '.') : nullptr;
+      const size_t len = strlen(lead.layer);
+      snprintf(lead.layer + len, sizeof(lead.layer) - len, "+%s", d2 ? d2 + 1 : nm);
+      lead.flops += m.flops; lead.wbytes += m.wbytes;   // (a block-diagonal fusion counts its diagonal blocks only)
+      m.flops = m.bytes = m.wbytes = 0;
+      m.fused_away = true;
+      snprintf(m.kernel, sizeof(m.kernel), "(none)");
+    }
+    lead.bytes = (double)t.H * t.W * (cin + cout) * 2;
+  }
 }
 
 // device copy of a fragment-ordered weight list (allocated on first use)
@@ -559,6 +636,30 @@ hipError_t put_frags(half_t** dst, const std::vector<half_t>& fp) {
   const size_t bytes = fp.size() * sizeof(half_t);
   const hipError_t st = *dst ? hipSuccess : hipMalloc((void**)dst, bytes);
   return st != hipSuccess ? st : hipMemcpy(*dst, fp.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// A head level's block-diagonal second stage (Op::diag_on): fragments and biases of all members, once their weights are here
+int pack_head_diag(m355_engine* e, size_t lead, int idx_now) {
+  const Op& l = e->ops[lead];
+  std::vector<std::vector<half_t>> rows(l.diag_n);
+  std::vector<float> bias;
+  const half_t* rp[4];
+  int cout[4], kpad[4], cin[4];
+  for (int i = 0; i < l.diag_n; ++i) {
+    const PhysConv& p = e->phys[e->ops[lead + i].conv];
+    if (p.logical[0] != idx_now && !e->conv_loaded[p.logical[0]]) return M355_OK;
+    rows[i].resize((size_t)p.cout * p.Kpad);
+    HIP_TRY(e, hipMemcpy(rows[i].data(), p.w, rows[i].size() * sizeof(half_t), hipMemcpyDeviceToHost));
+    bias.resize(bias.size() + p.cout);
+    HIP_TRY(e, hipMemcpy(bias.data() + bias.size() - p.cout, p.bias, p.cout * sizeof(float), hipMemcpyDeviceToHost));
+    rp[i] = rows[i].data(); cout[i] = p.cout; kpad[i] = p.Kpad; cin[i] = p.cin;
+  }
+  bias.resize((bias.size() + 63) / 64 * 64, 0.f);
+  PhysConv& pl = e->phys[l.conv];
+  HIP_TRY(e, put_frags(&pl.wf_diag, planes_frag_pack_diag(rp, cout, kpad, cin, l.diag_n)));
+  if (!pl.bias_diag) HIP_TRY(e, hipMalloc((void**)&pl.bias_diag, bias.size() * sizeof(float)));
+  HIP_TRY(e, hipMemcpy(pl.bias_diag, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+  return M355_OK;
 }
 
 }  // namespace
@@ -628,6 +729,8 @@ void m355_destroy(m355_engine* e) {
     if (p.stem_w) (void)hipFree(p.stem_w);
     if (p.wf) (void)hipFree(p.wf);
     if (p.wf2) (void)hipFree(p.wf2);
+    if (p.wf_diag) (void)hipFree(p.wf_diag);
+    if (p.bias_diag) (void)hipFree(p.bias_diag);
     if (p.w2) (void)hipFree(p.w2);
     if (p.bias2) (void)hipFree(p.bias2);
   }
@@ -732,6 +835,10 @@ int m355_set_conv_weights(m355_engine* e, int idx, const float* w, const float* 
         HIP_TRY(e, put_frags(&p.wf, frag_pack(full.data(), p.Kpad, head_level_frags(e->nc), false)));
       }
     }
+    if (p.diag_lead >= 0) {
+      const int rcd = pack_head_diag(e, (size_t)p.diag_lead, idx);
+      if (rcd != M355_OK) return rcd;
+    }
     if (p.planes && ci.k == 3 && p.cin % 32 == 0 && !p.diag && p.l3 < 0) {   // K-loop fragment order of the row-slab kernels, channel blocks padded with zero rows
       bool all = true;   // (a launch shared by several logical convs -- the head's first layer -- packs once all of them are here)
       for (int li : p.logical) all = all && (li == idx || e->conv_loaded[li]);
@@ -814,6 +921,10 @@ int m355_forward(m355_engine* e, const void* d_in, int B, float* d_preds, void* 
       case OP_PHASE: {
         if (op.headtail && e->headtail_active && !b0) {   // conv + decode of this level in one launch
           rc = launch_head_tail(head_tail_args(e, op, Bq, d_preds), s);   // (eligibility was checked for all three levels at the top of this forward)
+          break;
+        }
+        if (op.diag_on) {   // this conv and its neighbours in one block-diagonal launch (planned at creation: no other form is kept)
+          rc = launch_conv3x3_blockdiag(diag_args(e, oi, Bq, b0), s);
           break;
         }
         ConvArgs a = conv_args(e, op, Bq, b0, d_preds, d_protos);

@@ -63,6 +63,9 @@ struct Op {
   int tile = -1;          // im2col tile id: the launch of R_IGEMM, the run-time fallback of R_S2C32 / R_S2C64 / R_PROTOR
   int decode = 0;         // head output conv that also decodes its rows into the prediction tensor (no OP_DECODE launch)
   int headtail = 0;       // head output conv of a level that can run as conv + decode in one launch (head_tail.hip) when the raw maps are not kept
+  int diag_n = 0;         // > 0: this 3x3 conv and the diag_n - 1 ops behind it sit side by side in one input and one output tensor (the second
+                          // stage of a head level) and may run as ONE block-diagonal row-slab launch (conv3x3_planes.hip); set by the graph builder
+  int diag_on = 0;        // ... and do: decided once at engine creation for all such groups together; the ops behind this one are fused away
   int stemfuse = -1;      // >= 0: index of the stem op this launch also computes (conv_stem_s2c32.hip); that op is then skipped
   bool fused_away = false;
   // stream lanes (plan_lanes): lane 0 is the caller's stream, lanes >= 1 are engine-owned side streams
@@ -94,6 +97,9 @@ struct PhysConv {
   half_t* wf = nullptr;
   half_t* wf2 = nullptr;
   int planes = 0;            // wf = the K-loop fragment order of the row-slab 3x3 kernels (planes_frag_pack)
+  int diag_lead = -1;        // >= 0: member of a block-diagonal 3x3 launch; the index of the op that launches it (Op::diag_on)
+  half_t* wf_diag = nullptr; // the launching op's conv only: the fragments of all members (planes_frag_pack_diag) and their biases,
+  float* bias_diag = nullptr;   // side by side, padded to a multiple of 64 channels
 };
 
 }  // namespace m355

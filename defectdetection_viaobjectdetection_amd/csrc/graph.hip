@@ -291,10 +291,14 @@ struct Builder {
     const int hcat = tensor(h.HW[l][0], h.HW[l][1], hc), ucat = tensor(h.HW[l][0], h.HW[l][1], hc + extra);
     launch(OP_CONV, phys_from(first), feat, Slice{hcat, 0, hc});
     int off = 0;
+    const size_t second = e->ops.size();
     for (const Branch* br : brs) {
       launch(OP_CONV, phys_from({br->l[l][1]}), Slice{hcat, off, br->hc}, Slice{ucat, off, br->hc});
       off += br->hc;
     }
+    // box | class | coefficient branches: a block-diagonal 224 -> 224 3x3 conv, one launch where the engine's plan takes it.  The
+    // 80 x 80 level stays on its three launches (M355_HEADDIAG_L0: measured).
+    if (brs.size() == 3 && (l > 0 || e->sw.headdiag_l0)) e->ops[second].diag_n = 3;
     return ucat;
   }
   // Back of head level l: the 1x1 output convs `outs` (64 box bins, nc classes, nm mask coefficients: different inputs, side by

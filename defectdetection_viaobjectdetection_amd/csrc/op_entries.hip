@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -232,6 +233,81 @@ int m355_bneck_pair_fwd(const void* d_x, int B, int H, int W, int C, int ldx, co
   diag.dump(se == hipSuccess && rc == 0);
   if (!ok) return set_err(M355_ERR_INVALID, "bneck_pair: shape not eligible (C in {64, 128}, slab geometry must fit LDS)");
   return launch_status(rc, se, "bneck_pair");
+}
+
+}  // extern "C"
+
+// n 3x3 convs side by side as one block-diagonal launch of the row-slab kernel (the second stage of a head level)
+namespace {
+bool diag_shapes_ok(int n, const int* cin, const int* cout) {
+  if (n < 1 || n > 4 || !cin || !cout) return false;
+  for (int i = 0; i < n; ++i)
+    if (cin[i] < 32 || cin[i] % 32 || cout[i] < 16 || cout[i] % 16 || (i + 1 < n && cout[i] % 64)) return false;
+  return true;
+}
+// fp16 rows of every conv, packed as m355_set_conv_weights packs them, and their fragment list
+std::vector<half_t> diag_pack(int n, const int* cin, const int* cout, const float* const* h_w) {
+  std::vector<std::vector<half_t>> rows(n);
+  const half_t* rp[4];
+  int kp[4];
+  for (int i = 0; i < n; ++i) {
+    kp[i] = conv_kpad(cin[i], 3);
+    rows[i].assign((size_t)cout[i] * kp[i], (half_t)0.f);
+    pack_conv_rows(h_w[i], cout[i], cin[i], 3, kp[i], 0, rows[i]);
+    rp[i] = rows[i].data();
+  }
+  return planes_frag_pack_diag(rp, cout, kp, cin, n);
+}
+}  // namespace
+
+extern "C" {
+
+long m355_planes_diag_pack(int n, const int* cin, const int* cout, const float* const* h_w, void* h_out_f16, long out_bytes) {
+  if (!diag_shapes_ok(n, cin, cout) || !h_w) return set_err(M355_ERR_INVALID, "planes_diag_pack: bad shapes");
+  long need = 0;
+  for (int i = 0; i < n; ++i) need += (long)planes_cblocks(cout[i]) * (cin[i] / 32) * 18 * 1024;
+  if (!h_out_f16) return need;
+  if (out_bytes < need) return set_err(M355_ERR_INVALID, "planes_diag_pack: output buffer too small");
+  for (int i = 0; i < n; ++i)
+    if (!h_w[i]) return set_err(M355_ERR_INVALID, "null pointer");
+  const std::vector<half_t> f = diag_pack(n, cin, cout, h_w);
+  memcpy(h_out_f16, f.data(), f.size() * sizeof(half_t));
+  return need;
+}
+
+int m355_conv3x3_blockdiag_fwd(const void* d_x, int B, int H, int W, int ldx, int n, const int* cin, const int* cout,
+                               const float* const* h_w, const float* const* h_b, void* d_y, int ldy, int walk, void* stream) {
+  if (!d_x || !d_y || !h_w || !h_b) return set_err(M355_ERR_INVALID, "null pointer");
+  if (B <= 0 || H <= 0 || W <= 0 || walk < 0 || walk > 2 || !diag_shapes_ok(n, cin, cout)) return set_err(M355_ERR_INVALID, "bad shape");
+  for (int i = 0; i < n; ++i)
+    if (!h_w[i] || !h_b[i]) return set_err(M355_ERR_INVALID, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  PlanesArgs a{};
+  a.diag_n = n; a.diag_walk = walk;
+  std::vector<float> bias;
+  for (int i = 0; i < n; ++i) {
+    a.diag_cin[i] = cin[i]; a.diag_cout[i] = cout[i];
+    a.Cin += cin[i]; a.Cout += cout[i];
+    bias.insert(bias.end(), h_b[i], h_b[i] + cout[i]);
+    a.cblocks_b += planes_cblocks(cout[i]);
+  }
+  bias.resize((bias.size() + 63) / 64 * 64, 0.f);
+  if (ldx < a.Cin || ldy < a.Cout) return set_err(M355_ERR_INVALID, "bad shape");
+  DevBuf d;
+  SlabDiag diag;
+  a.x = (const half_t*)d_x; a.x_bstride = (long)H * W * ldx; a.ldx = ldx; a.H = H; a.W = W; a.B = B; a.stride = 1; a.act = 1;
+  a.wfb = d.put(diag_pack(n, cin, cout, h_w)); a.bb = d.put(bias);
+  a.y = (half_t*)d_y; a.y_bstride = (long)H * W * ldy; a.ldy = ldy;
+  if (!a.wfb || !a.bb || !diag.alloc(d, (size_t)256 * 4 * 8 * 2)) return alloc_failed();
+  a.stamps = diag.sink.d;
+  const bool ok = conv3x3_blockdiag_ok(a);
+  char what[80];
+  snprintf(what, sizeof(what), "conv3x3_blockdiag B=%d %dx%d %d->%d", B, H, W, a.Cin, a.Cout);
+  const int rc = diag.reps(ok ? launch_conv3x3_blockdiag(a, s) : -1, s, what, [&] { return launch_conv3x3_blockdiag(a, s); });
+  const hipError_t se = hipStreamSynchronize(s);
+  diag.dump(se == hipSuccess && rc == 0);
+  if (!ok) return set_err(M355_ERR_INVALID, "conv3x3_blockdiag: shape not eligible (at most eight 64-channel tiles, row slabs must fit LDS)");
+  return launch_status(rc, se, "conv3x3_blockdiag");
 }
 
 // ---- per-op parity entries of the round-3 fused launches (each: host weights packed as m355_set_conv_weights packs them, through

@@ -36,6 +36,7 @@ const ProcSwitches& proc_switches();
 struct PlanSwitches {
   // graph builders
   bool no_c2f32, no_pair, no_protofuse, no_protofuse3, no_upfuse;
+  bool no_headdiag, headdiag_l0;   // (no_headdiag is read by the fusion pass of annotate_ops)
   int lane_plan[4];   // stream lane of Proto and of the three segment head levels
   // passes over the built graph (fuse_conv_cv1, fuse_decode, plan_lanes, plan_sub_batches, the stem fusion of annotate_ops)
   bool no_cvfuse, decfuse, no_lanes, no_subbatch;

@@ -80,6 +80,9 @@ PlanSwitches read_plan_switches() {
   v.no_protofuse = env_set("M355_NO_PROTOFUSE");
   v.no_protofuse3 = env_set("M355_NO_PROTOFUSE3");
   v.no_upfuse = env_set("M355_NO_UPFUSE");
+  // the second 3x3 stage of head levels 1 and 2 (cv2.l.1 + cv3.l.1 + cv4.l.1) as three launches instead of one block-diagonal launch
+  v.no_headdiag = env_set("M355_NO_HEADDIAG");
+  v.headdiag_l0 = env_set("M355_HEADDIAG_L0");   // experiment: also the 80 x 80 level
   // digits 0..3, Proto first; a shorter string or a bad digit keeps the rest.  Default measured best on MI355X at batch 32
   const int lanes[4] = {1, 2, 2, 0};
   const char* lp = getenv("M355_LANE_PLAN");

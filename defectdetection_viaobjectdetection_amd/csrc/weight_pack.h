@@ -34,5 +34,6 @@ FragList epilogue_frags(int cout2, int k);
 std::vector<half_t> planes_frag_pack(const half_t* rows, int Kpad, int cin, int cblocks);
 inline int planes_cblocks(int cout) { return (cout + 63) / 64 * 2; }
 std::vector<half_t> planes_frag_pack_padded(const half_t* rows, int cout, int Kpad, int cin);
+std::vector<half_t> planes_frag_pack_diag(const half_t* const* rows, const int* cout, const int* kpad, const int* cin, int n);
 
 }  // namespace m355

@@ -164,4 +164,16 @@ std::vector<half_t> planes_frag_pack_padded(const half_t* rows, int cout, int Kp
   return planes_frag_pack(padded.data(), Kpad, cin, cbl);
 }
 
+// Block-diagonal single mode of the row-slab kernel (launch_conv3x3_blockdiag): n convs side by side, conv i's rows [cout[i]][kpad[i]]
+// over its OWN cin[i] input channels.  The list is the convs' planes_frag_pack_padded lists one after the other -- [conv][channel
+// block][plane of that conv][tap][slice] -- so a conv's fragments are exactly those of its own launch.
+std::vector<half_t> planes_frag_pack_diag(const half_t* const* rows, const int* cout, const int* kpad, const int* cin, int n) {
+  std::vector<half_t> out;
+  for (int i = 0; i < n; ++i) {
+    const std::vector<half_t> f = planes_frag_pack_padded(rows[i], cout[i], kpad[i], cin[i]);
+    out.insert(out.end(), f.begin(), f.end());
+  }
+  return out;
+}
+
 }  // namespace m355

@@ -149,6 +149,8 @@ int m355_postprocess_ex(m355_engine* e, const float* d_preds, const void* d_prot
  * described here.  Switches that change which kernels m355_forward launches (results stay within the parity tolerances; every
  * pair is A/B-tested in tests/test_c2f_fused_gpu.py / test_engine_gpu.py):
  *   M355_NO_PAIR        Bottleneck pairs as two launches instead of one bneck_pair launch (conv3x3_planes.hip)
+ *   M355_NO_HEADDIAG    cv2.l.1 / cv3.l.1 / cv4.l.1 of the 40 x 40 and 20 x 20 head levels as three launches instead of one block-diagonal
+ *                       row-slab launch (M355_HEADDIAG_L0=1: experiment, also the 80 x 80 level)
  *   M355_PAIR64=1       also use the pair launch for 64-channel bottlenecks (measured no gain: off)
  *   M355_NO_PLANES      the 20 x 20 level on conv3x3_slab instead of the row-slab kernel
  *   M355_NO_C2F32       model.2 as three launches instead of c2f_c32
@@ -195,6 +197,20 @@ int m355_c2f_c32_fwd(const void* d_x_f16_nhwc, int B, int H, int W, const float*
  * (M355_ERR_INVALID).  [sync] */
 int m355_bneck_pair_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int C, int ldx, const float* h_wa, const float* h_ba,
                         const float* h_wb, const float* h_bb, int shortcut, void* d_y_f16_nhwc, int ldy, void* stream);
+/* n <= 4 3x3 Conv+BN+SiLU layers (BN folded) that sit side by side in one tensor -- conv i reads the next cin[i] channels of d_x and
+ * writes the next cout[i] channels of d_y: a block-diagonal convolution, upstream's cv2.l.1 / cv3.l.1 / cv4.l.1 of a Segment head
+ * level -- in ONE launch of the row-slab kernel (csrc/conv3x3_planes.hip, block-diagonal single mode): every 64-channel tile runs
+ * its K loop over the input planes of its own conv only, in the order of that conv's own launch.  d_x fp16 NHWC (B,H,W,ldx), d_y fp16
+ * NHWC (B,H,W,ldy); cin[i] % 32 == 0, cout[i] % 16 == 0, every cout but the last a multiple of 64, at most eight 64-channel tiles;
+ * h_w[i] fp32 (cout[i],cin[i],3,3) and h_b[i] fp32 (cout[i]): HOST pointers, packed + uploaded here.  walk: 0 = the launcher chooses how
+ * a block walks the tiles (as inside m355_forward), 1 = single 64-channel tiles, 2 = every tile of a row slab (tests).  [sync]
+ * m355_planes_diag_pack is its weight packing alone, on the host (no device needed): the fp16 MFMA fragments [conv][32-channel block,
+ * padded to a multiple of two][input plane of that conv][tap][K slice], 1 KiB each -- element (lane, j) of a fragment = row
+ * 32 cb + 16 ((lane >> 2) & 1) + 4 ((lane & 31) >> 3) + (lane & 3), K = tap * cin + 32 p + 16 s + 8 (lane >> 5) + j.  Returns the byte
+ * size of the list (h_out_f16 = NULL: the size only), or an error code < 0. */
+int m355_conv3x3_blockdiag_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int ldx, int n, const int* cin, const int* cout,
+                               const float* const* h_w, const float* const* h_b, void* d_y_f16_nhwc, int ldy, int walk, void* stream);
+long m355_planes_diag_pack(int n, const int* cin, const int* cout, const float* const* h_w, void* h_out_f16, long out_bytes);
 /* Per-op parity entries of the fused launches (round 3 kernels; host weights fp32 with BN folded, packed + uploaded here exactly as
  * m355_set_conv_weights packs them; a shape the kernel does not take is refused with M355_ERR_INVALID).  [sync]
  *   m355_s2c64_cv1_fwd       csrc/conv3x3_s2c64.hip: Conv3x3/s2 (64 -> 128) + SiLU -> fp16 -> Conv1x1 (128 -> 128) + SiLU; upstream

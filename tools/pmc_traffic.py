@@ -31,6 +31,8 @@ def label(name):
     mw = re.search(r"conv1x1_wreg_kernel<(\d+), (\d+)", name)      # <K, CB, PB, SPLIT> since round 4 (<K, CB> before)
     if mw:
         return f"conv1x1_wreg<K{mw.group(1)},{int(mw.group(2)) * 32}ch>"
+    if "PCfg<2, 0, 4, false, 1, 4, false>, false, true>" in name or "PCfgILi2ELi0ELi4ELb0ELi1ELi4ELb0EEELb0ELb1E" in name:
+        return "conv3x3_planes<64ch,rows,diag>"      # the block-diagonal single mode (planes_kernel<S64, RES = false, DIAG = true>)
     for k, v in LABELS.items():
         if k in name:
             return v
