@@ -11,10 +11,11 @@ The input rotates over 8 distinct device-resident batches (315 MB > the 256 MiB 
 images from HBM.  `value` is PIPELINED THROUGHPUT: two batches are in flight on two engine instances and the
 post-processing of a batch overlaps later forwards, so `ms_per_step` is the step period, not a latency.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured live with HIP events recorded
-on the launch stream inside the timed region), at N=1 `cpu_baseline` (the CPU oracle, kind "port",
-timed on this node's host cores on a bounded sample of the same workload, batch 32) and `train_step`: the training
-path's step on a synthetic device-resident batch after the inference measurement -- N=1: YOLOv8s-seg, batch 64 @640
+Prints ONE JSON line (rank 0).  A plain run does what the headline figure needs and nothing else: set up, warm up, time
+the steps, write the outputs if `--dump-outputs` is given, print the line.  `--full` adds, all after the clock has been
+read: `roofline`, `kernels` and `c2f3x3` (event-sampled steps: the dominant kernel against its roof), at N=1
+`cpu_baseline` (the CPU oracle, kind "port", timed on this node's host cores on a bounded sample of the same workload,
+batch 32) and `train_step`: the training path's step on a synthetic device-resident batch -- N=1: YOLOv8s-seg, batch 64 @640
 (BASELINE config 3) with the forward / loss / backward / optimizer split; N>1: YOLOv8m-seg data parallel, 64 images per
 GPU (config 4), with the gradient all-reduce time alone, the part of it not hidden under backward and the overlap fraction.
 
@@ -41,11 +42,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--scale", default="s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the train_step measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the event-sampled steps "
+                         "(roofline, kernels, c2f3x3), the CPU baseline (one GPU) and the training step; --no-profile, "
+                         "--no-cpu-baseline and --no-train take single parts out of it again")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline measurement")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the train_step measurement")
     ap.add_argument("--input-batches", type=int, default=8,
                     help="distinct device-resident input batches the steps rotate over (8 x 39 MB > the 256 MiB Infinity Cache)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-op HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-op HIP events")
     ap.add_argument("--no-overlap", action="store_true",
                     help="run post-processing on the forward stream instead of overlapping it with the next batch")
     ap.add_argument("--engines", type=int, default=2,
@@ -58,7 +63,7 @@ def main():
                     help="one engine, one stream lane inside it (M355_NO_LANES), whole-batch launches (M355_NO_SUBBATCH): every kernel runs alone, so rocprofv3's "
                          "per-kernel averages and the live event samples describe the same launches")
     ap.add_argument("--profile-steps", type=int, default=4,
-                    help="event-sampled steps (forward alone, a HIP event pair per launch) run AFTER the timed region; at least 2")
+                    help="with --full: event-sampled steps (forward alone, a HIP event pair per launch) run AFTER the timed region; at least 2")
     ap.add_argument("--profile-every", type=int, default=100, help="(ignored since round 4: no step of the timed region is event-sampled)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
@@ -175,7 +180,7 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     if profile:
         for e_ in engs:
             e_.collect_op_times()  # drain + reset
@@ -221,7 +226,7 @@ def main():
         "metric": "images/sec @640x640 b32 YOLOv8s-seg" if args.scale == "s" else f"images/sec @640x640 YOLOv8{args.scale}-seg",
         "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "fp16", "data": "synthetic",
+        "vs_baseline": None, "dtype": "fp16", "data": "synthetic", "full": args.full,
         "config": {"workload": f"YOLOv8{args.scale}-seg inference (forward + NMS + masks), {B} synthetic 640x640 "
                                f"B-scans per GPU per step, nc=1, seeded synthetic weights; pipelined throughput, "
                                f"{n_eng} batch(es) in flight (ms_per_step is the step period, not a latency); inputs rotate "
@@ -298,9 +303,9 @@ def main():
                                  "ms_per_step": round(cf["ms"] / max(sampled, 1), 4), "launches_per_step": cf["launches"] // max(sampled, 1),
                                  "layers": cf["layers"] // max(sampled, 1), "gflop_per_image": round(cf["flops"] / max(sampled, 1) / B / 1e9, 3),
                                  "target_frac": 0.70}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.scale, sd)
-    if not args.no_train:
+    if args.full and not args.no_train:
         for e_ in engs:
             e_.close()
         del preds, protos, dets, masks, imgs_all

@@ -194,16 +194,17 @@ def test_resume_and_early_stopping(tmp_path):
 
 
 def test_bench_starts_its_own_launcher_for_two_ranks():
-    """`python bench.py --gpus 2 ...` exactly as a driver would type it, with no launcher environment: bench.py starts
-    torch.distributed.run as a child (before any GPU call), two ranks share this box's one GPU over gloo, rank 0 prints
-    ONE JSON line carrying the inference value and the data-parallel training step with its exchange figures."""
+    """`python bench.py --full --gpus 2 ...` typed at a shell, with no launcher environment: bench.py starts
+    torch.distributed.run as a child (before any GPU call), two ranks share the one GPU over gloo, rank 0 prints
+    ONE JSON line carrying the inference value and, because of `--full`, the data-parallel training step with its
+    exchange figures."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(M355_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
