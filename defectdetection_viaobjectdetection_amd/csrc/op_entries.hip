@@ -161,6 +161,7 @@ int conv_op_common(const void* d_x, int B, int H, int W, int cin, const float* h
                                                                        : launch_conv_igemm(a, force_tile, s));
   const hipError_t se = hipStreamSynchronize(s);
   diag.dump(se == hipSuccess);
+  if (rc == -1) return set_err(M355_ERR_INVALID, "conv launch failed: -1");   // the launcher refused the shape, as finish_entry reports it
   return launch_status(rc, se, "conv");
 }
 

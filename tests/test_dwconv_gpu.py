@@ -41,6 +41,11 @@ CASES = [  # C, H, W, ldx, xoff, ldy, yoff, act, B
     (128, 80, 80, 384, 256, 256, 128, 1, 1),
     (256, 20, 20, 256, 0, 256, 0, 1, 2),
     (256, 12, 20, 512, 256, 264, 8, 0, 2),
+    # narrow and tiny maps (net shapes 64 x 64, 64 x 640, 32 x 32, 640 x 32): every pixel on a border, one row, one column, one pixel
+    (64, 2, 2, 64, 0, 64, 0, 1, 2),
+    (128, 2, 20, 384, 256, 256, 128, 0, 2),
+    (256, 1, 1, 256, 0, 256, 0, 1, 3),
+    (80, 20, 1, 80, 0, 80, 0, 1, 2),
 ]
 
 

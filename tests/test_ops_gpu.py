@@ -183,7 +183,8 @@ def test_convt2x2(shape, cuda_device):
     assert rel_l2(y, y_ref) <= 1e-3
 
 
-@pytest.mark.parametrize("hw", [(64, 96), (40, 100), (66, 80)])   # W*3 a multiple of 16 (row-staged kernel) or not (gather kernel)
+@pytest.mark.parametrize("hw", [(64, 96), (40, 100), (66, 80),   # W*3 a multiple of 16 (row-staged kernel) or not (gather kernel)
+                                (32, 32), (32, 640)])             # the smallest net shape and the thinnest one
 @pytest.mark.parametrize("cout", [16, 32, 48])
 def test_stem(cout, hw, cuda_device):
     capi = _lib()
@@ -204,27 +205,29 @@ def test_stem(cout, hw, cuda_device):
 
 def test_sppf_pool_bit_exact(cuda_device):
     capi = _lib()
-    B, H, W, Cc = 3, 20, 20, 256
-    x = torch.randn(B, Cc, H, W, generator=torch.Generator().manual_seed(1)).half()
-    p1 = F.max_pool2d(x.float(), 5, 1, 2)
-    p2 = F.max_pool2d(p1, 5, 1, 2)
-    p3 = F.max_pool2d(p2, 5, 1, 2)
-    ref = torch.cat((p1, p2, p3), 1)
-    dx = nhwc16(x.float(), cuda_device)
-    dy = torch.empty((B, H, W, 3 * Cc), dtype=torch.float16, device=cuda_device)
-    capi.check(capi.lib.m355_sppf_pool(_p(dx), B, H, W, Cc, _p(dy), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    y = dy.float().cpu().permute(0, 3, 1, 2)
-    assert torch.equal(y, ref)
+    for H, W in ((20, 20), (1, 20), (20, 1), (1, 1)):      # the 5x5 window wider than the map in one or both directions
+        B, Cc = 3, 256
+        x = torch.randn(B, Cc, H, W, generator=torch.Generator().manual_seed(1)).half()
+        p1 = F.max_pool2d(x.float(), 5, 1, 2)
+        p2 = F.max_pool2d(p1, 5, 1, 2)
+        p3 = F.max_pool2d(p2, 5, 1, 2)
+        ref = torch.cat((p1, p2, p3), 1)
+        dx = nhwc16(x.float(), cuda_device)
+        dy = torch.empty((B, H, W, 3 * Cc), dtype=torch.float16, device=cuda_device)
+        capi.check(capi.lib.m355_sppf_pool(_p(dx), B, H, W, Cc, _p(dy), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        y = dy.float().cpu().permute(0, 3, 1, 2)
+        assert torch.equal(y, ref), (H, W)
 
 
 def test_upsample_bit_exact(cuda_device):
     capi = _lib()
-    B, H, W, Cc = 2, 20, 12, 64
-    x = torch.randn(B, Cc, H, W, generator=torch.Generator().manual_seed(2)).half()
-    ref = F.interpolate(x.float(), scale_factor=2, mode="nearest")
-    dx = nhwc16(x.float(), cuda_device)
-    dy = torch.empty((B, 2 * H, 2 * W, Cc), dtype=torch.float16, device=cuda_device)
-    capi.check(capi.lib.m355_upsample2x(_p(dx), B, H, W, Cc, _p(dy), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    assert torch.equal(dy.float().cpu().permute(0, 3, 1, 2), ref)
+    for H, W in ((20, 12), (1, 20), (20, 1), (1, 1)):
+        B, Cc = 2, 64
+        x = torch.randn(B, Cc, H, W, generator=torch.Generator().manual_seed(2)).half()
+        ref = F.interpolate(x.float(), scale_factor=2, mode="nearest")
+        dx = nhwc16(x.float(), cuda_device)
+        dy = torch.empty((B, 2 * H, 2 * W, Cc), dtype=torch.float16, device=cuda_device)
+        capi.check(capi.lib.m355_upsample2x(_p(dx), B, H, W, Cc, _p(dy), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        assert torch.equal(dy.float().cpu().permute(0, 3, 1, 2), ref), (H, W)

@@ -76,7 +76,8 @@ def _weights(rng, C):
 
 
 @pytest.mark.parametrize("heads", [2, 4])
-@pytest.mark.parametrize("H,W", [(8, 12), (10, 10), (20, 20), (32, 32)])
+@pytest.mark.parametrize("H,W", [(8, 12), (10, 10), (20, 20), (32, 32),
+                                 (2, 2), (2, 20), (1, 7), (20, 2)])     # 4 and 40 positions: what the graph reaches at 64 x 64 and 64 x 640
 def test_psa_attn_random(heads, H, W, cuda_device):
     rng = np.random.default_rng(heads * 100 + H * W)
     B, N, C = 2, H * W, heads * 64

@@ -21,7 +21,8 @@ def rel_l2(a, b):
 
 
 @pytest.mark.parametrize("c0", [16, 32, 48])
-@pytest.mark.parametrize("shape,batch", [((640, 640), 1), ((320, 320), 4), ((256, 384), 3), ((640, 640), 2)])
+@pytest.mark.parametrize("shape,batch", [((640, 640), 1), ((320, 320), 4), ((256, 384), 3), ((640, 640), 2),
+                                         ((64, 64), 3), ((64, 640), 2), ((640, 64), 2)])     # the smallest and the thinnest net shapes
 def test_stem6_matches_conv2d(c0, shape, batch, cuda_device):
     from defectdetection_viaobjectdetection_amd import _capi
     g = torch.Generator().manual_seed(c0 * 7 + batch)

@@ -71,6 +71,10 @@ def test_v9c_forward_and_postprocess_parity(nc, shape, batch, cuda_device):
     eng.close()
 
 
+def test_v9c_narrow_net_shape(cuda_device):
+    test_v9c_forward_and_postprocess_parity(1, (64, 96), 8, cuda_device)      # maps of 8 x 12, 4 x 6 and 2 x 3
+
+
 def test_reference_predict_call_with_a_v9c_model(tmp_path, cuda_device):
     """yolo8_seg_predict.py:5-9 with the architecture its checkpoint path names: YOLO(path) -> predict(png, save=True) -> print."""
     from ultralytics import YOLO

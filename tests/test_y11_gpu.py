@@ -78,6 +78,11 @@ def test_y11_forward_and_nms_parity(scale, nc, shape, batch, cuda_device):
     assert q(dsc, .99) <= 2e-3
 
 
+@pytest.mark.parametrize("shape,batch", [((64, 64), 12), ((64, 640), 2)])   # attention over 4 and 40 positions, depthwise convs on 2 x 2 and 2 x 20 maps
+def test_y11_narrow_net_shapes(shape, batch, cuda_device):
+    test_y11_forward_and_nms_parity("11s", 1, shape, batch, cuda_device)
+
+
 @pytest.mark.parametrize("scale", ["11n", "11s"])
 def test_y11_batch_invariance(scale, cuda_device):
     """An image's predictions are bit-identical alone and at position 2 of a batch of 4."""
