@@ -186,6 +186,8 @@ SIGNATURES = {
                                          C.c_int32, _P, _P]),
     "m355_box_loss_launch": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "m355_dfl_decode_launch": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "m355_cls_bce_workspace_floats": (C.c_size_t, []),
+    "m355_cls_bce_launch": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "m355_proto_masks": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "m355_postprocess_ex": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "m355_nms_ex": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P, _P]),

@@ -329,25 +329,31 @@ class Augmenter:
         self._copied.record()
         return out
 
-    def batch(self, indices: Sequence[int], mosaic_on: bool = True) -> Dict:
-        """Like SegDataset.batch, with `img` already on the device."""
+    def batch(self, indices: Sequence[int], mosaic_on: bool = True, with_masks: bool = True) -> Dict:
+        """Like SegDataset.batch (``with_masks`` included), with `img` already on the device."""
         H, W = self.ds.imgsz
         plans = self.plan(indices, mosaic_on)
         imgs = self.render(plans)
         bidx, cls, boxes = [], [], []
-        masks = np.zeros((len(plans), H // 4, W // 4), np.uint8)
-        if any(len(p["inst"]) > 255 for p in plans):                 # (a mosaic of four crowded images)
+        masks = np.zeros((len(plans), H // 4, W // 4) if with_masks else (0,), np.uint8)
+        if with_masks and any(len(p["inst"]) > 255 for p in plans):  # (a mosaic of four crowded images)
             masks = masks.astype(np.int32)
         for b, p in enumerate(plans):
             polys = [q for _, q in p["inst"]]
             if not polys:
                 continue
-            masks[b], order = overlap_mask(polys, (H, W))
+            if with_masks:
+                masks[b], order = overlap_mask(polys, (H, W))
+            else:
+                order = range(len(polys))
             for j in order:
                 q = polys[j]
                 x1, y1, x2, y2 = q[:, 0].min(), q[:, 1].min(), q[:, 0].max(), q[:, 1].max()
                 bidx.append(b)
                 cls.append(p["inst"][j][0])
                 boxes.append([(x1 + x2) / 2 / W, (y1 + y2) / 2 / H, (x2 - x1) / W, (y2 - y1) / H])
-        return {"img": imgs, "batch_idx": np.asarray(bidx, np.float32), "cls": np.asarray(cls, np.float32),
-                "bboxes": np.asarray(boxes, np.float32).reshape(-1, 4), "masks": masks, "plans": plans}
+        out = {"img": imgs, "batch_idx": np.asarray(bidx, np.float32), "cls": np.asarray(cls, np.float32),
+               "bboxes": np.asarray(boxes, np.float32).reshape(-1, 4), "plans": plans}
+        if with_masks:
+            out["masks"] = masks
+        return out

@@ -318,6 +318,10 @@ int launch_box_loss(const float* logits, const float* anchors, const float* targ
                     float* dfl_term, float* d_box, float* d_dfl, hipStream_t s);
 int launch_dfl_decode(const float* raw, long rows, int A, int rw, int nc, const float* anchors, const float* strides, float* boxes,
                       float* scores, hipStream_t s);
+// class term of the detection loss + its gradient in one pass (loss_kernels.hip); out: cls_bce_workspace_floats() floats
+int launch_cls_bce(const float* raw, int rw, const float* targets, long rows, int nc, const float* scale, float* d_raw, float* out,
+                   hipStream_t s);
+size_t cls_bce_workspace_floats();
 int launch_tal_assign(const float* scores, const float* boxes, const float* anchors_px, const int* gt_cls, const float* gt_boxes,
                       const unsigned char* gt_valid, int B, int A, int G, int nc, void* ws, float* t_boxes, float* t_scores,
                       unsigned char* fg, long* gt_idx, hipStream_t s);

@@ -570,7 +570,7 @@ void annotate_ops(m355_engine* e) {
       }
       case OP_DECODE:
         snprintf(op.kernel, sizeof(op.kernel), "head_decode");
-        snprintf(op.layer, sizeof(op.layer), e->nm > 0 ? "model.22.decode" : (e->desc.scale >> 8) == '1' ? "model.23.decode" : "model.24.decode");
+        snprintf(op.layer, sizeof(op.layer), e->nm > 0 || (e->desc.scale >> 8) == '8' ? "model.22.decode" : (e->desc.scale >> 8) == '1' ? "model.23.decode" : "model.24.decode");
         op.bytes = (double)e->A * ((64 + e->nc + e->nm) + (4 + e->nc + e->nm)) * 4;
         break;
     }
@@ -679,9 +679,10 @@ int m355_create(const m355_model_desc* desc, m355_engine** out) {
   {   // the family / scale code is checked before the device is: a bad descriptor is M355_ERR_INVALID on any machine
     const int fam = desc->scale >> 8, sc = desc->scale & 0xff;
     const bool ok = fam == 0 ? (sc == 'n' || sc == 's' || sc == 'm' || sc == 'l' || sc == 'x' || sc == 'c')
-                             : (fam == '5' || fam == '1') && (sc == 'n' || sc == 's' || sc == 'm');
+                   : fam == '8' ? (sc == 'n' || sc == 's' || sc == 'm' || sc == 'l' || sc == 'x')
+                                : (fam == '5' || fam == '1') && (sc == 'n' || sc == 's' || sc == 'm');
     if (!ok) {
-      g_err = "m355_model_desc.scale: unknown family or scale (0 | n,s,m,l,x,c; ('5' << 8) | n,s,m; ('1' << 8) | n,s,m)";
+      g_err = "m355_model_desc.scale: unknown family or scale (0 | n,s,m,l,x,c; ('5' << 8) | n,s,m; ('1' << 8) | n,s,m; ('8' << 8) | n,s,m,l,x)";
       return M355_ERR_INVALID;
     }
   }

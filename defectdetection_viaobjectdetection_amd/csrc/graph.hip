@@ -1,4 +1,4 @@
-// libmi355yolo.so graph construction: the four model families (YOLOv8-seg, YOLOv9c-seg, YOLOv5u, YOLO11) written as tensors,
+// libmi355yolo.so graph construction: the model families (YOLOv8-seg, YOLOv8 detect, YOLOv9c-seg, YOLOv5u, YOLO11) written as tensors,
 // logical convs, physical convs and ops of an m355_engine (engine_types.h).  Host C++ only: no kernel and no HIP runtime call;
 // engine.hip fuses, plans, allocates and runs what build_graph leaves.
 //
@@ -39,6 +39,9 @@ const Scale kScales[] = {
     {('5' << 8) | 'n', 0.33, 0.25, 1024, false}, {('5' << 8) | 's', 0.33, 0.50, 1024, false},
     {('5' << 8) | 'm', 0.67, 0.75, 1024, false}, {('1' << 8) | 'n', 0.50, 0.25, 1024, false},
     {('1' << 8) | 's', 0.50, 0.50, 1024, false}, {('1' << 8) | 'm', 0.50, 1.00, 512, true},
+    {('8' << 8) | 'n', 0.33, 0.25, 1024, false}, {('8' << 8) | 's', 0.33, 0.50, 1024, false},
+    {('8' << 8) | 'm', 0.67, 0.75, 768, false},  {('8' << 8) | 'l', 1.00, 1.00, 512, false},
+    {('8' << 8) | 'x', 1.00, 1.25, 512, false},
 };
 
 // What a family asks of the descriptor: its smallest image side and the texts of its two rejections, and its mask width
@@ -52,6 +55,7 @@ const Family kV8{32, 32, kBadScaleSeg, "in_h/in_w must be positive multiples of 
 const Family kV9c{64, 32, kBadScaleSeg, kBadSize64};
 const Family kV5u{64, 0, "YOLOv5u scale must be n, s or m (l and x are not built)", kBadSize64};
 const Family kY11{64, 0, "YOLO11 scale must be n, s or m (l and x are not built)", kBadSize64};
+const Family kV8Det{32, 0, "YOLOv8 detect scale must be one of n,s,m,l,x", "in_h/in_w must be positive multiples of 32"};
 
 // One branch of a head over the three levels: {pre}.{l}.0 (3x3, fch[l] -> hc), .1 (3x3, hc -> hc), .2 (1x1 with bias, hc -> cout)
 struct Branch {
@@ -464,7 +468,7 @@ int build_graph_v9c(m355_engine* e) {
   return build_segment_head(e, b, feats, fch, 256);
 }
 
-// model.24 = Detect(nc) of YOLOv5u (box-only, nm = 0): per level the two first 3x3 convs (cv2.l.0, cv3.l.0) share their input
+// model.24 = Detect(nc) of YOLOv5u, model.22 = Detect(nc) of YOLOv8 (box-only, nm = 0): per level the two first 3x3 convs (cv2.l.0, cv3.l.0) share their input
 // and run as one launch, the two second convs write side by side, and the two 1x1 output convs run as one block-diagonal launch
 // writing whole raw rows of 64 + nc.  The decode launch turns them into prediction rows of 4 + nc.
 int build_detect_head(m355_engine* e, Builder& b, const int feats[3], const int fch[3], const std::string& pre) {
@@ -690,11 +694,12 @@ int build_graph_y11(m355_engine* e) {
   return build_detect_head_y11(e, b, feats, fch, "model.23");
 }
 
-// yolov8{n,s,m,l,x}-seg.  (The tensors are made one by one between the convs here, in groups in the other three graphs: tensor
-// ids follow that order.)
-int build_graph_v8(m355_engine* e) {
+// yolov8{n,s,m,l,x}-seg, and with `detect` YOLOv8 detect (upstream yolov8.yaml: the same backbone and neck, layer for layer, under
+// the box-only Detect head at model.22).  (The tensors are made one by one between the convs here, in groups in the other three
+// graphs: tensor ids follow that order.)
+int build_graph_v8(m355_engine* e, bool detect) {
   Builder b{e};
-  if (int rc = b.begin(kV8)) return rc;
+  if (int rc = b.begin(detect ? kV8Det : kV8)) return rc;
   const int c64 = b.c64, c128 = b.c128, c256 = b.c256, c512 = b.c512, c1024 = b.c1024;
   const int H2 = b.H2, W2 = b.W2, H3 = b.H3, W3 = b.W3, H4 = b.H4, W4 = b.W4, H5 = b.H5, W5 = b.W5;
   if (c64 != 16 && c64 != 32 && c64 != 48 && c64 != 64 && c64 != 80)
@@ -736,9 +741,10 @@ int build_graph_v8(m355_engine* e) {
   const int t21 = b.tensor(H5, W5, c1024);
   b.c2f("model.21", Slice{cat20, 0, c512 + c1024}, Slice{t21, 0, c1024}, b.rep(3), false);
 
-  // 22: Segment head
+  // 22: Segment head, or the Detect head
   const int feats[3] = {t15, t18, t21};
   const int fch[3] = {c256, c512, c1024};
+  if (detect) return build_detect_head(e, b, feats, fch, "model.22");
   return build_segment_head(e, b, feats, fch, b.ch(256));
 }
 
@@ -748,8 +754,9 @@ int build_graph(m355_engine* e) {
   const int family = e->desc.scale >> 8;
   if (family == '5') return build_graph_v5u(e);
   if (family == '1') return build_graph_y11(e);
+  if (family == '8') return build_graph_v8(e, true);
   if (family != 0) return e->fail(M355_ERR_INVALID, "unknown model family in the high byte of m355_model_desc.scale");
-  return e->desc.scale == 'c' ? build_graph_v9c(e) : build_graph_v8(e);
+  return e->desc.scale == 'c' ? build_graph_v9c(e) : build_graph_v8(e, false);
 }
 
 }  // namespace m355

@@ -559,6 +559,126 @@ int launch_mask_loss(const float* coef, const void* protos, int protos_f16, cons
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Class term of the detection loss, value and gradient in one pass (upstream: BCEWithLogitsLoss(reduction="none")(scores, targets)
+// .sum() of v8DetectionLoss and its autograd).  As torch ops over the (B, A, nc) class block this was a strided copy of the logits,
+// the loss, its sum, and in the backward pass the gradient, its scaling and the scatter back into the raw rows: the 43 M elements
+// of batch 64 at 640 x 640 with 80 classes moved seven times.  Here every element is read once (logit in place in its raw row at
+// column 64, target from the dense map) and its gradient (sigmoid(x) - t) * s written once into the same column of d_raw; s is a
+// device scalar, so the target sum that normalises the loss never visits the host.
+//   * cls_bce_kernel: four consecutive elements of the flat (rows x nc) index space per thread and trip.  The targets are dense: one
+//     16-byte load.  The raw rows are rw = 64 + nc floats apart, so a group of four is 16-byte aligned inside its row only when rw
+//     and nc are multiples of 4 (nc = 80: rw = 144) -- VEC; otherwise the four logits and gradients go one by one, stepping to the
+//     next row where the group crosses a row end (nc = 1: every element).  One exp per element serves the loss and the sigmoid.
+//     Per-thread sums in index order, wave shuffle, the four wave sums in wave order, one partial per block in out[8 + b];
+//   * cls_bce_final_kernel (one block) adds the partials in block order into out[0].
+// The grid is a function of rows * nc alone and nothing is added atomically: bitwise reproducible.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int BCE_BLOCKS = 2048, BCE_WS = 8 + BCE_BLOCKS;
+
+// loss max(x, 0) - x t + log1p(exp(-|x|)) and gradient factor sigmoid(x) - t of one element from one exp
+__device__ __forceinline__ float cls_bce_elem(float x, float t, float& g) {
+  const float e = expf(-fabsf(x));
+  const float r = 1.0f / (1.0f + e);
+  g = (x >= 0.f ? r : e * r) - t;
+  return fmaxf(x, 0.f) - x * t + log1pf(e);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void cls_bce_kernel(const float* raw, int rw, const float* tgt, long n, int nc, const float* scale,
+                                                      float* d_raw, float* out) {
+  __shared__ float wsum[4];
+  const float s = *scale;
+  const bool small = n <= 0x7fffffffL;                     // 32-bit row / column split (a 64-bit division is ~4x the instructions)
+  const long groups = (n + 3) >> 2;
+  float acc = 0.f;
+  for (long gi = (long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long)gridDim.x * 256) {
+    const long i = gi * 4;
+    long r;
+    int c;
+    if (small) {
+      const unsigned q = (unsigned)i / (unsigned)nc;
+      r = q;
+      c = (int)((unsigned)i - q * (unsigned)nc);
+    } else {
+      r = i / nc;
+      c = (int)(i - r * nc);
+    }
+    if (VEC) {                                              // n, nc, rw multiples of 4: the group lies inside row r, 16-byte aligned
+      const long off = r * rw + 64 + c;
+      const float4v tv = *(const float4v*)(tgt + i);
+      const float4v xv = *(const float4v*)(raw + off);
+      float4v gv;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float g;
+        acc += cls_bce_elem(xv[j], tv[j], g);
+        gv[j] = g * s;
+      }
+      *(float4v*)(d_raw + off) = gv;
+    } else {
+      const int m = n - i < 4 ? (int)(n - i) : 4;
+      float t[4] = {0.f, 0.f, 0.f, 0.f};
+      if (m == 4) {
+        const float4v tv = *(const float4v*)(tgt + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = tv[j];
+      } else {
+        for (int j = 0; j < m; ++j) t[j] = tgt[i + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < m) {
+          const long off = r * rw + 64 + c;
+          float g;
+          acc += cls_bce_elem(raw[off], t[j], g);
+          d_raw[off] = g * s;
+          if (++c == nc) { c = 0; ++r; }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) out[8 + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+__global__ __launch_bounds__(256) void cls_bce_final_kernel(float* out, int nblocks) {
+  __shared__ float ts[256];
+  constexpr int PER = BCE_BLOCKS / 256;
+  float a = 0.f;
+  for (int b = threadIdx.x * PER; b < threadIdx.x * PER + PER && b < nblocks; ++b) a += out[8 + b];   // consecutive blocks, in order
+  ts[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < 256; ++i) t += ts[i];                                                        // thread partials in thread order
+    out[0] = t;
+  }
+}
+}  // namespace
+
+size_t cls_bce_workspace_floats() { return BCE_WS; }
+
+int launch_cls_bce(const float* raw, int rw, const float* targets, long rows, int nc, const float* scale, float* d_raw, float* out,
+                   hipStream_t s) {
+  if (!raw || !targets || !scale || !d_raw || !out || rows < 1 || nc < 1 || rw < 4 * REGM + nc || rows > (1L << 40)) return -1;
+  if (((size_t)targets & 15) || ((size_t)raw & 3) || ((size_t)d_raw & 3)) return -1;   // (the 16-byte target loads)
+  const long n = rows * nc, groups = (n + 3) >> 2;
+  long blocks = (groups + 255) / 256;
+  if (blocks > BCE_BLOCKS) blocks = BCE_BLOCKS;
+  const bool vec = rw % 4 == 0 && nc % 4 == 0 && !((size_t)raw & 15) && !((size_t)d_raw & 15);
+  if (vec)
+    hipLaunchKernelGGL(cls_bce_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, raw, rw, targets, n, nc, scale, d_raw, out);
+  else
+    hipLaunchKernelGGL(cls_bce_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, raw, rw, targets, n, nc, scale, d_raw, out);
+  hipLaunchKernelGGL(cls_bce_final_kernel, dim3(1), dim3(256), 0, s, out, (int)blocks);
+  return (int)hipGetLastError();
+}
+
 // Task-aligned assignment on the device.  scores (B,A,nc), boxes (B,A,4) xyxy px, anchors_px (A,2), gt_cls (B,G) int32, gt_boxes
 // (B,G,4), gt_valid (B,G) bytes; ws: (B * G * 10) ints + 2 x (B * G * 10) floats; the four outputs must be zero on entry.
 int launch_tal_assign(const float* scores, const float* boxes, const float* anchors_px, const int* gt_cls, const float* gt_boxes,

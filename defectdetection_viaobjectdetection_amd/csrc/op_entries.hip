@@ -950,6 +950,14 @@ int m355_dfl_decode_launch(const float* raw, int64_t rows, int32_t A, int32_t rw
   return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, "dfl-decode launch failed: " + std::to_string(rc));
 }
 
+size_t m355_cls_bce_workspace_floats(void) { return cls_bce_workspace_floats(); }
+
+int m355_cls_bce_launch(const float* raw, int32_t rw, const float* targets, int64_t rows, int32_t nc, const float* scale, float* d_raw,
+                        float* out, void* stream) {
+  const int rc = launch_cls_bce(raw, rw, targets, rows, nc, scale, d_raw, out, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, "class-BCE launch failed: " + std::to_string(rc));
+}
+
 int m355_tal_assign_launch(const float* scores, const float* boxes, const float* anchors_px, const int32_t* gt_cls, const float* gt_boxes,
                            const uint8_t* gt_valid, int32_t B, int32_t A, int32_t G, int32_t nc, void* ws, float* t_boxes, float* t_scores,
                            uint8_t* fg, int64_t* gt_idx, void* stream) {

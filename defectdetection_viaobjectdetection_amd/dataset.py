@@ -139,14 +139,15 @@ class SegDataset:
     def __len__(self) -> int:
         return len(self.files)
 
-    def batch(self, indices: Sequence[int], flip: Optional[Sequence[bool]] = None) -> Dict[str, np.ndarray]:
+    def batch(self, indices: Sequence[int], flip: Optional[Sequence[bool]] = None, with_masks: bool = True) -> Dict[str, np.ndarray]:
         """Collate: img (B,H,W,3) uint8 RGB; batch_idx (N,), cls (N,), bboxes (N,4) xywh normalised to the network
-        input (box = polygon bounds), masks (B,H/4,W/4) overlap-encoded, instances of an image sorted like the map."""
+        input (box = polygon bounds), masks (B,H/4,W/4) overlap-encoded, instances of an image sorted like the map.
+        ``with_masks=False`` (box-only training): nothing is rasterised, no "masks" entry, instances in label order."""
         H, W = self.imgsz
         imgs = self.images[list(indices)]
         bidx, cls, boxes = [], [], []
-        masks = np.zeros((len(indices), H // 4, W // 4), np.uint8)
-        if any(len(self.labels[i]) > 255 for i in indices):
+        masks = np.zeros((len(indices), H // 4, W // 4) if with_masks else (0,), np.uint8)
+        if with_masks and any(len(self.labels[i]) > 255 for i in indices):
             masks = masks.astype(np.int32)
         for b, i in enumerate(indices):
             polys = [p for _, p in self.labels[i]]
@@ -155,15 +156,21 @@ class SegDataset:
                 polys = [np.stack((W - p[:, 0], p[:, 1]), 1) for p in polys]
             if not polys:
                 continue
-            masks[b], order = overlap_mask(polys, self.imgsz)
+            if with_masks:
+                masks[b], order = overlap_mask(polys, self.imgsz)
+            else:
+                order = range(len(polys))
             for j in order:
                 p = polys[j]
                 x1, y1, x2, y2 = p[:, 0].min(), p[:, 1].min(), p[:, 0].max(), p[:, 1].max()
                 bidx.append(b)
                 cls.append(self.labels[i][j][0])
                 boxes.append([(x1 + x2) / 2 / W, (y1 + y2) / 2 / H, (x2 - x1) / W, (y2 - y1) / H])
-        return {"img": np.ascontiguousarray(imgs), "batch_idx": np.asarray(bidx, np.float32),
-                "cls": np.asarray(cls, np.float32), "bboxes": np.asarray(boxes, np.float32).reshape(-1, 4), "masks": masks}
+        out = {"img": np.ascontiguousarray(imgs), "batch_idx": np.asarray(bidx, np.float32),
+               "cls": np.asarray(cls, np.float32), "bboxes": np.asarray(boxes, np.float32).reshape(-1, 4)}
+        if with_masks:
+            out["masks"] = masks
+        return out
 
 
 def epoch_batches(n: int, batch: int, epoch: int, seed: int = 0, rank: int = 0, world: int = 1, shuffle: bool = True):

@@ -15,7 +15,7 @@ import torch
 from . import _capi
 from ._capi import ConvInfo, LetterboxImage, ModelDesc, OpInfo, check, lib
 from .preprocess import scale_boxes_to_original
-from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_detect, is_v5u, is_y11
+from .spec import V9C, ConvSpec, conv_specs, fold_bn, is_detect, is_v5u, is_v8det, is_y11
 
 
 def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
@@ -28,19 +28,21 @@ def _stream() -> C.c_void_p:
 
 def scale_code(scale: str) -> int:
     """m355_model_desc.scale of a scale tag: 'n'..'x' (yolov8-seg), 'c' (yolov9c-seg), ('5' << 8) | n/s/m (YOLOv5u),
-    ('1' << 8) | n/s/m (YOLO11)."""
+    ('1' << 8) | n/s/m (YOLO11), ('8' << 8) | n/s/m/l/x (YOLOv8 detect)."""
     if scale == V9C:
         return ord("c")
     if is_v5u(scale):
         return (ord("5") << 8) | ord(scale[1])
     if is_y11(scale):
         return (ord("1") << 8) | ord(scale[2])
+    if is_v8det(scale):
+        return (ord("8") << 8) | ord(scale[1])
     return ord(scale)
 
 
 class SegEngine:
     """One engine per device.  Not thread-safe (one handle, one caller).  Serves the segmentation graphs (nm = 32 mask
-    coefficients, prototypes) and the YOLOv5u and YOLO11 detection graphs (nm = 0: no prototypes, no masks)."""
+    coefficients, prototypes) and the YOLOv5u, YOLO11 and YOLOv8 detection graphs (nm = 0: no prototypes, no masks)."""
 
     def __init__(self, scale: str = "s", nc: int = 1, imgsz: Tuple[int, int] = (640, 640),
                  max_batch: int = 32, device: int = 0, keep_raw: bool = True):

@@ -1,4 +1,4 @@
-"""Segmentation training loss on the head outputs of the HIP engine.
+"""Segmentation and detection training losses on the head outputs of the HIP engine.
 
 Stands where ``v8SegmentationLoss`` + ``TaskAlignedAssigner`` + ``BboxLoss`` stand upstream (reached from
 /root/reference/BscanBased/yolo_seg_train.py:12).  Inputs are the engine's train-mode outputs -- raw head maps
@@ -257,21 +257,16 @@ class _MaskTerm(torch.autograd.Function):
         return d_coef * g, d_protos, None, None, None, None
 
 
-def loss_core(raw: torch.Tensor, protos: torch.Tensor, gt_cls: torch.Tensor, gt_boxes: torch.Tensor, gt_valid: torch.Tensor,
-              masks: torch.Tensor, nc: int, imgsz: Tuple[int, int], gains: Tuple[float, float, float] = (7.5, 0.5, 1.5)):
-    """The loss on padded targets: fixed shapes for a given G, no host synchronisation, no host-to-device copy."""
-    dev = raw.device
+def _assign_all(raw, logits_box, logits_cls, gt_cls, gt_boxes, gt_valid, nc: int, k: Dict, use_kernels: bool):
+    """Decoded boxes and class scores of ALL anchors (no gradient) and their task-aligned assignment: target boxes (B,A,4) px,
+    target scores (B,A,nc), foreground mask (B,A), assigned GT index (B,A).  Shared by the segmentation and the detection loss."""
     B, A, _ = raw.shape
-    mh, mw = protos.shape[1:3]
     G = gt_boxes.shape[1]
-    k = _consts(imgsz, mh, mw, dev, gains)
     anchors, strides, bins = k["anchors"], k["strides"], k["bins"]
-    logits_box, logits_cls, coefs = raw.split((4 * REG_MAX, nc, NM), 2)
-    # Decoded boxes of ALL anchors feed only the assignment (no gradient).  The box / DFL / mask terms below are evaluated on
+    # Decoded boxes of ALL anchors feed only the assignment (no gradient).  The box / DFL / mask terms are evaluated on
     # the <= 10 G foreground slots per image: every other anchor has weight zero, and carrying the (B, A, 4, 16) logits
     # through softmax, log-softmax, two gathers and their backward passes cost ~2 ms of a 5.3 ms loss for 0.2 % of the rows.
     # expectation over the 16 bins as multiply + reduce: `softmax @ bins` runs as a (B*A*4) x 16 rocBLAS gemv, 1.4 ms
-    use_kernels = raw.is_cuda and _loss_kernels_enabled()
     with torch.no_grad():
         if use_kernels and raw.shape[2] <= 255:            # one pass over the raw rows (csrc/loss_kernels.hip; 64 rows in LDS)
             boxes_px, scores = _decode_all(raw.detach(), anchors, k["strides_flat"], nc)
@@ -280,9 +275,52 @@ def loss_core(raw: torch.Tensor, protos: torch.Tensor, gt_cls: torch.Tensor, gt_
             boxes_px = torch.cat((anchors - ltrb[..., :2], anchors + ltrb[..., 2:]), -1) * strides       # pixels
             scores = logits_cls.detach().sigmoid()
     if use_kernels and G > 0 and A <= 18000 and G <= 900:        # two launches instead of ~40 (csrc/loss_kernels.hip: tal_topk / tal_resolve)
-        t_boxes, t_scores, fg, gt_idx = _assign_targets_device(scores, boxes_px, k["anchors_px"], gt_cls, gt_boxes, gt_valid)
-    else:
-        t_boxes, t_scores, fg, gt_idx = assign_targets(scores, boxes_px, k["anchors_px"], gt_cls, gt_boxes, gt_valid)
+        return _assign_targets_device(scores, boxes_px, k["anchors_px"], gt_cls, gt_boxes, gt_valid)
+    return assign_targets(scores, boxes_px, k["anchors_px"], gt_cls, gt_boxes, gt_valid)
+
+
+def _fg_slots(fg: torch.Tensor, w: torch.Tensor, G: int):
+    """Every GT claims at most 10 anchors, so K = 10 G slots per image hold all foreground anchors: (K, anchor index (B,K), occupied
+    (B,K), slot weight (B,K), 0 on an empty slot)."""
+    K = min(10 * G, fg.shape[1])
+    val, ai = fg.float().topk(K, dim=1)
+    valid = val > 0                                                              # (B,K)
+    return K, ai, valid, w.gather(1, ai) * valid
+
+
+def _box_dfl_terms(logits_box, t_boxes, ai, ws, denom, k: Dict, use_kernels: bool):
+    """(box loss, DFL loss) over the foreground slots `ai` with weights `ws`, both divided by `denom`."""
+    B, K = ai.shape
+    anchors, strides, bins = k["anchors"], k["strides"], k["bins"]
+    anc = anchors[ai]                                                            # (B,K,2) grid units
+    tb = (t_boxes / strides).gather(1, ai[..., None].expand(B, K, 4))
+    lb = logits_box.gather(1, ai[..., None].expand(B, K, 4 * REG_MAX)).view(B, K, 4, REG_MAX)
+    if use_kernels:                                    # value and gradient of both terms in one pass, one thread per slot
+        box_sum, dfl_sum = _BoxTerm.apply(lb, anc, tb.detach(), ws.detach())
+        return box_sum / denom, dfl_sum / denom
+    ltrb_s = (lb.softmax(3) * bins).sum(3)
+    pred_s = torch.cat((anc - ltrb_s[..., :2], anc + ltrb_s[..., 2:]), -1)
+    loss_box = ((1.0 - ciou(pred_s, tb)) * ws).sum() / denom
+    dist = torch.cat((anc - tb[..., :2], tb[..., 2:] - anc), -1).clamp(0, REG_MAX - 1 - 0.01)       # (B,K,4)
+    lo = dist.long()
+    logp = lb.log_softmax(3)
+    ce_lo = -logp.gather(3, lo[..., None]).squeeze(3)
+    ce_hi = -logp.gather(3, lo[..., None] + 1).squeeze(3)
+    loss_dfl = (((ce_lo * (lo + 1 - dist) + ce_hi * (dist - lo)).mean(2)) * ws).sum() / denom
+    return loss_box, loss_dfl
+
+
+def loss_core(raw: torch.Tensor, protos: torch.Tensor, gt_cls: torch.Tensor, gt_boxes: torch.Tensor, gt_valid: torch.Tensor,
+              masks: torch.Tensor, nc: int, imgsz: Tuple[int, int], gains: Tuple[float, float, float] = (7.5, 0.5, 1.5)):
+    """The loss on padded targets: fixed shapes for a given G, no host synchronisation, no host-to-device copy."""
+    dev = raw.device
+    B, A, _ = raw.shape
+    mh, mw = protos.shape[1:3]
+    G = gt_boxes.shape[1]
+    k = _consts(imgsz, mh, mw, dev, gains)
+    logits_box, logits_cls, coefs = raw.split((4 * REG_MAX, nc, NM), 2)
+    use_kernels = raw.is_cuda and _loss_kernels_enabled()
+    t_boxes, t_scores, fg, gt_idx = _assign_all(raw, logits_box, logits_cls, gt_cls, gt_boxes, gt_valid, nc, k, use_kernels)
     # Everything below runs over ALL anchors / a fixed number of slots per image with zero weights for the background,
     # so the step has no data-dependent shapes and no host synchronisation after the one that sized the GT padding.
     denom = t_scores.sum().clamp_min(1.0)
@@ -292,27 +330,8 @@ def loss_core(raw: torch.Tensor, protos: torch.Tensor, gt_cls: torch.Tensor, gt_
         zero = (protos * 0).sum() + (coefs * 0).sum() + (logits_box * 0).sum()
         items = torch.stack((zero, zero, loss_cls, zero))
     else:
-        # every GT claims at most 10 anchors, so K = 10 G slots per image hold all foreground anchors
-        K = min(10 * G, A)
-        val, ai = fg.float().topk(K, dim=1)
-        valid = val > 0                                                              # (B,K)
-        ws = w.gather(1, ai) * valid                                                 # slot weights, 0 on empty slots
-        anc = anchors[ai]                                                            # (B,K,2) grid units
-        tb = (t_boxes / strides).gather(1, ai[..., None].expand(B, K, 4))
-        lb = logits_box.gather(1, ai[..., None].expand(B, K, 4 * REG_MAX)).view(B, K, 4, REG_MAX)
-        if use_kernels:                                    # value and gradient of both terms in one pass, one thread per slot
-            box_sum, dfl_sum = _BoxTerm.apply(lb, anc, tb.detach(), ws.detach())
-            loss_box, loss_dfl = box_sum / denom, dfl_sum / denom
-        else:
-            ltrb_s = (lb.softmax(3) * bins).sum(3)
-            pred_s = torch.cat((anc - ltrb_s[..., :2], anc + ltrb_s[..., 2:]), -1)
-            loss_box = ((1.0 - ciou(pred_s, tb)) * ws).sum() / denom
-            dist = torch.cat((anc - tb[..., :2], tb[..., 2:] - anc), -1).clamp(0, REG_MAX - 1 - 0.01)       # (B,K,4)
-            lo = dist.long()
-            logp = lb.log_softmax(3)
-            ce_lo = -logp.gather(3, lo[..., None]).squeeze(3)
-            ce_hi = -logp.gather(3, lo[..., None] + 1).squeeze(3)
-            loss_dfl = (((ce_lo * (lo + 1 - dist) + ce_hi * (dist - lo)).mean(2)) * ws).sum() / denom
+        K, ai, valid, ws = _fg_slots(fg, w, G)
+        loss_box, loss_dfl = _box_dfl_terms(logits_box, t_boxes, ai, ws, denom, k, use_kernels)
         # masks: BCE(coef . proto, gt mask of the assigned instance) inside the target box, mean over the map, divided by
         # the normalised box area; one batched GEMM (B,K,32) x (B,32,mh*mw).
         nb = t_boxes.gather(1, ai[..., None].expand(B, K, 4)) / k["wh"]
@@ -336,6 +355,59 @@ def loss_core(raw: torch.Tensor, protos: torch.Tensor, gt_cls: torch.Tensor, gt_
         items = torch.stack((loss_box, loss_seg, loss_cls, loss_dfl))
     items = items * k["gains"]
     return items.sum() * B, items.detach()
+
+
+def cls_bce_device(raw: torch.Tensor, t_scores: torch.Tensor, s: torch.Tensor, d_raw: torch.Tensor) -> torch.Tensor:
+    """The class term of the detection loss on the device, value and gradient in one pass (``m355_cls_bce_launch``): reads the
+    class logits in place in the raw rows (B,A,rw) at column 64, writes (sigmoid(x) - t) * s into the same columns of ``d_raw`` and
+    returns the sum of BCEWithLogits(x, t) as a device scalar.  ``s`` is a device scalar too, so nothing here waits for the device."""
+    from ._capi import check, lib
+    B, A, rw = raw.shape
+    nc = t_scores.shape[2]
+    assert raw.dtype == torch.float32 and raw.is_contiguous() and d_raw.dtype == torch.float32 and d_raw.is_contiguous()
+    assert d_raw.shape == raw.shape and rw >= 4 * REG_MAX + nc
+    tg = t_scores.float().contiguous()
+    sc = s.detach().float().reshape(1).contiguous()
+    out = torch.empty(int(lib.m355_cls_bce_workspace_floats()), dtype=torch.float32, device=raw.device)
+    check(lib.m355_cls_bce_launch(raw.data_ptr(), rw, tg.data_ptr(), B * A, nc, sc.data_ptr(), d_raw.data_ptr(), out.data_ptr(),
+                                  _stream()))
+    return out[0]
+
+
+def det_loss_core(raw: torch.Tensor, gt_cls: torch.Tensor, gt_boxes: torch.Tensor, gt_valid: torch.Tensor, nc: int,
+                  imgsz: Tuple[int, int], gains: Tuple[float, float, float] = (7.5, 0.5, 1.5), scale: float = 1.0):
+    """The detection loss (upstream v8DetectionLoss) on padded targets with its gradient: raw (B,A,64+nc) -> (detached items (3,)
+    [box, cls, dfl] with the gains applied, d(scale * B * sum(items)) / d raw).  Assignment, box and DFL terms are the
+    segmentation loss's own (``_assign_all`` / ``_fg_slots`` / ``_box_dfl_terms``).  On the device the class term is one HIP pass
+    that writes its gradient straight into the class columns of d_raw (``cls_bce_device``); on CPU tensors (and with
+    M355_NO_LOSS_KERNELS=1) it is torch's BCE under autograd."""
+    dev = raw.device
+    B, A, rw = raw.shape
+    assert rw == 4 * REG_MAX + nc, f"raw rows of {rw} columns for a detection head of {4 * REG_MAX + nc}"
+    G = gt_boxes.shape[1]
+    k = _consts(imgsz, 0, 0, dev, gains)
+    use_kernels = raw.is_cuda and _loss_kernels_enabled()
+    r = raw.detach().float().contiguous().requires_grad_(True)   # shares the engine's buffer: the loss never writes to its inputs
+    logits_box, logits_cls = r.split((4 * REG_MAX, nc), 2)
+    t_boxes, t_scores, fg, _ = _assign_all(r, logits_box, logits_cls, gt_cls, gt_boxes, gt_valid, nc, k, use_kernels)
+    denom = t_scores.sum().clamp_min(1.0)
+    terms = []                                                   # (gain, term with a gradient path to r)
+    zero = torch.zeros((), device=dev)
+    loss_box = loss_dfl = zero
+    if G > 0:
+        _, ai, _, ws = _fg_slots(fg, t_scores.sum(-1), G)
+        loss_box, loss_dfl = _box_dfl_terms(logits_box, t_boxes, ai, ws, denom, k, use_kernels)
+        terms += [(gains[0], loss_box), (gains[2], loss_dfl)]
+    if not use_kernels:
+        loss_cls = F.binary_cross_entropy_with_logits(logits_cls, t_scores, reduction="sum") / denom
+        terms.append((gains[1], loss_cls))
+    if terms:
+        (sum(g * t for g, t in terms) * (B * scale)).backward()
+    d_raw = r.grad.contiguous() if r.grad is not None else torch.zeros_like(r)
+    if use_kernels:
+        loss_cls = cls_bce_device(r.detach(), t_scores, (gains[1] * B * scale) / denom, d_raw) / denom
+    items = torch.stack((loss_box.detach() * gains[0], loss_cls.detach() * gains[1], loss_dfl.detach() * gains[2]))
+    return items, d_raw
 
 
 class SegCriterion:
@@ -377,3 +449,23 @@ class SegCriterion:
         loss, items = loss_core(r, p, *gt, masks, self.nc, self.imgsz, self.gains)
         (loss * scale).backward()
         return items, r.grad, p.grad
+
+
+class DetCriterion:
+    """The criterion of a box-only training run (upstream ``v8DetectionLoss``; the reference's BscanBased/yolo/yolo_bbox_retrain.py
+    trains against it): same protocol as ``SegCriterion`` without the mask term.  ``prepare(batch, B, dev)`` pads the targets
+    before the forward pass is enqueued; ``__call__(raw, protos, prepared_or_batch, scale)`` -> (items (3,) [box, cls, dfl],
+    d(scale * loss)/d raw, None); ``protos`` is None for a detection head and is ignored."""
+
+    def __init__(self, nc: int, imgsz: Tuple[int, int], gains: Tuple[float, float, float] = (7.5, 0.5, 1.5)):
+        self.nc, self.imgsz, self.gains = nc, tuple(imgsz), tuple(gains)
+
+    def prepare(self, batch: Dict[str, torch.Tensor], B: int, dev) -> Dict[str, torch.Tensor]:
+        dev = torch.device(dev)
+        gt = pad_targets(batch, B, self.imgsz, batch["batch_idx"].device)
+        return {"_gt": tuple(t.to(dev, non_blocking=True) for t in gt)}
+
+    def __call__(self, raw: torch.Tensor, protos, batch: Dict[str, torch.Tensor], scale: float = 1.0):
+        gt = batch["_gt"] if "_gt" in batch else pad_targets(batch, raw.shape[0], self.imgsz, raw.device)
+        items, d_raw = det_loss_core(raw, *gt, self.nc, self.imgsz, self.gains, scale)
+        return items, d_raw, None

@@ -22,9 +22,10 @@ import torch
 
 from .preprocess import expand_sources, letterbox, letterbox_plan, scale_boxes_to_original
 from .results import Results
-from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_detect, state_dict_keys
+from .spec import SCALES, V9C, conv_specs, count_parameters, init_state_dict, is_detect, is_v8det, state_dict_keys
 
 _YAML_RE = re.compile(r"^yolov8([nsmlx])?-seg\.ya?ml$")
+_V8DET_RE = re.compile(r"^yolov8([nsmlx])?\.ya?ml$")
 _V9C_RE = re.compile(r"^yolov9c-seg\.ya?ml$")
 _V5U_RE = re.compile(r"^yolov5([nsmlx])u\.ya?ml$")
 _Y11_RE = re.compile(r"^yolo11([nsmlx])\.ya?ml$")
@@ -68,6 +69,15 @@ class YOLO:
             if os.path.isfile(model):
                 self._read_yaml_overrides(model)
             self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
+        elif _V8DET_RE.match(name):
+            # the detector the reference loads (signals/improved_multisignal/visualization/yolo_detector.py:20: yolov8n.pt)
+            self.scale = "8" + (_V8DET_RE.match(name).group(1) or "n")
+            self.task = "detect"
+            self.nc = 80
+            self.names = {i: f"class{i}" for i in range(self.nc)}
+            if os.path.isfile(model):
+                self._read_yaml_overrides(model)
+            self.state_dict = init_state_dict(self.scale, self.nc, seed=0)
         elif _V5U_RE.match(name):
             # the detection family the reference retrains (/root/reference/BscanBased/yolo5s_retrain.py:6: yolov5su.pt)
             sc = _V5U_RE.match(name).group(1)
@@ -95,7 +105,7 @@ class YOLO:
         elif name.endswith((".yaml", ".yml")):
             raise NotImplementedError(
                 f"architecture '{name}' is not built: this package implements the YOLOv8{{n,s,m,l,x}}-seg, YOLOv9c-seg, "
-                "YOLOv5{n,s,m}u and YOLO11{n,s,m} (detection) graphs")
+                "YOLOv8{n,s,m,l,x}, YOLOv5{n,s,m}u and YOLO11{n,s,m} (detection) graphs")
         elif name.endswith(".pt"):
             if not os.path.isfile(model):
                 raise OfflineModelError(
@@ -166,7 +176,7 @@ class YOLO:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         if upstream:
             if is_detect(self.scale):
-                raise NotImplementedError("upstream export of a detection model (YOLOv5u, YOLO11) is not built")
+                raise NotImplementedError("upstream export of a detection model (YOLOv8, YOLOv5u, YOLO11) is not built")
             from .upstream_export import export_upstream_checkpoint
             return export_upstream_checkpoint(path, self.scale, self.nc, self.names, self.state_dict, self.train_args)
         torch.save({"format": CKPT_FORMAT, "scale": self.scale, "nc": self.nc, "names": self.names,
@@ -287,17 +297,18 @@ class YOLO:
     # ------------------------------------------------------------------ training
     def train(self, data: Optional[str] = None, epochs: int = 100, imgsz: int = 640, batch: int = 16,
               project: Optional[str] = None, name: Optional[str] = None, device=0, **kwargs):
-        self._require_segment("train")
+        self._require_trainable("train")
         from .train import train as _train  # lazy: training pulls in the loss / dataset modules
         return _train(self, data=data, epochs=epochs, imgsz=imgsz, batch=batch, project=project, name=name,
                       device=device, **kwargs)
 
     def val(self, data: Optional[str] = None, imgsz: Optional[int] = None, batch: int = 16, device=0, **kwargs):
-        self._require_segment("val")
+        self._require_trainable("val")
         from .train import validate as _validate
         return _validate(self, data=data, imgsz=imgsz, batch=batch, device=device, **kwargs)
 
-    def _require_segment(self, what: str) -> None:
-        if self.task != "segment":
+    def _require_trainable(self, what: str) -> None:
+        """The graphs TrainEngine builds: the segmentation families and YOLOv8 detect."""
+        if self.task != "segment" and not is_v8det(self.scale):
             raise NotImplementedError(f"{what}() of a {self.task} model: detect training and validation (YOLOv5u, YOLO11) are not built "
-                                      "yet; this package trains and validates the segmentation graphs only")
+                                      "yet; this package trains and validates the segmentation graphs and YOLOv8 detect only")

@@ -25,6 +25,10 @@ V5U_SCALES = {"5n": (0.33, 0.25, 1024), "5s": (0.33, 0.50, 1024), "5m": (0.67, 0
 # YOLO11 detection graphs (BscanBased/yolo/yolo_bbox_retrain.py trains yolo11n): scale tags "11n" / "11s" /
 # "11m", (depth, width, max channels) of upstream's cfg/models/11/yolo11.yaml.  The C-ABI descriptor carries ('1' << 8) | n/s/m.
 Y11_SCALES = {"11n": (0.50, 0.25, 1024), "11s": (0.50, 0.50, 1024), "11m": (0.50, 1.00, 512)}
+# YOLOv8 detection graphs (signals/improved_multisignal/visualization/yolo_detector.py:20 loads yolov8n.pt): scale tags
+# "8n" .. "8x", the (depth, width, max channels) of SCALES -- the backbone and neck of yolov8-seg under the box-only Detect head at
+# model.22.  The C-ABI descriptor carries ('8' << 8) | n/s/m/l/x.
+V8DET_SCALES = {"8" + k: v for k, v in SCALES.items()}
 REG_MAX = 16
 NM = 32
 BN_EPS = 1e-3
@@ -109,14 +113,18 @@ def is_y11(scale: str) -> bool:
     return scale in Y11_SCALES
 
 
+def is_v8det(scale: str) -> bool:
+    return scale in V8DET_SCALES
+
+
 def is_detect(scale: str) -> bool:
-    """True for the box-only detection graphs (YOLOv5u, YOLO11): no mask coefficients, no Proto."""
-    return is_v5u(scale) or is_y11(scale)
+    """True for the box-only detection graphs (YOLOv5u, YOLO11, YOLOv8 detect): no mask coefficients, no Proto."""
+    return is_v5u(scale) or is_y11(scale) or is_v8det(scale)
 
 
 def head_prefix(scale: str) -> str:
     """State-dict prefix of the head: model.24 = Detect of YOLOv5u, model.23 = Detect of YOLO11, model.22 = Segment of the
-    seg graphs."""
+    seg graphs and Detect of YOLOv8 detect."""
     return "model.24" if is_v5u(scale) else "model.23" if is_y11(scale) else "model.22"
 
 
@@ -300,15 +308,30 @@ def _segment_specs(out: List[ConvSpec], nc: int, fch, npr: int) -> None:
     _branch_specs(out, "model.22.cv4", fch, max(fch[0] // 4, NM), NM)
 
 
+def conv_specs_v8det(scale: str, nc: int = 1) -> List[ConvSpec]:
+    """Canonical list of every convolution of YOLOv8 detect (upstream cfg/models/v8/yolov8.yaml): the backbone / neck list of
+    yolov8{scale}-seg followed by the Detect head at model.22."""
+    if scale not in V8DET_SCALES:
+        raise ValueError(f"YOLOv8 detect scale '{scale}' is not built: one of {sorted(V8DET_SCALES)}")
+    return _conv_specs_v8(scale[1:], nc, detect=True)
+
+
 def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
     """Canonical list of every convolution of yolov8{scale}-seg (A5/A9/A10); scale "9c": yolov9c-seg; "5n/5s/5m": YOLOv5u;
-    "11n/11s/11m": YOLO11."""
+    "11n/11s/11m": YOLO11; "8n" .. "8x": YOLOv8 detect."""
     if scale == V9C:
         return conv_specs_v9c(nc)
     if is_v5u(scale):
         return conv_specs_v5u(scale, nc)
     if is_y11(scale):
         return conv_specs_y11(scale, nc)
+    if is_v8det(scale):
+        return conv_specs_v8det(scale, nc)
+    return _conv_specs_v8(scale, nc, detect=False)
+
+
+def _conv_specs_v8(scale: str, nc: int, detect: bool) -> List[ConvSpec]:
+    """The YOLOv8 backbone and neck at width / depth `scale` under the Segment head, or (detect) the Detect head."""
     depth, width, maxc = SCALES[scale]
     ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
     rep = lambda n: max(round(n * depth), 1) if n > 1 else n  # noqa: E731
@@ -343,7 +366,10 @@ def conv_specs(scale: str = "s", nc: int = 1) -> List[ConvSpec]:
     c2f("model.18", c256 + c512, c512, rep(3))
     conv("model.19", c512, c512, 3, 2)
     c2f("model.21", c512 + c1024, c1024, rep(3))
-    _segment_specs(out, nc, (c256, c512, c1024), ch(256))
+    if detect:
+        _detect_specs(out, nc, (c256, c512, c1024), "model.22")
+    else:
+        _segment_specs(out, nc, (c256, c512, c1024), ch(256))
     return out
 
 
@@ -410,6 +436,8 @@ def init_state_dict(scale: str = "s", nc: int = 1, seed: int = 0) -> Dict[str, t
 def _load_gains(scale: str) -> Dict[str, float]:
     import json
     import os
+    if is_v8det(scale):     # the same layers under the same names as the seg graph of that letter (whose file also lists cv4 / proto)
+        scale = scale[1:]
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", f"synth_gains_{scale}.json")
     if not os.path.exists(path):
         return {}

@@ -35,8 +35,9 @@ import torch
 from . import metrics as M
 from ._capi import check, lib
 from .dataset import SegDataset, epoch_batches, rasterize_polygon, read_data_yaml
-from .loss import SegCriterion
+from .loss import DetCriterion, SegCriterion
 from .sharding import GradBucketReducer
+from .spec import is_detect
 
 DEFAULTS = dict(optimizer="auto", lr0=0.01, lrf=0.01, momentum=0.937, weight_decay=5e-4, warmup_epochs=3.0,
                 warmup_momentum=0.8, warmup_bias_lr=0.1, nbs=64, seed=0, fliplr=0.5, val=True, exist_ok=False,
@@ -58,8 +59,8 @@ def _devices(device) -> List[int]:
     return [int(device)]
 
 
-def _run_dir(project: Optional[str], name: Optional[str], exist_ok: bool) -> str:
-    base = os.path.join(project or os.path.join("runs", "segment"), name or "train")
+def _run_dir(project: Optional[str], name: Optional[str], exist_ok: bool, task: str = "segment") -> str:
+    base = os.path.join(project or os.path.join("runs", task), name or "train")
     if exist_ok or not os.path.exists(base):
         return base
     i = 2
@@ -94,7 +95,9 @@ class LossScaler:
 
 
 class Validator:
-    """A17: NMS at conf 0.001 on the inference engine, box and mask IoU matching, 101-point AP."""
+    """A17: NMS at conf 0.001 on the inference engine, box and mask IoU matching, 101-point AP.  A detection model (no mask
+    coefficients) is matched on boxes only: no ground-truth mask is rasterised, the engine is not asked for masks, and the
+    result has no (M) entries."""
 
     def __init__(self, dataset: SegDataset, scale: str, nc: int, device: int, batch: int = 16, conf: float = 0.001,
                  iou: float = 0.7, max_det: int = 300):
@@ -103,7 +106,8 @@ class Validator:
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.batch = max(1, min(batch, len(dataset)))
         self.engine = SegEngine(scale, nc, dataset.imgsz, max_batch=self.batch, device=device, keep_raw=False)
-        self._gt: Dict[int, Tuple[np.ndarray, np.ndarray, torch.Tensor]] = {}
+        self.detect = is_detect(scale)
+        self._gt: Dict[int, Tuple[np.ndarray, np.ndarray, Optional[torch.Tensor]]] = {}
 
     def _ground_truth(self, i: int):
         if i not in self._gt:
@@ -112,6 +116,9 @@ class Validator:
             cls = np.array([c for c, _ in inst], np.int64)
             boxes = np.array([[p[:, 0].min(), p[:, 1].min(), p[:, 0].max(), p[:, 1].max()] for _, p in inst],
                              np.float64).reshape(-1, 4)
+            if self.detect:
+                self._gt[i] = (cls, boxes, None)
+                return self._gt[i]
             masks = np.stack([rasterize_polygon(p, H, W) for _, p in inst]) if inst else np.zeros((0, H, W), bool)
             self._gt[i] = (cls, boxes, torch.from_numpy(masks))
         return self._gt[i]
@@ -126,7 +133,7 @@ class Validator:
                 idx = list(range(i0, min(i0 + self.batch, n)))
                 x = torch.from_numpy(self.ds.images[idx]).to(dev)
                 preds, protos = self.engine.forward(x)
-                dets, counts, masks = self.engine.postprocess(preds, protos, self.conf, self.iou, self.max_det, masks=True,
+                dets, counts, masks = self.engine.postprocess(preds, protos, self.conf, self.iou, self.max_det, masks=not self.detect,
                                                               multi_label=True)   # upstream's validator mode (a no-op for nc = 1)
                 counts_h = counts.cpu().tolist()
                 for j, i in enumerate(idx):
@@ -137,6 +144,12 @@ class Validator:
                     if k == 0:
                         continue
                     iou_b = M.box_iou(d[:, :4], g_boxes)
+                    c = d[:, 5].astype(np.int64)
+                    tp_b.append(M.match(c, g_cls, iou_b))
+                    confs.append(d[:, 4])
+                    pcls.append(c)
+                    if self.detect:
+                        continue
                     if g_cls.size:
                         pm = masks[j, :k].flatten(1).float()
                         gm = g_masks.to(dev).flatten(1).float()
@@ -145,20 +158,20 @@ class Validator:
                         iou_m = (inter / (union + 1e-7)).double().cpu().numpy()
                     else:
                         iou_m = np.zeros((k, 0))
-                    c = d[:, 5].astype(np.int64)
-                    tp_b.append(M.match(c, g_cls, iou_b))
                     tp_m.append(M.match(c, g_cls, iou_m))
-                    confs.append(d[:, 4])
-                    pcls.append(c)
         gt_all = np.concatenate(gcls) if gcls else np.zeros(0, np.int64)
         if confs:
             conf_all, cls_all = np.concatenate(confs), np.concatenate(pcls)
             rb = M.summarize(np.concatenate(tp_b), conf_all, cls_all, gt_all)
-            rm = M.summarize(np.concatenate(tp_m), conf_all, cls_all, gt_all)
+            rm = None if self.detect else M.summarize(np.concatenate(tp_m), conf_all, cls_all, gt_all)
         else:
-            rb = rm = (0.0, 0.0, 0.0, 0.0)
-        out = {"metrics/precision(B)": rb[0], "metrics/recall(B)": rb[1], "metrics/mAP50(B)": rb[2], "metrics/mAP50-95(B)": rb[3],
-               "metrics/precision(M)": rm[0], "metrics/recall(M)": rm[1], "metrics/mAP50(M)": rm[2], "metrics/mAP50-95(M)": rm[3]}
+            rb = (0.0, 0.0, 0.0, 0.0)
+            rm = None if self.detect else rb
+        out = {"metrics/precision(B)": rb[0], "metrics/recall(B)": rb[1], "metrics/mAP50(B)": rb[2], "metrics/mAP50-95(B)": rb[3]}
+        if rm is None:                                         # upstream's DetMetrics fitness
+            out["fitness"] = 0.1 * rb[2] + 0.9 * rb[3]
+            return out
+        out.update({"metrics/precision(M)": rm[0], "metrics/recall(M)": rm[1], "metrics/mAP50(M)": rm[2], "metrics/mAP50-95(M)": rm[3]})
         out["fitness"] = 0.1 * (rb[2] + rm[2]) + 0.9 * (rb[3] + rm[3])
         return out
 
@@ -167,8 +180,11 @@ class Validator:
 
 
 def _metrics_namespace(res: Dict[str, float], save_dir: Optional[str]) -> SimpleNamespace:
+    """Upstream's SegmentMetrics shape (.box and .seg), or DetMetrics' (.box only) for the result of a detection model."""
     box = SimpleNamespace(mp=res["metrics/precision(B)"], mr=res["metrics/recall(B)"], map50=res["metrics/mAP50(B)"],
                           map=res["metrics/mAP50-95(B)"])
+    if "metrics/mAP50(M)" not in res:
+        return SimpleNamespace(box=box, fitness=res["fitness"], results_dict=dict(res), save_dir=save_dir)
     seg = SimpleNamespace(mp=res["metrics/precision(M)"], mr=res["metrics/recall(M)"], map50=res["metrics/mAP50(M)"],
                           map=res["metrics/mAP50-95(M)"])
     return SimpleNamespace(box=box, seg=seg, fitness=res["fitness"], results_dict=dict(res), save_dir=save_dir)
@@ -196,7 +212,7 @@ def _spawn_ddp(model, devices: List[int], kwargs: Dict) -> str:
     generates a DDP script and re-launches itself).  Returns the run directory the children wrote."""
     import socket
     import tempfile
-    save_dir = _run_dir(kwargs.get("project"), kwargs.get("name"), kwargs.get("exist_ok", False))
+    save_dir = _run_dir(kwargs.get("project"), kwargs.get("name"), kwargs.get("exist_ok", False), model.task)
     os.makedirs(os.path.join(save_dir, "weights"), exist_ok=True)
     init = model.save(os.path.join(save_dir, "weights", "init.pt"))
     kw = dict(kwargs, device=devices, exist_ok=True, project=os.path.dirname(save_dir) or ".", name=os.path.basename(save_dir))
@@ -291,7 +307,10 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
     acc = torch.zeros(n_train, device=dev)
     sumsq = torch.zeros(int(lib.m355_grad_sumsq_workspace_floats()), device=dev)   # [0] sum g^2, [1] non-finite count, then workspace
     reducer = GradBucketReducer(flat_g, eng.grad_spans(), bucket_bytes=int(a.bucket_mb) << 20) if world > 1 else None
-    criterion = SegCriterion(model.nc, (imgsz, imgsz), (a.box, a.cls, a.dfl))
+    detect = is_detect(model.scale)                      # box-only run: no mask term, no mask targets, no (M) metrics
+    criterion = (DetCriterion if detect else SegCriterion)(model.nc, (imgsz, imgsz), (a.box, a.cls, a.dfl))
+    loss_names = ["box", "cls", "dfl"] if detect else ["box", "seg", "cls", "dfl"]
+    label_keys = ("batch_idx", "cls", "bboxes") + (() if detect else ("masks",))
 
     nb = len(epoch_batches(len(train_ds), local_batch, 0, a.seed, rank, world))
     opt_name = str(a.optimizer).lower()
@@ -310,7 +329,7 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
     nw = max(round(a.warmup_epochs * nb), 100) if a.warmup_epochs > 0 else -1
     max_steps = kwargs.get("max_steps")
 
-    save_dir = resume_state["save_dir"] if resume_state else _run_dir(project, name, a.exist_ok or world > 1)
+    save_dir = resume_state["save_dir"] if resume_state else _run_dir(project, name, a.exist_ok or world > 1, model.task)
     wdir = os.path.join(save_dir, "weights")
     if rank == 0:
         os.makedirs(wdir, exist_ok=True)
@@ -326,15 +345,17 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
     scaler = LossScaler()
     rng = np.random.default_rng(a.seed + 1000 * rank)
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
-    fields = ["epoch", "time", "train/box_loss", "train/seg_loss", "train/cls_loss", "train/dfl_loss",
-              "metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)",
-              "metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP50-95(M)", "lr/pg0", "loss_scale"]
+    fields = (["epoch", "time"] + [f"train/{n}_loss" for n in loss_names] +
+              ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)"] +
+              ([] if detect else ["metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP50-95(M)"]) +
+              ["lr/pg0", "loss_scale"])
     rows: List[Dict] = []
     best_fit, updates, opt_steps, skipped, global_step = -1.0, 0, 0, 0, 0
     last_res: Dict[str, float] = {}
     t_start = time.time()
     if rank == 0 and a.verbose:
-        print(f"train: yolov8{model.scale}-seg nc={model.nc} imgsz={imgsz} batch={batch} (x{world} GPU, {local_batch}/GPU) "
+        arch = f"yolov8{model.scale[1:]} (detect)" if detect else f"yolov8{model.scale}-seg"
+        print(f"train: {arch} nc={model.nc} imgsz={imgsz} batch={batch} (x{world} GPU, {local_batch}/GPU) "
               f"{len(train_ds)} images, {nb} it/epoch, optimizer={opt_name} lr0={lr0} wd={weight_decay:g} accumulate={accumulate}")
 
     best_epoch, start_epoch = -1, 0
@@ -366,7 +387,7 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
         lf = lr_factor(epoch, epochs, a.lrf)
         lr = lr_bias = lr0 * lf
         mom = momentum
-        mloss = torch.zeros(4, device=dev)
+        mloss = torch.zeros(len(loss_names), device=dev)
         batches = epoch_batches(len(train_ds), local_batch, epoch, a.seed, rank, world)
         micro = 0
         for i, idx in enumerate(batches):
@@ -378,13 +399,13 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
                 lr_bias = warmup_bias_lr + f * (lr0 * lf - warmup_bias_lr)
                 mom = a.warmup_momentum + f * (momentum - a.warmup_momentum) if opt_name == "sgd" else momentum
             if augmenter is not None:     # the whole augmentation chain rendered by one GPU kernel from the HBM image cache
-                b = augmenter.batch(idx, mosaic_on=epoch < epochs - a.close_mosaic)
+                b = augmenter.batch(idx, mosaic_on=epoch < epochs - a.close_mosaic, with_masks=not detect)
                 imgs = b["img"]
             else:
-                b = train_ds.batch(idx, flip=rng.random(len(idx)) < a.fliplr)
+                b = train_ds.batch(idx, flip=rng.random(len(idx)) < a.fliplr, with_masks=not detect)
                 imgs = torch.from_numpy(b["img"]).to(dev, non_blocking=True)
             # targets padded on the host before the forward is enqueued: the loss then needs no synchronisation of its own
-            labels = criterion.prepare({k: torch.from_numpy(b[k]) for k in ("batch_idx", "cls", "bboxes", "masks")}, eng.B, dev)
+            labels = criterion.prepare({k: torch.from_numpy(b[k]) for k in label_keys}, eng.B, dev)
             raw, protos = eng.forward(imgs)
             items, d_raw, d_protos = criterion(raw, protos, labels, scaler.scale)     # loss + its backward
             micro += 1
@@ -439,8 +460,8 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
             sd = eng.state_dict(flat=ema)
             if validator is not None:
                 last_res = validator(sd)
-            row = {"epoch": epoch + 1, "time": round(time.time() - t_start, 3), "train/box_loss": mloss[0], "train/seg_loss": mloss[1],
-                   "train/cls_loss": mloss[2], "train/dfl_loss": mloss[3], "lr/pg0": lr, "loss_scale": scaler.scale, **last_res}
+            row = {"epoch": epoch + 1, "time": round(time.time() - t_start, 3), **{f"train/{n}_loss": v for n, v in zip(loss_names, mloss)},
+                   "lr/pg0": lr, "loss_scale": scaler.scale, **last_res}
             rows.append(row)
             if a.save:
                 with open(os.path.join(save_dir, "results.csv"), "w", newline="") as fcsv:
@@ -448,7 +469,7 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
                     w.writeheader()
                     for rr in rows:
                         w.writerow({k: (f"{v:.5g}" if isinstance(v, float) else v) for k, v in rr.items()})
-                fit = last_res.get("fitness", -mloss[0] - mloss[1] - mloss[2] - mloss[3])
+                fit = last_res.get("fitness", -sum(mloss))
                 improved = fit > best_fit or not os.path.isfile(os.path.join(wdir, "best.pt"))
                 if improved:
                     best_fit, best_epoch = max(fit, best_fit), epoch
@@ -459,10 +480,10 @@ def train(model, data=None, epochs=100, imgsz=640, batch=16, project=None, name=
                 if a.verbose:
                     print(f"early stop: no fitness improvement for {a.patience} epochs (best epoch {best_epoch + 1})")
             if a.verbose:
-                msg = (f"epoch {epoch + 1}/{epochs}  box {mloss[0]:.4f} seg {mloss[1]:.4f} cls {mloss[2]:.4f} dfl {mloss[3]:.4f}"
+                msg = (f"epoch {epoch + 1}/{epochs}  " + " ".join(f"{n} {v:.4f}" for n, v in zip(loss_names, mloss)) +
                        f"  lr {lr:.2e} scale {scaler.scale:g}")
                 if last_res:
-                    msg += f"  mAP50(B) {last_res['metrics/mAP50(B)']:.4f} mAP50(M) {last_res['metrics/mAP50(M)']:.4f}"
+                    msg += "  " + " ".join(f"mAP50({t}) {last_res['metrics/mAP50(' + t + ')']:.4f}" for t in ("B" if detect else "BM"))
                 print(msg, flush=True)
         if world > 1:
             flag = torch.tensor([1 if stop else 0], device=dev)

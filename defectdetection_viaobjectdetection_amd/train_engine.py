@@ -1,4 +1,4 @@
-"""Train-mode forward / backward of YOLOv8-seg on the HIP kernels (SURVEY.md A13, A16 building blocks).
+"""Train-mode forward / backward of YOLOv8-seg, YOLOv9c-seg and YOLOv8 detect on the HIP kernels (SURVEY.md A13, A16 building blocks).
 
 Stands where ``SegmentationModel.forward`` in training mode + PyTorch autograd stand upstream (call site
 /root/reference/BscanBased/yolo_seg_train.py:12-19).  The graph, buffers and the order of kernel launches are
@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from ._capi import ConvLaunchArgs, WgradLaunchArgs, check, lib
-from .spec import BN_EPS, NM, REG_MAX, SCALES, V9C, ConvSpec, _make_divisible, conv_branches, conv_specs
+from .spec import BN_EPS, NM, REG_MAX, SCALES, V9C, ConvSpec, _make_divisible, conv_branches, conv_specs, is_v8det
 
 BN_MOMENTUM = 0.03
 
@@ -50,6 +50,9 @@ class TrainEngine:
             raise RuntimeError("TrainEngine needs a gfx950 GPU; there is no CPU fallback")
         self.dev = torch.device("cuda", device)
         self.scale, self.nc, self.imgsz, self.B = scale, nc, tuple(imgsz), batch
+        # "8n" .. "8x" (YOLOv8 detect): the backbone and neck of the seg graph of that letter under the box-only Detect head
+        self.detect = is_v8det(scale)
+        self.nm = 0 if self.detect else NM
         # RepConvN (yolov9c-seg) trains in its un-merged form: the 3x3 and the 1x1 branch are two Conv + BN of their own
         # (state-dict prefixes <name>.conv1 / <name>.conv2), summed before the SiLU
         self.specs: Dict[str, ConvSpec] = {}
@@ -88,7 +91,7 @@ class TrainEngine:
         # input gradients of the stride-2 3x3 convs as four phase convs over dY (16 tap slots for 9 taps) instead of the masked
         # transposed-stride gather (36): M355_NO_DGRAD_PHASES=1 restores the gather (A/B and the parity test)
         self._dgrad_phases = os.environ.get("M355_NO_DGRAD_PHASES") != "1"
-        # forward: the 1/8-level head + the prototype branch beside the rest of the neck (M355_NO_HEAD_STREAM=1: one stream)
+        # forward: the 1/8-level head (+ the prototype branch of a seg graph) beside the rest of the neck (M355_NO_HEAD_STREAM=1: one stream)
         self._head_stream = None if (os_no_side or os.environ.get("M355_NO_HEAD_STREAM") == "1") else torch.cuda.Stream(device=self.dev)
         self._head_ops = None
         self._build()
@@ -202,7 +205,7 @@ class TrainEngine:
     def _build(self):
         if self.scale == V9C:
             return self._build_v9c()
-        depth, width, maxc = SCALES[self.scale]
+        depth, width, maxc = SCALES[self.scale[1:] if self.detect else self.scale]
         ch = lambda c: _make_divisible(min(c, maxc) * width, 8)  # noqa: E731
         rep = lambda n: max(round(n * depth), 1) if n > 1 else n  # noqa: E731
         c64, c128, c256, c512, c1024 = ch(64), ch(128), ch(256), ch(512), ch(1024)
@@ -250,7 +253,8 @@ class TrainEngine:
         self._build_head((t15, t18, t21), (c256, c512, c1024), ch(256))
 
     def _build_head(self, feats, fch, npr):
-        """model.22 = Segment on the three feature tensors (shared by the yolov8-seg and the yolov9c-seg graphs)."""
+        """model.22 = Segment on the three feature tensors (shared by the yolov8-seg and the yolov9c-seg graphs), or Detect (the
+        detect form): the box and class branches only, raw rows of 64 + nc, no Proto ops and no ``protos_t``."""
         H, W = self.imgsz
         T = self._tensor
         t15, c256 = feats[0], fch[0]
@@ -258,18 +262,22 @@ class TrainEngine:
         hw = [(H // 8, W // 8), (H // 16, W // 16), (H // 32, W // 32)]
         self.level_n = [h * w for h, w in hw]
         self.A = sum(self.level_n)
-        self.rw = 64 + self.nc + NM
+        self.rw = 64 + self.nc + self.nm
         self.raw = torch.zeros((self.B, self.A, self.rw), dtype=torch.float32, device=self.dev)
+        branches = [("cv2", hc2, 64, 0), ("cv3", hc3, self.nc, 64)] + ([] if self.detect else [("cv4", hc4, NM, 64 + self.nc)])
         off = 0
         for l in range(3):
             f = Slice(feats[l], 0, fch[l])
-            for br, hc, cout, choff in (("cv2", hc2, 64, 0), ("cv3", hc3, self.nc, 64), ("cv4", hc4, NM, 64 + self.nc)):
+            for br, hc, cout, choff in branches:
                 u1, u2 = T(*hw[l], hc), T(*hw[l], hc)
                 self._conv(f"model.22.{br}.{l}.0", f, Slice(u1, 0, hc))
                 self._conv(f"model.22.{br}.{l}.1", Slice(u1, 0, hc), Slice(u2, 0, hc))
                 self.ops.append(dict(kind="plain", name=f"model.22.{br}.{l}.2", src=Slice(u2, 0, hc), cout=cout,
                                      level_off=off, ch_off=choff, hw=hw[l]))
             off += self.level_n[l]
+        self.protos_t = None
+        if self.detect:
+            return
         pr1, pr2, pr3 = T(H // 8, W // 8, npr), T(H // 4, W // 4, npr), T(H // 4, W // 4, npr)
         self.protos_t = T(H // 4, W // 4, NM)
         self._conv("model.22.proto.cv1", Slice(t15, 0, c256), Slice(pr1, 0, npr))
@@ -601,7 +609,7 @@ class TrainEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, images_u8_nhwc: torch.Tensor, update_running_stats: bool = True):
         """images uint8 (B,H,W,3) on the device.  Returns raw (B,A,64+nc+32) fp32 and protos (B,H/4,W/4,32) fp16
-        (views of engine buffers, valid until the next forward)."""
+        (views of engine buffers, valid until the next forward); a detect graph returns raw (B,A,64+nc) and None."""
         B = self.B
         assert tuple(images_u8_nhwc.shape) == (B, *self.imgsz, 3) and images_u8_nhwc.dtype == torch.uint8
         x8 = self.tensors[self.x8]
@@ -616,7 +624,8 @@ class TrainEngine:
             for op in self.ops:
                 self._fwd_op(op, update_running_stats)
         else:
-            # The head of the 1/8 level and the prototype branch (the large-map half of the head) need only model.15's output:
+            # The head of the 1/8 level and the prototype branch (the large-map half of the head; a detect graph has no prototype
+            # branch and the 1/8-level head alone goes over: the name filter below simply finds no proto op) need only model.15's output:
             # they go to a side stream while this stream walks the rest of the neck (40x40 / 20x20 maps that leave most CUs idle)
             # and the two smaller head levels.  The backward pass keeps the list order (its accumulations are ordered).
             if self._head_ops is None:
@@ -637,7 +646,7 @@ class TrainEngine:
                             self._fwd_op(hop, update_running_stats)
                         self._head_join.record(side)
             torch.cuda.current_stream().wait_event(self._head_join)
-        return self.raw, self.tensors[self.protos_t]
+        return self.raw, (None if self.protos_t is None else self.tensors[self.protos_t])
 
     # ------------------------------------------------------------------ backward
     def _gview(self, sl: Slice) -> torch.Tensor:
@@ -675,7 +684,8 @@ class TrainEngine:
         written.setdefault(sl.t, []).append((sl.off, sl.off + sl.c))
 
     def backward(self, d_raw: torch.Tensor, d_protos: torch.Tensor, on_ready=None) -> None:
-        """d_raw (B,A,64+nc+32) fp32, d_protos (B,H/4,W/4,32): gradients of the loss w.r.t. forward()'s outputs.
+        """d_raw (B,A,64+nc+32) fp32, d_protos (B,H/4,W/4,32): gradients of the loss w.r.t. forward()'s outputs (a detect graph:
+        d_raw (B,A,64+nc) and d_protos None).
         Fills ``self.grads`` (fp32, parameter layout).  ``on_ready(name)`` is called once the kernels producing that
         parameter's gradient have been enqueued (GradBucketReducer.mark_ready: the all-reduce is stream-ordered)."""
         B = self.B
@@ -688,8 +698,9 @@ class TrainEngine:
             self.gtensors[i] = self.gtensors[j]
         written: Dict[int, list] = {}                                     # tensor -> channel intervals written in this backward
         level_bias: Dict[int, torch.Tensor] = {}                          # level offset -> per-channel sums of d_raw over the level
-        self.gtensors[self.protos_t].copy_(d_protos.to(torch.float16))
-        written[self.protos_t] = [(0, self.tensors[self.protos_t].shape[-1])]
+        if self.protos_t is not None:
+            self.gtensors[self.protos_t].copy_(d_protos.to(torch.float16))
+            written[self.protos_t] = [(0, self.tensors[self.protos_t].shape[-1])]
         ready: List[str] = []
 
         def run(op):

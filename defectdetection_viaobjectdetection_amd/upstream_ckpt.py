@@ -163,7 +163,7 @@ def module_state_dict(module_like) -> "OrderedDict[str, torch.Tensor]":
 
 
 def load_upstream_checkpoint(path: str) -> Dict:
-    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg, YOLOv9c-seg, YOLOv5u or
+    """Returns {'state_dict', 'scale', 'nc', 'names', 'train_args'} of an upstream YOLOv8-seg, YOLOv9c-seg, or YOLOv8, YOLOv5u or
     YOLO11 detection checkpoint."""
     from .spec import SCALES, conv_specs, head_prefix, state_dict_keys
     ck = torch.load(path, map_location="cpu", pickle_module=_PickleModule, weights_only=False)
@@ -187,11 +187,25 @@ def load_upstream_checkpoint(path: str) -> Dict:
               "model.23.proto.cv1.conv.weight" not in sd)
     if is_y11:
         cls0 = sd["model.23.cv3.0.2.weight"]
-    if stem is None or cls0 is None or ("model.22.proto.cv1.conv.weight" not in sd and not is_v5u and not is_y11):
+    # YOLOv8 DetectionModel: the 3x3 stem and C2f blocks of the seg graph (m.0 sits between cv1 and cv2, and there is no cv3) with
+    # a head of box and class branches only.  Told apart explicitly: a head with cv4 / proto is the seg graph (below); a 6x6 stem
+    # with C3 blocks was YOLOv5u (above); the v8 layout with its head elsewhere than model.22 is refused by name.
+    v8_body = (stem is not None and tuple(stem.shape[1:]) == (3, 3, 3) and "model.2.m.0.cv1.conv.weight" in sd and
+               "model.2.cv3.conv.weight" not in sd and "model.9.cv2.conv.weight" in sd and
+               "model.10.m.0.attn.qkv.conv.weight" not in sd and not is_v9c and not is_v5u and not is_y11)
+    is_v8det = (v8_body and cls0 is not None and "model.22.cv2.0.2.weight" in sd and
+                not any(k.startswith(("model.22.cv4.", "model.22.proto.")) for k in sd))
+    if v8_body and cls0 is None:
+        heads = sorted({k.split(".cv3.")[0] for k in sd if ".cv3.0.2.weight" in k})
+        raise ValueError(f"{path}: a YOLOv8 backbone whose head is at {heads or 'no known index'}, not model.22: only the stock "
+                         "yolov8{n,s,m,l,x}.yaml / -seg.yaml layouts are implemented")
+    if stem is None or cls0 is None or ("model.22.proto.cv1.conv.weight" not in sd and not is_v5u and not is_y11 and not is_v8det):
         kind = getattr(type(model), "_upstream", type(model).__name__)
-        raise ValueError(f"{path}: not a YOLOv8-seg graph ({kind}); yolov8{{n,s,m,l,x}}-seg, yolov9c-seg and yolov5{{n,s,m}}u "
-                         "are implemented (SURVEY.md next row N4 lists yolo11)")
+        raise ValueError(f"{path}: not a YOLOv8-seg graph ({kind}); yolov8{{n,s,m,l,x}}-seg, yolov9c-seg, yolov8{{n,s,m,l,x}}, "
+                         "yolov5{n,s,m}u and yolo11{n,s,m} are implemented")
     width = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(int(stem.shape[0]))
+    if is_v8det and width is not None:
+        width = "8" + width
     if is_v5u:
         width = {16: "5n", 32: "5s", 48: "5m"}.get(int(stem.shape[0]))
         if width is None:
@@ -203,7 +217,7 @@ def load_upstream_checkpoint(path: str) -> Dict:
     elif is_v9c:
         from .spec import V9C
         width = V9C
-    if width is None or (width not in SCALES and not is_v9c and not is_v5u and not is_y11):
+    if width is None or (width not in SCALES and not is_v9c and not is_v5u and not is_y11 and not is_v8det):
         raise ValueError(f"{path}: stem width {int(stem.shape[0])} does not belong to a YOLOv8 scale")
     nc = int(cls0.shape[0])
     keys = state_dict_keys(width, nc)

@@ -41,10 +41,11 @@ typedef enum {
 /* Model description: replaces `YOLO("yolov8{n,s,m,l,x}-seg.yaml")` graph construction
  * (yolo_seg_train.py:7).  nc = number of classes (data-seg.yaml:4-5 -> 1).
  * scale selects the graph: 'n','s','m','l','x' = yolov8{scale}-seg; 'c' = yolov9c-seg; ('5' << 8) | 'n','s','m' = YOLOv5u
- * {n,s,m}; ('1' << 8) | 'n','s','m' = YOLO11{n,s,m} (both detection: box-only head, no prototypes or mask coefficients).
+ * {n,s,m}; ('1' << 8) | 'n','s','m' = YOLO11{n,s,m}; ('8' << 8) | 'n','s','m','l','x' = YOLOv8{scale} detect (the yolov8-seg backbone
+ * and neck under Detect at model.22).  The last three are detection graphs: box-only head, no prototypes or mask coefficients.
  * Any other high byte, or a scale letter its family does not build, is M355_ERR_INVALID (checked before the device is). */
 typedef struct {
-  int scale;      /* low byte: 'n','s','m','l','x','c'; high byte: 0 (segmentation families), '5' (YOLOv5u) or '1' (YOLO11) */
+  int scale;      /* low byte: 'n','s','m','l','x','c'; high byte: 0 (segmentation families), '5' (YOLOv5u), '1' (YOLO11) or '8' (YOLOv8 detect) */
   int nc;         /* classes */
   int in_h, in_w; /* network input size, multiples of 32 (640x640 headline) */
   int max_batch;  /* workspace is sized for this many images */
@@ -470,6 +471,16 @@ int m355_box_loss_launch(const float* logits, const float* anchors, const float*
  * scores (rows,nc) = sigmoid.  anchors (A,2) grid units, strides (A). */
 int m355_dfl_decode_launch(const float* raw, int64_t rows, int32_t A, int32_t rw, int32_t nc, const float* anchors, const float* strides,
                            float* boxes, float* scores, void* stream);
+/* Class term of the detection loss with its gradient, one pass (replaces BCEWithLogitsLoss(reduction="none").sum() over (B, A, nc) and
+ * its autograd in v8DetectionLoss).  raw / d_raw (rows, rw) head rows: the class logits x are read in place from columns
+ * [64, 64 + nc) and d_raw's same columns get (sigmoid(x) - t) * s; every other column of d_raw is left alone.  targets (rows, nc)
+ * dense.  s = *scale, a DEVICE scalar (gain * batch * loss scale / target sum: no host synchronisation).  out: DEVICE buffer of
+ * m355_cls_bce_workspace_floats() floats; out[0] = sum over all elements of max(x, 0) - x t + log1p(exp(-|x|)), the per-block
+ * partial sums sit behind it and a one-block kernel adds them in block order.  The grid depends on rows * nc only; no float atomics:
+ * bitwise reproducible.  16-byte accesses of the targets always, of the rows when rw and nc are multiples of 4. */
+size_t m355_cls_bce_workspace_floats(void);
+int m355_cls_bce_launch(const float* raw, int32_t rw, const float* targets, int64_t rows, int32_t nc, const float* scale, float* d_raw,
+                        float* out, void* stream);
 
 /* Optimizer step over a flat fp32 parameter buffer (replaces torch.optim.AdamW / SGD + ModelEMA.update reached from
  * /root/reference/BscanBased/yolo_seg_train.py:12).  group[i]: 0 decayed weights, 1 norm weights, 2 biases (lr_bias).

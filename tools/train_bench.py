@@ -1,5 +1,6 @@
 """Step-time breakdown of the training path on synthetic device-resident batches (BASELINE config 3 shape:
-YOLOv8s-seg, batch 64).  Usage: python tools/train_bench.py [scale] [batch] [imgsz] [steps]"""
+YOLOv8s-seg, batch 64).  Usage: python tools/train_bench.py [scale] [batch] [imgsz] [steps]
+scale "8n" .. "8x": the YOLOv8 detect graph of that letter with the detection criterion (no masks, no prototype gradient)."""
 import ctypes as C
 import sys
 import time
@@ -10,8 +11,8 @@ import torch
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from defectdetection_viaobjectdetection_amd._capi import check, lib  # noqa: E402
-from defectdetection_viaobjectdetection_amd.loss import SegCriterion  # noqa: E402
-from defectdetection_viaobjectdetection_amd.spec import init_state_dict  # noqa: E402
+from defectdetection_viaobjectdetection_amd.loss import DetCriterion, SegCriterion  # noqa: E402
+from defectdetection_viaobjectdetection_amd.spec import init_state_dict, is_detect  # noqa: E402
 from defectdetection_viaobjectdetection_amd.train_engine import TrainEngine  # noqa: E402
 
 scale = sys.argv[1] if len(sys.argv) > 1 else "s"
@@ -31,10 +32,13 @@ masks[:, 40:80, 40:80] = 1
 masks[:, 60:70, 60:70] = 2
 # labels as a loader hands them over: the small per-instance tensors on the host, the mask maps already on the device
 batch = {"batch_idx": bidx.cpu(), "cls": torch.zeros(n), "bboxes": boxes.cpu(), "masks": masks}
+detect = is_detect(scale)
+if detect:
+    del batch["masks"]
 st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
 m1 = torch.zeros(eng.n_train, device=dev); m2 = torch.zeros(eng.n_train, device=dev); ema = eng.flat_params.clone()
 tim = {k: 0.0 for k in ("fwd", "loss", "bwd", "opt", "repack")}
-criterion = SegCriterion(1, (S, S))
+criterion = (DetCriterion if detect else SegCriterion)(1, (S, S))
 
 
 def tick():
@@ -66,5 +70,5 @@ for it in range(steps + 2):
     for j, k in enumerate(tim):
         tim[k] += ev[j].elapsed_time(ev[j + 1]) * 1e-3
 total = tick() - t_all
-print(f"yolov8{scale}-seg train b{B} {S}x{S}: {total / steps * 1e3:.1f} ms/step = {B * steps / total:.1f} img/s; loss {loss:.3f}")
+print(f"{'yolov8' + scale[1:] + ' (detect)' if detect else 'yolov8' + scale + '-seg'} train b{B} {S}x{S}: {total / steps * 1e3:.1f} ms/step = {B * steps / total:.1f} img/s; loss {loss:.3f}")
 print("  " + "  ".join(f"{k} {v / steps * 1e3:.1f} ms" for k, v in tim.items()))

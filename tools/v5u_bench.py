@@ -1,4 +1,4 @@
-"""YOLOv5u detection throughput and its per-launch split (DESIGN.md section on YOLOv5u).
+"""Detection throughput and its per-launch split (DESIGN.md sections on YOLOv5u and on YOLOv8 detect; any detect scale tag: 5s, 8n, ...).
   python tools/v5u_bench.py [scale=5s] [batch=32] [imgsz=640] [steps=30] [out.json]
       images/s of forward + NMS (keep_raw off: the predict path), then the op table (HIP events per launch)
   python tools/v5u_bench.py --stem-only [batch=32] [imgsz=640] [C0=32] [reps=20]
@@ -55,7 +55,7 @@ def main(argv):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     ips = B / dt
-    print(f"yolov5{scale[1]}u b={B} {S}x{S}: {dt * 1e3:.3f} ms per batch (forward + NMS), {ips:.0f} images/s, "
+    print(f"{'yolov5' + scale[1] + 'u' if scale[0] == '5' else 'yolov8' + scale[1] if scale[0] == '8' else scale} b={B} {S}x{S}: {dt * 1e3:.3f} ms per batch (forward + NMS), {ips:.0f} images/s, "
           f"{eng.flops_per_image / 1e9:.2f} GFLOP per image")
     eng.set_profiling(True)
     for _ in range(10):
