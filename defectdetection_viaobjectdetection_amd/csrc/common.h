@@ -120,6 +120,13 @@ int launch_msda(const float* value, const float* loc, const float* attn, float* 
                 const float* ref = nullptr, float offset_scale = 0.f);
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
                         float reg_scale, int clamp01, hipStream_t s);
+// Hungarian matcher of the D-FINE loss (dfine_match.hip): cost matrix + assignment, one block per image.  The caller has
+// validated every argument; `work` holds dfine_match_workspace_bytes(B, Q, nmax) bytes (0: the matrices fit in LDS).
+size_t dfine_match_workspace_bytes(int B, int Q, int nmax);
+int launch_dfine_match(const float* logits, const float* boxes, int B, int Q, int C, const long long* labels, const float* tboxes,
+                       const int* d_offsets, int T, int nmax, float class_cost, float bbox_cost, float giou_cost, float alpha,
+                       float gamma, int focal, void* work, float* cost_out, long long* rows, long long* cols, int kmax, int* flags,
+                       hipStream_t s);
 // their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
 // grad_value and the per-head partials of grad_ref.  -1 = refused before any launch, -3 = workspace missing / too small.
 size_t msda_backward_workspace_bytes(int B, int Q, int H, int P);

@@ -864,6 +864,37 @@ int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, c
   if (rc == -1) return set_err(M355_ERR_INVALID, "dfine_decode_backward: null pointer, n < 0, fewer than 2 bins or reg_scale == 0");
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_decode_backward launch failed: " + std::to_string(rc));
 }
+size_t m355_dfine_match_workspace_bytes(int32_t B, int32_t Q, int32_t max_targets) {
+  return m355::dfine_match_workspace_bytes(B, Q, max_targets);
+}
+int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                     const int64_t* d_target_labels, const float* d_target_boxes, const int32_t* d_target_offsets,
+                     const int32_t* h_target_counts, float class_cost, float bbox_cost, float giou_cost, float alpha, float gamma,
+                     int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
+                     int32_t kmax, int32_t* d_flags, void* stream) {
+  // every argument before any HIP call
+  if (!d_logits || !d_pred_boxes || !d_target_labels || !d_target_boxes || !d_target_offsets || !h_target_counts || !d_rows ||
+      !d_cols || !d_flags)
+    return set_err(M355_ERR_INVALID, "dfine_match: null pointer");
+  if (B < 1 || B > 65535 || Q < 1 || Q > 2048 || C < 1) return set_err(M355_ERR_INVALID, "dfine_match: B >= 1, Q in [1, 2048], C >= 1");
+  int nmax = 0;
+  long total = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = h_target_counts[b];
+    if (n < 0 || n > 512) return set_err(M355_ERR_INVALID, "dfine_match: every target count must be in [0, 512]");
+    nmax = n > nmax ? n : nmax;
+    total += n;
+  }
+  if (kmax < (Q < nmax ? Q : nmax)) return set_err(M355_ERR_INVALID, "dfine_match: kmax is smaller than min(Q, largest target count)");
+  const size_t need = m355::dfine_match_workspace_bytes(B, Q, nmax);
+  if (need > 0 && (!d_work || work_bytes < 0 || (size_t)work_bytes < need))
+    return set_err(M355_ERR_INVALID, "dfine_match: workspace missing or smaller than m355_dfine_match_workspace_bytes");
+  const int rc = m355::launch_dfine_match(d_logits, d_pred_boxes, B, Q, C, (const long long*)d_target_labels, d_target_boxes,
+                                          d_target_offsets, (int)total, nmax, class_cost, bbox_cost, giou_cost, alpha, gamma,
+                                          use_focal_loss != 0, d_work, d_cost, (long long*)d_rows, (long long*)d_cols, kmax, d_flags,
+                                          (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_match launch failed: " + std::to_string(rc));
+}
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");

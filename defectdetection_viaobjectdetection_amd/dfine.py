@@ -9,6 +9,9 @@ HIP backward entries, bitwise-reproducible gradients); with nothing to different
 A maintainer binds them with
 ``modeling_d_fine.multi_scale_deformable_attention_v2 = dfine.multi_scale_deformable_attention_v2`` (the attention
 module keeps a reference in ``self.ms_deformable_attn_core``, :244) — see INTEGRATION.md.
+
+``hungarian_match`` / ``matcher_forward`` are the loss's Hungarian matcher (``RTDetrHungarianMatcher.forward``,
+transformers/loss/loss_rt_detr.py:68-120) in one launch: cost matrix and assignment on the device, no trip to the host.
 """
 from __future__ import annotations
 
@@ -18,6 +21,8 @@ from typing import List, Sequence
 import torch
 
 from ._capi import check, lib
+
+_raise_on_error = check   # for hungarian_match, whose keyword `check` is upstream-facing
 
 
 def _stream() -> C.c_void_p:
@@ -267,3 +272,136 @@ def distance2bbox(points: torch.Tensor, distance: torch.Tensor, reg_scale: float
     x1 = points[..., 0] + (0.5 * reg_scale + distance[..., 2]) * (points[..., 2] / reg_scale)
     y1 = points[..., 1] + (0.5 * reg_scale + distance[..., 3]) * (points[..., 3] / reg_scale)
     return torch.stack([(x0 + x1) / 2, (y0 + y1) / 2, x1 - x0, y1 - y0], -1)
+
+
+# ---- Hungarian matcher of the loss (RTDetrHungarianMatcher.forward, transformers/loss/loss_rt_detr.py:68-120) ----------------
+MATCH_MAX_QUERIES = 2048     # the limits of m355_dfine_match; anything outside them takes the torch + scipy expression
+MATCH_MAX_TARGETS = 512
+INVALID_COST_MESSAGE = "matrix contains invalid numeric entries"   # scipy.optimize.linear_sum_assignment's ValueError
+
+
+def hungarian_match(logits: torch.Tensor, pred_boxes: torch.Tensor, targets: Sequence[dict], *, class_cost: float = 2.0,
+                    bbox_cost: float = 5.0, giou_cost: float = 2.0, alpha: float = 0.25, gamma: float = 2.0,
+                    use_focal_loss: bool = True, check: bool = True, return_cost: bool = False):
+    """The matching of RTDetrHungarianMatcher.forward in ONE kernel launch, without the cost matrix's trip to the host.
+
+    logits (B, Q, C), pred_boxes (B, Q, 4) cx, cy, w, h; targets: upstream's list of {"class_labels": (n_b,), "boxes": (n_b, 4)}.
+    Returns a list of B tuples (query indices, target indices) of int64 DEVICE tensors, min(Q, n_b) long, ordered by ascending
+    query index as scipy's linear_sum_assignment orders them; they are views of two (B, Kmax) buffers.  Sizes come from the
+    tensor shapes on the host.  The result is scipy's on the same fp32 costs except where two assignments tie exactly (the
+    kernel's search takes the lowest index; scipy's order is its own).
+
+    check=True reads back the B flags (the one synchronisation of the call) and raises ValueError("matrix contains invalid
+    numeric entries"), scipy's exception, if an image has a NaN or infinite cost.  Deviation: a +inf entry raises too; scipy
+    tolerates +inf.  Upstream's generalized_box_iou additionally raises for boxes with negative width or height; here such a
+    box is matched by its (finite) cost.
+    check=False performs no device-to-host transfer and no synchronisation.  A tensor's length cannot follow a flag that is
+    only on the device, so an image with a non-finite cost then keeps its min(Q, n_b) entries, all -1 (no match); the caller
+    promises finite inputs or looks at the flags (return_cost=True) at a synchronisation point of its own.
+
+    return_cost=True returns (indices, costs, flags): costs a list of B (Q, n_b) fp32 views of the matrices the kernel solved,
+    flags the (B,) int32 device tensor (0 solved, 1 non-finite cost).
+    Shapes outside the kernel's limits (Q > 2048 or an image with more than 512 targets) take upstream's torch + scipy
+    expression, results moved to the device: the semantics do not change."""
+    B, Q, Cn = logits.shape
+    sizes = [int(t["boxes"].shape[0]) for t in targets]
+    if len(sizes) != B or tuple(pred_boxes.shape) != (B, Q, 4):
+        raise ValueError("logits (B, Q, C), pred_boxes (B, Q, 4) and one target dict per image are expected")
+    costs = (class_cost, bbox_cost, giou_cost, alpha, gamma, use_focal_loss)
+    if Q > MATCH_MAX_QUERIES or max(sizes, default=0) > MATCH_MAX_TARGETS or Q < 1 or Cn < 1 or B > 65535:
+        return _match_torch_scipy(logits, pred_boxes, targets, sizes, costs, return_cost)
+    lg, pb = _f32c(logits.detach(), "logits"), _f32c(pred_boxes.detach(), "pred_boxes")
+    dev = lg.device
+    nmax, total = max(sizes, default=0), sum(sizes)
+    kmax = min(Q, nmax)
+    ks = [min(Q, n) for n in sizes]
+    rows = torch.empty((B, kmax), dtype=torch.int64, device=dev)
+    cols = torch.empty((B, kmax), dtype=torch.int64, device=dev)
+    cost = torch.empty((B, Q, nmax), dtype=torch.float32, device=dev) if return_cost else None
+    if total == 0:   # nothing to match anywhere: no launch
+        flags = torch.zeros(B, dtype=torch.int32, device=dev) if return_cost else None
+    else:
+        if B == 1:
+            labels, tboxes = targets[0]["class_labels"], targets[0]["boxes"]
+        else:
+            labels, tboxes = torch.cat([t["class_labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        tboxes = _f32c(tboxes.detach(), "target boxes")
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        # pinned + non_blocking: the copy is queued on the stream, the host does not wait for it
+        d_offs = torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        h_counts = (C.c_int32 * B)(*sizes)
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        wbytes = int(lib.m355_dfine_match_workspace_bytes(B, Q, nmax))
+        work = torch.empty(wbytes, dtype=torch.uint8, device=dev) if wbytes else None
+        # (the keyword `check` shadows _capi.check in this function)
+        _raise_on_error(lib.m355_dfine_match(_ptr(lg), _ptr(pb), B, Q, Cn, _ptr(labels), _ptr(tboxes), _ptr(d_offs), h_counts,
+                                             float(class_cost), float(bbox_cost), float(giou_cost), float(alpha), float(gamma),
+                                             int(bool(use_focal_loss)), _ptr(work), wbytes, _ptr(cost), _ptr(rows), _ptr(cols),
+                                             kmax, _ptr(flags), _stream()))
+        if check and flags.cpu().any():   # the call's one read-back
+            raise ValueError(INVALID_COST_MESSAGE)
+    out = [(rows[b, :k], cols[b, :k]) for b, k in enumerate(ks)]
+    if return_cost:
+        return out, [cost[b, :, :n] for b, n in enumerate(sizes)], flags
+    return out
+
+
+def match_cost_torch(logits, pred_boxes, labels, tboxes, class_cost=2.0, bbox_cost=5.0, giou_cost=2.0, alpha=0.25, gamma=2.0,
+                     use_focal_loss=True) -> torch.Tensor:
+    """The cost expression of loss_rt_detr.py:99-114 in torch ops, in upstream's order, on whatever device and dtype the
+    tensors have: logits (N, C), pred_boxes (N, 4), labels (T), tboxes (T, 4) -> (N, T).  What hungarian_match falls back to
+    outside the kernel's limits, and what the tests measure the kernel's fp32 error against."""
+    if use_focal_loss:
+        p = torch.sigmoid(logits)[:, labels]
+        neg = (1 - alpha) * (p ** gamma) * (-(1 - p + 1e-8).log())
+        pos = alpha * ((1 - p) ** gamma) * (-(p + 1e-8).log())
+        cls = pos - neg
+    else:
+        cls = -logits.softmax(-1)[:, labels]
+    l1 = torch.cdist(pred_boxes, tboxes, p=1)
+
+    def corners(b):
+        cx, cy, w, h = b.unbind(-1)
+        return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
+
+    a, b = corners(pred_boxes), corners(tboxes)
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    wh = (torch.min(a[:, None, 2:], b[:, 2:]) - torch.max(a[:, None, :2], b[:, :2])).clamp(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    union = area_a[:, None] + area_b - inter
+    hull = (torch.max(a[:, None, 2:], b[:, 2:]) - torch.min(a[:, None, :2], b[:, :2])).clamp(min=0)
+    area = hull[:, :, 0] * hull[:, :, 1]
+    giou = inter / union - (area - union) / area
+    return bbox_cost * l1 + class_cost * cls + giou_cost * (-giou)
+
+
+def _match_torch_scipy(logits, pred_boxes, targets, sizes, costs, return_cost):
+    """hungarian_match for shapes the kernel does not take: per-image torch cost + scipy on the host"""
+    from scipy.optimize import linear_sum_assignment
+    class_cost, bbox_cost, giou_cost, alpha, gamma, use_focal_loss = costs
+    out, mats = [], []
+    for b, t in enumerate(targets):
+        labels = t["class_labels"].to(logits.device)
+        m = match_cost_torch(logits[b].detach().float(), pred_boxes[b].detach().float(), labels, t["boxes"].detach().float(),
+                             class_cost, bbox_cost, giou_cost, alpha, gamma, use_focal_loss)
+        i, j = linear_sum_assignment(m.cpu())   # raises ValueError("matrix contains invalid numeric entries") itself
+        out.append((torch.as_tensor(i, dtype=torch.int64, device=logits.device),
+                    torch.as_tensor(j, dtype=torch.int64, device=logits.device)))
+        mats.append(m)
+    if return_cost:
+        return out, mats, torch.zeros(len(sizes), dtype=torch.int32, device=logits.device)
+    return out
+
+
+@torch.no_grad()
+def matcher_forward(self, outputs, targets):
+    """Drop-in for RTDetrHungarianMatcher.forward (`RTDetrHungarianMatcher.forward = dfine.matcher_forward`, INTEGRATION.md):
+    the module's own costs, one launch, index tensors on the device of the logits.  As upstream (scipy) it raises ValueError
+    on a non-finite cost, which costs one read-back of B flags per call (hungarian_match(check=False) has none)."""
+    return hungarian_match(outputs["logits"], outputs["pred_boxes"], targets, class_cost=self.class_cost,
+                           bbox_cost=self.bbox_cost, giou_cost=self.giou_cost, alpha=self.alpha, gamma=self.gamma,
+                           use_focal_loss=self.use_focal_loss, check=True)

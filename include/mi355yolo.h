@@ -628,6 +628,34 @@ int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, c
                                float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
                                int32_t clamp01, void* stream);
 
+/* ---- Hungarian matcher of the D-FINE loss ------------------------------------------------------------------------------
+ * m355_dfine_match = RTDetrHungarianMatcher.forward (transformers/loss/loss_rt_detr.py:68-120), which the reference's D-FINE
+ * trainers reach through `self.dfine.loss_function(...)` once per frame: the (Q x n_b) cost matrix of every image
+ *   bbox_cost * L1(cxcywh) + class_cost * class_term + giou_cost * (-GIoU(xyxy))          (fp32, upstream's order)
+ *   class_term: use_focal_loss != 0: alpha (1-p)^gamma (-log(p + 1e-8)) - (1-alpha) p^gamma (-log(1 - p + 1e-8)), p = sigmoid(logit)
+ *               use_focal_loss == 0: -softmax(logits)[target class]
+ * and its optimal assignment (shortest augmenting paths as in scipy.optimize.linear_sum_assignment, duals in fp64), ONE launch,
+ * one block per image, asynchronous on `stream`, no host round trip.  All buffers are the caller's.
+ *   logits (B, Q, C) fp32; pred_boxes (B, Q, 4) fp32 cx, cy, w, h
+ *   target_labels (T) int64 and target_boxes (T, 4) fp32: the targets of all images, concatenated in image order
+ *   d_target_offsets (B + 1) int32 DEVICE: image b owns targets [offsets[b], offsets[b + 1]);
+ *   h_target_counts (B) int32 HOST: the same counts n_b, what the host validates and sizes buffers by.  A device offset that
+ *     disagrees with them is never followed out of bounds: that image gets flag 2 and no match
+ *   work: m355_dfine_match_workspace_bytes(B, Q, max n_b) bytes (may be NULL when that is 0: the matrices fit in LDS)
+ *   d_cost: NULL, or (B, Q, max n_b) fp32; entry [b][q][t] for t < n_b is written, the rest is left alone
+ *   rows, cols (B, kmax) int64, kmax >= min(Q, max n_b): the first K_b = min(Q, n_b) entries of image b are the matched query /
+ *     target (index within the image) pairs by ascending query index, scipy's output order; the entries behind them are -1
+ *   flags (B) int32: 0 solved; 1 some cost of the image is NaN or +-inf (a label outside [0, C) counts): the solve is skipped and
+ *     all kmax entries are -1; the other images are unaffected
+ * Limits, checked on the host before any HIP call (M355_ERR_INVALID): no NULL pointer, B >= 1, 1 <= Q <= 2048, C >= 1,
+ * 0 <= n_b <= 512, kmax and work_bytes large enough.  No atomics: bitwise reproducible; an exact tie goes to the lowest index. */
+size_t m355_dfine_match_workspace_bytes(int32_t B, int32_t Q, int32_t max_targets);
+int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                     const int64_t* d_target_labels, const float* d_target_boxes, const int32_t* d_target_offsets,
+                     const int32_t* h_target_counts, float class_cost, float bbox_cost, float giou_cost, float alpha, float gamma,
+                     int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
+                     int32_t kmax, int32_t* d_flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
