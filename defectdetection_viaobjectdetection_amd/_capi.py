@@ -167,6 +167,13 @@ SIGNATURES = {
     "m355_dfine_match_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "m355_dfine_match": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
+    "m355_dfine_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "m355_dfine_loss_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                          C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float,
+                                          _P, C.c_int64, _P, _P]),
+    "m355_dfine_loss_backward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                           C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float,
+                                           _P, _P, _P, _P, _P]),
     "m355_repack_launch": (C.c_int, [_P, _P, C.c_int32, _P]),
     "m355_sppf_pool_bwd_launch": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

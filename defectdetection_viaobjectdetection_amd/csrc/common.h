@@ -127,6 +127,35 @@ int launch_dfine_match(const float* logits, const float* boxes, int B, int Q, in
                        const int* d_offsets, int T, int nmax, float class_cost, float bbox_cost, float giou_cost, float alpha,
                        float gamma, int focal, void* work, float* cost_out, long long* rows, long long* cols, int kmax, int* flags,
                        hipStream_t s);
+// Loss terms of one D-FINE decoder output (dfine_loss.hip): loss_vfl, loss_bbox, loss_giou and, with the local group
+// (pred_corners != nullptr), loss_fgl and loss_ddf.  The caller has validated every argument.
+struct DfineLossArgs {
+  const float* logits;            // (B, Q, C)
+  const float* boxes;             // (B, Q, 4) cx, cy, w, h
+  const long long* match_q;       // (M) query index of each match entry, the entries of image b contiguous
+  const long long* match_t;       // (M) target index within the image
+  const int* offsets;             // device, 2 (B + 1): first entry of each image, then first target row of each image
+  const long long* labels;        // (T)
+  const float* tboxes;            // (T, 4)
+  int B, Q, C, M, T;
+  float num_boxes, alpha, gamma;
+  const float* pred_corners;      // (B, Q, 4 * nb1) or nullptr: no local group
+  const float* ref_points;        // (B, Q, 4)
+  const float* teacher_corners;   // (B, Q, 4 * nb1)
+  const float* teacher_logits;    // (B, Q, C)
+  const float* project;           // (nb1) W(n)
+  int nb1;
+  float reg_scale, temperature;
+  float* partials;                // dfine_loss_workspace_bytes(B, Q)
+  float* out;                     // (8): the five terms, two DDF gradient coefficients, 0
+  const float* grad_terms;        // backward: (5) upstream gradients, device
+  float* grad_logits;             // backward: any of the three may be nullptr
+  float* grad_boxes;
+  float* grad_corners;
+};
+size_t dfine_loss_workspace_bytes(int B, int Q);
+int launch_dfine_loss_forward(const DfineLossArgs& a, hipStream_t s);    // two launches
+int launch_dfine_loss_backward(const DfineLossArgs& a, hipStream_t s);   // one launch
 // their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
 // grad_value and the per-head partials of grad_ref.  -1 = refused before any launch, -3 = workspace missing / too small.
 size_t msda_backward_workspace_bytes(int B, int Q, int H, int P);

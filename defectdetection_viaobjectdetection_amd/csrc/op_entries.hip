@@ -895,6 +895,72 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
                                           (hipStream_t)stream);
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_match launch failed: " + std::to_string(rc));
 }
+size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q) { return m355::dfine_loss_workspace_bytes(B, Q); }
+namespace {
+// the argument checks m355_dfine_loss_forward and _backward share; nullptr = accepted, else the message
+const char* dfine_loss_check(const m355::DfineLossArgs& a) {
+  if (a.B < 1 || a.Q < 1 || a.C < 1 || (int64_t)a.B * a.Q > INT32_MAX) return "B, Q, C >= 1 and B * Q < 2^31";
+  if (a.M < 0 || a.T < 0) return "M >= 0 and T >= 0";
+  if (!a.logits || !a.boxes || !a.out || !(a.num_boxes > 0.f)) return "null pointer (logits, pred_boxes, out) or num_boxes <= 0";
+  if (a.M > 0 && a.T > 0 && (!a.match_q || !a.match_t || !a.offsets || !a.labels || !a.tboxes))
+    return "null pointer in the match list or the targets";
+  const int local = (a.pred_corners != nullptr) + (a.ref_points != nullptr) + (a.teacher_corners != nullptr) +
+                    (a.teacher_logits != nullptr) + (a.project != nullptr);
+  if (local != 0 && local != 5) return "the local group (pred_corners, ref_points, teacher_corners, teacher_logits, project) is all or none";
+  if (local && (a.nb1 < 2 || a.nb1 > 64 || a.reg_scale == 0.f || !(a.temperature > 0.f)))
+    return "2 <= bins + 1 <= 64, reg_scale != 0, temperature > 0";
+  return nullptr;
+}
+m355::DfineLossArgs dfine_loss_args(const float* logits, const float* boxes, int B, int Q, int C, const int64_t* mq, const int64_t* mt,
+                                    int M, const int32_t* offsets, const int64_t* labels, const float* tboxes, int T, float num_boxes,
+                                    float alpha, float gamma, const float* corners, const float* ref, const float* tcorners,
+                                    const float* tlogits, const float* project, int nb1, float reg_scale, float temperature) {
+  m355::DfineLossArgs a{};
+  a.logits = logits; a.boxes = boxes; a.match_q = (const long long*)mq; a.match_t = (const long long*)mt; a.offsets = offsets;
+  a.labels = (const long long*)labels; a.tboxes = tboxes; a.B = B; a.Q = Q; a.C = C; a.M = M; a.T = T;
+  a.num_boxes = num_boxes; a.alpha = alpha; a.gamma = gamma;
+  a.pred_corners = corners; a.ref_points = ref; a.teacher_corners = tcorners; a.teacher_logits = tlogits; a.project = project;
+  a.nb1 = nb1; a.reg_scale = reg_scale; a.temperature = temperature;
+  return a;
+}
+}  // namespace
+int m355_dfine_loss_forward(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                            const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                            const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                            float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                            const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                            float temperature, void* d_work, int64_t work_bytes, float* d_out, void* stream) {
+  m355::DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
+                                          d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
+                                          d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
+  a.out = d_out;
+  if (const char* why = dfine_loss_check(a)) return set_err(M355_ERR_INVALID, std::string("dfine_loss_forward: ") + why);
+  if (!d_work || work_bytes < 0 || (size_t)work_bytes < m355::dfine_loss_workspace_bytes(B, Q))
+    return set_err(M355_ERR_INVALID, "dfine_loss_forward: workspace missing or smaller than m355_dfine_loss_workspace_bytes");
+  a.partials = (float*)d_work;
+  const int rc = m355::launch_dfine_loss_forward(a, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_loss_forward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q,
+                             int32_t C, const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                             const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                             float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                             const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                             float temperature, const float* d_saved, float* d_grad_logits, float* d_grad_pred_boxes,
+                             float* d_grad_pred_corners, void* stream) {
+  m355::DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
+                                          d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
+                                          d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
+  a.out = const_cast<float*>(d_saved);   // read only here: out[5], out[6] of the forward
+  if (const char* why = dfine_loss_check(a)) return set_err(M355_ERR_INVALID, std::string("dfine_loss_backward: ") + why);
+  if (!d_grad_terms) return set_err(M355_ERR_INVALID, "dfine_loss_backward: null pointer (grad_terms)");
+  if (d_grad_pred_corners && !d_pred_corners)
+    return set_err(M355_ERR_INVALID, "dfine_loss_backward: grad_pred_corners without the local group");
+  a.grad_terms = d_grad_terms; a.grad_logits = d_grad_logits; a.grad_boxes = d_grad_pred_boxes; a.grad_corners = d_grad_pred_corners;
+  if (!d_grad_logits && !d_grad_pred_boxes && !d_grad_pred_corners) return M355_OK;   // nothing asked for
+  const int rc = m355::launch_dfine_loss_backward(a, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_loss_backward launch failed: " + std::to_string(rc));
+}
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");

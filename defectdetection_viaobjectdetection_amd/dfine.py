@@ -12,6 +12,10 @@ module keeps a reference in ``self.ms_deformable_attn_core``, :244) — see INTE
 
 ``hungarian_match`` / ``matcher_forward`` are the loss's Hungarian matcher (``RTDetrHungarianMatcher.forward``,
 transformers/loss/loss_rt_detr.py:68-120) in one launch: cost matrix and assignment on the device, no trip to the host.
+
+``detection_loss`` / ``criterion_forward`` are what those indices feed: loss_vfl, loss_bbox, loss_giou, loss_fgl and loss_ddf of a
+decoder output (``RTDetrLoss.loss_labels_vfl`` / ``loss_boxes``, ``DFineLoss.loss_local``) and their gradients as fused kernels,
+two launches forward and one backward per output, without a synchronisation; on CPU tensors the same expressions in torch ops.
 """
 from __future__ import annotations
 
@@ -405,3 +409,274 @@ def matcher_forward(self, outputs, targets):
     return hungarian_match(outputs["logits"], outputs["pred_boxes"], targets, class_cost=self.class_cost,
                            bbox_cost=self.bbox_cost, giou_cost=self.giou_cost, alpha=self.alpha, gamma=self.gamma,
                            use_focal_loss=self.use_focal_loss, check=True)
+
+
+# ---- loss terms of one decoder output (RTDetrLoss.loss_labels_vfl / loss_boxes, DFineLoss.loss_local) ---------------------------
+LOSS_MAX_BINS1 = 64          # the limit of m355_dfine_loss_forward: one lane per bin
+LOSS_KEYS = ("loss_vfl", "loss_bbox", "loss_giou", "loss_fgl", "loss_ddf")
+loss_calls = {"kernel": 0, "torch": 0}   # how many detection_loss calls took which path (tests and tools read it)
+
+
+def _xyxy(b: torch.Tensor) -> torch.Tensor:
+    cx, cy, w, h = b.unbind(-1)
+    return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
+
+
+def _pair_iou(a: torch.Tensor, b: torch.Tensor):
+    """box_iou of row i of `a` with row i of `b` (xyxy): the diagonal upstream takes from the full matrix"""
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    wh = (torch.min(a[:, 2:], b[:, 2:]) - torch.max(a[:, :2], b[:, :2])).clamp(min=0)
+    inter = wh[:, 0] * wh[:, 1]
+    union = area_a + area_b - inter
+    return inter / union, union
+
+
+def _pair_giou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    iou, union = _pair_iou(a, b)
+    wh = (torch.max(a[:, 2:], b[:, 2:]) - torch.min(a[:, :2], b[:, :2])).clamp(min=0)
+    area = wh[:, 0] * wh[:, 1]
+    return iou - (area - union) / area
+
+
+def _translate_gt(gt: torch.Tensor, project: torch.Tensor):
+    """translate_gt (loss_d_fine.py:74-134) followed by bbox2distance's clamp, with torch.where in place of the boolean-mask
+    assignments (which synchronise): left bin (int64), weight_right, weight_left"""
+    R = project.numel() - 1
+    idx = ((project.unsqueeze(0) - gt.unsqueeze(1)) <= 0).sum(1) - 1
+    ci = idx.clamp(0, R - 1)
+    left_diffs, right_diffs = (gt - project[ci]).abs(), (project[ci + 1] - gt).abs()
+    weight_right = left_diffs / (left_diffs + right_diffs)
+    neg, pos = idx < 0, idx >= R
+    one, zero = torch.ones_like(gt), torch.zeros_like(gt)
+    weight_right = torch.where(neg, zero, torch.where(pos, one, weight_right))
+    weight_left = torch.where(neg, one, torch.where(pos, zero, 1.0 - weight_right))
+    index = torch.where(neg, zero, torch.where(pos, torch.full_like(gt, R - 0.1), idx.to(gt.dtype)))
+    return index.clamp(min=0, max=R - 0.1).long(), weight_right, weight_left
+
+
+def detection_loss_torch(logits, pred_boxes, targets, indices, num_boxes, *, alpha, gamma, pred_corners=None, ref_points=None,
+                         teacher_corners=None, teacher_logits=None, project=None, reg_scale=None, temperature=5.0) -> dict:
+    """The terms of `detection_loss` in torch ops under autograd, upstream's expressions, on whatever device and dtype the
+    tensors have: what detection_loss evaluates on CPU tensors and beyond the kernel's limits, and the fp32 baseline of the
+    tests.  Unlike upstream it does not synchronise; every index entry must be valid here."""
+    B, Q, Cn = logits.shape
+    dtype = logits.dtype
+    batch_idx = torch.cat([torch.full_like(src, i) for i, (src, _) in enumerate(indices)]).to(logits.device)
+    src_idx = torch.cat([src for src, _ in indices]).to(logits.device)
+    tgt_boxes = torch.cat([t["boxes"][j] for t, (_, j) in zip(targets, indices)], 0).to(device=logits.device, dtype=pred_boxes.dtype)
+    tgt_labels = torch.cat([t["class_labels"][j] for t, (_, j) in zip(targets, indices)]).to(logits.device)
+    idx = (batch_idx, src_idx)
+    src_boxes = pred_boxes[idx]
+    ious, _ = _pair_iou(_xyxy(src_boxes.detach()), _xyxy(tgt_boxes))
+    # loss_labels_vfl
+    target_classes = torch.full((B, Q), Cn, dtype=torch.int64, device=logits.device)
+    target_classes[idx] = tgt_labels
+    target = torch.nn.functional.one_hot(target_classes, num_classes=Cn + 1)[..., :-1]
+    score = torch.zeros((B, Q), dtype=dtype, device=logits.device)
+    score[idx] = ious.to(dtype)
+    target_score = score.unsqueeze(-1) * target
+    weight = (alpha * torch.sigmoid(logits.detach()).pow(gamma) * (1 - target) + target_score).to(dtype)
+    vfl = torch.nn.functional.binary_cross_entropy_with_logits(logits, target_score, weight=weight, reduction="none")
+    out = {"loss_vfl": vfl.mean(1).sum() * Q / num_boxes}
+    # loss_boxes
+    out["loss_bbox"] = torch.nn.functional.l1_loss(src_boxes, tgt_boxes, reduction="none").sum() / num_boxes
+    out["loss_giou"] = (1 - _pair_giou(_xyxy(src_boxes), _xyxy(tgt_boxes))).sum() / num_boxes
+    if pred_corners is None:
+        return out
+    # loss_local: FGL
+    nb1 = project.numel()
+    project = project.detach().to(device=logits.device, dtype=pred_corners.dtype)
+    rs = abs(float(reg_scale))
+    ref = ref_points[idx].detach().to(pred_corners.dtype)
+    box = _xyxy(tgt_boxes).to(pred_corners.dtype)
+    four = torch.stack([(ref[:, 0] - box[:, 0]) / (ref[:, 2] / rs + 1e-16) - 0.5 * rs,
+                        (ref[:, 1] - box[:, 1]) / (ref[:, 3] / rs + 1e-16) - 0.5 * rs,
+                        (box[:, 2] - ref[:, 0]) / (ref[:, 2] / rs + 1e-16) - 0.5 * rs,
+                        (box[:, 3] - ref[:, 1]) / (ref[:, 3] / rs + 1e-16) - 0.5 * rs], -1).reshape(-1)
+    left, weight_right, weight_left = _translate_gt(four, project)
+    rows = pred_corners[idx].reshape(-1, nb1)
+    ce = torch.nn.functional.cross_entropy
+    fgl = ce(rows, left, reduction="none") * weight_left + ce(rows, left + 1, reduction="none") * weight_right
+    out["loss_fgl"] = (fgl * ious.to(rows.dtype).unsqueeze(-1).repeat(1, 4).reshape(-1)).sum() / num_boxes
+    # loss_local: DDF.  log q from the same log_softmax as log p: a teacher equal to the prediction gives exactly 0
+    T = float(temperature)
+    w_local = teacher_logits.detach().sigmoid().max(dim=-1)[0].to(pred_corners.dtype)
+    mask = torch.zeros((B, Q), dtype=torch.bool, device=logits.device)
+    mask[idx] = True
+    w_local = w_local.clone()
+    w_local[idx] = ious.to(w_local.dtype)
+    log_p = torch.log_softmax(pred_corners.reshape(B, Q, 4, nb1) / T, dim=-1)
+    log_q = torch.log_softmax(teacher_corners.detach().reshape(B, Q, 4, nb1).to(pred_corners.dtype) / T, dim=-1)
+    rows_loss = w_local.unsqueeze(-1) * (T ** 2) * (log_q.exp() * (log_q - log_p)).sum(-1)          # (B, Q, 4)
+    m4 = mask.unsqueeze(-1).to(rows_loss.dtype)
+    n_pos, n_neg = 4 * mask.sum().to(rows_loss.dtype), 4 * (~mask).sum().to(rows_loss.dtype)
+    num_pos, num_neg = (n_pos * (1 / B)) ** 0.5, (n_neg * (1 / B)) ** 0.5
+    mean_pos = torch.where(n_pos > 0, (rows_loss * m4).sum() / n_pos.clamp(min=1), torch.zeros_like(n_pos))
+    mean_neg = torch.where(n_neg > 0, (rows_loss * (1 - m4)).sum() / n_neg.clamp(min=1), torch.zeros_like(n_neg))
+    out["loss_ddf"] = (mean_pos * num_pos + mean_neg * num_neg) / (num_pos + num_neg)
+    return out
+
+
+class _DetectionLoss(torch.autograd.Function):
+    """m355_dfine_loss_forward / _backward: the five terms as five 0-d outputs; gradients for logits, pred_boxes, pred_corners.
+    The backward recomputes per query; the forward keeps its inputs and the two DDF group coefficients (in `out`)."""
+
+    @staticmethod
+    def forward(ctx, logits, pred_boxes, pred_corners, consts):
+        (mq, mt, M, offs, labels, tboxes, T, num_boxes, alpha, gamma, ref, tc, tl, project, nb1, reg_scale, temperature) = consts
+        lg, pb = _f32c(logits, "logits"), _f32c(pred_boxes, "pred_boxes")
+        pc = _f32c(pred_corners, "pred_corners") if pred_corners is not None else None
+        B, Q, Cn = lg.shape
+        wbytes = int(lib.m355_dfine_loss_workspace_bytes(B, Q))
+        work = torch.empty(wbytes, dtype=torch.uint8, device=lg.device)
+        out = torch.empty(8, dtype=torch.float32, device=lg.device)
+        ctx.args = (B, Q, Cn, _ptr(mq), _ptr(mt), M, _ptr(offs), _ptr(labels), _ptr(tboxes), T, num_boxes, alpha, gamma)
+        ctx.local = (_ptr(ref), _ptr(tc), _ptr(tl), _ptr(project), nb1, reg_scale, temperature)
+        check(lib.m355_dfine_loss_forward(_ptr(lg), _ptr(pb), *ctx.args, _ptr(pc), *ctx.local, _ptr(work), wbytes, _ptr(out),
+                                          _stream()))
+        ctx.save_for_backward(lg, pb, pc, out)
+        ctx.keep = consts   # the buffers behind the raw pointers
+        ctx.like = [(t.shape, t.dtype) if t is not None else None for t in (logits, pred_boxes, pred_corners)]
+        loss_calls["kernel"] += 1
+        return tuple(out[:5].unbind(0))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        lg, pb, pc, out = ctx.saved_tensors
+        zero = None
+        terms = []
+        for g in grads:
+            if g is None:
+                zero = torch.zeros((), dtype=torch.float32, device=lg.device) if zero is None else zero
+                g = zero
+            terms.append(g.reshape(()).to(torch.float32))
+        gt = torch.stack(terms)
+        need = ctx.needs_input_grad
+        gl, gb = _grad_like(need[0], lg), _grad_like(need[1], pb)
+        gc = _grad_like(need[2], pc) if pc is not None else None
+        check(lib.m355_dfine_loss_backward(_ptr(gt), _ptr(lg), _ptr(pb), *ctx.args, _ptr(pc), *ctx.local, _ptr(out), _ptr(gl),
+                                           _ptr(gb), _ptr(gc), _stream()))
+        res = [None if g is None else _as_input(g, *sd) for g, sd in zip((gl, gb, gc), ctx.like)]
+        return res[0], res[1], res[2], None
+
+
+def detection_loss(logits: torch.Tensor, pred_boxes: torch.Tensor, targets: Sequence[dict], indices, num_boxes, *, alpha: float,
+                   gamma: float, pred_corners=None, ref_points=None, teacher_corners=None, teacher_logits=None, project=None,
+                   reg_scale=None, temperature: float = 5.0) -> dict:
+    """The loss terms of ONE D-FINE / RT-DETR decoder output, unweighted, as 0-d tensors under upstream's keys: loss_vfl,
+    loss_bbox, loss_giou (RTDetrLoss.loss_labels_vfl, loss_boxes) and, when the local group (pred_corners, ref_points,
+    teacher_corners, teacher_logits, project = weighting_function(...), reg_scale) is given, loss_fgl and loss_ddf
+    (DFineLoss.loss_local with T = temperature).  Differentiable in logits, pred_boxes and pred_corners.
+
+    logits (B, Q, C), pred_boxes (B, Q, 4) cx, cy, w, h; targets: upstream's list of {"class_labels", "boxes"}; indices:
+    upstream's list of B (query idx, target idx) int64 tensors, as hungarian_match and get_cdn_matched_indices return them
+    (their lengths are read from the shapes on the host); num_boxes: a Python number.
+
+    CUDA tensors: three launches forward (two kernels and the copy of 2 (B + 1) offsets), one backward, no synchronisation in
+    either direction.  An entry whose query or target index is out of range (hungarian_match(check=False)'s -1 entries
+    included) is skipped in every term.  The caller promises at most one entry per (b, q); with duplicates one of them wins.
+    Deviations from upstream: a box with negative width or height is not refused (generalized_box_iou's ValueError is a
+    synchronising check; hungarian_match documents the same), and a teacher equal to the prediction gives loss_ddf == 0.0
+    by arithmetic (one log-softmax routine for both sides) where upstream compares the tensors with torch.equal.
+    CPU tensors, and more than 64 bins + 1: detection_loss_torch, the same expressions in torch ops."""
+    B, Q, Cn = logits.shape
+    if len(indices) != B or len(targets) != B or tuple(pred_boxes.shape) != (B, Q, 4):
+        raise ValueError("logits (B, Q, C), pred_boxes (B, Q, 4), one target dict and one index pair per image are expected")
+    group = (pred_corners, ref_points, teacher_corners, teacher_logits, project, reg_scale)
+    local = pred_corners is not None
+    if any((g is None) == local for g in group):
+        raise ValueError("pred_corners, ref_points, teacher_corners, teacher_logits, project and reg_scale go together")
+    nb1 = int(project.numel()) if local else 0
+    if local and (pred_corners.shape[-1] != 4 * nb1 or tuple(teacher_corners.shape) != tuple(pred_corners.shape)
+                  or tuple(teacher_logits.shape) != (B, Q, Cn) or tuple(ref_points.shape) != (B, Q, 4)):
+        raise ValueError("the local group's shapes do not fit logits / project")
+    if not logits.is_cuda or nb1 > LOSS_MAX_BINS1 or B < 1 or Q < 1 or Cn < 1:
+        loss_calls["torch"] += 1
+        return detection_loss_torch(logits, pred_boxes, targets, indices, num_boxes, alpha=alpha, gamma=gamma,
+                                    pred_corners=pred_corners, ref_points=ref_points, teacher_corners=teacher_corners,
+                                    teacher_logits=teacher_logits, project=project, reg_scale=reg_scale, temperature=temperature)
+    dev = logits.device
+    lens = [int(i.shape[0]) for i, _ in indices]
+    sizes = [int(t["boxes"].shape[0]) for t in targets]
+    M, T = sum(lens), sum(sizes)
+    mq = mt = offs = labels = tboxes = None
+    if M > 0 and T > 0:
+        if B == 1:
+            mq, mt = indices[0]
+            labels, tboxes = targets[0]["class_labels"], targets[0]["boxes"]
+        else:
+            mq, mt = torch.cat([i for i, _ in indices]), torch.cat([j for _, j in indices])
+            labels, tboxes = torch.cat([t["class_labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+        mq, mt = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (mq, mt))
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        tboxes = _f32c(tboxes.detach().to(dev), "target boxes")
+        table = [0]
+        for n in lens:
+            table.append(table[-1] + n)
+        table.append(0)
+        for n in sizes:
+            table.append(table[-1] + n)
+        # pinned + non_blocking: the copy is queued on the stream, the host does not wait for it
+        offs = torch.tensor(table, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    else:
+        M = 0
+    if local:
+        ref, tc = _f32c(ref_points.detach(), "ref_points"), _f32c(teacher_corners.detach(), "teacher_corners")
+        tl, pr = _f32c(teacher_logits.detach(), "teacher_logits"), _f32c(project.detach(), "project")
+        rs, temp = float(reg_scale), float(temperature)
+    else:
+        ref = tc = tl = pr = None
+        rs, temp = 1.0, 1.0
+    consts = (mq, mt, M, offs, labels, tboxes, T, float(num_boxes), float(alpha), float(gamma), ref, tc, tl, pr, nb1, rs, temp)
+    terms = _DetectionLoss.apply(logits, pred_boxes, pred_corners, consts)
+    return dict(zip(LOSS_KEYS[:5 if local else 3], terms))
+
+
+def criterion_forward(self, outputs, targets):
+    """Drop-in for RTDetrLoss.forward, which DFineLoss inherits (`RTDetrLoss.forward = dfine.criterion_forward`,
+    INTEGRATION.md): upstream's control flow (the main output, `auxiliary_outputs`, `dn_auxiliary_outputs` with
+    get_cdn_matched_indices and num_boxes * dn_num_group), keys, `_aux_i` / `_dn_i` suffixes and `weight_dict`; indices from
+    `self.matcher`, whatever is bound there; ONE detection_loss call per output.  num_boxes is max(sum of the target counts, 1)
+    from the shapes on the host, without `.item()`.  An output without `pred_corners` yields no loss_fgl / loss_ddf.
+    Deviations: as detection_loss (no ValueError for a negative-size box; loss_ddf's zero by arithmetic), and
+    `self.num_pos` / `self.num_neg` / `self.fgl_targets` are not set on the module.  W(n) is computed once per (module, device)
+    and kept in `self._m355_project` (upstream recomputes it per output from the same constants)."""
+    if not set(self.losses) <= {"vfl", "boxes", "local"}:
+        raise ValueError(f"criterion_forward covers the losses vfl, boxes and local, not {self.losses}")
+    outputs_without_aux = {k: v for k, v in outputs.items() if "auxiliary_outputs" not in k}
+    indices = self.matcher(outputs_without_aux, targets)
+    num_boxes = float(max(sum(int(t["class_labels"].shape[0]) for t in targets), 1))
+    with_local = "local" in self.losses
+
+    def project_for(device):
+        key = (str(device), self.up._version, self.max_num_bins, float(self.reg_scale))
+        cached = getattr(self, "_m355_project", None)
+        if cached is None or cached[0] != key:
+            with torch.no_grad():
+                cached = (key, weighting_function(self.max_num_bins, self.up.detach().to(device), self.reg_scale).float())
+            self._m355_project = cached
+        return cached[1]
+
+    def terms(out, indices, num_boxes, suffix):
+        kw = {}
+        if with_local and "pred_corners" in out:
+            kw = dict(pred_corners=out["pred_corners"], ref_points=out["ref_points"], teacher_corners=out["teacher_corners"],
+                      teacher_logits=out["teacher_logits"], project=project_for(out["logits"].device), reg_scale=self.reg_scale)
+        d = detection_loss(out["logits"], out["pred_boxes"], targets, indices, num_boxes, alpha=self.alpha, gamma=self.gamma, **kw)
+        return {k + suffix: v * self.weight_dict[k] for k, v in d.items() if k in self.weight_dict}
+
+    losses = terms(outputs, indices, num_boxes, "")
+    if "auxiliary_outputs" in outputs:
+        for i, aux in enumerate(outputs["auxiliary_outputs"]):
+            losses.update(terms(aux, self.matcher(aux, targets), num_boxes, f"_aux_{i}"))
+    if "dn_auxiliary_outputs" in outputs:
+        if "denoising_meta_values" not in outputs:
+            raise ValueError("The output must have the 'denoising_meta_values` key. Please, ensure that 'outputs' includes a "
+                             "'denoising_meta_values' entry.")
+        indices = self.get_cdn_matched_indices(outputs["denoising_meta_values"], targets)
+        num_boxes = num_boxes * outputs["denoising_meta_values"]["dn_num_group"]
+        for i, aux in enumerate(outputs["dn_auxiliary_outputs"]):
+            losses.update(terms(aux, indices, num_boxes, f"_dn_{i}"))
+    return losses

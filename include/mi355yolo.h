@@ -656,6 +656,44 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
                      int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
                      int32_t kmax, int32_t* d_flags, void* stream);
 
+/* ---- Loss terms of one D-FINE decoder output ---------------------------------------------------------------------------
+ * m355_dfine_loss_forward = RTDetrLoss.loss_labels_vfl + loss_boxes (transformers/loss/loss_rt_detr.py:165-254) and, with the
+ * local group, DFineLoss.loss_local (loss_d_fine.py:228-301): the five UNWEIGHTED terms, fp32, upstream's expressions.
+ *   logits (B, Q, C), pred_boxes (B, Q, 4) cx, cy, w, h: contiguous fp32
+ *   match_q, match_t (M) int64: the match entries, those of image b contiguous and in image order: query index and target index
+ *     WITHIN the image (what the matcher's rows / cols hold).  d_offsets (2 (B + 1)) int32 DEVICE: first entry of each image
+ *     (B + 1 values, the last one M), then first target row of each image (B + 1 values, the last one T).
+ *     An entry whose query is outside [0, Q) or whose target is outside the image's targets (the matcher's -1 entries included)
+ *     is skipped in every term; an offset outside [0, M] / [0, T] is clamped: nothing is followed out of bounds.
+ *     The caller promises at most one valid entry per (b, q).
+ *   target_labels (T) int64, target_boxes (T, 4) fp32: the targets of all images, concatenated in image order
+ *   num_boxes > 0: the host-side normaliser; alpha, gamma: the varifocal weight alpha * sigmoid(x)^gamma
+ *   local group, all NULL or all present: pred_corners, teacher_corners (B, Q, 4 * num_bins_plus1), ref_points (B, Q, 4),
+ *     teacher_logits (B, Q, C), project (num_bins_plus1) = W(n), with reg_scale and the temperature T of the KL term
+ *   work: m355_dfine_loss_workspace_bytes(B, Q) bytes
+ *   out (8) fp32: loss_vfl, loss_bbox, loss_giou, loss_fgl, loss_ddf (the last two 0 without the local group), then three
+ *     values the backward reads.  Pass the same buffer to m355_dfine_loss_backward as d_saved.
+ * Two launches (per-query partials; one block adds them in block order), asynchronous on `stream`, no read-back.
+ * m355_dfine_loss_backward: one launch that recomputes per query and writes EVERY element of grad_logits (B, Q, C),
+ * grad_pred_boxes (B, Q, 4) and grad_pred_corners (B, Q, 4 * num_bins_plus1) (zeros where no term reaches); any of the three
+ * may be NULL.  d_grad_terms (5) fp32 DEVICE: the upstream gradient of each term, any combination.
+ * No atomics: bitwise reproducible.  Limits, checked on the host before any HIP call (M355_ERR_INVALID): B, Q, C >= 1,
+ * B * Q < 2^31, M >= 0, num_bins_plus1 in [2, 64], no NULL among the required pointers, local group all or none, workspace. */
+size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q);
+int m355_dfine_loss_forward(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                            const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                            const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                            float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                            const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                            float temperature, void* d_work, int64_t work_bytes, float* d_out, void* stream);
+int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q,
+                             int32_t C, const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                             const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                             float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                             const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                             float temperature, const float* d_saved, float* d_grad_logits, float* d_grad_pred_boxes,
+                             float* d_grad_pred_corners, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
