@@ -16,6 +16,7 @@ namespace {
 constexpr int NMS_THREADS = 1024;
 constexpr int MAX_KEEP = 1024;      // upper bound for max_det
 constexpr float MAX_WH = 7680.0f;   // class offset (non-agnostic NMS)
+constexpr int MAX_NMS = 30000;      // candidates that enter the greedy pass: the top MAX_NMS by (score, lower anchor), as upstream's max_nms
 constexpr int MAX_MASK_WORDS = 32;  // class set of nms_kernel: up to 1024 classes
 
 struct Box { float x1, y1, x2, y2; };
@@ -37,8 +38,8 @@ __device__ __forceinline__ float iou_f32(const Box& a, const Box& b) {
 //     lower anchor index first (oracle order).
 //  2. bitonic sort of the keys in LDS (n padded to a power of two; <= 16384 keys = 128 KB) or, for
 //     larger anchor counts, in the global workspace.
-//  3. wave 0 runs greedy NMS over 64-candidate chunks: each lane owns one candidate, tests it against
-//     the kept list (LDS broadcast), then the chunk is resolved in order with ballot/ffs.
+//  3. wave 0 runs greedy NMS over 64-candidate chunks of the first min(n, MAX_NMS) sorted candidates: each lane owns one
+//     candidate, tests it against the kept list (LDS broadcast), then the chunk is resolved in order with ballot/ffs.
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, int A, int nc, int nm, float conf_thr,
                                                           float iou_thr, int max_det, float* dets, int* counts,
                                                           unsigned long long* gkeys, int keys_in_lds,
@@ -109,10 +110,11 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, in
   if (tid < 64) {
     const int lane = tid;
     int kept = 0;
-    const int nchunks = (n + 63) >> 6;
+    const int ncand = n < MAX_NMS ? n : MAX_NMS;   // (the sorted keys past the cap are never read)
+    const int nchunks = (ncand + 63) >> 6;
     for (int c = 0; c < nchunks && kept < max_det; ++c) {
       const int i = c * 64 + lane;
-      const bool valid = i < n;
+      const bool valid = i < ncand;
       int anchor = 0;
       Box bx = {0.f, 0.f, 0.f, 0.f};
       if (valid) {

@@ -289,7 +289,10 @@ int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void*
 int m355_upsample2x(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
 /* Head decode: raw (B,A,64+nc+32) f32 -> preds (B,A,4+nc+32) f32 for an in_h x in_w input. */
 int m355_head_decode(const float* d_raw, int B, int in_h, int in_w, int nc, float* d_preds, void* stream);
-/* Batched NMS only. preds (B,A,4+nc+nm). */
+/* Batched NMS only. preds (B,A,4+nc+nm).  An anchor is a candidate when its best class score is above conf
+ * (strictly); of an image's candidates only the first 30000 by score (equal scores: the lower anchor first) enter the greedy
+ * pass, as upstream's max_nms: with A <= 30000 that is all of them.  A box is suppressed by a kept one when their IoU is
+ * above iou (strictly); at most max_det (1..1024) rows per image.                                                 [sync] */
 int m355_nms(const float* d_preds, int B, int A, int nc, int nm, float conf, float iou, int max_det,
              float* d_dets, int* d_counts, void* stream);
 /* m355_nms with the agnostic / class-set options of m355_postprocess_ex (same meaning).  M355_ERR_INVALID, before any HIP
