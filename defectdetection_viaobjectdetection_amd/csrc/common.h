@@ -127,6 +127,10 @@ int launch_dfine_match(const float* logits, const float* boxes, int B, int Q, in
                        const int* d_offsets, int T, int nmax, float class_cost, float bbox_cost, float giou_cost, float alpha,
                        float gamma, int focal, void* work, float* cost_out, long long* rows, long long* cols, int kmax, int* flags,
                        hipStream_t s);
+// Detection post-processing of a D-FINE / RT-DETR output (dfine_postprocess.hip): top-Q rows of sigmoid(logits) with label, scaled
+// xyxy box and the {n_nan, n_keep} counts, one block per image.  The caller has validated every argument; sizes may be nullptr.
+int launch_dfine_postprocess(const float* logits, const float* boxes, int B, int Q, int C, const float* sizes, float threshold,
+                             float* scores, long long* labels, float* out_boxes, int* counts, hipStream_t s);
 // Loss terms of one D-FINE decoder output (dfine_loss.hip): loss_vfl, loss_bbox, loss_giou and, with the local group
 // (pred_corners != nullptr), loss_fgl and loss_ddf.  The caller has validated every argument.
 struct DfineLossArgs {

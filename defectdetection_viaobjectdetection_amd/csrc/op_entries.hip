@@ -895,6 +895,17 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
                                           (hipStream_t)stream);
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_match launch failed: " + std::to_string(rc));
 }
+int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
+                           float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream) {
+  // every argument before any HIP call
+  if (!d_logits || !d_pred_boxes || !d_scores || !d_labels || !d_boxes || !d_counts)
+    return set_err(M355_ERR_INVALID, "dfine_postprocess: null pointer");
+  if (B < 1 || Q < 1 || Q > 2048 || C < 1 || (int64_t)Q * C >= (int64_t)1 << 24)
+    return set_err(M355_ERR_INVALID, "dfine_postprocess: B >= 1, Q in [1, 2048], C >= 1, Q * C < 2^24");
+  const int rc = m355::launch_dfine_postprocess(d_logits, d_pred_boxes, B, Q, C, d_sizes, threshold, d_scores, (long long*)d_labels,
+                                                d_boxes, d_counts, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_postprocess launch failed: " + std::to_string(rc));
+}
 size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q) { return m355::dfine_loss_workspace_bytes(B, Q); }
 namespace {
 // the argument checks m355_dfine_loss_forward and _backward share; nullptr = accepted, else the message

@@ -16,10 +16,15 @@ transformers/loss/loss_rt_detr.py:68-120) in one launch: cost matrix and assignm
 ``detection_loss`` / ``criterion_forward`` are what those indices feed: loss_vfl, loss_bbox, loss_giou, loss_fgl and loss_ddf of a
 decoder output (``RTDetrLoss.loss_labels_vfl`` / ``loss_boxes``, ``DFineLoss.loss_local``) and their gradients as fused kernels,
 two launches forward and one backward per output, without a synchronisation; on CPU tensors the same expressions in torch ops.
+
+``topk_detections`` / ``post_process_detections`` / ``post_process_object_detection`` are the inference tail
+(``RTDetrImageProcessor.post_process_object_detection``, models/rt_detr/image_processing_rt_detr.py:482-552): sigmoid, top-K, labels,
+scaled xyxy boxes and the threshold in one launch for a whole sequence of frames, with one read-back of the kept counts.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections.abc import Mapping
 from typing import List, Sequence
 
 import torch
@@ -680,3 +685,131 @@ def criterion_forward(self, outputs, targets):
         for i, aux in enumerate(outputs["dn_auxiliary_outputs"]):
             losses.update(terms(aux, indices, num_boxes, f"_dn_{i}"))
     return losses
+
+
+# ---- detection post-processing (RTDetrImageProcessor.post_process_object_detection, image_processing_rt_detr.py:482-552) ------
+POST_MAX_QUERIES = 2048          # the limits of m355_dfine_postprocess; anything outside them takes post_process_torch
+POST_MAX_CANDIDATES = 1 << 24    # Q * C stays below it
+TARGET_SIZES_MESSAGE = "Make sure that you pass in as many target sizes as the batch dimension of the logits"   # upstream's
+post_calls = {"kernel": 0, "torch": 0}   # how many calls took which path (tests and tools read it)
+
+
+def _post_kernel_takes(logits: torch.Tensor, pred_boxes: torch.Tensor) -> bool:
+    B, Q, Cn = logits.shape
+    return (logits.is_cuda and pred_boxes.is_cuda and B >= 1 and 1 <= Q <= POST_MAX_QUERIES and Cn >= 1
+            and Q * Cn < POST_MAX_CANDIDATES and not _wants_grad(logits, pred_boxes))
+
+
+def _check_post_shapes(logits, pred_boxes, target_sizes):
+    if logits.dim() != 3 or tuple(pred_boxes.shape) != tuple(logits.shape[:2]) + (4,):
+        raise ValueError("logits (B, Q, C) and pred_boxes (B, Q, 4) are expected")
+    if target_sizes is not None and len(logits) != len(target_sizes):
+        raise ValueError(TARGET_SIZES_MESSAGE)
+
+
+def _device_sizes(target_sizes, B: int, dev) -> torch.Tensor:
+    """(B, 2) fp32 (height, width) on `dev` without a synchronisation: a device tensor is cast there, anything on the host goes
+    up as one pinned non-blocking copy"""
+    if torch.is_tensor(target_sizes) and target_sizes.is_cuda:
+        return target_sizes.to(device=dev, dtype=torch.float32).reshape(B, 2).contiguous()
+    host = target_sizes.to(torch.float32) if torch.is_tensor(target_sizes) else torch.tensor(
+        [[float(h), float(w)] for h, w in target_sizes], dtype=torch.float32)
+    return host.reshape(B, 2).contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def _topk_torch(logits, pred_boxes, target_sizes, use_focal_loss: bool = True):
+    """upstream's expression up to the per-image masks: scores (B, K), labels (B, K), boxes (B, K, 4)"""
+    cx, cy, w, h = pred_boxes.unbind(-1)
+    boxes = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], dim=-1)
+    if target_sizes is not None:
+        sizes = torch.as_tensor(target_sizes) if isinstance(target_sizes, (list, tuple)) else target_sizes
+        img_h, img_w = sizes.unbind(1)
+        boxes = boxes * torch.stack([img_w, img_h, img_w, img_h], dim=1).to(boxes.device)[:, None, :]
+    num_top_queries, num_classes = logits.shape[1], logits.shape[2]
+    if use_focal_loss:
+        scores, index = torch.topk(torch.sigmoid(logits).flatten(1), num_top_queries, dim=-1)
+        labels = index % num_classes
+        index = index // num_classes
+        boxes = boxes.gather(dim=1, index=index.unsqueeze(-1).repeat(1, 1, boxes.shape[-1]))
+    else:
+        scores, labels = torch.softmax(logits, dim=-1)[:, :, :-1].max(dim=-1)
+        if scores.shape[1] > num_top_queries:   # never: upstream keeps the branch
+            scores, index = torch.topk(scores, num_top_queries, dim=-1)
+            labels = torch.gather(labels, dim=1, index=index)
+            boxes = torch.gather(boxes, dim=1, index=index.unsqueeze(-1).tile(1, 1, boxes.shape[-1]))
+    return scores, labels, boxes
+
+
+def post_process_torch(logits: torch.Tensor, pred_boxes: torch.Tensor, target_sizes=None, threshold: float = 0.5,
+                       use_focal_loss: bool = True) -> List[dict]:
+    """Upstream's post_process_object_detection in torch ops, on whatever device and dtype the tensors have, its three
+    boolean-mask indexings per image included (each synchronises on a device): what the kernel-backed functions fall back to
+    (use_focal_loss=False, CPU tensors, shapes beyond the kernel's limits, inputs under autograd) and the fp32 baseline of the
+    tests.  Among equal scores the order is torch.topk's own."""
+    _check_post_shapes(logits, pred_boxes, target_sizes)
+    post_calls["torch"] += 1
+    scores, labels, boxes = _topk_torch(logits, pred_boxes, target_sizes, use_focal_loss)
+    return [{"scores": s[s > threshold], "labels": l[s > threshold], "boxes": b[s > threshold]}
+            for s, l, b in zip(scores, labels, boxes)]
+
+
+def topk_detections(logits: torch.Tensor, pred_boxes: torch.Tensor, target_sizes=None, threshold: float = 0.5):
+    """The focal branch of post_process_object_detection up to the threshold, in ONE kernel launch and without any
+    device-to-host transfer: (scores (B, Q) fp32, labels (B, Q) int64, boxes (B, Q, 4) fp32 xyxy, counts (B, 2) int32), all on
+    the device.  logits (B, Q, C), pred_boxes (B, Q, 4) cx, cy, w, h; target_sizes None, a list of (height, width), or a (B, 2)
+    tensor of any integer or float dtype on the host (one pinned non-blocking copy) or on the device (cast there).
+
+    Rows: NaN logits first (torch.topk's order), then descending logit, an exact tie to the lowest flat index q * C + c.
+    counts[b] = (n_nan, n_keep): upstream's `score > threshold` masks of image b are the slice [n_nan, n_nan + n_keep) of its
+    rows.  Boxes are torch's fp32 bits.  Deviation: the sizes are taken as fp32 (a float64 target_sizes tensor makes upstream
+    return float64 boxes).  CPU tensors, shapes beyond the kernel's limits (Q > 2048, Q * C >= 2^24) and inputs under autograd
+    take upstream's torch ops; the counts are then computed with torch ops too and ties keep torch.topk's order."""
+    _check_post_shapes(logits, pred_boxes, target_sizes)
+    B, Q, Cn = logits.shape
+    if not _post_kernel_takes(logits, pred_boxes):
+        post_calls["torch"] += 1
+        scores, labels, boxes = _topk_torch(logits, pred_boxes, target_sizes)
+        n_nan = torch.isnan(scores).sum(1)
+        counts = torch.stack([n_nan, (scores > threshold).sum(1)], dim=1).to(torch.int32)
+        return scores, labels, boxes, counts
+    lg, pb = _f32c(logits.detach(), "logits"), _f32c(pred_boxes.detach(), "pred_boxes")
+    dev = lg.device
+    sizes = _device_sizes(target_sizes, B, dev) if target_sizes is not None else None
+    scores = torch.empty((B, Q), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, Q), dtype=torch.int64, device=dev)
+    boxes = torch.empty((B, Q, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    check(lib.m355_dfine_postprocess(_ptr(lg), _ptr(pb), B, Q, Cn, _ptr(sizes), float(threshold), _ptr(scores), _ptr(labels),
+                                     _ptr(boxes), _ptr(counts), _stream()))
+    post_calls["kernel"] += 1
+    return scores, labels, boxes, counts
+
+
+def post_process_detections(logits: torch.Tensor, pred_boxes: torch.Tensor, target_sizes=None, threshold: float = 0.5) -> List[dict]:
+    """Upstream's list of {"scores", "labels", "boxes"} per image for a whole batch (a sequence of frames) at once: one
+    topk_detections launch and ONE read-back of the (B, 2) counts; the entries are device tensors, slices of the three
+    outputs.  A NaN score is in no image's entries, as upstream's `score > threshold` excludes it.  What a script calls once
+    per sequence in place of its per-frame loop."""
+    _check_post_shapes(logits, pred_boxes, target_sizes)
+    if not _post_kernel_takes(logits, pred_boxes):
+        return post_process_torch(logits, pred_boxes, target_sizes, threshold)
+    scores, labels, boxes, counts = topk_detections(logits, pred_boxes, target_sizes, threshold)
+    out = []
+    for b, (n_nan, n_keep) in enumerate(counts.cpu().tolist()):   # the call's one read-back
+        out.append({"scores": scores[b, n_nan:n_nan + n_keep], "labels": labels[b, n_nan:n_nan + n_keep],
+                    "boxes": boxes[b, n_nan:n_nan + n_keep]})
+    return out
+
+
+def post_process_object_detection(self, outputs, threshold: float = 0.5, target_sizes=None, use_focal_loss: bool = True):
+    """Drop-in for RTDetrImageProcessor.post_process_object_detection
+    (`RTDetrImageProcessor.post_process_object_detection = dfine.post_process_object_detection`, INTEGRATION.md).  `outputs`
+    has `logits` and `pred_boxes` as attributes or as keys (the reference's trainers pass a dict).  Upstream's ValueError for a
+    target_sizes of the wrong length is kept; use_focal_loss=False takes upstream's torch ops."""
+    if isinstance(outputs, Mapping):
+        logits, pred_boxes = outputs["logits"], outputs["pred_boxes"]
+    else:
+        logits, pred_boxes = outputs.logits, outputs.pred_boxes
+    if not use_focal_loss:
+        return post_process_torch(logits, pred_boxes, target_sizes, threshold, use_focal_loss=False)
+    return post_process_detections(logits, pred_boxes, target_sizes, threshold)

@@ -659,6 +659,28 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
                      int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
                      int32_t kmax, int32_t* d_flags, void* stream);
 
+/* ---- Detection post-processing of a D-FINE / RT-DETR output ------------------------------------------------------------
+ * m355_dfine_postprocess = RTDetrImageProcessor.post_process_object_detection (transformers
+ * models/rt_detr/image_processing_rt_detr.py:482-552, the use_focal_loss=True branch), which the reference's predict and eval
+ * scripts call once per frame: the K = Q best of the Q * C candidates of every image, ONE launch, one block per image,
+ * asynchronous on `stream`, no host round trip.  All buffers are the caller's.
+ *   logits (B, Q, C) fp32; pred_boxes (B, Q, 4) fp32 cx, cy, w, h
+ *   sizes: NULL, or DEVICE (B, 2) fp32 (height, width) of each image; threshold: the score threshold
+ * Order of the rows, a total order on the flat candidates i = q * C + c: NaN logits first (torch.topk treats NaN as the
+ * greatest), then descending logit (sigmoid is monotone; -0 == +0), an exact tie to the lowest i.  Row r of image b:
+ *   scores[b][r] = 1 / (1 + exp(-logit)) in fp32; labels[b][r] = i % C (int64); with q = i / C
+ *   boxes[b][r] = (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h) of query q, then * (W, H, W, H) when sizes is given: one fp32
+ *     operation each, upstream's order, so the bits are torch's fp32 result
+ *   counts[b] = {n_nan, n_keep} int32: the number of leading NaN rows, and the number of rows with score > threshold (the
+ *     kernel's own fp32 score; no NaN row is among them).  The rows being sorted, upstream's three boolean masks are the
+ *     slice [n_nan, n_nan + n_keep).
+ * scores (B, Q), labels (B, Q), boxes (B, Q, 4) and counts (B, 2) are written in full.
+ * Limits, checked on the host before any HIP call (M355_ERR_INVALID): no NULL among the required pointers, B >= 1,
+ * 1 <= Q <= 2048, C >= 1, Q * C < 2^24.  Integer LDS counters only, no float atomics: bitwise reproducible, and image b of a
+ * batch gives the bits of the same image alone. */
+int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
+                           float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream);
+
 /* ---- Loss terms of one D-FINE decoder output ---------------------------------------------------------------------------
  * m355_dfine_loss_forward = RTDetrLoss.loss_labels_vfl + loss_boxes (transformers/loss/loss_rt_detr.py:165-254) and, with the
  * local group, DFineLoss.loss_local (loss_d_fine.py:228-301): the five UNWEIGHTED terms, fp32, upstream's expressions.
