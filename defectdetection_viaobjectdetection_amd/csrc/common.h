@@ -160,6 +160,24 @@ struct DfineLossArgs {
 size_t dfine_loss_workspace_bytes(int B, int Q);
 int launch_dfine_loss_forward(const DfineLossArgs& a, hipStream_t s);    // two launches
 int launch_dfine_loss_backward(const DfineLossArgs& a, hipStream_t s);   // one launch
+// The temporal encoder layer between its GEMMs (dfine_encoder.hip): attention core on the packed (B, S, 3 * 32 H) projection,
+// LayerNorm(x + dropout(y)), dropout(relu(h)), each with its backward, and the dropout keep-mask they share (p = 0: no mask).
+// The caller has validated every argument; all tensors contiguous fp32, 16-byte aligned.
+int launch_dfine_attn_forward(const float* qkv, int B, int S, int H, float p, unsigned long long seed, int site, float* out,
+                              float* lse, hipStream_t s);                                  // lse may be nullptr
+int launch_dfine_attn_backward(const float* gout, const float* qkv, const float* out, const float* lse, int B, int S, int H, float p,
+                               unsigned long long seed, int site, float* gqkv, hipStream_t s);
+int dfine_addln_max_d();
+size_t dfine_addln_workspace_bytes(long M, int D);
+int launch_dfine_addln_forward(const float* x, const float* y, const float* w, const float* b, long M, int D, float eps, float p,
+                               unsigned long long seed, int site, float* out, float* mean, float* rstd, hipStream_t s);
+int launch_dfine_addln_backward(const float* g, const float* x, const float* y, const float* w, const float* mean, const float* rstd,
+                                long M, int D, float p, unsigned long long seed, int site, float* dx, float* dy, float* dweight,
+                                float* dbias, float* work, hipStream_t s);                 // two launches
+// saved == nullptr: out = dropout(relu(in)); else the backward: in = grad_out, saved = the forward's output
+int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, long n, float p, unsigned long long seed, int site,
+                              hipStream_t s);
+int launch_dfine_keep_mask(unsigned char* mask, long n, float p, unsigned long long seed, int site, hipStream_t s);
 // their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
 // grad_value and the per-head partials of grad_ref.  -1 = refused before any launch, -3 = workspace missing / too small.
 size_t msda_backward_workspace_bytes(int B, int Q, int H, int P);

@@ -51,6 +51,36 @@ __device__ __forceinline__ int row_operand(int rho) {
   return 16 * (q >> 1) + 8 * h + 4 * (q & 1) + i;
 }
 
+// ---- dropout keep-mask: a pure function of (seed, site, flat element index), nothing stored (dfine_encoder.hip)
+// Philox4x32-10 (Salmon et al., SC'11; Random123's constants and round): counter c[0..3], key (k0, k1), result in c.
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned lo0 = c[0] * 0xD2511F53u, hi0 = __umulhi(c[0], 0xD2511F53u);
+    const unsigned lo1 = c[2] * 0xCD9E8D57u, hi1 = __umulhi(c[2], 0xCD9E8D57u);
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+// What a dropout site of a kernel needs: thr = floor(p * 2^32), scale = 1 / (1 - p); element e is kept when its word >= thr.
+struct DropArgs {
+  unsigned long long seed;
+  unsigned site, thr;
+  float scale;
+};
+// The ONE definition of the mask: bit e (0..3) of the result is set when element 4 * group + e of the site's tensor (flat,
+// row-major index) is kept.  counter = (group lo, group hi, site, 0), key = (seed lo, seed hi): one Philox call per 4 elements.
+__device__ __forceinline__ unsigned dropout_keep4(const DropArgs& d, unsigned long long group) {
+  unsigned c[4] = {(unsigned)group, (unsigned)(group >> 32), d.site, 0u};
+  philox4x32_10(c, (unsigned)d.seed, (unsigned)(d.seed >> 32));
+  return (unsigned)(c[0] >= d.thr) | ((unsigned)(c[1] >= d.thr) << 1) | ((unsigned)(c[2] >= d.thr) << 2) |
+         ((unsigned)(c[3] >= d.thr) << 3);
+}
+
 // ---- SiLU and the conv epilogue
 // v * sigmoid(v);  exp2-based, rcp approx (1 ulp) -- far inside fp16 output rounding.
 // No FMA contraction in the epilogue arithmetic: the generic and the fast epilogue must give the same bits, so that an

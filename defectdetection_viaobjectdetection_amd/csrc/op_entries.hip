@@ -972,6 +972,94 @@ int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, c
   const int rc = m355::launch_dfine_loss_backward(a, (hipStream_t)stream);
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_loss_backward launch failed: " + std::to_string(rc));
 }
+// ---- the temporal encoder layer between its GEMMs (dfine_encoder.hip); every argument before any HIP call
+namespace {
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+// nullptr = accepted, else the message
+const char* dfine_dropout_check(float p, int32_t site) {
+  if (!(p >= 0.f && p < 1.f)) return "dropout p must be in [0, 1)";
+  if (site < 0) return "the dropout site id must be >= 0";
+  return nullptr;
+}
+const char* dfine_attn_check(int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, int32_t site) {
+  if (head_dim != 32) return "head dim must be 32";
+  if (B < 1 || B > 65535 || S < 1 || H < 1 || H > 65535) return "B and heads in [1, 65535], S >= 1";
+  if ((int64_t)B * S * 96 * H > (int64_t)1 << 40 || (int64_t)S > (int64_t)1 << 24) return "S <= 2^24 and B * S * 3 D <= 2^40";
+  return dfine_dropout_check(p, site);
+}
+const char* dfine_addln_check(int64_t M, int32_t D, float p, int32_t site) {
+  if (M < 1 || M > (int64_t)1 << 31) return "1 <= rows <= 2^31";
+  if (D < 4 || D % 4 != 0 || D > m355::dfine_addln_max_d()) return "D must be a multiple of 4 in [4, 1024]";
+  return dfine_dropout_check(p, site);
+}
+}  // namespace
+int m355_dfine_attn_forward(const float* d_qkv, int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, uint64_t seed,
+                            int32_t site, float* d_out, float* d_lse, void* stream) {
+  if (!d_qkv || !d_out) return set_err(M355_ERR_INVALID, "dfine_attn_forward: null pointer");
+  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_attn_forward: ") + why);
+  if (misaligned16(d_qkv) || misaligned16(d_out)) return set_err(M355_ERR_INVALID, "dfine_attn_forward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_attn_forward(d_qkv, B, S, H, p, seed, site, d_out, d_lse, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_attn_forward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_attn_backward(const float* d_grad_out, const float* d_qkv, const float* d_out, const float* d_lse, int32_t B, int32_t S,
+                             int32_t H, int32_t head_dim, float p, uint64_t seed, int32_t site, float* d_grad_qkv, void* stream) {
+  if (!d_grad_out || !d_qkv || !d_out || !d_lse || !d_grad_qkv) return set_err(M355_ERR_INVALID, "dfine_attn_backward: null pointer");
+  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_attn_backward: ") + why);
+  if (misaligned16(d_grad_out) || misaligned16(d_qkv) || misaligned16(d_out) || misaligned16(d_grad_qkv))
+    return set_err(M355_ERR_INVALID, "dfine_attn_backward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_attn_backward(d_grad_out, d_qkv, d_out, d_lse, B, S, H, p, seed, site, d_grad_qkv, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_attn_backward launch failed: " + std::to_string(rc));
+}
+size_t m355_dfine_addln_workspace_bytes(int64_t M, int32_t D) { return m355::dfine_addln_workspace_bytes(M, D); }
+int m355_dfine_addln_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
+                             float eps, float p, uint64_t seed, int32_t site, float* d_out, float* d_mean, float* d_rstd, void* stream) {
+  if (!d_x || !d_y || !d_weight || !d_bias || !d_out || !d_mean || !d_rstd) return set_err(M355_ERR_INVALID, "dfine_addln_forward: null pointer");
+  if (const char* why = dfine_addln_check(M, D, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_addln_forward: ") + why);
+  if (!(eps >= 0.f)) return set_err(M355_ERR_INVALID, "dfine_addln_forward: eps must be >= 0");
+  if (misaligned16(d_x) || misaligned16(d_y) || misaligned16(d_weight) || misaligned16(d_bias) || misaligned16(d_out))
+    return set_err(M355_ERR_INVALID, "dfine_addln_forward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_addln_forward(d_x, d_y, d_weight, d_bias, M, D, eps, p, seed, site, d_out, d_mean, d_rstd, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_addln_forward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_addln_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight, const float* d_mean,
+                              const float* d_rstd, int64_t M, int32_t D, float p, uint64_t seed, int32_t site, float* d_grad_x,
+                              float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work, int64_t work_bytes, void* stream) {
+  if (!d_grad_out || !d_x || !d_y || !d_weight || !d_mean || !d_rstd) return set_err(M355_ERR_INVALID, "dfine_addln_backward: null pointer");
+  if (const char* why = dfine_addln_check(M, D, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_addln_backward: ") + why);
+  if (!d_work || work_bytes < 0 || (size_t)work_bytes < m355::dfine_addln_workspace_bytes(M, D))
+    return set_err(M355_ERR_INVALID, "dfine_addln_backward: workspace missing or smaller than m355_dfine_addln_workspace_bytes");
+  if (misaligned16(d_grad_out) || misaligned16(d_x) || misaligned16(d_y) || misaligned16(d_weight) || misaligned16(d_grad_x) ||
+      misaligned16(d_grad_y) || misaligned16(d_work))
+    return set_err(M355_ERR_INVALID, "dfine_addln_backward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_addln_backward(d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd, M, D, p, seed, site, d_grad_x, d_grad_y,
+                                                   d_grad_weight, d_grad_bias, (float*)d_work, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_addln_backward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_relu_dropout_forward(const float* d_h, int64_t n, float p, uint64_t seed, int32_t site, float* d_out, void* stream) {
+  if (!d_h || !d_out) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: 1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_relu_dropout_forward: ") + why);
+  if (misaligned16(d_h) || misaligned16(d_out)) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_relu_dropout(d_h, nullptr, d_out, n, p, seed, site, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_relu_dropout_forward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out, int64_t n, float p, uint64_t seed, int32_t site,
+                                     float* d_grad_h, void* stream) {
+  if (!d_grad_out || !d_out || !d_grad_h) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: 1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_relu_dropout_backward: ") + why);
+  if (misaligned16(d_grad_out) || misaligned16(d_out) || misaligned16(d_grad_h))
+    return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_relu_dropout(d_grad_out, d_out, d_grad_h, n, p, seed, site, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_relu_dropout_backward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream) {
+  if (!d_mask) return set_err(M355_ERR_INVALID, "dfine_dropout_mask: null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_dropout_mask: 1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_dropout_mask: ") + why);
+  const int rc = m355::launch_dfine_keep_mask(d_mask, n, p, seed, site, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_dropout_mask launch failed: " + std::to_string(rc));
+}
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");

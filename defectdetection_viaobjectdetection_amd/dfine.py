@@ -20,6 +20,11 @@ two launches forward and one backward per output, without a synchronisation; on 
 ``topk_detections`` / ``post_process_detections`` / ``post_process_object_detection`` are the inference tail
 (``RTDetrImageProcessor.post_process_object_detection``, models/rt_detr/image_processing_rt_detr.py:482-552): sigmoid, top-K, labels,
 scaled xyxy boxes and the threshold in one launch for a whole sequence of frames, with one read-back of the kept counts.
+
+``self_attention`` / ``add_layer_norm`` / ``relu_dropout`` / ``encoder_layer_forward`` / ``bind_encoder`` are the temporal
+encoder the D-FINE trainers train (``nn.TransformerEncoderLayer``, post-norm, ReLU, head dim 32) between its torch GEMMs:
+attention core with online softmax on the packed in-projection output, LayerNorm(x + dropout(y)) and dropout(relu(h)), each
+with a HIP backward, and a counter-based dropout mask that the backward recomputes (``dropout_keep_mask`` shows it).
 """
 from __future__ import annotations
 
@@ -813,3 +818,252 @@ def post_process_object_detection(self, outputs, threshold: float = 0.5, target_
     if not use_focal_loss:
         return post_process_torch(logits, pred_boxes, target_sizes, threshold, use_focal_loss=False)
     return post_process_detections(logits, pred_boxes, target_sizes, threshold)
+
+
+# ---- temporal encoder layers (nn.TransformerEncoderLayer, post-norm, ReLU, head dim 32) between their GEMMs ---------------------
+# The D-FINE trainers put nn.TransformerEncoder(nn.TransformerEncoderLayer(256, 8, 1024, 0.1, batch_first=True), 4) on the frozen
+# decoder's last_hidden_state (T frames = batch, Q queries = sequence) and train nothing else.  The nn.Linear layers stay torch
+# GEMMs (autograd yields their weight gradients); everything between them is csrc/dfine_encoder.hip.
+SITE_ATTN, SITE_ATTN_OUT, SITE_FFN, SITE_FFN_OUT = 0, 1, 2, 3   # dropout sites of a layer: the mask is f(seed, site, element)
+ENCODER_HEAD_DIM = 32
+ADDLN_MAX_D = 1024
+encoder_calls = {"kernel": 0, "torch": 0}   # how many encoder_layer_forward calls took which path (tests and tools read it)
+
+
+def _draw_seed() -> int:
+    """one 62-bit integer from torch.default_generator (a host generator: no device synchronisation); torch.manual_seed
+    makes the sequence reproducible"""
+    return int(torch.randint(0, 1 << 62, (), dtype=torch.int64))
+
+
+def _dropout_args(dropout_p: float, seed):
+    p = float(dropout_p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    if p == 0.0:
+        return 0.0, 0
+    seed = _draw_seed() if seed is None else int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit in 64 unsigned bits")
+    return p, seed
+
+
+def _f32c16(t: torch.Tensor, name: str) -> torch.Tensor:
+    """contiguous fp32 CUDA, 16-byte aligned: a view that is not (a column slice, an odd storage offset) is copied once"""
+    t = _f32c(t, name)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def dropout_keep_mask(seed: int, site: int, shape, p: float, device=None) -> torch.Tensor:
+    """The bool keep-mask the encoder kernels use for a tensor of `shape` at dropout site `site`, computed on the device by
+    the same device function (dropout_keep4): element e (flat, row-major) is kept when word e % 4 of
+    Philox4x32-10(counter = (e // 4, site, 0), key = seed) is >= floor(float32(p) * 2^32).  Not torch's mask stream."""
+    shape = tuple(int(s) for s in shape)
+    dev = torch.device("cuda") if device is None else torch.device(device)
+    out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if out.numel():
+        check(lib.m355_dfine_dropout_mask(out.numel(), float(p), int(seed), int(site), _ptr(out), _stream()))
+    return out.bool()
+
+
+class _SelfAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, n_heads, p, seed, site):
+        x = _f32c16(qkv, "qkv")
+        out, lse = _attn_forward(x, n_heads, p, seed, site, True)
+        ctx.save_for_backward(x, out, lse)   # the packed projection, the output and per-row statistics: no probabilities, no mask
+        ctx.meta = (n_heads, p, seed, site, qkv.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, lse = ctx.saved_tensors
+        n_heads, p, seed, site, dtype = ctx.meta
+        B, S, _ = x.shape
+        g = _f32c16(grad_out, "grad_output")
+        gx = torch.empty_like(x)
+        check(lib.m355_dfine_attn_backward(_ptr(g), _ptr(x), _ptr(out), _ptr(lse), B, S, n_heads, ENCODER_HEAD_DIM, p, seed, site,
+                                           _ptr(gx), _stream()))
+        return gx.to(dtype), None, None, None, None
+
+
+def _attn_forward(x, n_heads, p, seed, site, keep_stats: bool):
+    B, S, _ = x.shape
+    out = torch.empty((B, S, n_heads * ENCODER_HEAD_DIM), dtype=torch.float32, device=x.device)
+    lse = torch.empty((B, n_heads, S, 2), dtype=torch.float32, device=x.device) if keep_stats else None   # (max, log2 sum)
+    check(lib.m355_dfine_attn_forward(_ptr(x), B, S, n_heads, ENCODER_HEAD_DIM, p, seed, site, _ptr(out), _ptr(lse), _stream()))
+    return out, lse
+
+
+def self_attention(qkv: torch.Tensor, n_heads: int, dropout_p: float = 0.0, seed=None, site: int = SITE_ATTN) -> torch.Tensor:
+    """The core of nn.MultiheadAttention for head dim 32: qkv (B, S, 3 D), D = 32 * n_heads, exactly what
+    F.linear(x, in_proj_weight, in_proj_bias) leaves (head h's q, k, v at columns 32 h, D + 32 h, 2 D + 32 h, read through
+    strides) -> softmax(q k^T / sqrt(32)) [dropout on the probabilities] v as (B, S, D), the layout out_proj reads.  ONE launch
+    forward, one backward; the S x S scores never reach memory and only the per-row log-sum-exp (B, H, S, held as the pair
+    maximum, log2 of the sum) and the output are kept for the backward.  A qkv that is not contiguous (or not 16-byte aligned) is copied first.  dropout_p > 0 with seed=None draws
+    a seed from torch.default_generator on the host."""
+    if qkv.dim() != 3 or n_heads < 1 or qkv.shape[-1] != 3 * ENCODER_HEAD_DIM * n_heads:
+        raise ValueError(f"qkv must be (B, S, 3 * {ENCODER_HEAD_DIM} * n_heads): the kernel takes head dim {ENCODER_HEAD_DIM} only")
+    if qkv.shape[0] < 1 or qkv.shape[1] < 1:
+        raise ValueError("qkv must have at least one frame and one token")
+    p, seed = _dropout_args(dropout_p, seed)
+    if _wants_grad(qkv):
+        return _SelfAttention.apply(qkv, int(n_heads), p, seed, int(site))
+    return _attn_forward(_f32c16(qkv, "qkv"), int(n_heads), p, seed, int(site), False)[0]
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, weight, bias, eps, p, seed, site):
+        xs, ys, w, b = _f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias")
+        out, mean, rstd = _addln_forward(xs, ys, w, b, eps, p, seed, site)
+        ctx.save_for_backward(xs, ys, w, mean, rstd)
+        ctx.meta = (p, seed, site, [(t.shape, t.dtype) for t in (x, y, weight, bias)])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xs, ys, w, mean, rstd = ctx.saved_tensors
+        p, seed, site, like = ctx.meta
+        D = xs.shape[-1]
+        M = xs.numel() // D
+        need = ctx.needs_input_grad
+        g = _f32c16(grad_out, "grad_output")
+        gx, gy = _grad_like(need[0], xs), _grad_like(need[1], ys)
+        gw = torch.empty(D, dtype=torch.float32, device=xs.device) if need[2] else None
+        gb = torch.empty(D, dtype=torch.float32, device=xs.device) if need[3] else None
+        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D))
+        work = torch.empty(wbytes, dtype=torch.uint8, device=xs.device)
+        check(lib.m355_dfine_addln_backward(_ptr(g), _ptr(xs), _ptr(ys), _ptr(w), _ptr(mean), _ptr(rstd), M, D, p, seed, site, _ptr(gx),
+                                            _ptr(gy), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
+        return tuple(_as_input(t, *sd) for t, sd in zip((gx, gy, gw, gb), like)) + (None, None, None, None)
+
+
+def _addln_forward(xs, ys, w, b, eps, p, seed, site):
+    D = xs.shape[-1]
+    M = xs.numel() // D
+    out = torch.empty_like(xs)
+    mean = torch.empty(M, dtype=torch.float32, device=xs.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=xs.device)
+    check(lib.m355_dfine_addln_forward(_ptr(xs), _ptr(ys), _ptr(w), _ptr(b), M, D, float(eps), p, seed, site, _ptr(out), _ptr(mean),
+                                       _ptr(rstd), _stream()))
+    return out, mean, rstd
+
+
+def add_layer_norm(x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, dropout_p: float = 0.0,
+                   seed=None, site: int = SITE_ATTN_OUT) -> torch.Tensor:
+    """LayerNorm(x + dropout(y)) over the last axis (D a multiple of 4, at most 1024) in one pass: the residual, the dropout of
+    the branch and the normalisation that torch runs as separate launches.  Differentiable in x, y, weight and bias; the
+    backward recomputes the mask and the normalised rows from x, y and the saved per-row mean and rstd, and sums dweight and
+    dbias in a fixed order (two launches)."""
+    D = x.shape[-1] if x.dim() else 0
+    if x.dim() < 1 or x.shape != y.shape or tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
+        raise ValueError("x and y must have one shape (..., D), weight and bias the shape (D,)")
+    if D < 4 or D % 4 or D > ADDLN_MAX_D or x.numel() == 0:
+        raise ValueError(f"add_layer_norm takes a non-empty x with D a multiple of 4 in [4, {ADDLN_MAX_D}]")
+    p, seed = _dropout_args(dropout_p, seed)
+    if _wants_grad(x, y, weight, bias):
+        return _AddLayerNorm.apply(x, y, weight, bias, float(eps), p, seed, int(site))
+    return _addln_forward(_f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, p, seed,
+                          int(site))[0]
+
+
+class _ReluDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, p, seed, site):
+        out = _relu_dropout_forward(_f32c16(h, "h"), p, seed, site)
+        ctx.save_for_backward(out)
+        ctx.meta = (p, seed, site, h.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (out,) = ctx.saved_tensors
+        p, seed, site, dtype = ctx.meta
+        g = _f32c16(grad_out, "grad_output")
+        gh = torch.empty_like(out)
+        check(lib.m355_dfine_relu_dropout_backward(_ptr(g), _ptr(out), out.numel(), p, seed, site, _ptr(gh), _stream()))
+        return gh.to(dtype), None, None, None
+
+
+def _relu_dropout_forward(hs, p, seed, site):
+    out = torch.empty_like(hs)
+    check(lib.m355_dfine_relu_dropout_forward(_ptr(hs), hs.numel(), p, seed, site, _ptr(out), _stream()))
+    return out
+
+
+def relu_dropout(h: torch.Tensor, dropout_p: float = 0.0, seed=None, site: int = SITE_FFN) -> torch.Tensor:
+    """dropout(relu(h)) in one elementwise launch; the backward (one launch) recomputes the mask and reads the sign of the
+    saved output, the only tensor kept."""
+    if h.numel() == 0:
+        raise ValueError("relu_dropout takes a non-empty tensor")
+    p, seed = _dropout_args(dropout_p, seed)
+    if _wants_grad(h):
+        return _ReluDropout.apply(h, p, seed, int(site))
+    return _relu_dropout_forward(_f32c16(h, "h"), p, seed, int(site))
+
+
+def _layer_is_kernel_shaped(layer) -> bool:
+    """the module's own settings: post-norm, ReLU, batch_first, one packed in-projection, head dim 32, affine LayerNorms"""
+    F = torch.nn.functional
+    attn, act = layer.self_attn, layer.activation
+    if layer.norm_first or not (act is F.relu or isinstance(act, torch.nn.ReLU)) or not getattr(attn, "batch_first", False):
+        return False
+    if not attn._qkv_same_embed_dim or attn.in_proj_weight is None or attn.bias_k is not None or attn.add_zero_attn:
+        return False
+    D = attn.embed_dim
+    if attn.head_dim != ENCODER_HEAD_DIM or D > ADDLN_MAX_D:
+        return False
+    return all(isinstance(n, torch.nn.LayerNorm) and tuple(n.normalized_shape) == (D,) and n.weight is not None and n.bias is not None
+               for n in (layer.norm1, layer.norm2))
+
+
+def _encoder_layer_takes(layer, src, src_mask, src_key_padding_mask, is_causal) -> bool:
+    """True when the kernels cover this call of an nn.TransformerEncoderLayer; anything else goes to torch's forward"""
+    if src_mask is not None or src_key_padding_mask is not None or is_causal:
+        return False
+    if src.is_nested or src.dim() != 3 or not src.is_cuda or src.dtype != torch.float32 or src.numel() == 0:
+        return False
+    if torch.is_autocast_enabled() or not _layer_is_kernel_shaped(layer) or src.shape[-1] != layer.self_attn.embed_dim:
+        return False
+    return all(p.is_cuda and p.dtype == torch.float32 for p in layer.parameters())
+
+
+def encoder_layer_forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False):
+    """nn.TransformerEncoderLayer.forward for the post-norm ReLU layer with head dim 32 on fp32 CUDA tensors: the four nn.Linear
+    products are torch GEMMs on the module's own parameters, everything between them is three kernel-backed ops,
+        x = add_layer_norm(x, out_proj(self_attention(in_proj(x))), norm1)
+        x = add_layer_norm(x, linear2(relu_dropout(linear1(x))), norm2)
+    with dropout (the module's own probabilities, one host-drawn seed per op) only when self.training.  A mask or padding mask,
+    is_causal, norm_first=True, another activation, batch_first=False, head dim != 32, non-fp32 or CPU tensors and autocast go
+    to the class's own forward, untouched.  Bound per instance by bind_encoder."""
+    if not _encoder_layer_takes(self, src, src_mask, src_key_padding_mask, is_causal):
+        encoder_calls["torch"] += 1
+        return type(self).forward(self, src, src_mask=src_mask, src_key_padding_mask=src_key_padding_mask, is_causal=is_causal)
+    encoder_calls["kernel"] += 1
+    F = torch.nn.functional
+    attn = self.self_attn
+    train = self.training
+    qkv = F.linear(src, attn.in_proj_weight, attn.in_proj_bias)
+    a = self_attention(qkv, attn.num_heads, attn.dropout if train else 0.0, site=SITE_ATTN)
+    y = F.linear(a, attn.out_proj.weight, attn.out_proj.bias)
+    x = add_layer_norm(src, y, self.norm1.weight, self.norm1.bias, self.norm1.eps, self.dropout1.p if train else 0.0,
+                       site=SITE_ATTN_OUT)
+    h = relu_dropout(F.linear(x, self.linear1.weight, self.linear1.bias), self.dropout.p if train else 0.0, site=SITE_FFN)
+    y = F.linear(h, self.linear2.weight, self.linear2.bias)
+    return add_layer_norm(x, y, self.norm2.weight, self.norm2.bias, self.norm2.eps, self.dropout2.p if train else 0.0,
+                          site=SITE_FFN_OUT)
+
+
+def bind_encoder(encoder):
+    """Set encoder_layer_forward on every nn.TransformerEncoderLayer INSTANCE inside `encoder` (an nn.TransformerEncoder, a
+    single layer, or any module that holds some); torch's class is never touched, parameters, buffers and the state dict stay as
+    they are, so existing checkpoints load unchanged.  Returns `encoder`."""
+    import types
+    for m in encoder.modules():
+        if isinstance(m, torch.nn.TransformerEncoderLayer):
+            m.forward = types.MethodType(encoder_layer_forward, m)
+    return encoder

@@ -719,6 +719,48 @@ int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, c
                              float temperature, const float* d_saved, float* d_grad_logits, float* d_grad_pred_boxes,
                              float* d_grad_pred_corners, void* stream);
 
+/* ---- The temporal encoder layer of the D-FINE trainers, between its GEMMs ----------------------------------------------
+ * nn.TransformerEncoderLayer(d_model = 32 * heads, post-norm, ReLU, batch_first) with the nn.Linear layers left to the caller:
+ *   x1  = addln(x,  out_proj(attn(in_proj(x))), norm1)
+ *   out = addln(x1, linear2(relu_dropout(linear1(x1))), norm2)
+ * All tensors contiguous fp32 on the device, 16-byte aligned; fp32 accumulation; asynchronous on `stream`; no float atomics:
+ * bitwise reproducible, and row / frame b of a batch gives the bits of the same row / frame alone.
+ * Dropout (p, seed, site): element e of a site's tensor (flat row-major index) is kept when word e % 4 of
+ * Philox4x32-10(counter = (e / 4 lo, e / 4 hi, site, 0), key = (seed lo, seed hi)) is >= floor(p * 2^32), and a kept value is
+ * scaled by 1 / (1 - p).  The backward recomputes the mask from the same three numbers; no mask is stored.  p = 0 runs the
+ * kernels built without the generator.  m355_dfine_dropout_mask writes that mask (n bytes, 0 / 1) with the same device function.
+ *
+ * m355_dfine_attn_forward: qkv (B, S, 3 D), D = 32 heads, exactly F.linear(x, in_proj_weight, in_proj_bias): head h reads q, k, v at
+ *   columns 32 h, D + 32 h, 2 D + 32 h.  out (B, S, D) = softmax(q k^T / sqrt(32)) [dropout on the (B, heads, S, S) probabilities] v
+ *   in the layout out_proj reads; lse (B, heads, S, 2), the log-sum-exp of each row's logits * log2(e) as the pair (maximum,
+ *   log2 of the sum of exp2(logit - maximum)), or NULL when nothing is kept for a backward.  The scores never reach memory.
+ * m355_dfine_attn_backward: grad_qkv (B, S, 3 D), every element written, from grad_out, qkv, out and lse (probabilities recomputed;
+ *   dK / dV summed by the block that owns the key rows, dQ by the block that owns the query rows).
+ * m355_dfine_addln_forward: out (M, D) = LayerNorm(x + dropout(y)) * weight + bias over the last axis (biased variance, eps inside
+ *   the root); mean, rstd (M) are written for the backward.
+ * m355_dfine_addln_backward: grad_x, grad_y (M, D), grad_weight, grad_bias (D); any of the four may be NULL.  The two parameter
+ *   gradients are column sums in a fixed order (partial rows per block in work, then one ordered pass): two launches.
+ *   work: m355_dfine_addln_workspace_bytes(M, D) bytes.
+ * m355_dfine_relu_dropout_forward: out (n) = dropout(relu(h)).  _backward: grad_h = grad_out * 1 / (1 - p) where the mask keeps
+ *   the element and the forward's output is positive, else 0.
+ * Limits, checked on the host before any HIP call (M355_ERR_INVALID): no NULL among the required pointers, 16-byte alignment,
+ * head_dim == 32, B and heads in [1, 65535], S >= 1, M >= 1, D a multiple of 4 in [4, 1024], n >= 1, p in [0, 1), site >= 0,
+ * the workspace size. */
+int m355_dfine_attn_forward(const float* d_qkv, int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, uint64_t seed,
+                            int32_t site, float* d_out, float* d_lse, void* stream);
+int m355_dfine_attn_backward(const float* d_grad_out, const float* d_qkv, const float* d_out, const float* d_lse, int32_t B, int32_t S,
+                             int32_t H, int32_t head_dim, float p, uint64_t seed, int32_t site, float* d_grad_qkv, void* stream);
+size_t m355_dfine_addln_workspace_bytes(int64_t M, int32_t D);
+int m355_dfine_addln_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
+                             float eps, float p, uint64_t seed, int32_t site, float* d_out, float* d_mean, float* d_rstd, void* stream);
+int m355_dfine_addln_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight, const float* d_mean,
+                              const float* d_rstd, int64_t M, int32_t D, float p, uint64_t seed, int32_t site, float* d_grad_x,
+                              float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work, int64_t work_bytes, void* stream);
+int m355_dfine_relu_dropout_forward(const float* d_h, int64_t n, float p, uint64_t seed, int32_t site, float* d_out, void* stream);
+int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out, int64_t n, float p, uint64_t seed, int32_t site,
+                                     float* d_grad_h, void* stream);
+int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
