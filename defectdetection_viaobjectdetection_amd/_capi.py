@@ -186,6 +186,11 @@ SIGNATURES = {
     "m355_dfine_relu_dropout_forward": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
     "m355_dfine_relu_dropout_backward": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
     "m355_dfine_dropout_mask": (C.c_int, [C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
+    "m355_dfine_gru_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "m355_dfine_gru_forward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32,
+                                         _P, _P]),
+    "m355_dfine_gru_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,
+                                          _P, _P]),
     "m355_repack_launch": (C.c_int, [_P, _P, C.c_int32, _P]),
     "m355_sppf_pool_bwd_launch": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -188,6 +188,15 @@ int launch_msda_backward(const float* grad_out, const float* value, const float*
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
                                  hipStream_t s);
+// The recurrence of a one-layer GRU with hidden size 256 (dfine_gru.hip): every chain (sequence x direction) on 8 persistent
+// workgroups, one launch each way.  dfine_gru_check: nullptr = the shape is taken, else why not.  work: the exchange ring first
+// (zeroed on the stream by the launchers), then the saved gates when `keep` / in the backward; status: one sticky int32.
+const char* dfine_gru_check(int B, long S, int H, int D);
+size_t dfine_gru_workspace_bytes(int B, long S, int H, int D);   // S == 0: the ring alone
+int launch_dfine_gru_forward(const float* gi, const float* w_hh, const float* b_hh, const float* h0, int B, int S, int D, float* out,
+                             float* h_n, void* work, bool keep, int* status, hipStream_t s);
+int launch_dfine_gru_backward(const float* gout, const float* gh_n, const float* w_hh, const float* h0, const float* out, int B, int S,
+                              int D, float* ggi, float* gan, float* gh0, void* work, int* status, hipStream_t s);
 // 1x1, K <= 512, Cout % 128 == 0: weights in registers, persistent (conv1x1_wreg.hip)
 bool conv1x1_wreg_ok(const ConvArgs& a);
 int launch_conv1x1_wreg(const ConvArgs& a, hipStream_t s);

@@ -1060,6 +1060,37 @@ int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uin
   const int rc = m355::launch_dfine_keep_mask(d_mask, n, p, seed, site, (hipStream_t)stream);
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_dropout_mask launch failed: " + std::to_string(rc));
 }
+// ---- the GRU recurrence (dfine_gru.hip); every argument before any HIP call
+size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return m355::dfine_gru_workspace_bytes(B, S, H, D); }
+int m355_dfine_gru_forward(const float* d_gi, const float* d_w_hh, const float* d_b_hh, const float* d_h0, int32_t B, int64_t S,
+                           int32_t H, int32_t D, float* d_out, float* d_h_n, void* d_work, int64_t work_bytes, int32_t keep,
+                           int32_t* d_status, void* stream) {
+  if (!d_gi || !d_w_hh || !d_b_hh || !d_out || !d_h_n || !d_work || !d_status) return set_err(M355_ERR_INVALID, "dfine_gru_forward: null pointer");
+  if (const char* why = m355::dfine_gru_check(B, S, H, D)) return set_err(M355_ERR_INVALID, std::string("dfine_gru_forward: ") + why);
+  if (work_bytes < 0 || (size_t)work_bytes < m355::dfine_gru_workspace_bytes(B, keep ? S : 0, H, D))
+    return set_err(M355_ERR_INVALID, "dfine_gru_forward: workspace smaller than m355_dfine_gru_workspace_bytes");
+  if (misaligned16(d_gi) || misaligned16(d_w_hh) || misaligned16(d_b_hh) || misaligned16(d_h0) || misaligned16(d_out) ||
+      misaligned16(d_h_n) || misaligned16(d_work) || ((uintptr_t)d_status & 3u))
+    return set_err(M355_ERR_INVALID, "dfine_gru_forward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_gru_forward(d_gi, d_w_hh, d_b_hh, d_h0, B, (int)S, D, d_out, d_h_n, d_work, keep != 0, d_status,
+                                                (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_gru_forward launch failed: " + std::to_string(rc));
+}
+int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, const float* d_w_hh, const float* d_h0, const float* d_out,
+                            int32_t B, int64_t S, int32_t H, int32_t D, float* d_grad_gi, float* d_grad_an, float* d_grad_h0,
+                            void* d_work, int64_t work_bytes, int32_t* d_status, void* stream) {
+  if (!d_grad_out || !d_w_hh || !d_out || !d_grad_gi || !d_grad_an || !d_grad_h0 || !d_work || !d_status)
+    return set_err(M355_ERR_INVALID, "dfine_gru_backward: null pointer");
+  if (const char* why = m355::dfine_gru_check(B, S, H, D)) return set_err(M355_ERR_INVALID, std::string("dfine_gru_backward: ") + why);
+  if (work_bytes < 0 || (size_t)work_bytes < m355::dfine_gru_workspace_bytes(B, S, H, D))
+    return set_err(M355_ERR_INVALID, "dfine_gru_backward: workspace smaller than m355_dfine_gru_workspace_bytes");
+  if (misaligned16(d_grad_out) || misaligned16(d_grad_h_n) || misaligned16(d_w_hh) || misaligned16(d_h0) || misaligned16(d_out) ||
+      misaligned16(d_grad_gi) || misaligned16(d_grad_an) || misaligned16(d_grad_h0) || misaligned16(d_work) || ((uintptr_t)d_status & 3u))
+    return set_err(M355_ERR_INVALID, "dfine_gru_backward: pointers must be 16-byte aligned");
+  const int rc = m355::launch_dfine_gru_backward(d_grad_out, d_grad_h_n, d_w_hh, d_h0, d_out, B, (int)S, D, d_grad_gi, d_grad_an,
+                                                 d_grad_h0, d_work, d_status, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_gru_backward launch failed: " + std::to_string(rc));
+}
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");

@@ -25,6 +25,10 @@ scaled xyxy boxes and the threshold in one launch for a whole sequence of frames
 encoder the D-FINE trainers train (``nn.TransformerEncoderLayer``, post-norm, ReLU, head dim 32) between its torch GEMMs:
 attention core with online softmax on the packed in-projection output, LayerNorm(x + dropout(y)) and dropout(relu(h)), each
 with a HIP backward, and a counter-based dropout mask that the backward recomputes (``dropout_keep_mask`` shows it).
+
+``gru_recurrence`` / ``gru_forward`` / ``bind_gru`` / ``gru_status`` are the context GRU of the improved trainer
+(``nn.GRU(256, 256, batch_first=True, bidirectional=True)`` on one sequence of T * Q steps): the input projection is one torch
+GEMM, the serial chain of both directions one persistent launch forward and one backward (csrc/dfine_gru.hip).
 """
 from __future__ import annotations
 
@@ -1067,3 +1071,162 @@ def bind_encoder(encoder):
         if isinstance(m, torch.nn.TransformerEncoderLayer):
             m.forward = types.MethodType(encoder_layer_forward, m)
     return encoder
+
+
+# ---- the context GRU of the improved temporal trainer (nn.GRU(256, 256, batch_first, bidirectional) on ONE sequence of T * Q steps)
+# The input projection stays one torch GEMM for all steps and both directions; the serial chain is csrc/dfine_gru.hip.
+GRU_HIDDEN = 256
+GRU_MAX_BATCH = 8
+gru_calls = {"kernel": 0, "torch": 0}   # how many gru_forward calls took which path (tests and tools read it)
+_gru_status_words = {}                  # device index -> the int32 word the kernels OR their give-up bit into
+
+
+def _gru_status_word(device: torch.device) -> torch.Tensor:
+    word = _gru_status_words.get(device.index)
+    if word is None:
+        # zeroed on the host and copied synchronously once, so that no stream can meet the word before its zero
+        word = _gru_status_words[device.index] = torch.zeros(1, dtype=torch.int32).to(device)
+        torch.cuda.synchronize(device)
+    return word
+
+
+def gru_status() -> int:
+    """0, or the OR of the give-up bits the GRU kernels have set on any device since import (1: a forward workgroup, 2: a backward
+    workgroup stopped waiting for its chain's other workgroups and wrote NaN to the rest of its outputs).  One synchronising
+    read per device that ran the kernels, on demand; nothing else reads the word."""
+    bits = 0
+    for word in _gru_status_words.values():
+        bits |= int(word[0].item())
+    return bits
+
+
+def _gru_work(B: int, S: int, D: int, device) -> torch.Tensor:
+    return torch.empty(int(lib.m355_dfine_gru_workspace_bytes(B, S, GRU_HIDDEN, D)), dtype=torch.uint8, device=device)
+
+
+def _gru_forward(gi, w_hh, b_hh, h0, keep: bool):
+    """contiguous aligned fp32 CUDA tensors -> out, h_n and the workspace (the saved gates behind the exchange area when keep)"""
+    B, S, _ = gi.shape
+    D = w_hh.shape[0]
+    out = torch.empty((B, S, D * GRU_HIDDEN), dtype=torch.float32, device=gi.device)
+    h_n = torch.empty((D, B, GRU_HIDDEN), dtype=torch.float32, device=gi.device)
+    work = _gru_work(B, S if keep else 0, D, gi.device)
+    check(lib.m355_dfine_gru_forward(_ptr(gi), _ptr(w_hh), _ptr(b_hh), _ptr(h0), B, S, GRU_HIDDEN, D, _ptr(out), _ptr(h_n), _ptr(work),
+                                     work.numel(), int(keep), _ptr(_gru_status_word(gi.device)), _stream()))
+    return out, h_n, work
+
+
+def _gru_h_prev(out, h0, B, S, D):
+    """(B, S, D, H): the state each step started from, by time index (direction 1 reads the step after it)"""
+    o = out.view(B, S, D, GRU_HIDDEN)
+    hp = torch.empty_like(o)
+    hp[:, 1:, 0] = o[:, :-1, 0]
+    hp[:, 0, 0] = h0[0] if h0 is not None else 0.0
+    if D == 2:
+        hp[:, :-1, 1] = o[:, 1:, 1]
+        hp[:, -1, 1] = h0[1] if h0 is not None else 0.0
+    return hp
+
+
+class _GruRecurrence(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, h0):
+        g, w, b = _f32c16(gi, "gi"), _f32c16(w_hh, "weight_hh"), _f32c16(b_hh, "bias_hh")
+        h = None if h0 is None else _f32c16(h0, "h0")
+        out, h_n, work = _gru_forward(g, w, b, h, True)
+        ctx.save_for_backward(w, h, out, work)   # the gates live in work; gi itself is not kept
+        ctx.meta = [(t.shape, t.dtype) if t is not None else None for t in (gi, w_hh, b_hh, h0)]
+        ctx.set_materialize_grads(False)
+        return out, h_n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, grad_h_n):
+        w, h0, out, work = ctx.saved_tensors
+        B, S, DH = out.shape
+        H = GRU_HIDDEN
+        D = DH // H
+        need = ctx.needs_input_grad
+        g = _f32c16(grad_out, "grad_output") if grad_out is not None else torch.zeros_like(out)
+        gh = _f32c16(grad_h_n, "grad_h_n") if grad_h_n is not None else None
+        ggi = torch.empty((B, S, D * 3 * H), dtype=torch.float32, device=out.device)
+        gan = torch.empty((B, S, D * H), dtype=torch.float32, device=out.device)
+        gh0 = torch.empty((D, B, H), dtype=torch.float32, device=out.device)
+        check(lib.m355_dfine_gru_backward(_ptr(g), _ptr(gh), _ptr(w), _ptr(h0), _ptr(out), B, S, H, D, _ptr(ggi), _ptr(gan), _ptr(gh0),
+                                          _ptr(work), work.numel(), _ptr(_gru_status_word(out.device)), _stream()))
+        gw = gb = None
+        if need[1] or need[2]:
+            ga = ggi.view(B, S, D, 3 * H).clone()      # what W_hh saw: the n-part carries the reset gate
+            ga[..., 2 * H:] = gan.view(B, S, D, H)
+            if need[2]:
+                gb = ga.sum(dim=(0, 1))
+            if need[1]:
+                hp = _gru_h_prev(out, h0, B, S, D)
+                gw = torch.stack([ga[:, :, d].reshape(B * S, 3 * H).t() @ hp[:, :, d].reshape(B * S, H) for d in range(D)])
+        grads = (ggi if need[0] else None, gw, gb, gh0 if need[3] else None)
+        return tuple(_as_input(t, *sd) if sd is not None else None for t, sd in zip(grads, ctx.meta))
+
+
+def gru_recurrence(gi: torch.Tensor, weight_hh: torch.Tensor, bias_hh: torch.Tensor, h0=None):
+    """The serial part of torch's one-layer GRU with hidden size 256: gi (B, S, D * 768) = the input-side pre-activations of all
+    steps (x @ cat(W_ih, W_ih_reverse).T + b_ih; gate order r, z, n; direction 1 in the second half of the last axis),
+    weight_hh (D, 768, 256), bias_hh (D, 768), h0 (D, B, 256) or None -> out (B, S, D * 256), h_n (D, B, 256); D in {1, 2},
+    B <= 8.  ONE launch forward and one backward for all chains; differentiable in all four inputs (grad_weight_hh and
+    grad_bias_hh are one GEMM and one column sum over what the backward kernel stored).  With nothing to differentiate no gate
+    is saved.  A gi that is not contiguous (or not 16-byte aligned) is copied first."""
+    H = GRU_HIDDEN
+    if weight_hh.dim() != 3 or weight_hh.shape[0] not in (1, 2) or tuple(weight_hh.shape[1:]) != (3 * H, H):
+        raise ValueError(f"weight_hh must be (D, {3 * H}, {H}) with D in (1, 2): the kernel takes hidden size {H} only")
+    D = weight_hh.shape[0]
+    if tuple(bias_hh.shape) != (D, 3 * H):
+        raise ValueError(f"bias_hh must be (D, {3 * H})")
+    if gi.dim() != 3 or gi.shape[2] != D * 3 * H or gi.shape[1] < 1 or not 1 <= gi.shape[0] <= GRU_MAX_BATCH:
+        raise ValueError(f"gi must be (B, S, D * {3 * H}) with 1 <= B <= {GRU_MAX_BATCH} and S >= 1")
+    if h0 is not None and tuple(h0.shape) != (D, gi.shape[0], H):
+        raise ValueError(f"h0 must be (D, B, {H})")
+    if _wants_grad(gi, weight_hh, bias_hh, *(() if h0 is None else (h0,))):
+        return _GruRecurrence.apply(gi, weight_hh, bias_hh, h0)
+    out, h_n, _ = _gru_forward(_f32c16(gi, "gi"), _f32c16(weight_hh, "weight_hh"), _f32c16(bias_hh, "bias_hh"),
+                               None if h0 is None else _f32c16(h0, "h0"), False)
+    return out, h_n
+
+
+def _gru_takes(gru, input, hx) -> bool:
+    """True when the kernel covers this call of an nn.GRU; anything else goes to torch's forward"""
+    if not torch.is_tensor(input) or input.dim() != 3 or not input.is_cuda or input.dtype != torch.float32:
+        return False
+    if gru.num_layers != 1 or not gru.batch_first or not gru.bias or gru.hidden_size != GRU_HIDDEN or getattr(gru, "proj_size", 0):
+        return False
+    if torch.is_autocast_enabled() or input.shape[2] != gru.input_size or input.shape[1] < 1 or not 1 <= input.shape[0] <= GRU_MAX_BATCH:
+        return False
+    D = 2 if gru.bidirectional else 1
+    if hx is not None and not (torch.is_tensor(hx) and hx.is_cuda and hx.dtype == torch.float32
+                               and tuple(hx.shape) == (D, input.shape[0], GRU_HIDDEN)):
+        return False
+    return all(p.is_cuda and p.dtype == torch.float32 for p in gru.parameters())
+
+
+def gru_forward(self, input, hx=None):
+    """nn.GRU.forward (same arguments, same (output, h_n)) for one layer, batch_first, hidden size 256, uni- or bidirectional, on a
+    3-d fp32 CUDA input with B <= 8: one torch GEMM on the module's own weight_ih / bias_ih for all steps and both directions,
+    then gru_recurrence.  num_layers > 1 (and its dropout), proj_size, bias=False, batch_first=False, a PackedSequence, a 2-d
+    input, another hidden size, non-fp32 or CPU tensors and autocast go to the class's own forward, untouched.  Bound per
+    instance by bind_gru."""
+    if not _gru_takes(self, input, hx):
+        gru_calls["torch"] += 1
+        return type(self).forward(self, input, hx)
+    gru_calls["kernel"] += 1
+    sfx = ("", "_reverse") if self.bidirectional else ("",)
+    par = lambda name: [getattr(self, f"{name}_l0{s}") for s in sfx]
+    gi = torch.nn.functional.linear(input, torch.cat(par("weight_ih")), torch.cat(par("bias_ih")))
+    return gru_recurrence(gi, torch.stack(par("weight_hh")), torch.stack(par("bias_hh")), hx)
+
+
+def bind_gru(module):
+    """Set gru_forward on every nn.GRU INSTANCE inside `module` (an nn.GRU or any module that holds some); torch's class is never
+    touched, parameters and the state dict stay as they are, so existing checkpoints load unchanged.  Returns `module`."""
+    import types
+    for m in module.modules():
+        if isinstance(m, torch.nn.GRU):
+            m.forward = types.MethodType(gru_forward, m)
+    return module

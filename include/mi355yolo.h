@@ -761,6 +761,38 @@ int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out
                                      float* d_grad_h, void* stream);
 int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream);
 
+/* ---- The recurrence of the D-FINE trainer's context GRU -----------------------------------------------------------------
+ * torch's one-layer nn.GRU(*, 256, batch_first, uni- or bidirectional) without its input projection: the caller's GEMM gives
+ * gi = x cat(W_ih, W_ih_reverse)^T + b_ih for all steps and both directions; these entries run the serial chain.  Gate order
+ * r, z, n;  a = W_hh h_{t-1} + b_hh;  r = s(gi_r + a_r), z = s(gi_z + a_z), n = tanh(gi_n + r a_n), h_t = (1 - z) n + z h_{t-1};
+ * direction 1 walks t = S - 1 .. 0 with its own parameters.  All tensors contiguous fp32 on the device, 16-byte aligned;
+ * asynchronous on `stream`; no float atomics: bitwise reproducible, and sequence b of a batch gives the bits of the same
+ * sequence alone.  H = 256, D = directions.
+ *
+ * m355_dfine_gru_forward: gi (B, S, D 3H), w_hh (D, 3H, H), b_hh (D, 3H), h0 (D, B, H) or NULL (zeros) -> out (B, S, D H) =
+ *   cat(forward, reverse) per step, h_n (D, B, H).  ONE launch for all B D chains: each chain runs on 8 workgroups that keep a
+ *   32-unit slice of w_hh in registers and pass h_t to each other through `work`.  keep != 0 also stores r, z, n and a_n of
+ *   every step in work for the backward (16 H bytes per step and chain); keep == 0 writes nothing beyond the exchange area.
+ * m355_dfine_gru_backward: grad_out (B, S, D H), grad_h_n (D, B, H) or NULL, w_hh, h0 or NULL and out as in the forward, work as
+ *   the keep != 0 forward left it -> grad_gi (B, S, D 3H), grad_an (B, S, D H), grad_h0 (D, B, H), every element written.  The
+ *   gradient of a is grad_gi with its n-part replaced by grad_an; grad_w_hh[d] = sum_t grad_a[d]^T h_{t-1} and grad_b_hh are the
+ *   caller's GEMM and column sum.  ONE launch, the same split.
+ * work: m355_dfine_gru_workspace_bytes(B, S, H, D) bytes (S = 0 in this query, and only here: the size a keep == 0 forward
+ *   needs); 0 for a shape outside the limits.  Its head is the exchange area, zeroed on `stream` by both entries; one buffer
+ *   serves one call at a time.  status: one int32 the caller zeroes once.  A workgroup whose bounded wait for its chain's other
+ *   workgroups runs out writes NaN to the rest of its outputs, ORs 1 (forward) or 2 (backward) into *status and returns; nothing
+ *   else writes it and the library never reads it.
+ * Limits, checked on the host before any HIP call (M355_ERR_INVALID): H == 256, D in {1, 2}, B in [1, 8] (the grid is 64 or 128
+ *   workgroups, resident on any gfx950), S in [1, 2^24], no NULL among the required pointers, 16-byte alignment, the
+ *   workspace size. */
+size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D);
+int m355_dfine_gru_forward(const float* d_gi, const float* d_w_hh, const float* d_b_hh, const float* d_h0, int32_t B, int64_t S,
+                           int32_t H, int32_t D, float* d_out, float* d_h_n, void* d_work, int64_t work_bytes, int32_t keep,
+                           int32_t* d_status, void* stream);
+int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, const float* d_w_hh, const float* d_h0, const float* d_out,
+                            int32_t B, int64_t S, int32_t H, int32_t D, float* d_grad_gi, float* d_grad_an, float* d_grad_h0,
+                            void* d_work, int64_t work_bytes, int32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
