@@ -97,25 +97,37 @@ def _banded_input(t_nchw, dev):
     return d, d.data_ptr() + 2 * XGUARD
 
 
+def _guarded_output(nbytes, dtype, dev):
+    """A NaN-filled body of nbytes between two bands of GUARD bytes 0xA5.  Returns (the allocation, the body as a flat dtype view)."""
+    raw = torch.full((2 * GUARD + nbytes,), 0xA5, dtype=torch.uint8, device=dev)
+    body = raw[GUARD:GUARD + nbytes].view(dtype)
+    body.fill_(float("nan"))
+    return raw, body
+
+
+def _guards_intact(raw, what):
+    """Host copy of the body's bytes after asserting that no byte of either band changed."""
+    h = raw.cpu()
+    nbytes = h.numel() - 2 * GUARD
+    assert bool((h[:GUARD] == 0xA5).all()) and bool((h[GUARD + nbytes:] == 0xA5).all()), f"{what}: a byte around the output changed"
+    return h[GUARD:GUARD + nbytes]
+
+
 def _launch(capi, case, tile, xp, rp, w, b, out_shape, dev):
     """One call into a fresh guard-banded, NaN-filled output.  Returns (rc, output (B, cout, Ho, Wo) on the host or None)."""
     B, H, W, cin, cout, k, s, act, use_res, f32 = case
     dt = torch.float32 if f32 else torch.float16
     n = B * out_shape[2] * out_shape[3] * cout
-    nbytes = n * (4 if f32 else 2)
-    raw = torch.full((2 * GUARD + nbytes,), 0xA5, dtype=torch.uint8, device=dev)
-    body = raw[GUARD:GUARD + nbytes].view(dt)
-    body.fill_(float("nan"))
+    raw, body = _guarded_output(n * (4 if f32 else 2), dt, dev)
     rc = capi.lib.m355_conv2d_fwd(C.c_void_p(xp), B, H, W, cin, C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), cout, k, s, act,
                                   C.c_void_p(rp), C.c_void_p(body.data_ptr()), int(f32), tile,
                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    h = raw.cpu()
-    assert bool((h[:GUARD] == 0xA5).all()) and bool((h[GUARD + nbytes:] == 0xA5).all()), f"tile {tile} {case}: a byte around the output changed"
+    got = _guards_intact(raw, f"tile {tile} {case}").view(dt)
     if rc != 0:
-        assert bool(torch.isnan(h[GUARD:GUARD + nbytes].view(dt)).all()), f"tile {tile} {case}: rc {rc} but the output was written"
+        assert bool(torch.isnan(got).all()), f"tile {tile} {case}: rc {rc} but the output was written"
         return rc, None
-    return 0, h[GUARD:GUARD + nbytes].view(dt).reshape(B, out_shape[2], out_shape[3], cout).permute(0, 3, 1, 2)
+    return 0, got.reshape(B, out_shape[2], out_shape[3], cout).permute(0, 3, 1, 2)
 
 
 @pytest.mark.parametrize("tile", sorted(TILE_CASES))
