@@ -114,10 +114,10 @@ int launch_conv_s2c32_cv1(const ConvArgs& a, hipStream_t s);
 // narrow maps (W <= 26): slabs of full-width rows, linear pixel groups (conv3x3_small.hip)
 bool conv3x3_slab_ok(const ConvArgs& a);
 int launch_conv3x3_slab(const ConvArgs& a, hipStream_t s);
-// D-FINE decoder ops (dfine_kernels.hip)
-int launch_msda(const float* value, const float* loc, const float* attn, float* out, int B, int S, int H, int D, int Q, int P,
-                int L, const int* shapes_hw, const int* points_per_level, int discrete, hipStream_t s,
-                const float* ref = nullptr, float offset_scale = 0.f);
+// D-FINE decoder ops (dfine_kernels.hip), head_dim 32.  The caller (dfine_entries.hip) has validated every argument.
+struct MsdaLevels { int L; int lh[8], lw[8], lstart[8], pend[8]; };   // per level: height, width, first pixel, one past its last point
+int launch_msda(const float* value, const float* loc, const float* attn, float* out, int B, int S, int H, int Q, int P,
+                const MsdaLevels& lv, int discrete, hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f);
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
                         float reg_scale, int clamp01, hipStream_t s);
 // Hungarian matcher of the D-FINE loss (dfine_match.hip): cost matrix + assignment, one block per image.  The caller has
@@ -179,12 +179,13 @@ int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, l
                               hipStream_t s);
 int launch_dfine_keep_mask(unsigned char* mask, long n, float p, unsigned long long seed, int site, hipStream_t s);
 // their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
-// grad_value and the per-head partials of grad_ref.  -1 = refused before any launch, -3 = workspace missing / too small.
+// grad_value and the per-head partials of grad_ref (msda_backward_workspace_bytes, needed for those two only).  The caller has
+// validated every argument.  msda_backward_value_blocks: the grid of the grad_value pass and its ownership split (own, blk0[9]).
 size_t msda_backward_workspace_bytes(int B, int Q, int H, int P);
+long msda_backward_value_blocks(const MsdaLevels& lv, int B, int H, int* own, int* blk0);
 int launch_msda_backward(const float* grad_out, const float* value, const float* loc, const float* attn, float* grad_value,
-                         float* grad_loc, float* grad_attn, int B, int S, int H, int D, int Q, int P, int L,
-                         const int* shapes_hw, const int* points_per_level, int discrete, void* work, long long work_bytes,
-                         hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f, float* grad_ref = nullptr);
+                         float* grad_loc, float* grad_attn, int B, int S, int H, int Q, int P, const MsdaLevels& lv, int discrete,
+                         void* work, hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f, float* grad_ref = nullptr);
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
                                  hipStream_t s);

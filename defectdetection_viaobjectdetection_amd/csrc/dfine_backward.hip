@@ -298,57 +298,39 @@ size_t msda_backward_workspace_bytes(int B, int Q, int H, int P) {
   return list_bytes(B, Q, H, P) + (size_t)B * Q * H * sizeof(float4);   // contribution list + per-head partials of grad_ref
 }
 
+// ownership: the largest share per wave that still gives every CU a few blocks; the result does not depend on it
+long msda_backward_value_blocks(const MsdaLevels& lv, int B, int H, int* own, int* blk0) {
+  for (*own = kOwnMax; ; *own >>= 1) {
+    int per = 0;
+    for (int l = 0; l < lv.L; ++l) {
+      blk0[l] = per;
+      per += (int)(((long)lv.lh[l] * lv.lw[l] + 4 * *own - 1) / (4 * *own));
+    }
+    blk0[lv.L] = per;
+    const long blocks = (long)B * H * per;
+    if (blocks >= 1024 || *own == 8) return blocks;
+  }
+}
+
 int launch_msda_backward(const float* grad_out, const float* value, const float* loc, const float* attn, float* grad_value,
-                         float* grad_loc, float* grad_attn, int B, int S, int H, int D, int Q, int P, int L,
-                         const int* shapes_hw, const int* points_per_level, int discrete, void* work, long long work_bytes,
-                         hipStream_t s, const float* ref, float offset_scale, float* grad_ref) {
-  if (!grad_out || !value || !loc || !attn || !shapes_hw || !points_per_level) return -1;
-  if (ref && (P > 16 || discrete)) return -1;
-  if (!ref && grad_ref) return -1;
-  if (D != 32 || L < 1 || L > 8 || P < 1 || P > 32 || B < 1 || Q < 1 || H < 1) return -1;
-  if (4L * Q * P > 0x7fffffffL) return -1;   // entries of one (b, h) list are indexed with int
+                         float* grad_loc, float* grad_attn, int B, int S, int H, int Q, int P, const MsdaLevels& lv, int discrete,
+                         void* work, hipStream_t s, const float* ref, float offset_scale, float* grad_ref) {
   MsdaBwdArgs a{};
   a.grad_out = grad_out; a.value = value; a.loc = loc; a.attn = attn; a.ref = ref; a.offset_scale = offset_scale;
   a.grad_value = grad_value; a.grad_loc = grad_loc; a.grad_attn = grad_attn; a.grad_ref = grad_ref;
-  a.B = B; a.S = S; a.H = H; a.Q = Q; a.P = P; a.L = L; a.discrete = discrete;
-  int start = 0, pend = 0;
-  for (int l = 0; l < L; ++l) {
-    a.lh[l] = shapes_hw[2 * l]; a.lw[l] = shapes_hw[2 * l + 1];
-    if (a.lh[l] < 1 || a.lw[l] < 1 || points_per_level[l] < 0) return -1;
-    if ((long)a.lh[l] * a.lw[l] > 0x7fffffffL - start) return -1;
-    a.lstart[l] = start;
-    start += a.lh[l] * a.lw[l];
-    if (4L * Q * pend > 0x7fffffffL) return -1;
-    a.seg[l] = 4 * Q * pend;
-    pend += points_per_level[l];
-    a.pend[l] = pend;
+  a.B = B; a.S = S; a.H = H; a.Q = Q; a.P = P; a.L = lv.L; a.discrete = discrete;
+  for (int l = 0; l < lv.L; ++l) {
+    a.lh[l] = lv.lh[l]; a.lw[l] = lv.lw[l]; a.lstart[l] = lv.lstart[l]; a.pend[l] = lv.pend[l];
+    a.seg[l] = l ? 4 * Q * lv.pend[l - 1] : 0;
   }
-  if (start != S || pend != P) return -1;
-  if (grad_value || grad_ref) {
-    if (!work || work_bytes < (long long)msda_backward_workspace_bytes(B, Q, H, P)) return -3;
-    if (((uintptr_t)work & 15) != 0) return -1;
-    if (grad_value) a.list = (int2*)work;
-    if (grad_ref) a.ref_part = (float4*)((char*)work + list_bytes(B, Q, H, P));
-  }
+  if (grad_value) a.list = (int2*)work;
+  if (grad_ref) a.ref_part = (float4*)((char*)work + list_bytes(B, Q, H, P));
   const long ntriples = (long)B * Q * H;
-  if ((ntriples + 3) / 4 > 0x7fffffffL) return -1;
   if (grad_value || grad_loc || grad_attn || grad_ref)
     hipLaunchKernelGGL(msda_bwd_points_kernel, dim3((unsigned)((ntriples + 3) / 4)), dim3(256), 0, s, a);
   if (grad_ref) hipLaunchKernelGGL(msda_bwd_ref_kernel, dim3((unsigned)(((long)B * Q + 127) / 128)), dim3(128), 0, s, a);
   if (grad_value) {
-    // ownership: the largest share per wave that still gives every CU a few blocks; the result does not depend on it
-    long blocks = 0;
-    for (a.own = kOwnMax; ; a.own >>= 1) {
-      int per = 0;
-      for (int l = 0; l < L; ++l) {
-        a.blk0[l] = per;
-        per += (a.lh[l] * a.lw[l] + 4 * a.own - 1) / (4 * a.own);
-      }
-      a.blk0[L] = per;
-      blocks = (long)B * H * per;
-      if (blocks >= 1024 || a.own == 8) break;
-    }
-    if (blocks > 0x7fffffffL) return -1;
+    const long blocks = msda_backward_value_blocks(lv, B, H, &a.own, a.blk0);
     hipLaunchKernelGGL(msda_bwd_value_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
   }
   return (int)hipGetLastError();
@@ -357,7 +339,6 @@ int launch_msda_backward(const float* grad_out, const float* value, const float*
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
                                  hipStream_t s) {
-  if (!grad_boxes || !dist || !project || !ref || n < 0 || nbins1 < 2 || reg_scale == 0.f) return -1;
   if (n == 0 || (!grad_dist && !grad_ref)) return 0;
   hipLaunchKernelGGL(dfine_decode_bwd_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, grad_boxes, dist, project,
                      ref, grad_dist, grad_ref, n, nbins1, reg_scale, clamp01);

@@ -1,0 +1,331 @@
+// libmi355yolo.so C entries of the D-FINE ops (include/mi355yolo.h: m355_msda_*, m355_dfine_*) and their workspace queries.
+// Every entry validates on the host, before any HIP call and in this order: null pointers, shape and range (every grid dimension
+// that an argument decides included), workspace, alignment.  Then it launches and reports the launcher's HIP status; the
+// launchers (dfine_*.hip) validate nothing.  A refused call has queued nothing.
+#include <initializer_list>
+#include <string>
+
+#include "../../include/mi355yolo.h"
+#include "common.h"
+#include "weight_pack.h"
+
+using namespace m355;
+
+namespace {
+
+constexpr long kGridMax = 0x7fffffffL;   // blocks of one launch
+const char* const kAlign16 = "pointers must be 16-byte aligned";
+
+// fn: the entry's __func__; its messages carry that name without the "m355_"
+int invalid(const char* fn, const std::string& why) { return set_err(M355_ERR_INVALID, std::string(fn + 5) + ": " + why); }
+int launched(const char* fn, int rc) {
+  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, std::string(fn + 5) + " launch failed: " + std::to_string(rc));
+}
+bool any_null(std::initializer_list<const void*> ps) {
+  for (const void* p : ps) if (!p) return true;
+  return false;
+}
+bool any_misaligned16(std::initializer_list<const void*> ps) {   // nullptr (an optional tensor left out) counts as aligned
+  for (const void* p : ps) if ((uintptr_t)p & 15u) return true;
+  return false;
+}
+bool workspace_short(const void* work, int64_t bytes, size_t need) { return !work || bytes < 0 || (size_t)bytes < need; }
+
+// The level table of the msda kernels, forward and backward, from the caller's (h, w) pairs and points per level.
+// nullptr = accepted and lv filled, else the reason.
+const char* msda_levels(const int32_t* shapes_hw, int L, const int32_t* points_per_level, int S, int Q, int P, MsdaLevels& lv) {
+  if (L < 1 || L > 8) return "1..8 levels tiling S";
+  lv = {}; lv.L = L;
+  long start = 0, pend = 0;
+  for (int l = 0; l < L; ++l) {
+    const int h = shapes_hw[2 * l], w = shapes_hw[2 * l + 1], n = points_per_level[l];
+    if (h < 1 || w < 1 || n < 0) return "every level needs h, w >= 1 and a point count >= 0";
+    if ((long)h * w > 0x7fffffffL - start) return "1..8 levels tiling S";   // pixels are indexed with int
+    if ((pend += n) > P) return "points tiling P";
+    lv.lh[l] = h; lv.lw[l] = w; lv.lstart[l] = (int)start; lv.pend[l] = (int)pend;
+    start += (long)h * w;
+  }
+  if (start != S) return "1..8 levels tiling S";
+  if (pend != P) return "points tiling P";
+  // entries of one (b, h) contribution list are indexed with int: 4 Q P of them, level l's segment starts at 4 Q pend[l - 1]
+  if ((long)Q * P > 0x7fffffffL / 4) return "4 * Q * P must fit in int";
+  return nullptr;
+}
+
+// What the four msda entries check after their null pointers.  max_points: 32, module mode (the wave kernel: bilinear) 16.
+// The backward passes grad_value (asked for: its owner-computes launch has a grid too) and, when the gradients asked for need
+// the workspace, `work`.  nullptr = accepted and lv filled, else the reason.
+const char* msda_check(int B, int S, int H, int D, const int32_t* shapes_hw, int L, const int32_t* points_per_level, int Q, int P,
+                       int max_points, MsdaLevels& lv, const void* grad_value = nullptr, bool needs_work = false,
+                       const void* work = nullptr, int64_t work_bytes = 0) {
+  if (D != 32) return "head_dim must be 32";
+  if (B < 1 || Q < 1 || H < 1) return "B, Q and heads must be >= 1";
+  if (P < 1 || P > max_points) return max_points == 16 ? "1..16 points tiling P" : "1..32 points tiling P";
+  if (const char* why = msda_levels(shapes_hw, L, points_per_level, S, Q, P, lv)) return why;
+  // (B Q H + 3) / 4 blocks of one wave per (b, q, h); it bounds the (B Q + 127) / 128 blocks of the grad_ref kernel too
+  if ((long)B * Q > 4 * kGridMax / H) return "B * Q * heads is too large for one launch";
+  int own, blk0[9];
+  if (grad_value && msda_backward_value_blocks(lv, B, H, &own, blk0) > kGridMax) return "B * heads * S is too large for one launch";
+  if (needs_work && workspace_short(work, work_bytes, msda_backward_workspace_bytes(B, Q, H, P)))
+    return "workspace missing or smaller than m355_msda_backward_workspace_bytes";
+  if (needs_work && any_misaligned16({work})) return "workspace 16-byte aligned";
+  return nullptr;
+}
+
+// the argument checks m355_dfine_loss_forward and _backward share; nullptr = accepted, else the message
+const char* dfine_loss_check(const DfineLossArgs& a) {
+  if (a.B < 1 || a.Q < 1 || a.C < 1 || (int64_t)a.B * a.Q > INT32_MAX) return "B, Q, C >= 1 and B * Q < 2^31";
+  if (a.M < 0 || a.T < 0) return "M >= 0 and T >= 0";
+  if (!a.logits || !a.boxes || !a.out || !(a.num_boxes > 0.f)) return "null pointer (logits, pred_boxes, out) or num_boxes <= 0";
+  if (a.M > 0 && a.T > 0 && (!a.match_q || !a.match_t || !a.offsets || !a.labels || !a.tboxes))
+    return "null pointer in the match list or the targets";
+  const int local = (a.pred_corners != nullptr) + (a.ref_points != nullptr) + (a.teacher_corners != nullptr) +
+                    (a.teacher_logits != nullptr) + (a.project != nullptr);
+  if (local != 0 && local != 5) return "the local group (pred_corners, ref_points, teacher_corners, teacher_logits, project) is all or none";
+  if (local && (a.nb1 < 2 || a.nb1 > 64 || a.reg_scale == 0.f || !(a.temperature > 0.f)))
+    return "2 <= bins + 1 <= 64, reg_scale != 0, temperature > 0";
+  return nullptr;
+}
+DfineLossArgs dfine_loss_args(const float* logits, const float* boxes, int B, int Q, int C, const int64_t* mq, const int64_t* mt,
+                              int M, const int32_t* offsets, const int64_t* labels, const float* tboxes, int T, float num_boxes,
+                              float alpha, float gamma, const float* corners, const float* ref, const float* tcorners,
+                              const float* tlogits, const float* project, int nb1, float reg_scale, float temperature) {
+  DfineLossArgs a{};
+  a.logits = logits; a.boxes = boxes; a.match_q = (const long long*)mq; a.match_t = (const long long*)mt; a.offsets = offsets;
+  a.labels = (const long long*)labels; a.tboxes = tboxes; a.B = B; a.Q = Q; a.C = C; a.M = M; a.T = T;
+  a.num_boxes = num_boxes; a.alpha = alpha; a.gamma = gamma;
+  a.pred_corners = corners; a.ref_points = ref; a.teacher_corners = tcorners; a.teacher_logits = tlogits; a.project = project;
+  a.nb1 = nb1; a.reg_scale = reg_scale; a.temperature = temperature;
+  return a;
+}
+
+// the temporal encoder layer between its GEMMs (dfine_encoder.hip); nullptr = accepted, else the message
+const char* dfine_dropout_check(float p, int32_t site) {
+  if (!(p >= 0.f && p < 1.f)) return "dropout p must be in [0, 1)";
+  if (site < 0) return "the dropout site id must be >= 0";
+  return nullptr;
+}
+const char* dfine_attn_check(int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, int32_t site) {
+  if (head_dim != 32) return "head dim must be 32";
+  if (B < 1 || B > 65535 || S < 1 || H < 1 || H > 65535) return "B and heads in [1, 65535], S >= 1";
+  if ((int64_t)B * S * 96 * H > (int64_t)1 << 40 || (int64_t)S > (int64_t)1 << 24) return "S <= 2^24 and B * S * 3 D <= 2^40";
+  return dfine_dropout_check(p, site);
+}
+const char* dfine_addln_check(int64_t M, int32_t D, float p, int32_t site) {
+  if (M < 1 || M > (int64_t)1 << 31) return "1 <= rows <= 2^31";
+  if (D < 4 || D % 4 != 0 || D > dfine_addln_max_d()) return "D must be a multiple of 4 in [4, 1024]";
+  return dfine_dropout_check(p, site);
+}
+
+}  // namespace
+
+int m355_msda_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
+                      int32_t num_levels, const float* d_loc, const float* d_attn, const int32_t* points_per_level,
+                      int32_t Q, int32_t P, int32_t discrete, float* d_out, void* stream) {
+  if (any_null({d_value, d_loc, d_attn, d_out, shapes_hw, points_per_level})) return invalid(__func__, "null pointer");
+  MsdaLevels lv;
+  if (const char* why = msda_check(B, S, heads, head_dim, shapes_hw, num_levels, points_per_level, Q, P, 32, lv)) return invalid(__func__, why);
+  return launched(__func__, launch_msda(d_value, d_loc, d_attn, d_out, B, S, heads, Q, P, lv, discrete, (hipStream_t)stream));
+}
+int m355_msda_module_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
+                             int32_t num_levels, const float* d_ref, const float* d_offsets, const float* d_logits,
+                             const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale, float* d_out,
+                             void* stream) {
+  if (any_null({d_value, d_ref, d_offsets, d_logits, d_out, shapes_hw, points_per_level})) return invalid(__func__, "null pointer");
+  MsdaLevels lv;
+  if (const char* why = msda_check(B, S, heads, head_dim, shapes_hw, num_levels, points_per_level, Q, P, 16, lv)) return invalid(__func__, why);
+  return launched(__func__, launch_msda(d_value, d_offsets, d_logits, d_out, B, S, heads, Q, P, lv, 0, (hipStream_t)stream, d_ref, offset_scale));
+}
+size_t m355_msda_backward_workspace_bytes(int32_t B, int32_t Q, int32_t heads, int32_t P) { return msda_backward_workspace_bytes(B, Q, heads, P); }
+int m355_msda_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                       const int32_t* shapes_hw, int32_t num_levels, const float* d_loc, const float* d_attn,
+                       const int32_t* points_per_level, int32_t Q, int32_t P, int32_t discrete, float* d_grad_value,
+                       float* d_grad_loc, float* d_grad_attn, void* d_work, int64_t work_bytes, void* stream) {
+  if (any_null({d_grad_out, d_value, d_loc, d_attn, shapes_hw, points_per_level})) return invalid(__func__, "null pointer");
+  MsdaLevels lv;   // the workspace holds the contribution list of grad_value
+  if (const char* why = msda_check(B, S, heads, head_dim, shapes_hw, num_levels, points_per_level, Q, P, 32, lv, d_grad_value,
+                                   d_grad_value != nullptr, d_work, work_bytes))
+    return invalid(__func__, why);
+  return launched(__func__, launch_msda_backward(d_grad_out, d_value, d_loc, d_attn, d_grad_value, d_grad_loc, d_grad_attn, B, S, heads,
+                                                 Q, P, lv, discrete, d_work, (hipStream_t)stream));
+}
+int m355_msda_module_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                              const int32_t* shapes_hw, int32_t num_levels, const float* d_ref, const float* d_offsets,
+                              const float* d_logits, const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale,
+                              float* d_grad_value, float* d_grad_ref, float* d_grad_offsets, float* d_grad_logits, void* d_work,
+                              int64_t work_bytes, void* stream) {
+  // d_ref is required, so d_grad_ref never comes without it
+  if (any_null({d_grad_out, d_value, d_ref, d_offsets, d_logits, shapes_hw, points_per_level})) return invalid(__func__, "null pointer");
+  MsdaLevels lv;   // the workspace holds the contribution list of grad_value and the per-head partials of grad_ref
+  if (const char* why = msda_check(B, S, heads, head_dim, shapes_hw, num_levels, points_per_level, Q, P, 16, lv, d_grad_value,
+                                   d_grad_value || d_grad_ref, d_work, work_bytes))
+    return invalid(__func__, why);
+  return launched(__func__, launch_msda_backward(d_grad_out, d_value, d_offsets, d_logits, d_grad_value, d_grad_offsets, d_grad_logits,
+                                                 B, S, heads, Q, P, lv, 0, d_work, (hipStream_t)stream, d_ref, offset_scale, d_grad_ref));
+}
+int m355_dfine_decode(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
+                      int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream) {
+  if (any_null({d_dist, d_project, d_ref, d_boxes})) return invalid(__func__, "null pointer");
+  if (n < 0 || num_bins_plus1 < 2 || reg_scale == 0.f) return invalid(__func__, "n < 0, fewer than 2 bins or reg_scale == 0");
+  if (n > 128 * kGridMax) return invalid(__func__, "n is too large for one launch");   // (n + 127) / 128 blocks
+  return launched(__func__, launch_dfine_decode(d_dist, d_project, d_ref, d_boxes, (long)n, num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream));
+}
+int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
+                               float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
+                               int32_t clamp01, void* stream) {
+  if (any_null({d_grad_boxes, d_dist, d_project, d_ref})) return invalid(__func__, "null pointer");
+  if (n < 0 || num_bins_plus1 < 2 || reg_scale == 0.f) return invalid(__func__, "n < 0, fewer than 2 bins or reg_scale == 0");
+  if (n > 128 * kGridMax) return invalid(__func__, "n is too large for one launch");   // (n + 127) / 128 blocks
+  return launched(__func__, launch_dfine_decode_backward(d_grad_boxes, d_dist, d_project, d_ref, d_grad_dist, d_grad_ref, (long)n,
+                                                         num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream));
+}
+size_t m355_dfine_match_workspace_bytes(int32_t B, int32_t Q, int32_t max_targets) { return dfine_match_workspace_bytes(B, Q, max_targets); }
+int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                     const int64_t* d_target_labels, const float* d_target_boxes, const int32_t* d_target_offsets,
+                     const int32_t* h_target_counts, float class_cost, float bbox_cost, float giou_cost, float alpha, float gamma,
+                     int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
+                     int32_t kmax, int32_t* d_flags, void* stream) {
+  if (any_null({d_logits, d_pred_boxes, d_target_labels, d_target_boxes, d_target_offsets, h_target_counts, d_rows, d_cols, d_flags}))
+    return invalid(__func__, "null pointer");
+  if (B < 1 || B > 65535 || Q < 1 || Q > 2048 || C < 1) return invalid(__func__, "B >= 1, Q in [1, 2048], C >= 1");
+  int nmax = 0;
+  long total = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = h_target_counts[b];
+    if (n < 0 || n > 512) return invalid(__func__, "every target count must be in [0, 512]");
+    nmax = n > nmax ? n : nmax;
+    total += n;
+  }
+  if (kmax < (Q < nmax ? Q : nmax)) return invalid(__func__, "kmax is smaller than min(Q, largest target count)");
+  const size_t need = dfine_match_workspace_bytes(B, Q, nmax);
+  if (need > 0 && workspace_short(d_work, work_bytes, need))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_match_workspace_bytes");
+  return launched(__func__, launch_dfine_match(d_logits, d_pred_boxes, B, Q, C, (const long long*)d_target_labels, d_target_boxes,
+                                               d_target_offsets, (int)total, nmax, class_cost, bbox_cost, giou_cost, alpha, gamma,
+                                               use_focal_loss != 0, d_work, d_cost, (long long*)d_rows, (long long*)d_cols, kmax,
+                                               d_flags, (hipStream_t)stream));
+}
+int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
+                           float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream) {
+  if (any_null({d_logits, d_pred_boxes, d_scores, d_labels, d_boxes, d_counts})) return invalid(__func__, "null pointer");
+  if (B < 1 || Q < 1 || Q > 2048 || C < 1 || (int64_t)Q * C >= (int64_t)1 << 24)
+    return invalid(__func__, "B >= 1, Q in [1, 2048], C >= 1, Q * C < 2^24");
+  return launched(__func__, launch_dfine_postprocess(d_logits, d_pred_boxes, B, Q, C, d_sizes, threshold, d_scores, (long long*)d_labels,
+                                                     d_boxes, d_counts, (hipStream_t)stream));
+}
+size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q) { return dfine_loss_workspace_bytes(B, Q); }
+int m355_dfine_loss_forward(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
+                            const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                            const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                            float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                            const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                            float temperature, void* d_work, int64_t work_bytes, float* d_out, void* stream) {
+  DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
+                                    d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
+                                    d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
+  a.out = d_out;
+  if (const char* why = dfine_loss_check(a)) return invalid(__func__, why);
+  if (workspace_short(d_work, work_bytes, dfine_loss_workspace_bytes(B, Q)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_loss_workspace_bytes");
+  a.partials = (float*)d_work;
+  return launched(__func__, launch_dfine_loss_forward(a, (hipStream_t)stream));
+}
+int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q,
+                             int32_t C, const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
+                             const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
+                             float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
+                             const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
+                             float temperature, const float* d_saved, float* d_grad_logits, float* d_grad_pred_boxes,
+                             float* d_grad_pred_corners, void* stream) {
+  DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
+                                    d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
+                                    d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
+  a.out = const_cast<float*>(d_saved);   // read only here: out[5], out[6] of the forward
+  if (const char* why = dfine_loss_check(a)) return invalid(__func__, why);
+  if (!d_grad_terms) return invalid(__func__, "null pointer (grad_terms)");
+  if (d_grad_pred_corners && !d_pred_corners) return invalid(__func__, "grad_pred_corners without the local group");
+  a.grad_terms = d_grad_terms; a.grad_logits = d_grad_logits; a.grad_boxes = d_grad_pred_boxes; a.grad_corners = d_grad_pred_corners;
+  if (!d_grad_logits && !d_grad_pred_boxes && !d_grad_pred_corners) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_loss_backward(a, (hipStream_t)stream));
+}
+int m355_dfine_attn_forward(const float* d_qkv, int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, uint64_t seed,
+                            int32_t site, float* d_out, float* d_lse, void* stream) {
+  if (any_null({d_qkv, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return invalid(__func__, why);
+  if (any_misaligned16({d_qkv, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_attn_forward(d_qkv, B, S, H, p, seed, site, d_out, d_lse, (hipStream_t)stream));
+}
+int m355_dfine_attn_backward(const float* d_grad_out, const float* d_qkv, const float* d_out, const float* d_lse, int32_t B, int32_t S,
+                             int32_t H, int32_t head_dim, float p, uint64_t seed, int32_t site, float* d_grad_qkv, void* stream) {
+  if (any_null({d_grad_out, d_qkv, d_out, d_lse, d_grad_qkv})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return invalid(__func__, why);
+  if (any_misaligned16({d_grad_out, d_qkv, d_out, d_grad_qkv})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_attn_backward(d_grad_out, d_qkv, d_out, d_lse, B, S, H, p, seed, site, d_grad_qkv, (hipStream_t)stream));
+}
+size_t m355_dfine_addln_workspace_bytes(int64_t M, int32_t D) { return dfine_addln_workspace_bytes(M, D); }
+int m355_dfine_addln_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
+                             float eps, float p, uint64_t seed, int32_t site, float* d_out, float* d_mean, float* d_rstd, void* stream) {
+  if (any_null({d_x, d_y, d_weight, d_bias, d_out, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, p, site)) return invalid(__func__, why);
+  if (!(eps >= 0.f)) return invalid(__func__, "eps must be >= 0");
+  if (any_misaligned16({d_x, d_y, d_weight, d_bias, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_addln_forward(d_x, d_y, d_weight, d_bias, M, D, eps, p, seed, site, d_out, d_mean, d_rstd,
+                                                       (hipStream_t)stream));
+}
+int m355_dfine_addln_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight, const float* d_mean,
+                              const float* d_rstd, int64_t M, int32_t D, float p, uint64_t seed, int32_t site, float* d_grad_x,
+                              float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work, int64_t work_bytes, void* stream) {
+  if (any_null({d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, p, site)) return invalid(__func__, why);
+  if (workspace_short(d_work, work_bytes, dfine_addln_workspace_bytes(M, D)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_addln_workspace_bytes");
+  if (any_misaligned16({d_grad_out, d_x, d_y, d_weight, d_grad_x, d_grad_y, d_work})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_addln_backward(d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd, M, D, p, seed, site, d_grad_x,
+                                                        d_grad_y, d_grad_weight, d_grad_bias, (float*)d_work, (hipStream_t)stream));
+}
+int m355_dfine_relu_dropout_forward(const float* d_h, int64_t n, float p, uint64_t seed, int32_t site, float* d_out, void* stream) {
+  if (any_null({d_h, d_out})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return invalid(__func__, why);
+  if (any_misaligned16({d_h, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_relu_dropout(d_h, nullptr, d_out, n, p, seed, site, (hipStream_t)stream));
+}
+int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out, int64_t n, float p, uint64_t seed, int32_t site,
+                                     float* d_grad_h, void* stream) {
+  if (any_null({d_grad_out, d_out, d_grad_h})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return invalid(__func__, why);
+  if (any_misaligned16({d_grad_out, d_out, d_grad_h})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_relu_dropout(d_grad_out, d_out, d_grad_h, n, p, seed, site, (hipStream_t)stream));
+}
+int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream) {
+  if (!d_mask) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
+  if (const char* why = dfine_dropout_check(p, site)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_keep_mask(d_mask, n, p, seed, site, (hipStream_t)stream));
+}
+// the GRU recurrence (dfine_gru.hip)
+size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return dfine_gru_workspace_bytes(B, S, H, D); }
+int m355_dfine_gru_forward(const float* d_gi, const float* d_w_hh, const float* d_b_hh, const float* d_h0, int32_t B, int64_t S,
+                           int32_t H, int32_t D, float* d_out, float* d_h_n, void* d_work, int64_t work_bytes, int32_t keep,
+                           int32_t* d_status, void* stream) {
+  if (any_null({d_gi, d_w_hh, d_b_hh, d_out, d_h_n, d_work, d_status})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_gru_check(B, S, H, D)) return invalid(__func__, why);
+  if (workspace_short(d_work, work_bytes, dfine_gru_workspace_bytes(B, keep ? S : 0, H, D)))
+    return invalid(__func__, "workspace smaller than m355_dfine_gru_workspace_bytes");
+  if (any_misaligned16({d_gi, d_w_hh, d_b_hh, d_h0, d_out, d_h_n, d_work}) || ((uintptr_t)d_status & 3u)) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_gru_forward(d_gi, d_w_hh, d_b_hh, d_h0, B, (int)S, D, d_out, d_h_n, d_work, keep != 0, d_status,
+                                                     (hipStream_t)stream));
+}
+int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, const float* d_w_hh, const float* d_h0, const float* d_out,
+                            int32_t B, int64_t S, int32_t H, int32_t D, float* d_grad_gi, float* d_grad_an, float* d_grad_h0,
+                            void* d_work, int64_t work_bytes, int32_t* d_status, void* stream) {
+  if (any_null({d_grad_out, d_w_hh, d_out, d_grad_gi, d_grad_an, d_grad_h0, d_work, d_status})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_gru_check(B, S, H, D)) return invalid(__func__, why);
+  if (workspace_short(d_work, work_bytes, dfine_gru_workspace_bytes(B, S, H, D)))
+    return invalid(__func__, "workspace smaller than m355_dfine_gru_workspace_bytes");
+  if (any_misaligned16({d_grad_out, d_grad_h_n, d_w_hh, d_h0, d_out, d_grad_gi, d_grad_an, d_grad_h0, d_work}) || ((uintptr_t)d_status & 3u))
+    return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_gru_backward(d_grad_out, d_grad_h_n, d_w_hh, d_h0, d_out, B, (int)S, D, d_grad_gi, d_grad_an,
+                                                      d_grad_h0, d_work, d_status, (hipStream_t)stream));
+}

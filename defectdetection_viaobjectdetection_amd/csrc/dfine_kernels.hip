@@ -194,26 +194,12 @@ __global__ void dfine_decode_kernel(const float* dist, const float* project, con
 
 }  // namespace
 
-int launch_msda(const float* value, const float* loc, const float* attn, float* out, int B, int S, int H, int D, int Q,
-                int P, int L, const int* shapes_hw, const int* points_per_level, int discrete, hipStream_t s, const float* ref,
-                float offset_scale) {
-  if (!value || !loc || !attn || !out || !shapes_hw || !points_per_level) return -1;
-  if (ref && (P > 16 || discrete)) return -1;   // module mode lives in the wave kernel (bilinear, at most 16 points)
-  if (D != 32 || L < 1 || L > 8 || P < 1 || P > 32 || B < 1 || Q < 1 || H < 1) return -1;
+int launch_msda(const float* value, const float* loc, const float* attn, float* out, int B, int S, int H, int Q, int P,
+                const MsdaLevels& lv, int discrete, hipStream_t s, const float* ref, float offset_scale) {
   MsdaArgs a{};
-  a.value = value; a.loc = loc; a.attn = attn; a.out = out;
-  a.B = B; a.S = S; a.H = H; a.Q = Q; a.P = P; a.L = L; a.discrete = discrete;
-  a.ref = ref; a.offset_scale = offset_scale;
-  int start = 0, pend = 0;
-  for (int l = 0; l < L; ++l) {
-    a.lh[l] = shapes_hw[2 * l]; a.lw[l] = shapes_hw[2 * l + 1];
-    if (a.lh[l] < 1 || a.lw[l] < 1 || points_per_level[l] < 0) return -1;
-    a.lstart[l] = start;
-    start += a.lh[l] * a.lw[l];
-    pend += points_per_level[l];
-    a.pend[l] = pend;
-  }
-  if (start != S || pend != P) return -1;   // the level table must tile the value sequence and the point axis
+  a.value = value; a.loc = loc; a.attn = attn; a.out = out; a.ref = ref; a.offset_scale = offset_scale;
+  a.B = B; a.S = S; a.H = H; a.Q = Q; a.P = P; a.L = lv.L; a.discrete = discrete;
+  for (int l = 0; l < lv.L; ++l) { a.lh[l] = lv.lh[l]; a.lw[l] = lv.lw[l]; a.lstart[l] = lv.lstart[l]; a.pend[l] = lv.pend[l]; }
   const long ntriples = (long)B * Q * H;
   if (P <= 16)
     hipLaunchKernelGGL(msda_wave_kernel, dim3((unsigned)((ntriples + 3) / 4)), dim3(256), 0, s, a);
@@ -224,7 +210,6 @@ int launch_msda(const float* value, const float* loc, const float* attn, float* 
 
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
                         float reg_scale, int clamp01, hipStream_t s) {
-  if (!dist || !project || !ref || !boxes || n < 0 || nbins1 < 2 || reg_scale == 0.f) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(dfine_decode_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, dist, project, ref, boxes, n,
                      nbins1, reg_scale, clamp01);

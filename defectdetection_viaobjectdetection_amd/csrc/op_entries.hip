@@ -1,6 +1,7 @@
 // libmi355yolo.so per-op C entries (include/mi355yolo.h) that need no m355_engine: the unit-parity entries of single launches
 // (host weights packed by weight_pack.hip exactly as m355_set_conv_weights packs them, one launch, stream synchronised), and
-// the training step's launch wrappers (conv, weight gradient, bn, optimizers, losses, augment, D-FINE) and workspace queries.
+// the training step's launch wrappers (conv, weight gradient, bn, optimizers, losses, augment) and workspace queries.  The
+// D-FINE entries are in dfine_entries.hip.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,11 +19,6 @@
 using namespace m355;
 
 namespace {
-
-int set_err(int code, const std::string& m) {
-  g_err = m;
-  return code;
-}
 
 struct DevBuf {   // device allocations of one entry call, freed on scope exit; nullptr = the allocation or its copy failed
   std::vector<void*> p;
@@ -794,302 +790,6 @@ int m355_augment_ex(const void* d_cache, int32_t n_images, const m355_aug_ex_par
   if (rc == -1)
     return set_err(M355_ERR_INVALID, "augment_ex: bad argument (shape, n_layers, src index, polygon or vertex range, paste cap, workspace)");
   return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "augment_ex launch failed: " + std::to_string(rc));
-}
-int m355_msda_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
-                      int32_t num_levels, const float* d_loc, const float* d_attn, const int32_t* points_per_level,
-                      int32_t Q, int32_t P, int32_t discrete, float* d_out, void* stream) {
-  if (!d_value || !d_loc || !d_attn || !d_out || !shapes_hw || !points_per_level) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = m355::launch_msda(d_value, d_loc, d_attn, d_out, B, S, heads, head_dim, Q, P, num_levels, shapes_hw,
-                                   points_per_level, discrete, (hipStream_t)stream);
-  if (rc == -1)
-    return set_err(M355_ERR_INVALID, "msda: head_dim must be 32, 1..8 levels tiling S, 1..32 points tiling P");
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "msda launch failed: " + std::to_string(rc));
-}
-int m355_msda_module_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
-                             int32_t num_levels, const float* d_ref, const float* d_offsets, const float* d_logits,
-                             const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale, float* d_out,
-                             void* stream) {
-  if (!d_value || !d_ref || !d_offsets || !d_logits || !d_out || !shapes_hw || !points_per_level)
-    return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = m355::launch_msda(d_value, d_offsets, d_logits, d_out, B, S, heads, head_dim, Q, P, num_levels, shapes_hw,
-                                   points_per_level, 0, (hipStream_t)stream, d_ref, offset_scale);
-  if (rc == -1)
-    return set_err(M355_ERR_INVALID, "msda module: head_dim must be 32, 1..8 levels tiling S, 1..16 points tiling P");
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "msda launch failed: " + std::to_string(rc));
-}
-int m355_dfine_decode(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
-                      int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream) {
-  const int rc = m355::launch_dfine_decode(d_dist, d_project, d_ref, d_boxes, (long)n, num_bins_plus1, reg_scale, clamp01,
-                                           (hipStream_t)stream);
-  if (rc == -1) return set_err(M355_ERR_INVALID, "dfine_decode: null pointer, n < 0, fewer than 2 bins or reg_scale == 0");
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_decode launch failed: " + std::to_string(rc));
-}
-size_t m355_msda_backward_workspace_bytes(int32_t B, int32_t Q, int32_t heads, int32_t P) {
-  return m355::msda_backward_workspace_bytes(B, Q, heads, P);
-}
-static int msda_backward_rc(int rc, const char* what) {
-  if (rc == -1)
-    return set_err(M355_ERR_INVALID, std::string(what) + ": head_dim must be 32, 1..8 levels tiling S, points tiling P, workspace 16-byte aligned");
-  if (rc == -3) return set_err(M355_ERR_INVALID, std::string(what) + ": workspace missing or smaller than m355_msda_backward_workspace_bytes");
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, std::string(what) + " launch failed: " + std::to_string(rc));
-}
-int m355_msda_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                       const int32_t* shapes_hw, int32_t num_levels, const float* d_loc, const float* d_attn,
-                       const int32_t* points_per_level, int32_t Q, int32_t P, int32_t discrete, float* d_grad_value,
-                       float* d_grad_loc, float* d_grad_attn, void* d_work, int64_t work_bytes, void* stream) {
-  if (!d_grad_out || !d_value || !d_loc || !d_attn || !shapes_hw || !points_per_level) return set_err(M355_ERR_INVALID, "null pointer");
-  return msda_backward_rc(m355::launch_msda_backward(d_grad_out, d_value, d_loc, d_attn, d_grad_value, d_grad_loc, d_grad_attn, B, S,
-                                                     heads, head_dim, Q, P, num_levels, shapes_hw, points_per_level, discrete,
-                                                     d_work, work_bytes, (hipStream_t)stream),
-                          "msda backward");
-}
-int m355_msda_module_backward(const float* d_grad_out, const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                              const int32_t* shapes_hw, int32_t num_levels, const float* d_ref, const float* d_offsets,
-                              const float* d_logits, const int32_t* points_per_level, int32_t Q, int32_t P, float offset_scale,
-                              float* d_grad_value, float* d_grad_ref, float* d_grad_offsets, float* d_grad_logits, void* d_work,
-                              int64_t work_bytes, void* stream) {
-  if (!d_grad_out || !d_value || !d_ref || !d_offsets || !d_logits || !shapes_hw || !points_per_level)
-    return set_err(M355_ERR_INVALID, "null pointer");
-  return msda_backward_rc(m355::launch_msda_backward(d_grad_out, d_value, d_offsets, d_logits, d_grad_value, d_grad_offsets,
-                                                     d_grad_logits, B, S, heads, head_dim, Q, P, num_levels, shapes_hw,
-                                                     points_per_level, 0, d_work, work_bytes, (hipStream_t)stream, d_ref,
-                                                     offset_scale, d_grad_ref),
-                          "msda module backward (at most 16 points)");
-}
-int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
-                               float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
-                               int32_t clamp01, void* stream) {
-  const int rc = m355::launch_dfine_decode_backward(d_grad_boxes, d_dist, d_project, d_ref, d_grad_dist, d_grad_ref, (long)n,
-                                                    num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream);
-  if (rc == -1) return set_err(M355_ERR_INVALID, "dfine_decode_backward: null pointer, n < 0, fewer than 2 bins or reg_scale == 0");
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_decode_backward launch failed: " + std::to_string(rc));
-}
-size_t m355_dfine_match_workspace_bytes(int32_t B, int32_t Q, int32_t max_targets) {
-  return m355::dfine_match_workspace_bytes(B, Q, max_targets);
-}
-int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
-                     const int64_t* d_target_labels, const float* d_target_boxes, const int32_t* d_target_offsets,
-                     const int32_t* h_target_counts, float class_cost, float bbox_cost, float giou_cost, float alpha, float gamma,
-                     int32_t use_focal_loss, void* d_work, int64_t work_bytes, float* d_cost, int64_t* d_rows, int64_t* d_cols,
-                     int32_t kmax, int32_t* d_flags, void* stream) {
-  // every argument before any HIP call
-  if (!d_logits || !d_pred_boxes || !d_target_labels || !d_target_boxes || !d_target_offsets || !h_target_counts || !d_rows ||
-      !d_cols || !d_flags)
-    return set_err(M355_ERR_INVALID, "dfine_match: null pointer");
-  if (B < 1 || B > 65535 || Q < 1 || Q > 2048 || C < 1) return set_err(M355_ERR_INVALID, "dfine_match: B >= 1, Q in [1, 2048], C >= 1");
-  int nmax = 0;
-  long total = 0;
-  for (int b = 0; b < B; ++b) {
-    const int n = h_target_counts[b];
-    if (n < 0 || n > 512) return set_err(M355_ERR_INVALID, "dfine_match: every target count must be in [0, 512]");
-    nmax = n > nmax ? n : nmax;
-    total += n;
-  }
-  if (kmax < (Q < nmax ? Q : nmax)) return set_err(M355_ERR_INVALID, "dfine_match: kmax is smaller than min(Q, largest target count)");
-  const size_t need = m355::dfine_match_workspace_bytes(B, Q, nmax);
-  if (need > 0 && (!d_work || work_bytes < 0 || (size_t)work_bytes < need))
-    return set_err(M355_ERR_INVALID, "dfine_match: workspace missing or smaller than m355_dfine_match_workspace_bytes");
-  const int rc = m355::launch_dfine_match(d_logits, d_pred_boxes, B, Q, C, (const long long*)d_target_labels, d_target_boxes,
-                                          d_target_offsets, (int)total, nmax, class_cost, bbox_cost, giou_cost, alpha, gamma,
-                                          use_focal_loss != 0, d_work, d_cost, (long long*)d_rows, (long long*)d_cols, kmax, d_flags,
-                                          (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_match launch failed: " + std::to_string(rc));
-}
-int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
-                           float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream) {
-  // every argument before any HIP call
-  if (!d_logits || !d_pred_boxes || !d_scores || !d_labels || !d_boxes || !d_counts)
-    return set_err(M355_ERR_INVALID, "dfine_postprocess: null pointer");
-  if (B < 1 || Q < 1 || Q > 2048 || C < 1 || (int64_t)Q * C >= (int64_t)1 << 24)
-    return set_err(M355_ERR_INVALID, "dfine_postprocess: B >= 1, Q in [1, 2048], C >= 1, Q * C < 2^24");
-  const int rc = m355::launch_dfine_postprocess(d_logits, d_pred_boxes, B, Q, C, d_sizes, threshold, d_scores, (long long*)d_labels,
-                                                d_boxes, d_counts, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_postprocess launch failed: " + std::to_string(rc));
-}
-size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q) { return m355::dfine_loss_workspace_bytes(B, Q); }
-namespace {
-// the argument checks m355_dfine_loss_forward and _backward share; nullptr = accepted, else the message
-const char* dfine_loss_check(const m355::DfineLossArgs& a) {
-  if (a.B < 1 || a.Q < 1 || a.C < 1 || (int64_t)a.B * a.Q > INT32_MAX) return "B, Q, C >= 1 and B * Q < 2^31";
-  if (a.M < 0 || a.T < 0) return "M >= 0 and T >= 0";
-  if (!a.logits || !a.boxes || !a.out || !(a.num_boxes > 0.f)) return "null pointer (logits, pred_boxes, out) or num_boxes <= 0";
-  if (a.M > 0 && a.T > 0 && (!a.match_q || !a.match_t || !a.offsets || !a.labels || !a.tboxes))
-    return "null pointer in the match list or the targets";
-  const int local = (a.pred_corners != nullptr) + (a.ref_points != nullptr) + (a.teacher_corners != nullptr) +
-                    (a.teacher_logits != nullptr) + (a.project != nullptr);
-  if (local != 0 && local != 5) return "the local group (pred_corners, ref_points, teacher_corners, teacher_logits, project) is all or none";
-  if (local && (a.nb1 < 2 || a.nb1 > 64 || a.reg_scale == 0.f || !(a.temperature > 0.f)))
-    return "2 <= bins + 1 <= 64, reg_scale != 0, temperature > 0";
-  return nullptr;
-}
-m355::DfineLossArgs dfine_loss_args(const float* logits, const float* boxes, int B, int Q, int C, const int64_t* mq, const int64_t* mt,
-                                    int M, const int32_t* offsets, const int64_t* labels, const float* tboxes, int T, float num_boxes,
-                                    float alpha, float gamma, const float* corners, const float* ref, const float* tcorners,
-                                    const float* tlogits, const float* project, int nb1, float reg_scale, float temperature) {
-  m355::DfineLossArgs a{};
-  a.logits = logits; a.boxes = boxes; a.match_q = (const long long*)mq; a.match_t = (const long long*)mt; a.offsets = offsets;
-  a.labels = (const long long*)labels; a.tboxes = tboxes; a.B = B; a.Q = Q; a.C = C; a.M = M; a.T = T;
-  a.num_boxes = num_boxes; a.alpha = alpha; a.gamma = gamma;
-  a.pred_corners = corners; a.ref_points = ref; a.teacher_corners = tcorners; a.teacher_logits = tlogits; a.project = project;
-  a.nb1 = nb1; a.reg_scale = reg_scale; a.temperature = temperature;
-  return a;
-}
-}  // namespace
-int m355_dfine_loss_forward(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
-                            const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
-                            const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
-                            float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
-                            const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
-                            float temperature, void* d_work, int64_t work_bytes, float* d_out, void* stream) {
-  m355::DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
-                                          d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
-                                          d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
-  a.out = d_out;
-  if (const char* why = dfine_loss_check(a)) return set_err(M355_ERR_INVALID, std::string("dfine_loss_forward: ") + why);
-  if (!d_work || work_bytes < 0 || (size_t)work_bytes < m355::dfine_loss_workspace_bytes(B, Q))
-    return set_err(M355_ERR_INVALID, "dfine_loss_forward: workspace missing or smaller than m355_dfine_loss_workspace_bytes");
-  a.partials = (float*)d_work;
-  const int rc = m355::launch_dfine_loss_forward(a, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_loss_forward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_loss_backward(const float* d_grad_terms, const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q,
-                             int32_t C, const int64_t* d_match_q, const int64_t* d_match_t, int32_t M, const int32_t* d_offsets,
-                             const int64_t* d_target_labels, const float* d_target_boxes, int32_t T, float num_boxes, float alpha,
-                             float gamma, const float* d_pred_corners, const float* d_ref_points, const float* d_teacher_corners,
-                             const float* d_teacher_logits, const float* d_project, int32_t num_bins_plus1, float reg_scale,
-                             float temperature, const float* d_saved, float* d_grad_logits, float* d_grad_pred_boxes,
-                             float* d_grad_pred_corners, void* stream) {
-  m355::DfineLossArgs a = dfine_loss_args(d_logits, d_pred_boxes, B, Q, C, d_match_q, d_match_t, M, d_offsets, d_target_labels,
-                                          d_target_boxes, T, num_boxes, alpha, gamma, d_pred_corners, d_ref_points, d_teacher_corners,
-                                          d_teacher_logits, d_project, num_bins_plus1, reg_scale, temperature);
-  a.out = const_cast<float*>(d_saved);   // read only here: out[5], out[6] of the forward
-  if (const char* why = dfine_loss_check(a)) return set_err(M355_ERR_INVALID, std::string("dfine_loss_backward: ") + why);
-  if (!d_grad_terms) return set_err(M355_ERR_INVALID, "dfine_loss_backward: null pointer (grad_terms)");
-  if (d_grad_pred_corners && !d_pred_corners)
-    return set_err(M355_ERR_INVALID, "dfine_loss_backward: grad_pred_corners without the local group");
-  a.grad_terms = d_grad_terms; a.grad_logits = d_grad_logits; a.grad_boxes = d_grad_pred_boxes; a.grad_corners = d_grad_pred_corners;
-  if (!d_grad_logits && !d_grad_pred_boxes && !d_grad_pred_corners) return M355_OK;   // nothing asked for
-  const int rc = m355::launch_dfine_loss_backward(a, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_loss_backward launch failed: " + std::to_string(rc));
-}
-// ---- the temporal encoder layer between its GEMMs (dfine_encoder.hip); every argument before any HIP call
-namespace {
-bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-// nullptr = accepted, else the message
-const char* dfine_dropout_check(float p, int32_t site) {
-  if (!(p >= 0.f && p < 1.f)) return "dropout p must be in [0, 1)";
-  if (site < 0) return "the dropout site id must be >= 0";
-  return nullptr;
-}
-const char* dfine_attn_check(int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, int32_t site) {
-  if (head_dim != 32) return "head dim must be 32";
-  if (B < 1 || B > 65535 || S < 1 || H < 1 || H > 65535) return "B and heads in [1, 65535], S >= 1";
-  if ((int64_t)B * S * 96 * H > (int64_t)1 << 40 || (int64_t)S > (int64_t)1 << 24) return "S <= 2^24 and B * S * 3 D <= 2^40";
-  return dfine_dropout_check(p, site);
-}
-const char* dfine_addln_check(int64_t M, int32_t D, float p, int32_t site) {
-  if (M < 1 || M > (int64_t)1 << 31) return "1 <= rows <= 2^31";
-  if (D < 4 || D % 4 != 0 || D > m355::dfine_addln_max_d()) return "D must be a multiple of 4 in [4, 1024]";
-  return dfine_dropout_check(p, site);
-}
-}  // namespace
-int m355_dfine_attn_forward(const float* d_qkv, int32_t B, int32_t S, int32_t H, int32_t head_dim, float p, uint64_t seed,
-                            int32_t site, float* d_out, float* d_lse, void* stream) {
-  if (!d_qkv || !d_out) return set_err(M355_ERR_INVALID, "dfine_attn_forward: null pointer");
-  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_attn_forward: ") + why);
-  if (misaligned16(d_qkv) || misaligned16(d_out)) return set_err(M355_ERR_INVALID, "dfine_attn_forward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_attn_forward(d_qkv, B, S, H, p, seed, site, d_out, d_lse, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_attn_forward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_attn_backward(const float* d_grad_out, const float* d_qkv, const float* d_out, const float* d_lse, int32_t B, int32_t S,
-                             int32_t H, int32_t head_dim, float p, uint64_t seed, int32_t site, float* d_grad_qkv, void* stream) {
-  if (!d_grad_out || !d_qkv || !d_out || !d_lse || !d_grad_qkv) return set_err(M355_ERR_INVALID, "dfine_attn_backward: null pointer");
-  if (const char* why = dfine_attn_check(B, S, H, head_dim, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_attn_backward: ") + why);
-  if (misaligned16(d_grad_out) || misaligned16(d_qkv) || misaligned16(d_out) || misaligned16(d_grad_qkv))
-    return set_err(M355_ERR_INVALID, "dfine_attn_backward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_attn_backward(d_grad_out, d_qkv, d_out, d_lse, B, S, H, p, seed, site, d_grad_qkv, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_attn_backward launch failed: " + std::to_string(rc));
-}
-size_t m355_dfine_addln_workspace_bytes(int64_t M, int32_t D) { return m355::dfine_addln_workspace_bytes(M, D); }
-int m355_dfine_addln_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
-                             float eps, float p, uint64_t seed, int32_t site, float* d_out, float* d_mean, float* d_rstd, void* stream) {
-  if (!d_x || !d_y || !d_weight || !d_bias || !d_out || !d_mean || !d_rstd) return set_err(M355_ERR_INVALID, "dfine_addln_forward: null pointer");
-  if (const char* why = dfine_addln_check(M, D, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_addln_forward: ") + why);
-  if (!(eps >= 0.f)) return set_err(M355_ERR_INVALID, "dfine_addln_forward: eps must be >= 0");
-  if (misaligned16(d_x) || misaligned16(d_y) || misaligned16(d_weight) || misaligned16(d_bias) || misaligned16(d_out))
-    return set_err(M355_ERR_INVALID, "dfine_addln_forward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_addln_forward(d_x, d_y, d_weight, d_bias, M, D, eps, p, seed, site, d_out, d_mean, d_rstd, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_addln_forward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_addln_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight, const float* d_mean,
-                              const float* d_rstd, int64_t M, int32_t D, float p, uint64_t seed, int32_t site, float* d_grad_x,
-                              float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work, int64_t work_bytes, void* stream) {
-  if (!d_grad_out || !d_x || !d_y || !d_weight || !d_mean || !d_rstd) return set_err(M355_ERR_INVALID, "dfine_addln_backward: null pointer");
-  if (const char* why = dfine_addln_check(M, D, p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_addln_backward: ") + why);
-  if (!d_work || work_bytes < 0 || (size_t)work_bytes < m355::dfine_addln_workspace_bytes(M, D))
-    return set_err(M355_ERR_INVALID, "dfine_addln_backward: workspace missing or smaller than m355_dfine_addln_workspace_bytes");
-  if (misaligned16(d_grad_out) || misaligned16(d_x) || misaligned16(d_y) || misaligned16(d_weight) || misaligned16(d_grad_x) ||
-      misaligned16(d_grad_y) || misaligned16(d_work))
-    return set_err(M355_ERR_INVALID, "dfine_addln_backward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_addln_backward(d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd, M, D, p, seed, site, d_grad_x, d_grad_y,
-                                                   d_grad_weight, d_grad_bias, (float*)d_work, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_addln_backward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_relu_dropout_forward(const float* d_h, int64_t n, float p, uint64_t seed, int32_t site, float* d_out, void* stream) {
-  if (!d_h || !d_out) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: null pointer");
-  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: 1 <= n <= 2^40");
-  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_relu_dropout_forward: ") + why);
-  if (misaligned16(d_h) || misaligned16(d_out)) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_forward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_relu_dropout(d_h, nullptr, d_out, n, p, seed, site, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_relu_dropout_forward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out, int64_t n, float p, uint64_t seed, int32_t site,
-                                     float* d_grad_h, void* stream) {
-  if (!d_grad_out || !d_out || !d_grad_h) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: null pointer");
-  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: 1 <= n <= 2^40");
-  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_relu_dropout_backward: ") + why);
-  if (misaligned16(d_grad_out) || misaligned16(d_out) || misaligned16(d_grad_h))
-    return set_err(M355_ERR_INVALID, "dfine_relu_dropout_backward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_relu_dropout(d_grad_out, d_out, d_grad_h, n, p, seed, site, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_relu_dropout_backward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream) {
-  if (!d_mask) return set_err(M355_ERR_INVALID, "dfine_dropout_mask: null pointer");
-  if (n < 1 || n > (int64_t)1 << 40) return set_err(M355_ERR_INVALID, "dfine_dropout_mask: 1 <= n <= 2^40");
-  if (const char* why = dfine_dropout_check(p, site)) return set_err(M355_ERR_INVALID, std::string("dfine_dropout_mask: ") + why);
-  const int rc = m355::launch_dfine_keep_mask(d_mask, n, p, seed, site, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_dropout_mask launch failed: " + std::to_string(rc));
-}
-// ---- the GRU recurrence (dfine_gru.hip); every argument before any HIP call
-size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return m355::dfine_gru_workspace_bytes(B, S, H, D); }
-int m355_dfine_gru_forward(const float* d_gi, const float* d_w_hh, const float* d_b_hh, const float* d_h0, int32_t B, int64_t S,
-                           int32_t H, int32_t D, float* d_out, float* d_h_n, void* d_work, int64_t work_bytes, int32_t keep,
-                           int32_t* d_status, void* stream) {
-  if (!d_gi || !d_w_hh || !d_b_hh || !d_out || !d_h_n || !d_work || !d_status) return set_err(M355_ERR_INVALID, "dfine_gru_forward: null pointer");
-  if (const char* why = m355::dfine_gru_check(B, S, H, D)) return set_err(M355_ERR_INVALID, std::string("dfine_gru_forward: ") + why);
-  if (work_bytes < 0 || (size_t)work_bytes < m355::dfine_gru_workspace_bytes(B, keep ? S : 0, H, D))
-    return set_err(M355_ERR_INVALID, "dfine_gru_forward: workspace smaller than m355_dfine_gru_workspace_bytes");
-  if (misaligned16(d_gi) || misaligned16(d_w_hh) || misaligned16(d_b_hh) || misaligned16(d_h0) || misaligned16(d_out) ||
-      misaligned16(d_h_n) || misaligned16(d_work) || ((uintptr_t)d_status & 3u))
-    return set_err(M355_ERR_INVALID, "dfine_gru_forward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_gru_forward(d_gi, d_w_hh, d_b_hh, d_h0, B, (int)S, D, d_out, d_h_n, d_work, keep != 0, d_status,
-                                                (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_gru_forward launch failed: " + std::to_string(rc));
-}
-int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, const float* d_w_hh, const float* d_h0, const float* d_out,
-                            int32_t B, int64_t S, int32_t H, int32_t D, float* d_grad_gi, float* d_grad_an, float* d_grad_h0,
-                            void* d_work, int64_t work_bytes, int32_t* d_status, void* stream) {
-  if (!d_grad_out || !d_w_hh || !d_out || !d_grad_gi || !d_grad_an || !d_grad_h0 || !d_work || !d_status)
-    return set_err(M355_ERR_INVALID, "dfine_gru_backward: null pointer");
-  if (const char* why = m355::dfine_gru_check(B, S, H, D)) return set_err(M355_ERR_INVALID, std::string("dfine_gru_backward: ") + why);
-  if (work_bytes < 0 || (size_t)work_bytes < m355::dfine_gru_workspace_bytes(B, S, H, D))
-    return set_err(M355_ERR_INVALID, "dfine_gru_backward: workspace smaller than m355_dfine_gru_workspace_bytes");
-  if (misaligned16(d_grad_out) || misaligned16(d_grad_h_n) || misaligned16(d_w_hh) || misaligned16(d_h0) || misaligned16(d_out) ||
-      misaligned16(d_grad_gi) || misaligned16(d_grad_an) || misaligned16(d_grad_h0) || misaligned16(d_work) || ((uintptr_t)d_status & 3u))
-    return set_err(M355_ERR_INVALID, "dfine_gru_backward: pointers must be 16-byte aligned");
-  const int rc = m355::launch_dfine_gru_backward(d_grad_out, d_grad_h_n, d_w_hh, d_h0, d_out, B, (int)S, D, d_grad_gi, d_grad_an,
-                                                 d_grad_h0, d_work, d_status, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "dfine_gru_backward launch failed: " + std::to_string(rc));
 }
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {

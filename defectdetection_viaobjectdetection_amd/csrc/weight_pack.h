@@ -10,8 +10,13 @@
 
 namespace m355 {
 
-// the error text of the C-ABI calls made without an engine (m355_last_error(nullptr)), set in engine.hip and op_entries.hip
+// the error text of the C-ABI calls made without an engine (m355_last_error(nullptr)), set in engine.hip and, through
+// set_err, by the per-op entries (op_entries.hip, dfine_entries.hip)
 extern thread_local std::string g_err;
+inline int set_err(int code, const std::string& m) {
+  g_err = m;
+  return code;
+}
 
 using FragList = std::vector<std::pair<int, int>>;   // (first row of a 32-row block, first K element of a 16-deep slice)
 

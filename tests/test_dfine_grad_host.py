@@ -96,6 +96,54 @@ def test_backward_arguments_are_refused_before_any_device_work():
     assert _capi.lib.m355_dfine_decode_backward(fake, fake, fake, fake, fake, None, 4, 33, 0.0, 0, None) == -1
 
 
+# level tables and batch shapes whose int arithmetic would wrap: (shapes, points per level, S, B, Q, heads), P = sum of points
+_WRAPPING = {
+    "hw_wraps_to_zero": ([(65536, 65536)], [4], 0, 1, 3, 2),
+    "hw_wraps_negative": ([(46341, 46341)], [4], 46341 * 46341 - (1 << 32), 1, 3, 2),
+    "level_sum_wraps": ([(65536, 32768), (65536, 32768), (5, 5)], [2, 1, 1], 25, 1, 3, 2),
+    "grid_over_32_bits": ([(5, 5)], [4], 25, 65536, 65536, 8),
+}
+
+
+@pytest.mark.parametrize("case", list(_WRAPPING))
+def test_msda_arguments_that_wrap_int_are_refused_before_any_device_work(case):
+    """Forward and backward build the level table with one function: sizes whose pixel sum or grid leaves int are refused by
+    every msda entry.  Refused calls only: the pointers are fake."""
+    import ctypes as C
+    from defectdetection_viaobjectdetection_amd import _capi
+    lib, fake = _capi.lib, C.c_void_p(0x1000)   # never dereferenced
+    shapes, pts, S, B, Q, H = _WRAPPING[case]
+    L, P = len(shapes), sum(pts)
+    sh, pp = (C.c_int32 * (2 * L))(*[v for hw in shapes for v in hw]), (C.c_int32 * L)(*pts)
+    fwd = lambda D: lib.m355_msda_forward(fake, B, S, H, D, sh, L, fake, fake, pp, Q, P, 0, fake, None)  # noqa: E731
+    assert fwd(16) == -1                       # control: the head dim
+    assert fwd(32) == -1 and b"head_dim" not in lib.m355_last_error(None), lib.m355_last_error(None)
+    assert lib.m355_msda_module_forward(fake, B, S, H, 32, sh, L, fake, fake, fake, pp, Q, P, 0.5, fake, None) == -1
+    if case == "level_sum_wraps":
+        assert lib.m355_msda_backward(fake, fake, B, S, H, 32, sh, L, fake, fake, pp, Q, P, 0, fake, None, None, fake, 1 << 20,
+                                      None) == -1
+
+
+def test_msda_backward_value_grid_over_int_is_refused_before_any_device_work():
+    """The grad_value pass is the backward's third launch: its block count (B * heads * blocks per map, one per 256 pixels at
+    the least) is checked with the other grids, not after the first two launches."""
+    import ctypes as C
+    from defectdetection_viaobjectdetection_amd import _capi
+    lib, fake = _capi.lib, C.c_void_p(0x1000)   # never dereferenced
+    sh, pp, heads = (C.c_int32 * 2)(4096, 2049), (C.c_int32 * 1)(4), 65536          # 65536 * ceil(4096 * 2049 / 256) > 2^31
+    assert lib.m355_msda_backward(fake, fake, 1, 4096 * 2049, heads, 32, sh, 1, fake, fake, pp, 1, 4, 0, fake, fake, fake, fake,
+                                  1 << 40, None) == -1
+    assert b"B * heads * S is too large for one launch" in lib.m355_last_error(None)
+
+
+def test_decode_grid_over_32_bits_is_refused_before_any_device_work():
+    import ctypes as C
+    from defectdetection_viaobjectdetection_amd import _capi
+    fake, n = C.c_void_p(0x1000), 1 << 40      # (n + 127) / 128 blocks = 2^33
+    assert _capi.lib.m355_dfine_decode(fake, fake, fake, fake, n, 33, 4.0, 0, None) == -1
+    assert _capi.lib.m355_dfine_decode_backward(fake, fake, fake, fake, fake, None, n, 33, 4.0, 0, None) == -1
+
+
 def test_deformable_attention_refuses_mismatched_linear_layers():
     """The fused module kernel indexes the two linear outputs as (heads, points, 2) / (heads, points): a layer of another
     width is refused before anything is launched (the check precedes every device call, so it runs here)."""
