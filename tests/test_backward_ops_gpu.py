@@ -1,10 +1,17 @@
-"""Backward building blocks (SURVEY A13 backward) vs PyTorch autograd on the CPU (fp32 on fp16-rounded operands)."""
+"""Backward building blocks (SURVEY A13 backward) vs PyTorch autograd on the CPU (fp32 on fp16-rounded operands).
+
+The whole-op conv entries m355_conv2d_dgrad / m355_conv2d_wgrad (they pack their own weights and pick their own form) are judged
+element by element as well: float64 reference, launch_ref.elem_bound with K = cout k k (dgrad) and K = B Ho Wo (wgrad), dY between
+NaN bands, dX NaN-filled between guard bands, dW between fp32 sentinels, a second launch for identical bits."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import conv_harness as ch
+import launch_ref as lr
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +43,30 @@ DGRAD_CASES = [
     (1, 48, 80, 256, 512, 3, 2),
     (2, 32, 32, 64, 96, 3, 2),       # cin % 64 == 0 but cout 96 (not whole 64-wide K slices): window-slot phases, not compact
     (2, 32, 32, 8, 32, 3, 2),        # cin 8: no phase form tiles 4 x 8 virtual channels -> the transposed-stride gather
+    # the smallest maps of the wave-private chunk stream (conv_dgrad_s2c32.hip): every dY row a top or bottom row or next to one
+    (1, 8, 64, 32, 64, 3, 2),        # dY 4 x 32: one chunk per row
+    (1, 6, 192, 32, 64, 3, 2),       # dY 3 x 96: three chunks per row, a first, a middle and a last row
 ]
+
+
+def _dgrad_reference(dy, w, H, W, s):
+    """(float64 input gradient (B, H, W, cin) NHWC of the fp16-rounded dY (B, cout, Ho, Wo) and w, its launch_ref.elem_bound with
+    K = cout k k)."""
+    k = w.shape[2]
+    dy64, w64 = dy.half().double().permute(0, 2, 3, 1), w.half().double()
+    ref = lr.dgrad_ref(dy64, w64, H, W, s, k // 2)
+    S = lr.dgrad_ref(dy64.abs(), w64.abs(), H, W, s, k // 2)
+    return ref, lr.elem_bound(ref, S, w.shape[0] * k * k)
+
+
+def _dgrad_guarded(capi, dy, w, B, H, W, cin, cout, k, s, dev, what):
+    """m355_conv2d_dgrad with dY between NaN bands into a NaN-filled dX between guard bands.  Returns dX (B, H, W, cin) on the host."""
+    yd, yp = ch.banded_input(dy, dev)
+    raw, body = ch.guarded_output(B * H * W * cin * 2, torch.float16, dev)
+    capi.check(capi.lib.m355_conv2d_dgrad(C.c_void_p(yp), B, H, W, cin, _p(w.contiguous()), cout, k, s, C.c_void_p(body.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    return ch.guards_intact(raw, what).view(torch.float16).reshape(B, H, W, cin)
 
 
 @pytest.mark.parametrize("case", DGRAD_CASES)
@@ -56,6 +86,13 @@ def test_conv2d_dgrad(case, cuda_device):
     got = d_dx.float().cpu().permute(0, 3, 1, 2)
     assert torch.isfinite(got).all()
     assert rel_l2(got, x.grad) <= 1e-3
+    # per element against the float64 reference, between guard bands, twice for identical bits
+    what = f"dgrad {case}"
+    ref, bound = _dgrad_reference(dy, w, H, W, s)
+    g1 = _dgrad_guarded(_capi, dy, w, B, H, W, cin, cout, k, s, cuda_device, what)
+    ch.judged_elementwise(g1, ref, bound, what)
+    g2 = _dgrad_guarded(_capi, dy, w, B, H, W, cin, cout, k, s, cuda_device, what)
+    assert ch.same_bits(g1, g2), f"{what}: two runs differ"
 
 
 def test_stride2_dgrad_phase_form_equals_the_gather_form(cuda_device, monkeypatch):
@@ -65,7 +102,9 @@ def test_stride2_dgrad_phase_form_equals_the_gather_form(cuda_device, monkeypatc
     B, H, W, cin, cout = 2, 40, 48, 128, 256
     g = torch.Generator().manual_seed(5)
     w = (torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5).half().float().contiguous()
-    d_dy = nhwc16(torch.randn(B, cout, H // 2, W // 2, generator=g), cuda_device)
+    dy = torch.randn(B, cout, H // 2, W // 2, generator=g)
+    d_dy = nhwc16(dy, cuda_device)
+    ref, bound = _dgrad_reference(dy, w, H, W, 2)
     outs = []
     for off in (False, True):
         if off:
@@ -74,7 +113,13 @@ def test_stride2_dgrad_phase_form_equals_the_gather_form(cuda_device, monkeypatc
         _capi.check(_capi.lib.m355_conv2d_dgrad(_p(d_dy), B, H, W, cin, _p(w), cout, 3, 2, _p(d_dx),
                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         outs.append(d_dx.float().cpu())
-    assert torch.isfinite(outs[0]).all()
+        # each form per element against the float64 reference, between guard bands, twice for identical bits
+        what = "stride-2 dgrad, " + ("gather form" if off else "phase form")
+        g1 = _dgrad_guarded(_capi, dy.half().float(), w, B, H, W, cin, cout, 3, 2, cuda_device, what)
+        ch.judged_elementwise(g1, ref, bound, what)
+        assert ch.same_bits(g1, _dgrad_guarded(_capi, dy.half().float(), w, B, H, W, cin, cout, 3, 2, cuda_device, what)), f"{what}: two runs differ"
+        assert torch.equal(g1.float(), outs[-1]), f"{what}: the guarded launch gave other values than the plain one"
+    assert torch.isfinite(outs[0]).all() and torch.isfinite(outs[1]).all()
     assert rel_l2(outs[0], outs[1]) <= 5e-4
 
 
@@ -151,6 +196,14 @@ WGRAD_CASES = [
     (4, 320, 256, 32, 64, 3, 2),      # 1 280 chunks on 512 blocks: the register prefetch of a block's next chunk, 512 partial slabs
     (2, 96, 320, 32, 64, 3, 2),       # 160 output columns = 2.5 chunks: the partial last chunk of a row (the s scale at 640 x 640)
     (3, 8, 32, 16, 24, 3, 1),         # n-scale widths
+    # the smallest shapes that still cross every tile boundary of each kernel
+    # patch kernel: conv_wgrad3_ok refuses (2, 17, 33, 48, 96) -- its 8 x 16 tiles would cover 24 x 48 = 1152 pixels of 561, beyond the
+    # 25 % waste clause (as (1, 19, 35, 32, 64) above: 1152 of 665; both take the pixel-axis GEMM).  The nearest map with ragged rows
+    # and columns the clause takes: 23 x 45 (1152 <= 1.25 x 1035), 2.9 x 2.8 tiles, half-empty channel tiles on both sides
+    (2, 23, 45, 48, 96, 3, 1),
+    (2, 17, 33, 48, 96, 3, 1),        # the same channels on the refused map: the pixel-axis GEMM with ragged tiles on every side
+    (1, 16, 128, 8, 48, 3, 2),        # stem kernel: one 64-pixel chunk per output row, first and last rows padded
+    (1, 8, 160, 32, 64, 3, 2),        # wgrad_s2c32: 80 output columns = 1.25 chunks, the partial last chunk of every row
 ]
 
 
@@ -178,6 +231,23 @@ def test_conv2d_wgrad(case, cuda_device):
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
     assert torch.equal(d_dw, d_dw2)
+    # per element against the float64 reference (K = B Ho Wo products per element), dW inside a band of fp32 sentinels
+    what = f"wgrad {case}"
+    ref64, S = lr.wgrad_reference(x.double().permute(0, 2, 3, 1), dy.double().permute(0, 2, 3, 1), k, s, k // 2, cout)
+    n = cout * k * k * cin
+    runs = []
+    for _ in range(2):
+        dwb = torch.full((lr.GUARD + n + lr.GUARD,), lr.SENT32, dtype=torch.int32, device=cuda_device)
+        _capi.check(_capi.lib.m355_conv2d_wgrad(_p(d_x), _p(d_dy), B, H, W, cin, cout, k, s, C.c_void_p(dwb.data_ptr() + 4 * lr.GUARD),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        bits = dwb.cpu()
+        assert bool((bits[:lr.GUARD] == lr.SENT32).all()) and bool((bits[lr.GUARD + n:] == lr.SENT32).all()), f"{what}: a word around dW changed"
+        runs.append(bits[lr.GUARD:lr.GUARD + n])
+    g1 = runs[0].view(torch.float32).view(cout, k, k, cin)
+    ch.judged_elementwise(g1, ref64, lr.elem_bound(ref64, S, B * y.shape[2] * y.shape[3]), what)
+    assert torch.equal(runs[0], runs[1]), f"{what}: two runs differ"
+    assert torch.equal(g1, got), f"{what}: the guarded launch gave other values than the plain one"
 
 
 @pytest.mark.parametrize("B,H,W,Cc,acc", [(3, 20, 20, 32, 0), (2, 13, 17, 16, 1), (2, 5, 4, 8, 0)])

@@ -95,28 +95,21 @@ def test_bneck_pair_refuses_what_it_cannot_tile(cuda_device):
     assert rc != 0            # a 700-pixel row does not fit the pixel blocks of one slab
 
 
-def _ragged_per_element(dev, x, w, b, r, stride):
-    """The same operands once more through the row-slab kernel (tile 33), now between guard bands (x and the residual between NaNs,
-    the output a NaN-filled body between bands that must not change) and judged element by element with conv_bound's derived bound."""
+def _per_element(dev, x, w, b, r, stride):
+    """The same operands once more through the row-slab kernel (tile 33) on the common path of tests/conv_harness.py: x and the residual
+    between NaN bands, the output a NaN-filled body between bands that must not change, every element judged with conv_bound's derived
+    bound, rel-L2, and a second launch for identical bits."""
     import conv_bound as cb
+    import conv_harness as ch
     from defectdetection_viaobjectdetection_amd import _capi
-    from test_narrow_maps_gpu import _banded_input, _guarded_output, _guards_intact
     B, cin, H, W = x.shape
-    cout, Ho, Wo = w.shape[0], H // stride, W // stride
-    y64, z64, S = cb.conv_ref(x.float(), w, b, 3, stride, 1, None if r is None else r.float())
-    tol = cb.conv_tol(y64, z64, S, 9 * cin, 1, r)
-    xd, xp = _banded_input(x.float(), dev)
-    rd, rp = _banded_input(r.float(), dev) if r is not None else (None, 0)
-    raw, body = _guarded_output(B * Ho * Wo * cout * 2, torch.float16, dev)
-    wn, bn = w.numpy().astype(np.float32).copy(), b.numpy().astype(np.float32).copy()
-    _capi.check(_capi.lib.m355_conv2d_fwd(C.c_void_p(xp), B, H, W, cin, _h(wn), _h(bn), cout, 3, stride, 1, C.c_void_p(rp),
-                                          C.c_void_p(body.data_ptr()), 0, 33, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    what = f"planes {(B, H, W, cin, cout)} stride {stride} res={r is not None}"
-    got = _guards_intact(raw, what).view(torch.float16).reshape(B, Ho, Wo, cout).permute(0, 3, 1, 2).float()
-    assert torch.isfinite(got).all(), f"{what}: non-finite output (an element not written, or a read outside the input feeds it)"
-    worst, idx, _ = cb.check_elements(got, y64, tol, what)
-    print(f"{what}: worst |err|/tol {worst:.3f} at (image, channel, row, col) = {idx}, median tol {float(tol.median()):.2e}")
+    cout = w.shape[0]
+    rf = None if r is None else r.float()
+    y64, z64, S = cb.conv_ref(x.float(), w, b, 3, stride, 1, rf)
+    tol = cb.conv_tol(y64, z64, S, 9 * cin, 1, rf)
+    case = (B, H, W, cin, cout, 3, stride, 1, r is not None, False)
+    ch.judge(_capi, case, 33, (x.float(), w.contiguous(), b.contiguous(), rf, y64, tol), dev,
+             f"planes {(B, H, W, cin, cout)} stride {stride} res={r is not None}")
 
 
 S2_CASES = [
@@ -151,7 +144,7 @@ def test_conv3x3_planes_stride2_against_torch(cuda_device, B, H, W, cin, cout):
     print(f"s2 B={B} {H}x{W} {cin}->{cout}: rel-L2 {rel:.2e}")
     assert rel <= 1e-3
     if (B, H, W, cin, cout) == (1, 28, 44, 64, 192):      # the ragged case: per element, between guard bands
-        _ragged_per_element(cuda_device, x, w, b, None, 2)
+        _per_element(cuda_device, x, w, b, None, 2)
 
 
 SINGLE_CASES = [
@@ -168,7 +161,8 @@ SINGLE_CASES = [
 @pytest.mark.parametrize("B,H,W,cin,cout,res", SINGLE_CASES)
 def test_conv3x3_planes_single_against_torch(cuda_device, B, H, W, cin, cout, res):
     """The row-slab kernel in single-conv mode (TILE_PLANES = 33 of m355_conv2d_fwd): y = SiLU(conv3x3(x) + b) (+ residual) against
-    fp32 F.conv2d on the fp16-rounded operands, rel-L2 <= 1e-3 like every other conv kernel."""
+    fp32 F.conv2d on the fp16-rounded operands, rel-L2 <= 1e-3 like every other conv kernel, and element by element against the
+    float64 reference (tests/conv_harness.py)."""
     from defectdetection_viaobjectdetection_amd import _capi
     g = torch.Generator().manual_seed(B * 100 + H + cin + cout)
     r16 = lambda t: t.half().float()
@@ -191,5 +185,4 @@ def test_conv3x3_planes_single_against_torch(cuda_device, B, H, W, cin, cout, re
     rel = float((got - want).norm() / want.norm())
     print(f"B={B} {H}x{W} {cin}->{cout} res={res}: rel-L2 {rel:.2e}")
     assert rel <= 1e-3
-    if (B, H, W, cin, cout, res) == (1, 13, 17, 128, 192, True):      # the ragged case: per element, between guard bands
-        _ragged_per_element(cuda_device, x, w, b, r, 1)
+    _per_element(cuda_device, x, w, b, r, 1)       # every case: per element, between guard bands, twice for identical bits

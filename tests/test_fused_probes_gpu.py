@@ -46,7 +46,7 @@ import torch.nn.functional as F
 
 import conv_bound as cb
 import fused_probe as fp
-from test_narrow_maps_gpu import _banded_input, _guarded_output, _guards_intact
+from conv_harness import banded_input as _banded_input, guarded_output as _guarded_output, guards_intact as _guards_intact
 
 pytestmark = pytest.mark.gpu
 

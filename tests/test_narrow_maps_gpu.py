@@ -9,20 +9,13 @@ too, so a read outside them poisons the output.
 A forced tile may refuse a shape: m355_conv2d_fwd then returns M355_ERR_INVALID and m355_last_error() reads "conv launch failed:
 -1" (the launcher's -1).  A refusal is recorded and printed and the case is skipped; any other nonzero rc fails the test; every
 tile id must accept at least one of its shapes, and the dispatcher (tile -1) must accept every one."""
-import ctypes as C
-
 import pytest
 import torch
 
 import conv_bound as cb
+from conv_harness import ERR_INVALID, REFUSED_TEXT, banded_input as _banded_input, launch as _launch, reference as _reference
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096            # bytes around the output
-XGUARD = 32768          # fp16 NaNs around the input and the residual (more than a halo row of the widest case: 160 x 128 channels)
-ERR_INVALID = -1        # M355_ERR_INVALID (include/mi355yolo.h)
-REFUSED_TEXT = "conv launch failed: -1"
-
 
 def _c(B, H, W, cin, cout, k=3, s=1, act=1, res=False, f32=False):
     return (B, H, W, cin, cout, k, s, act, res, f32)
@@ -73,62 +66,6 @@ TILE_CASES[32] = [_c(2, 1, 20, 256, 256, k=1), _c(1, 1, 1, 128, 128, k=1), _c(2,
 TILE_CASES[33] = [_c(2, 2, 20, 256, 256), _c(2, 4, 20, 256, 64), _c(2, 20, 2, 256, 256), _c(2, 1, 20, 256, 256),
                   _c(2, 8, 40, 128, 256, s=2), _c(2, 4, 40, 256, 512, s=2), _c(2, 40, 4, 128, 128, s=2), _c(2, 2, 2, 64, 128, s=2),
                   _c(2, 8, 20, 256, 256, res=True), _c(2, 64, 2, 64, 64), _c(2, 16, 40, 128, 256, s=2), _c(1, 128, 4, 64, 128, s=2)]
-
-_REFS = {}
-
-
-def _reference(case):
-    """Operands and the float64 reference of a case: computed once, shared by every tile id, never modified."""
-    if case not in _REFS:
-        B, H, W, cin, cout, k, s, act, use_res, f32 = case
-        x, w, b, res = cb.draw_operands(case, B, H, W, cin, cout, k, use_res, s)
-        y64, z64, S = cb.conv_ref(x, w, b, k, s, act, res)
-        tol = cb.conv_tol(y64, z64, S, cin * k * k, act, res, out_f32=f32)
-        _REFS[case] = (x, w.contiguous(), b.contiguous(), res, y64, tol)
-    return _REFS[case]
-
-
-def _banded_input(t_nchw, dev):
-    """NHWC fp16 copy of t between two bands of XGUARD NaNs.  Returns (the allocation, the data pointer)."""
-    flat = t_nchw.permute(0, 2, 3, 1).contiguous().to(torch.float16).reshape(-1)
-    buf = torch.full((flat.numel() + 2 * XGUARD,), float("nan"), dtype=torch.float16)
-    buf[XGUARD:XGUARD + flat.numel()] = flat
-    d = buf.to(dev)
-    return d, d.data_ptr() + 2 * XGUARD
-
-
-def _guarded_output(nbytes, dtype, dev):
-    """A NaN-filled body of nbytes between two bands of GUARD bytes 0xA5.  Returns (the allocation, the body as a flat dtype view)."""
-    raw = torch.full((2 * GUARD + nbytes,), 0xA5, dtype=torch.uint8, device=dev)
-    body = raw[GUARD:GUARD + nbytes].view(dtype)
-    body.fill_(float("nan"))
-    return raw, body
-
-
-def _guards_intact(raw, what):
-    """Host copy of the body's bytes after asserting that no byte of either band changed."""
-    h = raw.cpu()
-    nbytes = h.numel() - 2 * GUARD
-    assert bool((h[:GUARD] == 0xA5).all()) and bool((h[GUARD + nbytes:] == 0xA5).all()), f"{what}: a byte around the output changed"
-    return h[GUARD:GUARD + nbytes]
-
-
-def _launch(capi, case, tile, xp, rp, w, b, out_shape, dev):
-    """One call into a fresh guard-banded, NaN-filled output.  Returns (rc, output (B, cout, Ho, Wo) on the host or None)."""
-    B, H, W, cin, cout, k, s, act, use_res, f32 = case
-    dt = torch.float32 if f32 else torch.float16
-    n = B * out_shape[2] * out_shape[3] * cout
-    raw, body = _guarded_output(n * (4 if f32 else 2), dt, dev)
-    rc = capi.lib.m355_conv2d_fwd(C.c_void_p(xp), B, H, W, cin, C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), cout, k, s, act,
-                                  C.c_void_p(rp), C.c_void_p(body.data_ptr()), int(f32), tile,
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    got = _guards_intact(raw, f"tile {tile} {case}").view(dt)
-    if rc != 0:
-        assert bool(torch.isnan(got).all()), f"tile {tile} {case}: rc {rc} but the output was written"
-        return rc, None
-    return 0, got.reshape(B, out_shape[2], out_shape[3], cout).permute(0, 3, 1, 2)
-
 
 @pytest.mark.parametrize("tile", sorted(TILE_CASES))
 def test_conv_on_narrow_maps(tile, cuda_device):

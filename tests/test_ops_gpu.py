@@ -2,6 +2,10 @@
 
 Tolerance: fp16 in / fp32 accumulate conv output rel-L2 <= 1e-3 vs the fp32 reference
 evaluated on the same fp16-rounded inputs and weights; pooling / upsample are bit-exact.
+
+The conv-family tests (conv2d_fwd on every forced tile id, the fp32-output head, ConvT 2x2) are judged element by element as well:
+float64 reference of the same operands, the derived bounds of tests/conv_bound.py and tests/launch_ref.py, input between NaN bands,
+output NaN-filled between guard bands, a second launch for identical bits (tests/conv_harness.py).
 """
 import ctypes as C
 
@@ -9,6 +13,10 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import conv_bound as cb
+import conv_harness as ch
+import launch_ref as lr
 
 pytestmark = pytest.mark.gpu
 
@@ -143,12 +151,19 @@ def test_conv2d_fwd(case, cuda_device):
     assert torch.isfinite(y).all()
     err = rel_l2(y, y_ref)
     assert err <= 1e-3, f"rel-L2 {err}"
+    # the same draw (conv_bound.draw_operands seeds and draws as above) once more between guard bands, judged element by element
+    # against the float64 reference: bound, bands, finite, identical bits on a second launch
+    c10 = (B, H, W, cin, cout, k, s, act, use_res, False)
+    ops = ch.reference(c10, key=case, keep=False)
+    assert torch.equal(ops[0], xh) and torch.equal(ops[1], wh) and torch.equal(ops[2], b), "the harness drew other operands"
+    ch.judge(capi, c10, tile, ops, cuda_device, f"tile {tile} {case}")
 
 
 def test_conv2d_f32_out_small_cout(cuda_device):
-    """Head-final 1x1 convs: fp32 output, Cout = nc = 1 and 64, no activation."""
+    """Head-final 1x1 convs: fp32 output, Cout = nc = 1 and 64, no activation; 65 is the odd width of the raw head (64 box + 1 class).
+    Judged per element with conv_bound's fp32-output bound in a NaN-filled fp32 body between guard bands."""
     capi = _lib()
-    for cout in (1, 3, 64):
+    for cout in (1, 3, 64, 65):
         B, H, W, cin = 2, 20, 20, 128
         g = torch.Generator().manual_seed(cout)
         x = torch.randn(B, cin, H, W, generator=g)
@@ -161,12 +176,24 @@ def test_conv2d_f32_out_small_cout(cuda_device):
                                       _p(None), _p(dy), 1, -1, C.c_void_p(torch.cuda.current_stream().cuda_stream))
         capi.check(rc)
         y = dy.cpu().permute(0, 3, 1, 2)
+        assert torch.isfinite(y).all()
         assert rel_l2(y, y_ref) <= 1e-5
+        c10 = (B, H, W, cin, cout, 1, 1, 0, False, True)
+        xh, wh = x.half().float(), w.half().float().contiguous()
+        y64, z64, S = cb.conv_ref(xh, wh, b, 1, 1, 0, None)
+        tol = cb.conv_tol(y64, z64, S, cin, 0, None, out_f32=True)
+        ch.judge(capi, c10, -1, (xh, wh, b.contiguous(), None, y64, tol), cuda_device, f"fp32 out, cout {cout}")
 
 
-@pytest.mark.parametrize("shape", [(2, 20, 12, 128, 128), (2, 16, 32, 128, 128), (3, 8, 16, 64, 256), (1, 12, 16, 128, 48)])
+CONVT_SHAPES = [(2, 20, 12, 128, 128), (2, 16, 32, 128, 128), (3, 8, 16, 64, 256), (1, 12, 16, 128, 48)]
+
+
+@pytest.mark.parametrize("shape", CONVT_SHAPES)
 def test_convt2x2(shape, cuda_device):
-    """(W % 16 == 0 and Co % 128 == 0 take the fast pixel-shuffle epilogue, the others the generic one)"""
+    """(W % 16 == 0 and Co % 128 == 0 take the fast pixel-shuffle epilogue, the others the generic one)
+    Per element: float64 launch_ref.convt_ref of the fp16-rounded operands plus the bias, S from |x|, |w| and |bias|,
+    launch_ref.elem_bound with K = cin; every output pixel (2h + dy, 2w + dx) is compared at its own place, and the worst ratio of
+    each of the four shuffle positions is printed."""
     capi = _lib()
     B, H, W, cin, cout = shape
     g = torch.Generator().manual_seed(5)
@@ -180,7 +207,27 @@ def test_convt2x2(shape, cuda_device):
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
     capi.check(rc)
     y = dy.float().cpu().permute(0, 3, 1, 2)
+    assert torch.isfinite(y).all()
     assert rel_l2(y, y_ref) <= 1e-3
+    x64, w64 = x.half().double().permute(0, 2, 3, 1), w.half().double()
+    ref = lr.convt_ref(x64, w64) + b.double()
+    S = lr.convt_ref(x64.abs(), w64.abs()) + b.double().abs()
+    bound = lr.elem_bound(ref, S, cin)
+    xd, xp = ch.banded_input(x, cuda_device)
+    outs = []
+    for _ in range(2):
+        raw, body = ch.guarded_output(B * 4 * H * W * cout * 2, torch.float16, cuda_device)
+        capi.check(capi.lib.m355_convt2x2_fwd(C.c_void_p(xp), B, H, W, cin, _p(w.contiguous()), _p(b.contiguous()), cout,
+                                              C.c_void_p(body.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        outs.append(ch.guards_intact(raw, f"convt {shape}").view(torch.float16).reshape(B, 2 * H, 2 * W, cout))
+    got = outs[0]
+    for dyy in (0, 1):
+        for dxx in (0, 1):
+            r, _, _ = lr.check_elementwise(got[:, dyy::2, dxx::2], ref[:, dyy::2, dxx::2], bound[:, dyy::2, dxx::2])
+            print(f"convt {shape}: shuffle position ({dyy}, {dxx}): worst |err|/bound {r:.3f}")
+    ch.judged_elementwise(got, ref, bound, f"convt {shape}")
+    assert ch.same_bits(outs[0], outs[1]), f"convt {shape}: two runs differ"
 
 
 @pytest.mark.parametrize("hw", [(64, 96), (40, 100), (66, 80),   # W*3 a multiple of 16 (row-staged kernel) or not (gather kernel)
