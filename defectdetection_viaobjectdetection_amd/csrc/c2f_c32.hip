@@ -85,6 +85,7 @@ __device__ __forceinline__ half8 to_half8(const float16v& v, int lo) {
   return o;
 }
 
+template <bool PROBE>
 __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int tiles_x, int tiles_y, int ntiles, int sx, int sy, int sb,
                                                         unsigned long long* stamps, int prio) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -92,23 +93,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, W = a.W, nwg = gridDim.x;
   const int n = lane & 31, h = lane >> 5;
-  // diagnostic builds of a launch only (M355_C2F_STAMPS): cycles per section and wave
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-#define C2F_STAMP(k)                                                                                      \
-  if (stamps) {                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime();                                           \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    tacc[k] += tn - tlast;                                                                                \
-    tlast = tn;                                                                                           \
-  }
-  auto stamps_out = [&]() __attribute__((always_inline)) {
-    if (stamps && lane == 0) {
-      unsigned long long* o = stamps + ((long)blockIdx.x * NWAVES + wave) * 8;
-      for (int k = 0; k < 8; ++k) o[k] = tacc[k];
-    }
-  };
+  SectionClock<PROBE, 8> clk(stamps);   // probe instance only (M355_C2F_STAMPS): cycles per section and wave
 
   if (tid < 32) ((float*)(smem + BIAS_OFF))[tid] = a.ba[tid];
   else if (tid < 64) ((float*)(smem + BIAS_OFF))[tid] = a.bb[tid - 32];
@@ -252,7 +237,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
       if (have[2]) issue_patch(tbi[2], ty0[2], tx0[2], 1);
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                          // patches 0 and 1 landed, biases and Wc visible
-      if (stamps) tlast = __builtin_amdgcn_s_memtime();
+      clk.start();
       for (int it = -1;; ++it) {
         plan(3);
         // the K loop runs in rows of three taps: the fragments of row kh + 1 are read under the MFMAs of row kh (the
@@ -270,7 +255,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
         if (have[1]) read_row(0, 0);
         const bool issued = LOADER && have[3];
         if (issued) issue_patch(tbi[3], ty0[3], tx0[3], (it + 3) & (NBUF - 1));
-        C2F_STAMP(0)   // tile step + DMA issue
+        clk.mark(0);   // tile step + DMA issue
         if (have[1]) {
           char* const tbuf = smem + T_OFF + ((it + 1) & 1) * T_BYTES;
           float16v acc[NB];
@@ -296,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
                   acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[2 * (3 * kh + kw) + s], fr[kh & 1][(kw * 2 + s) * NB + k], acc[k], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
-          C2F_STAMP(1)   // reads + MFMAs
+          clk.mark(1);   // reads + MFMAs
           // t outside the image is the ZERO PADDING of the second conv, not the first conv evaluated on padding
 #pragma unroll
           for (int k = 0; k < NB; ++k) {
@@ -310,18 +295,18 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
             }
           }
         }
-        C2F_STAMP(2)   // SiLU + t writes
+        clk.mark(2);   // SiLU + t writes
         // the patch of tile it + 2 (issued one iteration ago) has landed: everything but this iteration's pieces
         if (!issued) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         else if (wave == 2) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory");
-        C2F_STAMP(3)   // own DMA landed
+        clk.mark(3);   // own DMA landed
         __builtin_amdgcn_s_barrier();
-        C2F_STAMP(4)   // barrier
+        clk.mark(4);   // barrier
         if (!have[1]) break;
         advance();
       }
-      stamps_out();
+      clk.flush(stamps, NWAVES, wave);
     };
     if (wave < 2) team_x(std::integral_constant<int, 2>{});
     else team_x(std::integral_constant<int, 1>{});
@@ -400,10 +385,10 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
     // team Y is the critical path (48 of a SIMD's 64-80 SiLU groups per tile): it wins the issue arbitration against its
     // partner wave of team X, which has the slack (M355_C2F_NOPRIO=1 in the launcher turns this off for A/B runs)
     if (prio) __builtin_amdgcn_s_setprio(1);
-    if (stamps) tlast = __builtin_amdgcn_s_memtime();
+    clk.start();
     for (int it = -1;; ++it) {
       plan(3);
-      C2F_STAMP(0)   // tile step
+      clk.mark(0);   // tile step
       const char* const pb = smem + (it & (NBUF - 1)) * PATCH_BYTES;
       const char* const tb_ = smem + T_OFF + (it & 1) * T_BYTES;
       half8 fr[2][6], f0[2], f1[2];
@@ -419,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
         for (int s = 0; s < 2; ++s) { f0[s] = *(const half8*)(pb + offy0[s]); f1[s] = *(const half8*)(pb + offy1[s]); }
       }
       if (it >= 1) flush();                                // tile it - 1
-      C2F_STAMP(1)   // deferred output epilogue + stores
+      clk.mark(1);   // deferred output epilogue + stores
       if (it >= 0) {
         // ---- Bottleneck.cv2: 18 K slices over t, rows of three taps
         float16v acc = bias_vec(32 + 8 * h, 32 + 16 + 8 * h);
@@ -438,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
               acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[2 * (3 * kh + kw) + s], fr[kh & 1][kw * 2 + s], acc, 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
-        C2F_STAMP(2)   // Bottleneck.cv2 reads + MFMAs
+        clk.mark(2);   // Bottleneck.cv2 reads + MFMAs
         // ---- C2f.cv2 over [y0, y1]
         o0 = bias_vec(64 + 16 * h, 64 + 16 * h + 8);
         o1 = bias_vec(96 + 16 * h, 96 + 16 * h + 8);
@@ -456,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
         o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[1][2], f1[1], o0, 0, 0, 0);
         o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[1][3], f1[1], o1, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        C2F_STAMP(3)   // 1x1 over y0, y1
+        clk.mark(3);   // 1x1 over y0, y1
         // ---- y2 = y1 + SiLU(.) -> fp16 (the rounding point of the unfused path's HBM store): B fragments of slices 4, 5
         half8 y2[2];
         silu16_c2f(acc);
@@ -476,20 +461,19 @@ __global__ __launch_bounds__(512, 2) void c2f_c32_kernel(const C2fC32Args a, int
         o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[0][1], y2[0], o1, 0, 0, 0);
         o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[0][2], y2[1], o0, 0, 0, 0);
         o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[0][3], y2[1], o1, 0, 0, 0);
-        C2F_STAMP(4)   // y2 epilogue + the last four MFMAs
+        clk.mark(4);   // y2 epilogue + the last four MFMAs
         out_off = (int)((long)tbi[0] * a.y_bstride + ((long)(ty0[0] + 2 * q) * W + tx0[0]) * a.ldy);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this team issues no loads: its stores stay in flight)
-      C2F_STAMP(5)
+      clk.mark(5);
       __builtin_amdgcn_s_barrier();
-      C2F_STAMP(6)   // barrier
+      clk.mark(6);   // barrier
       if (!have[1]) break;
       advance();
     }
     flush();                                               // the block's last tile
-    stamps_out();
+    clk.flush(stamps, NWAVES, wave);
   }
-#undef C2F_STAMP
 }
 
 }  // namespace
@@ -509,7 +493,8 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s) {
   const int ntiles = a.B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)c2f_c32_kernel, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)c2f_c32_kernel<false>, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)c2f_c32_kernel<true>, LDS_BYTES)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
@@ -518,14 +503,12 @@ int launch_c2f_c32(const C2fC32Args& a, hipStream_t s) {
   const int grid = ntiles <= slots ? ntiles : slots;
   const int step = grid >> 3;                         // linear tile stride of a block's walk inside its XCD group
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
-  // diagnostic: M355_C2F_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
+  // probe instance: M355_C2F_STAMPS=<file> -> per-wave section cycles of the LAST launch, written after a stream sync [sync]
   const int prio = proc_switches().c2f_noprio ? 0 : 1;
-  const char* st_path = proc_switches().c2f_stamps;
-  static StampSink sink;
-  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
-  hipLaunchKernelGGL(c2f_c32_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, sink.d, prio);
-  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
-  return (int)hipGetLastError();
+  return launch_stamped(proc_switches().c2f_stamps, (size_t)slots * NWAVES * 64, (size_t)grid * NWAVES * 64, s, [&](unsigned long long* st) {
+    auto k = st ? c2f_c32_kernel<true> : c2f_c32_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, st, prio);
+  });
 }
 
 }  // namespace m355

@@ -37,8 +37,25 @@ struct ConvArgs {
   int convt_co;        // >0: ConvTranspose 2x2/s2 pixel-shuffle store with Co = convt_co
   const half_t* zero;  // >=16 bytes of zeros in device memory (source for padded taps)
   int tmode;           // 1: transposed-stride gather = dgrad of a 3x3 / stride-2 / pad-1 conv (x is dY, y is dX)
-  int dbg;             // ablation switches for profiling experiments (0 in production)
-  unsigned long long* stamps;  // diagnostic builds: per-block s_memtime stamps (nullptr in production)
+  int dbg;             // the bits of the table below (0 in production)
+  unsigned long long* stamps;  // probe instances: the stamp buffer (nullptr in production)
+  // ---- dbg / stamps.  A kernel's production instance (PROBE = false, device_prims.h) reads neither `stamps` nor an ablation bit; the
+  // launcher starts the PROBE = true instance exactly when conv_probe_wanted() holds.  m355_conv2d_fwd puts force_tile >> 8 here.
+  //   Ablation bits: skip work, WRONG output by design, timing experiments only (tools/ablate_*.py, tools/stamps_*.py):
+  //     bit   conv_igemm          conv3x3_halo / _wide / _small (slab)          conv3x3_m32
+  //       1   no activation DMA   no patch DMA of the next chunk                no patch DMA
+  //       2   no weight DMA       no weight DMA (halo; wide / slab: unread)     no weight DMA in the loop
+  //       4   --                  no SiLU, general epilogue                     no barrier
+  //       8   no barrier          no stores, general epilogue                   --
+  //      32   no SiLU, general epilogue                                   --                            --
+  //     M355_S2C32_DBG (conv3x3_s2c32, its own word): 1 no patch DMA after the first tile, 2 no 3x3 stage, 4 no 1x1 stage,
+  //       8 no barrier, 16 no epilogue + stores.  M355_MASK_DBG (postprocess.hip, its own word): 1 zero fill only, 2 no stores;
+  //       its bit 4 (plain instead of non-temporal stores) is a path selector.
+  //   Path selectors: choose between two correct paths, read at run time by every instance:
+  //      64   conv_igemm: persistent grid (M355_PERSIST)
+  //     256   general epilogue on every tile (M355_NO_FAST_EPI; igemm, halo, wide, slab, c32)
+  //     512   conv_igemm: full wait instead of the counted wait behind a tile's stores
+  //   16 and 128 have no reader.
   // Upsample read-through (1x1 convs only): input channels [0, csplit) are NOT in x but in the half-resolution tensor
   // x2 -- output pixel (h, w) reads x2 pixel (h >> 1, w >> 1), i.e. Upsample(2x, nearest) + Concat without the copy.
   const half_t* x2;
@@ -77,6 +94,10 @@ struct ConvArgs {
   const half_t* wf2;   // the same for `w2` (proto_phase_wreg.hip: the eight fragments of proto.cv3)
   int bias_lds;        // set by the implicit-GEMM launcher: this many bias floats are staged in LDS behind the stages (0: none)
 };
+
+// the ablation bits each kernel family reads (the table at ConvArgs::dbg), and when a launcher takes the probe instance
+constexpr int DBG_ABLATE_IGEMM = 1 | 2 | 8 | 32, DBG_ABLATE_HALO = 1 | 2 | 4 | 8, DBG_ABLATE_M32 = 1 | 2 | 4;
+inline bool conv_probe_wanted(const ConvArgs& a, int ablation_bits) { return a.stamps || (a.dbg & ablation_bits); }
 
 // tile ids for launch_conv_igemm(force_tile)
 enum { TILE_AUTO = -1, TILE_128x128 = 0, TILE_64x128 = 1, TILE_32x256 = 2, TILE_64x256 = 3, TILE_64x128W8 = 5, TILE_HALO = 16, TILE_HALO8W = 17, TILE_HALO4W = 18, TILE_HALOWIDE = 19, TILE_C32 = 20, TILE_SLAB = 25, TILE_M32 = 26, TILE_M32_128 = 27, TILE_M32_64x16 = 28, TILE_M32_64x8 = 29, TILE_W1 = 32, TILE_PLANES = 33 };
@@ -255,7 +276,7 @@ struct PlanesArgs {
   half_t* y; long y_bstride; int ldy;
   const half_t* res; long r_bstride; int ldr;    // optional residual (the shortcut of a Bottleneck: x itself)
   int act;
-  unsigned long long* stamps;                    // diagnostic: 8 uint64 per wave (nullptr in production)
+  unsigned long long* stamps;                    // probe instances: 2 x 8 uint64 per wave (nullptr in production)
   // block-diagonal single mode (launch_conv3x3_blockdiag): diag_n convs side by side, conv i = the next diag_cin[i] input channels ->
   // the next diag_cout[i] output channels (Cin / Cout = their sums; every cout but the last a multiple of 64).  wfb = the convs'
   // planes_frag_pack_padded lists one after the other (each over its OWN input planes), bb = their biases at their channel offsets,

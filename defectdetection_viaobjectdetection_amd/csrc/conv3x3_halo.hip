@@ -34,7 +34,7 @@ constexpr int PW = TS + 2;        // patch width (18)
 constexpr int ROWB = 128;         // one LDS row = 64 halves = one pixel's (or weight row's) 64-deep K chunk
 
 // TH = tile rows (16 with 8 waves, 8 with 4 waves): NWAVES = WCH * WPX, NT * WPX = TH.
-template <int MT, int NT, int WCH, int WPX>
+template <int MT, int NT, int WCH, int WPX, bool PROBE>
 __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const ConvArgs a, int tiles_x,
                                                                          int tiles_y, int nchunks, int npatch) {
   constexpr int NWAVES = WCH * WPX;
@@ -53,11 +53,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const wbase = smem + npatch * PATCH_BYTES;
 
-  unsigned long long st0 = 0, st1 = 0, st2 = 0, rt0 = 0;
-  if (a.stamps) {
-    st0 = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
+  BlockStamps<PROBE> bs(a.stamps);   // probe instance only (tools/stamps_halo.py): entry, K loop start / end, block end
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
 
   // Fast epilogue (device_prims.h) when this wave's rows x 16 columns x 64 channels are all inside the tensor: the bias is
   // fetched here, before the K loop, and waits in registers.
-  const bool fast = y0 + wpx * NT + NT <= H && x0 + TS <= W && ch_base + wch * MT * 16 + MT * 16 <= a.Cout && !(a.dbg & (12 | 256));
+  const bool fast = y0 + wpx * NT + NT <= H && x0 + TS <= W && ch_base + wch * MT * 16 + MT * 16 <= a.Cout && !(a.dbg & 256) && !probe_bit<PROBE>(a.dbg, 12);
   float4v bv[MT / 2][2];
   if (fast) {
     const float* bp = a.bias + ch_base + wch * MT * 16 + g * 8;
@@ -174,7 +170,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       bv[sg][1] = *(const float4v*)(bp + sg * 32 + 4);
     }
   }
-  if (a.stamps) st1 = __builtin_amdgcn_s_memtime();
+  bs.at(1);
   const int nsteps = nchunks * 9;
   int chunk = 0, tap = 0;  // of step s
   for (int s = 0; s < nsteps; ++s) {
@@ -221,8 +217,8 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       for (int nt = 0; nt < NT; ++nt)
         acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af1[mt], bf1[nt], acc[mt][nt], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    if (s + NWB < nsteps && !(a.dbg & 2)) issue_weights(cN, tN, s & (NWB - 1));  // dbg: timing ablations only
-    if (tap < P_IT && chunk + 1 < nchunks && !(a.dbg & 1)) {
+    if (s + NWB < nsteps && !probe_bit<PROBE>(a.dbg, 2)) issue_weights(cN, tN, s & (NWB - 1));
+    if (tap < P_IT && chunk + 1 < nchunks && !probe_bit<PROBE>(a.dbg, 1)) {
 #pragma unroll
       for (int i = 0; i < P_IT; ++i)
         if (i == tap) issue_patch_piece(chunk + 1, i);
@@ -243,7 +239,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
     tap = t1;
   }
 
-  if (a.stamps) st2 = __builtin_amdgcn_s_memtime();
+  bs.at(2);
   // ---- epilogue (bias, SiLU, residual, fp16 pack, 16-byte stores at a channel offset)
   if (fast) {
     const long pix0 = (long)(y0 + wpx * NT) * W + x0 + l15;
@@ -259,12 +255,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       if (a.act) conv_epilogue_fast<MT, NT, true, false>(acc, bv, yp, ystep, nullptr, 0);
       else conv_epilogue_fast<MT, NT, false, false>(acc, bv, yp, ystep, nullptr, 0);
     }
-    if (a.stamps && tid == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-      unsigned long long* o = a.stamps + (long)blockIdx.x * 8;
-      o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-    }
+    if (tid == 0) bs.flush(blockIdx.x);
     return;
   }
   constexpr int GROUPS = (MT >= 2) ? MT / 2 : 1;
@@ -290,7 +281,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       }
 #pragma unroll
       for (int j = 0; j < GW; ++j) v[j] += a.bias[ch0 + j];
-      if (a.act && !(a.dbg & 4)) {
+      if (a.act && !probe_bit<PROBE>(a.dbg, 4)) {
 #pragma unroll
         for (int j = 0; j < GW; ++j) v[j] = m355_silu(v[j]);
       }
@@ -307,7 +298,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
         }
       }
       half_t* yp = (half_t*)a.y + (long)b * a.y_bstride + pix * a.ldy + ch0;
-      if ((a.dbg & 8) && v[0] != 123.f) continue;  // dbg: no stores
+      if (probe_bit<PROBE>(a.dbg, 8) && v[0] != 123.f) continue;
       if (GW == 8) {
         half8 o;
 #pragma unroll
@@ -321,12 +312,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, 2) void conv3x3_halo_kernel(const C
       }
     }
   }
-  if (a.stamps && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* o = a.stamps + (long)blockIdx.x * 8;  // [4..5]: 100 MHz realtime -> in-kernel clock
-    o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-  }
+  if (tid == 0) bs.flush(blockIdx.x);
 }
 
 template <int MT, int NT, int WCH, int WPX>
@@ -341,7 +327,7 @@ int launch_halo_variant(const ConvArgs& a, hipStream_t s) {
   const int B = a.M / (a.Ho * a.Wo);
   if (!conv_rows_covered(a, BCH)) return -1;
   const int lds = npatch * PGROUPS * 8 * ROWB + ((WCH * WPX == 8) ? 4 : 2) * BCH * ROWB;
-  auto k = conv3x3_halo_kernel<MT, NT, WCH, WPX>;
+  auto k = conv_probe_wanted(a, DBG_ABLATE_HALO) ? conv3x3_halo_kernel<MT, NT, WCH, WPX, true> : conv3x3_halo_kernel<MT, NT, WCH, WPX, false>;
   if (lds > 65536) {
     if (const int e = prepare_kernel((const void*)k, lds)) return e;
   }

@@ -72,7 +72,7 @@ struct M32 {
 };
 
 // Everything a step needs, in registers.
-template <int BCH, int NB>
+template <int BCH, int NB, bool PROBE>
 struct M32State {
   using C = M32<BCH, NB>;
   float16v acc[2][NB];
@@ -87,12 +87,12 @@ struct M32State {
   char* smem;
   int wave, woff;                  // woff = npatch * PATCH_BYTES: start of the weight ring
   int cin2;                        // bytes per tap in a packed weight row
-  int dbg;                         // timing-only ablations (tools/stamps_m32.py): 1 no patch DMA, 2 no weight DMA in the loop, 4 no barrier
+  int dbg;                         // the ablation bits of ConvArgs::dbg (table: common.h), read by the probe instance only
 };
 
 // One K step of the chunk in patch buffer PB, tap TAP.  Entering, fragment set 0 holds K slice 0 of this step.
-template <int BCH, int NB, int TAP, int PB>
-__device__ __forceinline__ void m32_step(M32State<BCH, NB>& st) {
+template <int BCH, int NB, int TAP, int PB, bool PROBE>
+__device__ __forceinline__ void m32_step(M32State<BCH, NB, PROBE>& st) {
   using C = M32<BCH, NB>;
   constexpr int KH = TAP / 3, KW = TAP % 3;
   constexpr int PARW = (PB + TAP) & 1;                       // weight stage of this step
@@ -123,7 +123,7 @@ __device__ __forceinline__ void m32_step(M32State<BCH, NB>& st) {
   __builtin_amdgcn_sched_barrier(0);
   // every wave: its reads of this stage have returned, its DMA of the next step (and patch pieces) has landed
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  if (!(st.dbg & 4)) __builtin_amdgcn_s_barrier();
+  if (!probe_bit<PROBE>(st.dbg, 4)) __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   // K slice 0 of the next step (tap 0 of the next chunk after tap 8: only if the stream goes on)
   if (TAP < 8 || st.has_next) {
@@ -136,7 +136,7 @@ __device__ __forceinline__ void m32_step(M32State<BCH, NB>& st) {
   // weights of step n + 2 into the stage this step has just finished with
   {
     char* dst = st.smem + st.woff + PARW * C::WBUF + st.wave * 1024;
-    if (st.dbg & 2) {
+    if (probe_bit<PROBE>(st.dbg, 2)) {
     } else if (TAP <= 6) {
       const int soff = st.kcur + (TAP + 2) * st.cin2;
 #pragma unroll
@@ -149,7 +149,7 @@ __device__ __forceinline__ void m32_step(M32State<BCH, NB>& st) {
   }
   // one (or two) pieces of the next chunk's patch into the other patch buffer; taps 0..7 only, so that the last piece
   // has landed (this wait + this barrier, one step later) before tap 0 of the next chunk reads it
-  if (TAP < 8 && st.has_next && !(st.dbg & 1)) {
+  if (TAP < 8 && st.has_next && !probe_bit<PROBE>(st.dbg, 1)) {
 #pragma unroll
     for (int i = 0; i < C::P_IT; ++i) {
       if ((i % 8) != TAP) continue;
@@ -163,8 +163,8 @@ __device__ __forceinline__ void m32_step(M32State<BCH, NB>& st) {
 #undef M32_MFMA
 }
 
-template <int BCH, int NB, int PB>
-__device__ __forceinline__ void m32_chunk(M32State<BCH, NB>& st) {
+template <int BCH, int NB, int PB, bool PROBE>
+__device__ __forceinline__ void m32_chunk(M32State<BCH, NB, PROBE>& st) {
   m32_step<BCH, NB, 0, PB>(st);
   m32_step<BCH, NB, 1, PB>(st);
   m32_step<BCH, NB, 2, PB>(st);
@@ -180,16 +180,12 @@ struct M32Tile {
   int b, y0, x0, ch;   // image, first row, first column, first channel
 };
 
-template <int BCH, int NB>
+template <int BCH, int NB, bool PROBE>
 __global__ __launch_bounds__(256, 2) void conv3x3_m32_kernel(const ConvArgs a, int tiles_x, int tiles_y, int nchunks,
                                                             int npatch, int ntiles) {
   using C = M32<BCH, NB>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long st0 = 0, st1 = 0, rt0 = 0;   // diagnostic runs only (tools/stamps_m32.py)
-  if (a.stamps) {
-    st0 = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
+  BlockStamps<PROBE> bs(a.stamps);   // probe instance only (tools/stamps_m32.py): entry, stream start, (unused), block end
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_m32_kernel(const ConvArgs a, i
     return t;
   };
 
-  M32State<BCH, NB> st;
+  M32State<BCH, NB, PROBE> st;
   st.smem = smem;
   st.wave = wave;
   st.woff = npatch * C::PATCH_BYTES;
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_m32_kernel(const ConvArgs a, i
   for (int mt = 0; mt < 2; ++mt) st.fa[0][mt] = *(const half8*)(smem + (st.ta[0] + mt * 32 * ROWB));
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) st.fb[0][nb] = *(const half8*)(smem + (st.tb[0][0] + nb * 2 * PP * ROWB));
-  if (a.stamps) st1 = __builtin_amdgcn_s_memtime();
+  bs.at(1);
 
   int c = 0, ntile_done = 0;
   // Before a chunk: where does the stream go next?  Same tile -> same buffers, K offset + 128 bytes; last chunk of a tile ->
@@ -385,11 +381,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_m32_kernel(const ConvArgs a, i
     m32_chunk<BCH, NB, 1>(st);
     if (!end_chunk()) break;
   }
-  if (a.stamps && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned long long* o = a.stamps + (long)blockIdx.x * 8;
-    o[0] = st0; o[1] = st1; o[2] = 0; o[3] = __builtin_amdgcn_s_memtime(); o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-    o[6] = (unsigned long long)ntile_done;
+  if (tid == 0) {
+    bs.flush(blockIdx.x);
+    bs.put((long)blockIdx.x * 8 + 6, (unsigned long long)ntile_done);
   }
 }
 
@@ -404,11 +398,12 @@ int launch_m32(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x * tiles_ch;
   // a persistent block streams chunk after chunk, also across tiles: it needs both patch buffers unless it never has a
   // second chunk at all (one chunk per tile AND one tile per block)
-  auto k = conv3x3_m32_kernel<BCH, NB>;
+  auto k = conv_probe_wanted(a, DBG_ABLATE_M32) ? conv3x3_m32_kernel<BCH, NB, true> : conv3x3_m32_kernel<BCH, NB, false>;
   static int slots[2] = {0, 0};   // resident blocks for (one, two) patch buffers
   constexpr int LDS1 = C::PATCH_BYTES + 2 * C::WBUF, LDS2 = 2 * C::PATCH_BYTES + 2 * C::WBUF;
   if (!slots[0]) {
-    if (const int e = prepare_kernel((const void*)k, LDS2)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_m32_kernel<BCH, NB, false>, LDS2)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_m32_kernel<BCH, NB, true>, LDS2)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     for (int i = 0; i < 2; ++i) {

@@ -43,6 +43,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <utility>
 
 #include "common.h"
@@ -253,7 +254,7 @@ struct PTile {
   int p0, np, wo;  // block-diagonal mode: first input plane, input planes, fragment offset in phases
 };
 
-template <class C, bool RES, bool DIAG = false>
+template <class C, bool RES, bool DIAG, bool PROBE>
 __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const PlanesArgs a, const PlanesGeom g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -265,9 +266,9 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
   const int H = a.H, W = a.W, PW = g.PW, R = g.R;   // H, W: input map
   const int Ho = C::S2 ? H / 2 : H, Wo = C::S2 ? W / 2 : W;   // output map (PW = Wo + 1)
   const int nwg = gridDim.x, ntiles = g.ntiles;
-  unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long pst[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // diagnostic: start of phase 0, 1, 2, last of either conv, end
-  if (a.stamps) stamp[0] = __builtin_amdgcn_s_memtime();
+  // probe instance only, per wave.  Points: entry, first patch landed, last phase of the first conv, hidden tensor complete, last phase of
+  // the second conv, end.  Second list: start of phase 0, 1, 2 and of the last phase of either conv (the block's last tile).
+  BlockStamps<PROBE, 6, 8> bs(a.stamps);
 
   // XCD-aware persistent walk (as conv3x3_m32.hip): the virtual blocks of one XCD cover a contiguous run of tiles; channel
   // tiles fastest (they share the input slab in L2), then slabs, then images.
@@ -391,7 +392,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  if (a.stamps) stamp[1] = __builtin_amdgcn_s_memtime();
+  bs.at(1);
 
   const int xslot = g.xrows * ROWB;   // bytes of an input ring slot
   const int iplane = g.irows * ROWB;  // bytes of an intermediate plane
@@ -424,15 +425,16 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
         ++xg;
       };
       setup1(0);
-      if (a.stamps) pst[0] = __builtin_amdgcn_s_memtime();
+      bs.at2(0);
       planes_phase<C, C::NPB1, true, 0, false>(st, bv, store1);
       for (int p = 1; p + 1 < NP; ++p) {
         setup1(p);
-        if (a.stamps && p < 3) pst[p] = __builtin_amdgcn_s_memtime();
+        bs.at2(1, p == 1);
+        bs.at2(2, p == 2);
         planes_phase<C, C::NPB1, false, 0, true>(st, bv, store1);
       }
       setup1(NP - 1);
-      if (a.stamps) stamp[2] = pst[3] = __builtin_amdgcn_s_memtime();
+      bs.both(2, 3);
       planes_phase<C, C::NPB1, false, 1, true>(st, bv, store1);
       if (more) piece_offsets(nxt);   // every piece of this tile has been issued: the loader moves on
       // zero padding (a wave's LDS operations complete in order).  Only the wp == 0 wave of a channel block writes it -- after
@@ -455,7 +457,7 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
       }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if (a.stamps) stamp[3] = __builtin_amdgcn_s_memtime();
+      bs.at(3);
     }
     // =========================== second (or only) convolution: R rows ===========================
     {
@@ -518,10 +520,10 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
         st.rs_wn = __builtin_amdgcn_make_buffer_rsrc((void*)(p + 1 < npl ? wbase_b + (p + 1) * pbytes : (C::PAIR ? wbase_a : wbase_b_next)), 0, pbytes, 0x00020000);
       };
       setup2(0);
-      if (a.stamps) pst[4] = __builtin_amdgcn_s_memtime();
+      bs.at2(4);
       if constexpr (DIAG) {   // a diagonal block of one input plane: its only phase is the first and the last
         if (npl == 1) {
-          if (a.stamps) stamp[4] = pst[7] = pst[4];
+          bs.both(4, 7);
           planes_phase<C, C::NPB2, true, RES ? 3 : 2, false>(st, bv2, store2);
         }
       }
@@ -529,11 +531,12 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
         planes_phase<C, C::NPB2, true, 0, false>(st, bv2, store2);
         for (int p = 1; p + 1 < npl; ++p) {
           setup2(p);
-          if (a.stamps && p < 3) pst[4 + p] = __builtin_amdgcn_s_memtime();
+          bs.at2(5, p == 1);
+          bs.at2(6, p == 2);
           planes_phase<C, C::NPB2, false, 0, true>(st, bv2, store2);
         }
         setup2(npl - 1);
-        if (a.stamps) stamp[4] = pst[7] = __builtin_amdgcn_s_memtime();
+        bs.both(4, 7);
         planes_phase<C, C::NPB2, false, RES ? 3 : 2, true>(st, bv2, store2);
       }
     }
@@ -554,15 +557,10 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void planes_kernel(const Pla
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
-  if (a.stamps && lane == 0) {
-    stamp[5] = __builtin_amdgcn_s_memtime();
-    unsigned long long* o = a.stamps + ((long)blockIdx.x * C::NW + wave) * 8;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) o[i] = stamp[i];
-    o[6] = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* o2 = a.stamps + (long)gridDim.x * C::NW * 8 + ((long)blockIdx.x * C::NW + wave) * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o2[i] = pst[i];
+  if (lane == 0) {
+    const long slot = (long)blockIdx.x * C::NW + wave;
+    bs.flush(slot, false);
+    bs.flush2(((long)gridDim.x * C::NW + slot) * 8, 0, 8);
   }
 }
 
@@ -613,12 +611,13 @@ bool planes_common_ok(const PlanesArgs& a) {
 
 template <class C>
 int planes_launch(const PlanesArgs& a, const PlanesGeom& g, hipStream_t s) {
-  auto k = a.res ? planes_kernel<C, true> : planes_kernel<C, false>;
+  auto k = a.stamps ? (a.res ? planes_kernel<C, true, false, true> : planes_kernel<C, false, false, true>)
+                    : (a.res ? planes_kernel<C, true, false, false> : planes_kernel<C, false, false, false>);
   static int slots = 0;
   if (!slots) {
-    int e = prepare_kernel((const void*)planes_kernel<C, true>, LDS_MAX);
-    if (!e) e = prepare_kernel((const void*)planes_kernel<C, false>, LDS_MAX);
-    if (e) return e;
+    for (const void* fn : {(const void*)planes_kernel<C, true, false, false>, (const void*)planes_kernel<C, false, false, false>,
+                           (const void*)planes_kernel<C, true, false, true>, (const void*)planes_kernel<C, false, false, true>})
+      if (const int e = prepare_kernel(fn, LDS_MAX)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
@@ -753,7 +752,8 @@ int launch_conv3x3_blockdiag(const PlanesArgs& a, hipStream_t s) {
   if (!diag_geometry(a, &g)) return -1;
   static int slots = 0;
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)planes_kernel<S64, false, true>, LDS_MAX)) return e;
+    if (const int e = prepare_kernel((const void*)planes_kernel<S64, false, true, false>, LDS_MAX)) return e;
+    if (const int e = prepare_kernel((const void*)planes_kernel<S64, false, true, true>, LDS_MAX)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = std::max(cus & ~7, 8);   // as planes_launch
@@ -777,7 +777,8 @@ int launch_conv3x3_blockdiag(const PlanesArgs& a, hipStream_t s) {
   // last one reach 2 PW + 2 storage indices past the block -- inside the allocation for any fill of the slab
   const int reach = g.off_x + g.xrows * ROWB + (32 * S64::NB2 + 2 * g.PW + 3) * ROWB;
   const int lds = std::min(std::max(g.off_s + 1024, (reach + 1023) & ~1023), LDS_MAX);
-  hipLaunchKernelGGL((planes_kernel<S64, false, true>), dim3(grid), dim3(64 * S64::NW), lds, s, a, g);
+  auto k = a.stamps ? planes_kernel<S64, false, true, true> : planes_kernel<S64, false, true, false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * S64::NW), lds, s, a, g);
   return (int)hipGetLastError();
 }
 

@@ -58,9 +58,12 @@ __device__ __forceinline__ int chl_of(int R) {
   return (R & ~31) + 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3);
 }
 
+template <bool PROBE>
 __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ntiles, int dbg) {
-  const unsigned long long t_entry = a.stamps ? __builtin_amdgcn_s_memtime() : 0, rt_entry = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-  // dbg: timing-only ablations (M355_S2C32_DBG): 1 no patch DMA after the first tile, 2 no 3x3 stage, 4 no 1x1 stage + epilogue, 8 no barrier
+  SectionClock<PROBE, 6> clk(a.stamps);   // probe instance only (M355_S2C32_STAMPS): cycles per section and wave
+  const unsigned long long t_entry = clk.now(), rt_entry = clk.realtime();
+  // dbg: the ablation bits of M355_S2C32_DBG (table: common.h), read by the probe instance only
+  auto skip = [&](int bit) __attribute__((always_inline)) { return probe_bit<PROBE>(dbg, bit); };
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -159,16 +162,6 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
     return v;
   };
 
-  unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;   // diagnostic stamps (M355_S2C32_STAMPS): cycles per section
-#define S2_STAMP(k)                                                                                       \
-  if (a.stamps) {                                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime();                                           \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    tacc[k] += tn - tlast;                                                                                \
-    tlast = tn;                                                                                           \
-  }
   // tile queue: wave 0 claims (one lane, returning atomic, in flight under a whole tile), publishes through LDS
   int* const nslot = (int*)(smem + BIAS_OFF + 512);
   int claim = 0;
@@ -194,8 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
   __builtin_amdgcn_s_barrier();
   int nvb = tq ? __builtin_amdgcn_readfirstlane(*nslot) : (vb + nwg < ntiles ? vb + nwg : -1);
 
-  if (a.stamps) tlast = __builtin_amdgcn_s_memtime();
-  const unsigned long long t_loop = tlast;
+  const unsigned long long t_loop = clk.start();
   for (int it = 0;; ++it) {
     const int buf = it & 1;
     const bool more = nvb >= 0;
@@ -203,14 +195,14 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
     if (more) {                                   // the next tile's patch streams in under this tile's arithmetic
       decode(nvb, ntb, ny0, nx0);
       patch_offsets(ny0, nx0);
-      if (!(dbg & 1)) issue_patch(ntb, buf ^ 1);
+      if (!skip(1)) issue_patch(ntb, buf ^ 1);
       if (tq) claim_issue();                      // ... and so does the claim of the tile after it
     }
-    S2_STAMP(0)   // decode + offsets + DMA issue
+    clk.mark(0);   // decode + offsets + DMA issue
     // ---- stage B: 3x3 / s2, K = 9 taps x 32 channels = 18 slices of 16
     float16v acc = bias_vec(0);
     const char* const pb = smem + buf * PATCH_BYTES;
-    if (!(dbg & 2))
+    if (!skip(2))
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int kh = tap / 3, kw = tap - 3 * kh;
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc, 0, 0, 0);
       }
     }
-    S2_STAMP(1)   // stage B reads + MFMAs
+    clk.mark(1);   // stage B reads + MFMAs
     // SiLU -> fp16 -> this lane's intermediate row (16 channels: two 16-byte writes)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -235,18 +227,18 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
       *(half8*)(smem + tz + (wm * 32 + 16 * h + half * 8) * 2) = o;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (no vmcnt wait here: the next patch keeps streaming)
-    if (!(dbg & 8)) __builtin_amdgcn_s_barrier();         // both channel halves of every pixel row are in LDS
-    S2_STAMP(2)   // stage B epilogue + barrier
+    if (!skip(8)) __builtin_amdgcn_s_barrier();         // both channel halves of every pixel row are in LDS
+    clk.mark(2);   // stage B epilogue + barrier
     // ---- stage C: 1x1, K = 64 = 4 slices over the 32 pixel rows of this column block
     float16v acc2 = bias_vec(1);
-    if (!(dbg & 4))
+    if (!skip(4))
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const half8 bf = *(const half8*)(smem + tz + s * 32 + h * 16);
       const half8 af = *(const half8*)(smem + ta2 + s * 32);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc2, 0, 0, 0);
     }
-    S2_STAMP(3)   // stage C reads + MFMAs
+    clk.mark(3);   // stage C reads + MFMAs
     // the next patch has landed for every wave (and every wave is done reading the intermediate) BEFORE this tile's stores
     // are issued: the wait does not drain them, they fly under the next tile's arithmetic
     int nnvb = -1;
@@ -256,13 +248,13 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
         claim_publish();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
-      if (!(dbg & 8)) __builtin_amdgcn_s_barrier();
+      if (!skip(8)) __builtin_amdgcn_s_barrier();
       nnvb = tq ? __builtin_amdgcn_readfirstlane(*nslot) : (nvb + nwg < ntiles ? nvb + nwg : -1);
     } else {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    S2_STAMP(4)   // wait for the next patch + barrier
-    if (!(dbg & 16)) {
+    clk.mark(4);   // wait for the next patch + barrier
+    if (!skip(16)) {
       const int yy = y0 + 2 * wq + r2, xx = x0 + x15;
       half_t* const yp = (half_t*)a.y + (long)tb * a.y_bstride + ((long)yy * a.Wo + xx) * a.ldy + wm * 32 + 16 * h;
 #pragma unroll
@@ -273,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
         *(half8*)(yp + half * 8) = o;
       }
     }
-    S2_STAMP(5)   // stage C epilogue + stores issued
+    clk.mark(5);   // stage C epilogue + stores issued
     if (!more) break;
     vb = nvb; nvb = nnvb;
     tb = ntb; y0 = ny0; x0 = nx0;
@@ -284,13 +276,8 @@ __global__ __launch_bounds__(512, 2) void conv_s2c32_cv1_kernel(const ConvArgs a
       __hip_atomic_store(tq + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if (a.stamps && lane == 0) {
-    unsigned long long* o = a.stamps + ((long)blockIdx.x * NWAVES + wave) * 8;
-    for (int k = 0; k < 6; ++k) o[k] = tacc[k];
-    o[6] = t_loop - t_entry;                                                                  // prologue cycles
-    o[7] = (__builtin_amdgcn_s_memrealtime() << 32) | (rt_entry & 0xffffffffull);             // 100 MHz entry / exit times
-  }
-#undef S2_STAMP
+  // words 6, 7: prologue cycles; 100 MHz exit (high half) and entry times
+  clk.flush(a.stamps, NWAVES, wave, t_loop - t_entry, (clk.realtime() << 32) | (rt_entry & 0xffffffffull));
 }
 
 }  // namespace
@@ -312,39 +299,38 @@ int launch_conv_s2c32_cv1(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)conv_s2c32_cv1_kernel, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv_s2c32_cv1_kernel<false>, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv_s2c32_cv1_kernel<true>, LDS_BYTES)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = cus & ~7;   // one block per CU; the XCD-aware tile order needs gridDim.x % 8 == 0 whenever a block walks > 1 tile
     if (slots < 8) slots = 8;
   }
   const int grid = ntiles <= slots ? ntiles : slots;
-  // diagnostic (M355_S2C32_STAMPS, M355_S2C32_RING): per-wave section cycles of the last launch, or of the last `ring` launches
+  // probe instance (M355_S2C32_STAMPS, M355_S2C32_DBG): per-wave section cycles of the last launch [sync], timing ablations
   static const int dbg = proc_switches().s2c32_dbg, ring = proc_switches().s2c32_ring;
   static const char* st_path = proc_switches().s2c32_stamps;
+  auto launch = [&](unsigned long long* st) {
+    ConvArgs aa = a;
+    aa.stamps = st;
+    auto k = st || dbg ? conv_s2c32_cv1_kernel<true> : conv_s2c32_cv1_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, aa, tiles_x, tiles_y, ntiles, dbg);
+  };
+  const size_t per_launch = (size_t)slots * NWAVES * 64;
+  if (!st_path || ring <= 0) return launch_stamped(st_path, per_launch, (size_t)grid * NWAVES * 64, s, launch);
+  // M355_S2C32_RING: the stamps of the last `ring` launches, no synchronisation, written when the process exits
   static StampSink sink;
+  static size_t ring_bytes = 0;
   static long launches = 0;
-  static size_t per_launch = 0;
-  ConvArgs aa = a;
-  if (st_path) {
-    if (!sink.d) {
-      per_launch = (size_t)slots * NWAVES * 8 * 8;
-      if (!sink.alloc(per_launch * (ring > 0 ? ring : 1))) return -2;
-      if (ring > 0)
-        atexit([] {
-          (void)hipDeviceSynchronize();
-          const size_t n = per_launch * ring;
-          unsigned long long* h = (unsigned long long*)malloc(n);
-          (void)hipMemcpy(h, sink.d, n, hipMemcpyDeviceToHost);
-          FILE* f = fopen(st_path, "wb");
-          if (f) { fwrite(h, 1, n, f); fclose(f); }
-          free(h);
-        });
-    }
-    aa.stamps = sink.d + (ring > 0 ? (launches++ % ring) * (per_launch / 8) : 0);
+  if (!sink.d) {
+    ring_bytes = per_launch * ring;
+    if (!sink.alloc(ring_bytes)) return -2;
+    atexit([] {
+      (void)hipDeviceSynchronize();
+      sink.write(st_path, ring_bytes);
+    });
   }
-  hipLaunchKernelGGL(conv_s2c32_cv1_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, aa, tiles_x, tiles_y, ntiles, dbg);
-  if (ring <= 0 && sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
+  launch(sink.d + (launches++ % ring) * (per_launch / 8));
   return (int)hipGetLastError();
 }
 

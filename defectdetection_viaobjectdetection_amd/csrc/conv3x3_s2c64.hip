@@ -45,6 +45,7 @@ constexpr int BIAS_OFF = STG_OFF + NWAVES * 2048;    // 128 + 128 floats
 constexpr int W2_OFF = BIAS_OFF + 1024;              // the 1x1's 4 x 8 fragments (lane-linear: conflict-free reads)
 constexpr int LDS_BYTES = W2_OFF + 32 * 1024;        // 154624
 
+template <bool PROBE>
 __global__ __launch_bounds__(512, 2) void conv3x3_s2c64_cv1_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ntiles, int sx,
                                                                   int sy, int sb, int prio, unsigned long long* stamps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -125,17 +126,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2c64_cv1_kernel(const ConvArg
   char* const zt = smem + Z_OFF + team * 8192;
   char* const stg = smem + STG_OFF + wave * 2048;
 
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = stamps ? __builtin_amdgcn_s_memtime() : 0;
+  SectionClock<PROBE, 7> clk(stamps);
+  clk.start();
   int ntile = 0;
-#define S2_STAMP(k)                                                                                        \
-  if (stamps) {                                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                                     \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime();                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                                     \
-    tacc[k] += tn - tlast;                                                                                 \
-    tlast = tn;                                                                                            \
-  }
 
   float16v acc;
   // K: the 3x3 / s2 conv of this wave's 32 channels x 32 pixels out of patch buffer `pbuf`
@@ -253,38 +246,38 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2c64_cv1_kernel(const ConvArg
       ntb = tb; ny0 = ty * TH; nx0 = tx * TW;
       if (team == 1) issue_patch(ntb, ny0, nx0, (it + 1) & 1, 0, G_SPLIT);
     }
-    S2_STAMP(0)   // decode + DMA issue
+    clk.mark(0);   // decode + DMA issue
     if (team == 0) {
       if (it > 0) stage2(ptb, py0, px0);
-      S2_STAMP(1)   // S2 (team 0)
+      clk.mark(1);   // S2 (team 0)
       k_loop(smem + (it & 1) * PATCH_BYTES);
-      S2_STAMP(2)   // K (team 0)
+      clk.mark(2);   // K (team 0)
     } else {
       if (it > 0) z_write();
-      S2_STAMP(3)   // Z (team 1)
+      clk.mark(3);   // Z (team 1)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    S2_STAMP(4)   // barrier 1
+    clk.mark(4);   // barrier 1
     // ---- slot 2
     if (team == 0) {
       if (more) issue_patch(ntb, ny0, nx0, (it + 1) & 1, G_SPLIT, NPIECES);   // (before Z: the pieces land under the SiLUs)
-      S2_STAMP(0)   // DMA issue (team 0)
+      clk.mark(0);   // DMA issue (team 0)
       z_write();
-      S2_STAMP(3)   // Z (team 0)
+      clk.mark(3);   // Z (team 0)
     } else {
       if (it > 0) stage2(ptb, py0, px0);
-      S2_STAMP(1)   // S2 (team 1)
+      clk.mark(1);   // S2 (team 1)
       k_loop(smem + (it & 1) * PATCH_BYTES);
-      S2_STAMP(2)   // K (team 1)
+      clk.mark(2);   // K (team 1)
     }
     // the next patch has landed for this wave: team 1's pieces are older than its two stores of this slot; team 0's are the
     // youngest operations it has in flight
     if (team == 1 && it > 0) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    S2_STAMP(5)   // wait patch
+    clk.mark(5);   // wait patch
     __builtin_amdgcn_s_barrier();
-    S2_STAMP(6)   // barrier 2
+    clk.mark(6);   // barrier 2
     ptb = ctb; py0 = y0; px0 = x0;
     if (!more) break;
     vb += nwg;
@@ -296,12 +289,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2c64_cv1_kernel(const ConvArg
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (team == 1) stage2(ptb, py0, px0);
-  if (stamps && lane == 0) {
-    unsigned long long* o = stamps + ((long)blockIdx.x * NWAVES + wave) * 8;
-    for (int k = 0; k < 7; ++k) o[k] = tacc[k];
-    o[7] = (unsigned long long)ntile;
-  }
-#undef S2_STAMP
+  clk.flush(stamps, NWAVES, wave, (unsigned long long)ntile);
 }
 
 }  // namespace
@@ -325,7 +313,8 @@ int launch_conv_s2c64_cv1(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;
   static int slots = 0;
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)conv3x3_s2c64_cv1_kernel, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_s2c64_cv1_kernel<false>, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_s2c64_cv1_kernel<true>, LDS_BYTES)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = cus & ~7;
@@ -335,12 +324,11 @@ int launch_conv_s2c64_cv1(const ConvArgs& a, hipStream_t s) {
   const int step = grid >> 3;                          // tiles between two visits of a block (it walks only when grid = slots, % 8 == 0)
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
   const int prio = proc_switches().s2c64_prio;
-  const char* st_path = proc_switches().s2c64_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
-  static StampSink sink;
-  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
-  hipLaunchKernelGGL(conv3x3_s2c64_cv1_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, sink.d);
-  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
-  return (int)hipGetLastError();
+  // probe instance (M355_S2C64_STAMPS): per-wave section cycles of the LAST launch [sync]
+  return launch_stamped(proc_switches().s2c64_stamps, (size_t)slots * NWAVES * 64, (size_t)grid * NWAVES * 64, s, [&](unsigned long long* st) {
+    auto k = st ? conv3x3_s2c64_cv1_kernel<true> : conv3x3_s2c64_cv1_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, st);
+  });
 }
 
 }  // namespace m355

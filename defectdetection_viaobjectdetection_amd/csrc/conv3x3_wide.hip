@@ -51,17 +51,16 @@ constexpr int LDS_BYTES = 2 * PATCH_BYTES + NWB * WBUF + 2 * BCH * 4;
 //   * the patch of the next chunk streams in 9 affine pieces: at tap t waves 0-2 load LDS rows 40 t .. 40 t + 47
 //     (= patch rows 2t, 2t+1 and the first 8 pixels of 2t+2, rewritten identically by tap t+1), source offset
 //     = lane base + t * 2 W ldx; out-of-image pixels read a zero page instead of being EXEC-masked.
+template <bool PROBE>
 __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, int tiles_x, int tiles_y, int nchunks,
                                                               int ntiles, int stagger) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const wbase = smem + 2 * PATCH_BYTES;
   float* const sbias = (float*)(wbase + NWB * WBUF);   // two buffers of BCH floats (tile parity)
 
-  unsigned long long st0 = 0, st1 = 0, st2 = 0, rt0 = 0, sa = 0, sb = 0, sc = 0, sd = 0, sa2 = 0;
-  if (a.stamps) {
-    st0 = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
+  // probe instance only: entry, K loop start / end of the first tile, block end; of the second tile: epilogue start / end, K loop
+  // start / end; the start of the third
+  BlockStamps<PROBE, 4, 5> bs(a.stamps);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
   // epilogue of a finished tile (bias from LDS, SiLU, residual, fp16 pack, 16-byte stores at a channel offset)
   auto epilogue = [&](int eb, int ey0, int ex0, int ech, int par) __attribute__((always_inline)) {
     // fast path: this wave's 8 rows x 16 columns x 64 channels are all inside the tensor
-    if (ey0 + wpx * NT + NT <= H && ex0 + TS <= W && ech + wch * 64 + 64 <= a.Cout && !(a.dbg & (12 | 256))) {
+    if (ey0 + wpx * NT + NT <= H && ex0 + TS <= W && ech + wch * 64 + 64 <= a.Cout && !(a.dbg & 256) && !probe_bit<PROBE>(a.dbg, 12)) {
       const float* sb = sbias + par * BCH + wch * 64 + g * 8;
       float4v bv[MT / 2][2];
 #pragma unroll
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
           v[j] = acc[2 * sg][nt][j] + b0[j];
           v[4 + j] = acc[2 * sg + 1][nt][j] + b1[j];
         }
-        if (a.act && !(a.dbg & 4)) {
+        if (a.act && !probe_bit<PROBE>(a.dbg, 4)) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = m355_silu(v[j]);
         }
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] += (float)rv[j];
         }
-        if ((a.dbg & 8) && v[0] != 123.f) continue;  // dbg: no stores
+        if (probe_bit<PROBE>(a.dbg, 8) && v[0] != 123.f) continue;
         half8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = m355_to_half(v[j]);
@@ -230,17 +229,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
     // The finished tile's epilogue runs while this tile's prologue DMA is in flight.  Its stores are the youngest
     // vector-memory operations, so the counted wait below lets all 16 of them (full tile) stay outstanding.
     bool prev_full = false;
-    if (a.stamps && ntile == 1) sa = __builtin_amdgcn_s_memtime();
-    if (a.stamps && ntile == 2) sa2 = __builtin_amdgcn_s_memtime();
+    bs.at2(0, ntile == 1);
+    bs.at2(4, ntile == 2);
     if (have_prev) {
-      prev_full = (py0_ + wpx * NT + NT <= H) && (pch_ + wch * 64 + 64 <= a.Cout) && !(a.dbg & 8);
+      prev_full = (py0_ + wpx * NT + NT <= H) && (pch_ + wch * 64 + 64 <= a.Cout) && !probe_bit<PROBE>(a.dbg, 8);
       epilogue(pb_, py0_, px0_, pch_, par ^ 1);
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = float4v{0.f, 0.f, 0.f, 0.f};
-    if (a.stamps && ntile == 1) sb = __builtin_amdgcn_s_memtime();
+    bs.at2(1, ntile == 1);
     if (prev_full)
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NWB - 1) * W_IT + 2 * NT) : "memory");
     else
@@ -256,8 +255,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
 #pragma unroll
     for (int nt = 0; nt < NT / 2; ++nt) bf[nt] = *(const half8*)(smem + (be ^ ((nt & 1) << 5)) + nt * (PP * ROWB));
 
-    if (a.stamps && ntile == 0) st1 = __builtin_amdgcn_s_memtime();
-    if (a.stamps && ntile == 1) sc = __builtin_amdgcn_s_memtime();
+    bs.at(1, ntile == 0);
+    bs.at2(2, ntile == 1);
 
 #define M355_SB __builtin_amdgcn_sched_barrier(0);
 #define M355_MF(AC, mt, nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AC[mt], bf[nt], acc[mt][nt], 0, 0, 0);
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
     const int pbk_n = pb + kh_n * PP;                                                                            \
     const int wnext = (3 * kh_n * a.Cin + chunk_n * 32) * 2;                                                     \
     const bool lastrow = row + 1 >= nrows;                                                                       \
-    const bool do_p = chunk + 1 < nchunks && !(a.dbg & 1);
+    const bool do_p = chunk + 1 < nchunks && !probe_bit<PROBE>(a.dbg, 1);
 #define M355_ROW_END                                                                                             \
     kh = kh_n; chunk = chunk_n; pbuf = pbuf_n; pbk = pbk_n; ++row;
 
@@ -329,8 +328,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
 #undef M355_RA
 #undef M355_ROW
 
-    if (a.stamps && ntile == 0) st2 = __builtin_amdgcn_s_memtime();
-    if (a.stamps && ntile == 1) sd = __builtin_amdgcn_s_memtime();
+    bs.at(2, ntile == 0);
+    bs.at2(3, ntile == 1);
     // After the last step's barrier no wave reads live LDS data any more (its second half only pre-reads the
     // never-used step after the end), so the next tile's DMA may start without another barrier.
     pb_ = tb; py0_ = ty0; px0_ = tx0; pch_ = tch;
@@ -344,15 +343,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wide_kernel(const ConvArgs a, 
     issue_prologue(par);
   }
   epilogue(pb_, py0_, px0_, pch_, par ^ 1);
-  if (a.stamps && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long st3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* o = a.stamps + (long)blockIdx.x * 8;  // [0..2]: first tile; [3]: block end; [6]: tiles done
-    o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-    o[6] = (unsigned long long)ntile;
-    unsigned long long* o2 = a.stamps + (1 << 19) + (long)blockIdx.x * 4;  // second tile: epilogue start / end, loop start / end
-    o2[0] = sa; o2[1] = sb; o2[2] = sc; o2[3] = sd;
-    a.stamps[(1 << 19) + (1 << 18) + blockIdx.x] = sa2;
+  if (tid == 0) {
+    bs.flush(blockIdx.x);
+    bs.put((long)blockIdx.x * 8 + 6, (unsigned long long)ntile);   // tiles done
+    bs.flush2((1 << 19) + (long)blockIdx.x * 4, 0, 4);
+    bs.flush2((1 << 19) + (1 << 18) + blockIdx.x, 4, 1);
   }
 }
 
@@ -373,7 +368,8 @@ int launch_conv3x3_wide(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x * tiles_ch;
   static int slots = 0;   // resident blocks: two per CU
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)conv3x3_wide_kernel, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_wide_kernel<false>, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)conv3x3_wide_kernel<true>, LDS_BYTES)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = proc_switches().wide_slots >= 0 ? proc_switches().wide_slots : 2 * cus;
@@ -382,7 +378,8 @@ int launch_conv3x3_wide(const ConvArgs& a, hipStream_t s) {
   }
   const int grid = ntiles <= slots ? ntiles : slots;
   const int stagger = proc_switches().wide_stagger >= 0 ? proc_switches().wide_stagger : 0;
-  hipLaunchKernelGGL(conv3x3_wide_kernel, dim3(grid), dim3(256), LDS_BYTES, s, a, tiles_x, tiles_y, a.Cin / 32, ntiles,
+  auto k = conv_probe_wanted(a, DBG_ABLATE_HALO) ? conv3x3_wide_kernel<true> : conv3x3_wide_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS_BYTES, s, a, tiles_x, tiles_y, a.Cin / 32, ntiles,
                      ntiles > grid ? stagger : 0);
   return (int)hipGetLastError();
 }

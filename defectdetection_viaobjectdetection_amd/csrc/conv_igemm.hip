@@ -43,7 +43,7 @@ namespace {
 // Compiled into the one 128x128 1x1 kernel, the decode epilogue's register peak made the allocator spill 5 VGPRs at the top of
 // EVERY 1x1 launch (24 B of scratch per lane, stored whether or not the epilogue ran: 8 MB of scratch writes per launch beside
 // 75 MB of tensors, PMC WRITE_SIZE) -- the dominant kernel family paid for an epilogue that is off by default.
-template <int MT, int NT, int WCH, int WPX, int KS, int EPI = 0>
+template <int MT, int NT, int WCH, int WPX, int KS, int EPI, bool PROBE>
 __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv_igemm_kernel(const ConvArgs a) {  // (threads, min waves per SIMD)
   constexpr int NW = WCH * WPX;       // waves per workgroup: 4, or 8 (half-size wave tiles: four waves per SIMD with two
                                       // workgroups per CU hide the ~100-cycle issue cost of each LDS-DMA piece)
@@ -57,11 +57,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
   static_assert(W_IT >= 1 && A_IT >= 1, "tile too small");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  unsigned long long st0 = 0, st1 = 0, st2 = 0, rt0 = 0;
-  if (a.stamps) {
-    st0 = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
+  BlockStamps<PROBE> bs(a.stamps);   // probe instance only (tools/stamps_igemm.py): entry, K loop start / end of the first tile, its end
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
   auto stage_next = [&]() __attribute__((always_inline)) {
     const int t = ld_t;
     char* sb = smem + (ld_g & 1) * STAGE;
-    const bool skip_w = (a.dbg & 2) && ld_g > 1, skip_a = (a.dbg & 1) && ld_g > 1;
+    const bool skip_w = probe_bit<PROBE>(a.dbg, 2) && ld_g > 1, skip_a = probe_bit<PROBE>(a.dbg, 1) && ld_g > 1;
 #pragma unroll
     for (int i = 0; i < W_IT; ++i) {
       if (!skip_w) glds16(wsrc[i] + t * BK, sb + (wave * (BCH / NW) + i * 8) * ROWB);
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af0[mt], bf0[nt], acc[mt][nt], 0, 0, 0);
     if (after_stores) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NST) : "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (!(a.dbg & 8)) __builtin_amdgcn_s_barrier();
+    if (!probe_bit<PROBE>(a.dbg, 8)) __builtin_amdgcn_s_barrier();
     // ks=0 fragments of the next stage (after the very last stage this reads stale bytes, never used)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) af0[mt] = *(const half8*)(sn + aoff[mt]);
@@ -333,12 +329,12 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
     // Fast epilogue (device_prims.h): the whole tile is inside the tensor and images are contiguous, so the output address
     // is affine in the pixel index; the bias is fetched before the K loop and waits in registers.
     const bool fast = MT >= 2 && !a.out_f32 && a.convt_co == 0 && px_base + BPX <= a.M && ch_base + BCH <= a.Cout &&
-                      a.y_bstride == (long)HoWo * a.ldy && (!a.res || a.r_bstride == (long)HoWo * a.ldr) && !(a.dbg & (32 | 256));
+                      a.y_bstride == (long)HoWo * a.ldy && (!a.res || a.r_bstride == (long)HoWo * a.ldr) && !(a.dbg & 256) && !probe_bit<PROBE>(a.dbg, 32);
     // ConvTranspose 2x2 / s2 (virtual channel q * Co + co, q = dy * 2 + dx): when a channel tile lies inside one q
     // (Co a multiple of the tile) and the 16-pixel groups do not straddle image rows, (dy, dx) are uniform per block
     // and each group's 16 pixels go to 16 output pixels two apart in one row
     const bool fast_t = MT >= 2 && !a.out_f32 && a.convt_co > 0 && a.convt_co % BCH == 0 && a.Wo % 16 == 0 && !a.res &&
-                        px_base + BPX <= a.M && ch_base + BCH <= a.Cout && !(a.dbg & (32 | 256));
+                        px_base + BPX <= a.M && ch_base + BCH <= a.Cout && !(a.dbg & 256) && !probe_bit<PROBE>(a.dbg, 32);
     float4v bv[MT >= 2 ? MT / 2 : 1][2];
     if ((fast || fast_t) && !a.bias_lds) {
       const int cb0 = fast_t ? ch_base % a.convt_co : ch_base;   // the bias is indexed by the real output channel
@@ -349,7 +345,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         bv[sg][1] = *(const float4v*)(bp + sg * 32 + 4);
       }
     }
-    if (a.stamps && tile == lb) st1 = __builtin_amdgcn_s_memtime();
+    bs.at(1, tile == lb);
     kstep(stores_pending);
     for (int t = 1; t < nk; ++t) kstep(false);
     stores_pending = false;
@@ -362,7 +358,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         bv[sg][1] = *(const float4v*)(bp + sg * 32 + 4);
       }
     }
-    if (a.stamps && tile == lb) st2 = __builtin_amdgcn_s_memtime();
+    bs.at(2, tile == lb);
 
     // ---- epilogue of this tile (the next tile's first two stages are already in flight / landed)
     const float* bias_fin = a.bias;   // bias of the conv whose output is stored
@@ -660,7 +656,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
     // stride-2 dgrad with 32 forward input channels (phase == 2, convt_co == 32): every 32-channel group of the tile is one phase of
     // the same 32 dX channels.  Whole tiles only; the generic epilogue below did this with two divisions per group at 0.74 TB/s.
     if (KS == 2 && MT >= 2 && a.phase == 2 && a.convt_co == 32 && !a.out_f32 && !a.res && !a.act && px_base + BPX <= a.M &&
-        ch_base + BCH <= a.Cout && !(a.dbg & (32 | 256))) {
+        ch_base + BCH <= a.Cout && !(a.dbg & 256) && !probe_bit<PROBE>(a.dbg, 32)) {
       const float4v b0 = *(const float4v*)(a.bias + g * 8), b1 = *(const float4v*)(a.bias + g * 8 + 4);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
@@ -714,11 +710,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         else conv_epilogue_fast<(MT >= 2 ? MT : 2), NT, false, false>(acc, bv, yp, ystep, nullptr, 0);
         stores_pending = a.bias_lds > 0 && !(a.dbg & 512);   // (no other vector-memory instruction between these stores and the next wait)
       }
-      if (a.stamps && tid == 0 && tile == lb) {   // diagnostic builds only (tools/stamps_igemm.py)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned long long* o = a.stamps + (long)blockIdx.x * 8;
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memtime(); o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
-      }
+      if (tid == 0 && tile == lb) bs.flush(blockIdx.x);
       continue;
     }
 #pragma unroll
@@ -753,7 +745,7 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         }
 #pragma unroll
         for (int j = 0; j < GW; ++j) v[j] += bias_fin[cidx + j];
-        if (a.act && !(a.dbg & 32)) {
+        if (a.act && !probe_bit<PROBE>(a.dbg, 32)) {
 #pragma unroll
           for (int j = 0; j < GW; ++j) v[j] = m355_silu(v[j]);
         }
@@ -797,12 +789,13 @@ __global__ __launch_bounds__(WCH * WPX * 64, (WCH * WPX == 8 ? 4 : 2)) void conv
         }
       }
     }
+    if (tid == 0 && tile == lb) bs.flush(blockIdx.x);   // (a first tile on the general epilogue is stamped too)
   }
   // every LDS-DMA this wave issued was waited for by the last kstep's vmcnt(0): no DMA can land after exit
 }
 
-template <int MT, int NT, int WCH, int WPX>
-int launch_variant(const ConvArgs& a, hipStream_t s) {
+template <int MT, int NT, int WCH, int WPX, bool PROBE>
+int launch_instance(const ConvArgs& a, hipStream_t s) {
   constexpr int BCH = WCH * MT * 16, BPX = WPX * NT * 16;
   constexpr int LDS = 2 * (BCH + BPX) * BK * 2;
   const int tiles_ch = (a.Cout + BCH - 1) / BCH;
@@ -839,17 +832,17 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
     }
   }
   const dim3 grid(grid_x), block(WCH * WPX * 64);
-  auto k1 = conv_igemm_kernel<MT, NT, WCH, WPX, 1>;
-  auto k2 = conv_igemm_kernel<MT, NT, WCH, WPX, 2>;
-  auto k3 = conv_igemm_kernel<MT, NT, WCH, WPX, 3>;
+  auto k1 = conv_igemm_kernel<MT, NT, WCH, WPX, 1, 0, PROBE>;
+  auto k2 = conv_igemm_kernel<MT, NT, WCH, WPX, 2, 0, PROBE>;
+  auto k3 = conv_igemm_kernel<MT, NT, WCH, WPX, 3, 0, PROBE>;
   auto k = a.ksize == 1 ? k1 : (a.ksize == 2 ? k2 : k3);
   if constexpr (MT == 4 && NT == 4 && WCH == 2 && WPX == 2) {          // the special epilogues live in instantiations of their own
     if (a.dec_preds) {
       if (a.ksize != 1) return -1;
-      k = conv_igemm_kernel<MT, NT, WCH, WPX, 1, 1>;
+      k = conv_igemm_kernel<MT, NT, WCH, WPX, 1, 1, PROBE>;
     } else if (a.phase && a.w2) {
       if (a.ksize != 2) return -1;
-      k = conv_igemm_kernel<MT, NT, WCH, WPX, 2, 2>;
+      k = conv_igemm_kernel<MT, NT, WCH, WPX, 2, 2, PROBE>;
     }
   } else {
     if (a.dec_preds || (a.phase && a.w2)) return -1;
@@ -859,6 +852,12 @@ int launch_variant(const ConvArgs& a, hipStream_t s) {
   }
   hipLaunchKernelGGL(k, grid, block, lds_bytes, s, aa);
   return (int)hipGetLastError();
+}
+// every instance has a probe form: m355_conv2d_fwd reaches each tile and kernel size with stamps or ablation bits (tools/tile_sweep.py,
+// tools/ablate_conv.py, tools/stamps_igemm.py)
+template <int MT, int NT, int WCH, int WPX>
+int launch_variant(const ConvArgs& a, hipStream_t s) {
+  return conv_probe_wanted(a, DBG_ABLATE_IGEMM) ? launch_instance<MT, NT, WCH, WPX, true>(a, s) : launch_instance<MT, NT, WCH, WPX, false>(a, s);
 }
 
 }  // namespace

@@ -81,6 +81,102 @@ __device__ __forceinline__ unsigned dropout_keep4(const DropArgs& d, unsigned lo
          ((unsigned)(c[3] >= d.thr) << 3);
 }
 
+// ---- probe instances: in-kernel stamps and timing ablations
+// A kernel that can stamp or ablate takes one template parameter `bool PROBE`.  Production is PROBE = false: the helpers below are
+// then empty (no members, every method an empty inline) and `probe_bit<false>` is the constant false, so the instance holds no
+// clock read, no stamp store and no ablation branch.  The launcher starts the PROBE = true instance exactly when a stamp buffer
+// or an ablation bit (the table at ConvArgs::dbg, common.h) is set.  A call site reads the same in both instances.
+template <bool PROBE>
+__device__ __forceinline__ bool probe_bit(int dbg, int bits) { return PROBE && (dbg & bits); }
+
+// Per-wave section accumulator: mark(k) adds the cycles since the last mark to section k.
+template <bool PROBE, int N>
+struct SectionClock {
+  __device__ __forceinline__ explicit SectionClock(const unsigned long long*) {}
+  __device__ __forceinline__ unsigned long long start() { return 0; }
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ unsigned long long now() const { return 0; }
+  __device__ __forceinline__ unsigned long long realtime() const { return 0; }
+  __device__ __forceinline__ void flush(unsigned long long*, int, int, unsigned long long = 0, unsigned long long = 0) {}
+};
+template <int N>
+struct SectionClock<true, N> {
+  static_assert(N <= 8, "a record is 8 words");
+  unsigned long long acc[N] = {}, last = 0;
+  bool on;                                             // false: an ablation-only launch of the probe instance, nothing is stamped
+  __device__ __forceinline__ explicit SectionClock(const unsigned long long* out) : on(out != nullptr) {}
+  __device__ __forceinline__ unsigned long long start() { return last = now(); }   // the clock the first section is counted from
+  __device__ __forceinline__ void mark(int k) {
+    if (on) {
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long tn = __builtin_amdgcn_s_memtime();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      acc[k] += tn - last;
+      last = tn;
+    }
+  }
+  __device__ __forceinline__ unsigned long long now() const { return on ? __builtin_amdgcn_s_memtime() : 0; }
+  __device__ __forceinline__ unsigned long long realtime() const { return on ? __builtin_amdgcn_s_memrealtime() : 0; }   // 100 MHz
+  // record (block, wave) of `waves` per block, 8 words: the N sections, then `extra` in the last word (N = 7) or the last two (N = 6)
+  __device__ __forceinline__ void flush(unsigned long long* out, int waves, int wave, unsigned long long extra = 0,
+                                        unsigned long long extra2 = 0) {
+    if (!on || (threadIdx.x & 63)) return;
+    unsigned long long* o = out + ((long)blockIdx.x * waves + wave) * 8;
+#pragma unroll
+    for (int k = 0; k < N; ++k) o[k] = acc[k];
+    if (N == 6) { o[6] = extra; o[7] = extra2; }
+    if (N == 7) o[7] = extra;
+  }
+};
+
+// Point stamps: the clock at NA named points of the first tile of a block (point 0 = kernel entry, the last one = the flush) and
+// at NB points of a later tile, plus the 100 MHz realtime at entry and at the flush.
+template <bool PROBE, int NA = 4, int NB = 0>
+struct BlockStamps {
+  __device__ __forceinline__ explicit BlockStamps(unsigned long long*) {}
+  __device__ __forceinline__ void at(int, bool = true) {}
+  __device__ __forceinline__ void at2(int, bool = true) {}
+  __device__ __forceinline__ void both(int, int) {}
+  __device__ __forceinline__ void flush(long, bool = true) {}
+  __device__ __forceinline__ void put(long, unsigned long long) {}
+  __device__ __forceinline__ void flush2(long, int, int) {}
+};
+template <int NA, int NB>
+struct BlockStamps<true, NA, NB> {
+  unsigned long long* out;                             // nullptr: an ablation-only launch of the probe instance
+  unsigned long long a[NA] = {}, b[NB ? NB : 1] = {}, rt0 = 0;
+  __device__ __forceinline__ explicit BlockStamps(unsigned long long* o) : out(o) {
+    if (out) {
+      a[0] = __builtin_amdgcn_s_memtime();
+      rt0 = __builtin_amdgcn_s_memrealtime();
+    }
+  }
+  __device__ __forceinline__ void at(int k, bool cond = true) { if (out && cond) a[k] = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void at2(int k, bool cond = true) { if (out && cond) b[k] = __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ void both(int k, int j) { if (out) a[k] = b[j] = __builtin_amdgcn_s_memtime(); }
+  // record `slot` (8 words, one thread calls): the NA points; then the realtime pair (NA = 4) or the realtime now (NA = 6).
+  // drain: the thread's stores have left before the last point is taken.
+  __device__ __forceinline__ void flush(long slot, bool drain = true) {
+    if (!out) return;
+    if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    a[NA - 1] = __builtin_amdgcn_s_memtime();
+    unsigned long long* o = out + slot * 8;
+#pragma unroll
+    for (int k = 0; k < NA; ++k) o[k] = a[k];
+    if (NA <= 4) o[4] = rt0;
+    o[NA <= 4 ? 5 : NA] = __builtin_amdgcn_s_memrealtime();
+  }
+  __device__ __forceinline__ void put(long word, unsigned long long v) { if (out) out[word] = v; }
+  // points [first, first + n) of the later tile to words off ..
+  __device__ __forceinline__ void flush2(long off, int first, int n) {
+    if (!out) return;
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+      if (k >= first && k < first + n) out[off + k - first] = b[k];   // (constant indices: the points stay in scalar registers)
+  }
+};
+
 // ---- SiLU and the conv epilogue
 // v * sigmoid(v);  exp2-based, rcp approx (1 ulp) -- far inside fp16 output rounding.
 // No FMA contraction in the epilogue arithmetic: the generic and the fast epilogue must give the same bits, so that an

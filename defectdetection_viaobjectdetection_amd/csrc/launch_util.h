@@ -1,5 +1,5 @@
-// Host-side helpers shared by the launchers.  Nothing here reads the environment or keeps per-kernel state: each launcher keeps
-// its own first-call flag and derives its own grid from the CU count.
+// Host-side helpers shared by the launchers.  Nothing here reads the environment, and the only per-kernel state is the stamp buffer
+// of launch_stamped: each launcher keeps its own first-call flag and derives its own grid from the CU count.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -23,7 +23,7 @@ inline int num_cus() {
   return cus;
 }
 
-// Device buffer of a kernel's diagnostic stamps and its way to a file (the M355_*_STAMPS switches).
+// Device buffer of a probe instance's stamps and its way to a file (the M355_*_STAMPS switches).
 struct StampSink {
   unsigned long long* d = nullptr;
   bool alloc(size_t bytes) {   // zeroed, once; false: the allocation failed
@@ -46,5 +46,18 @@ struct StampSink {
     return 0;
   }
 };
+
+// The launch of a kernel whose stamps go to a file named by a process-lifetime switch (M355_C2F_STAMPS and its like).  `launch(st)`
+// starts the kernel with the stamp buffer st (nullptr: none, the production instance unless an ablation asks for the probe one).
+// With `path` set the buffer (cap bytes, one per call site: the lambda's type is the key) is allocated and zeroed on first use, the
+// stream is waited for and the first n bytes go to `path`.  0, a HIP error code, or -2.
+template <class Launch>
+int launch_stamped(const char* path, size_t cap, size_t n, hipStream_t s, Launch launch) {
+  static StampSink sink;
+  if (path && !sink.alloc(cap)) return -2;
+  launch(path ? sink.d : nullptr);
+  if (sink.dump(s, path, n)) return -2;
+  return (int)hipGetLastError();
+}
 
 }  // namespace m355

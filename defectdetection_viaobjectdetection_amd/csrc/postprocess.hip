@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "device_prims.h"
 #include "launch_util.h"
 #include "switches.h"
 
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* preds, in
 // Tile = TR x TC prototype cells -> 4 TR x 4 TC output pixels.  8 x 32 (not 16 x 16): a row segment of the tile is then 128
 // output bytes = one whole cache line per 8 lanes (16 x 16 wrote 64-byte half lines: 1.67 TB/s of masks at batch 32, 22
 // detections per image); same number of cells per block, same LDS.
-template <int NM, int TR, int TC>
+template <int NM, int TR, int TC, bool PROBE>
 __global__ __launch_bounds__(256) void proto_masks_kernel(const float* dets, const int* counts, const half_t* protos,
                                                           int max_det, int mh, int mw, int in_h, int in_w,
                                                           uint8_t* masks, int dbg) {
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(256) void proto_masks_kernel(const float* dets, con
   for (int d = tid; d < n; d += 256) {
     const float* dp = dets + ((long)b * max_det + d) * (6 + NM);
     const float x1 = dp[0] * wr, y1 = dp[1] * hr, x2 = dp[2] * wr, y2 = dp[3] * hr;
-    const bool touches = !(dbg & 1) && !(wx1 < x1 || wx0 >= x2 || wy1 < y1 || wy0 >= y2);
+    const bool touches = !probe_bit<PROBE>(dbg, 1) && !(wx1 < x1 || wx0 >= x2 || wy1 < y1 || wy0 >= y2);
     touch_flag[d] = touches ? 1 : 0;
     if (touches) touch_list[atomicAdd(&ntouch_s, 1)] = (short)d;   // (order is irrelevant: every detection's mask is independent)
   }
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(256) void proto_masks_kernel(const float* dets, con
   // these stores (the prototype patch, the coefficients) would wait for every one of them -- fill and compute were additive
   // (76 + 48 us) with the fill first.
   auto zero_fill = [&]() __attribute__((always_inline)) {
-    if (Y < in_h && !(dbg & 2)) {
+    if (Y < in_h && !probe_bit<PROBE>(dbg, 2)) {
       typedef unsigned uint4v __attribute__((ext_vector_type(4)));
       for (int d = 0; d < n; ++d) {
         if (touch_flag[d]) continue;
@@ -339,7 +340,7 @@ __global__ __launch_bounds__(256) void proto_masks_kernel(const float* dets, con
           }
         }
         uint8_t* mp = masks + (((long)b * max_det + touch_list[c0 + d]) * in_h + Y) * in_w + X0;
-        if (dbg & 2) continue;
+        if (probe_bit<PROBE>(dbg, 2)) continue;
         if (X0 + 16 <= in_w) {
           typedef unsigned uint4v __attribute__((ext_vector_type(4)));
           if (dbg & 4) *(uint4v*)mp = *(const uint4v*)o;
@@ -394,16 +395,14 @@ int launch_proto_masks(const float* dets, const int* counts, const half_t* proto
                        int mh, int mw, int in_h, int in_w, uint8_t* masks, hipStream_t s) {
   if (nm != 32) return -1;
   if (in_h % mh || in_w % mw || in_w / mw != 4 || in_h / mh != 4 || in_w % 16) return -1;
-  const int dbg = proc_switches().mask_dbg, shape = proc_switches().mask_tile;   // timing ablations / the 16 x 16-cell tile
-  if (shape == 1) {
-    const int tiles = ((mw + 15) / 16) * ((mh + 15) / 16);
-    hipLaunchKernelGGL((proto_masks_kernel<32, 16, 16>), dim3(tiles, B), dim3(256), 0, s, dets, counts, protos, max_det, mh, mw,
-                       in_h, in_w, masks, dbg);
-  } else {
-    const int tiles = ((mw + 31) / 32) * ((mh + 7) / 8);
-    hipLaunchKernelGGL((proto_masks_kernel<32, 8, 32>), dim3(tiles, B), dim3(256), 0, s, dets, counts, protos, max_det, mh, mw,
-                       in_h, in_w, masks, dbg);
-  }
+  // M355_MASK_DBG (table: common.h): bits 1 and 2 are timing ablations and take the probe instance, bit 4 selects plain stores
+  const int dbg = proc_switches().mask_dbg, shape = proc_switches().mask_tile;   // shape 1: the 16 x 16-cell tile
+  const bool probe = dbg & 3;
+  const int tr = shape == 1 ? 16 : 8, tc = shape == 1 ? 16 : 32;
+  const int tiles = ((mw + tc - 1) / tc) * ((mh + tr - 1) / tr);
+  auto k = shape == 1 ? (probe ? proto_masks_kernel<32, 16, 16, true> : proto_masks_kernel<32, 16, 16, false>)
+                      : (probe ? proto_masks_kernel<32, 8, 32, true> : proto_masks_kernel<32, 8, 32, false>);
+  hipLaunchKernelGGL(k, dim3(tiles, B), dim3(256), 0, s, dets, counts, protos, max_det, mh, mw, in_h, in_w, masks, dbg);
   return (int)hipGetLastError();
 }
 

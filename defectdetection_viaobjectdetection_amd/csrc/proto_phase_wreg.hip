@@ -44,6 +44,7 @@ constexpr int STG_OFF = BIAS_OFF + 9 * 512 + 128;    // output staging: 4 waves 
 constexpr int TAB_OFF = STG_OFF + 4 * 2048;          // DMA offset table: [39 pieces][64 lanes] ints
 constexpr int LDS_BYTES = TAB_OFF + 39 * 256;        // 143744
 
+template <bool PROBE>
 __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs a, int tiles_x, int tiles_y, int ntiles, int sx, int sy,
                                                                  int sb, int prio, unsigned long long* stamps) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -140,18 +141,10 @@ __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs
   __builtin_amdgcn_s_waitcnt(0x0070);                  // (the builtin: the compiler does not re-wait for the weight loads in the loop)
   __builtin_amdgcn_s_barrier();
 
-  // diagnostic launches only (M355_PROTOR_STAMPS): cycles per section and wave
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = stamps ? __builtin_amdgcn_s_memtime() : 0;
+  // probe instance only (M355_PROTOR_STAMPS): cycles per section and wave
+  SectionClock<PROBE, 7> clk(stamps);
+  clk.start();
   int ntile = 0;
-#define PP_STAMP(k)                                                                                       \
-  if (stamps) {                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime();                                           \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    tacc[k] += tn - tlast;                                                                                \
-    tlast = tn;                                                                                           \
-  }
   // proto.cv3 of one finished tile: 32 channels x 128 pixels x K = 128 from Z; waves 0-3 take one 32-pixel block each
   auto cv3_tile = [&](int tb, int y0, int x0) __attribute__((always_inline)) {
     // (lane-derived values are rebuilt from mbcnt here: kept live across the phase conv they are spilled, and a scratch reload
@@ -213,14 +206,14 @@ __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs
       ntb = wb; ny0 = wy * TH; nx0 = wx * TW;
       issue_patch(ntb, ny0, nx0, (it + 1) & 1);
     }
-    PP_STAMP(0)   // tile decode + DMA issue
+    clk.mark(0);   // tile decode + DMA issue
     if (wave < 4) {
       if (it > 0) cv3_tile(ptb, py0, px0);
-      PP_STAMP(1)   // proto.cv3 + stores of the previous tile (waves 0-3)
+      clk.mark(1);   // proto.cv3 + stores of the previous tile (waves 0-3)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                    // A (waves 0-3)
     }
-    PP_STAMP(2)   // barrier A, waves 0-3
+    clk.mark(2);   // barrier A, waves 0-3
     const char* const pbuf = smem + (it & 1) * PATCH_BYTES;
     // ---- phase conv: 4 taps x 8 slices x 2 pixel blocks; the fragments of the next half tap are read under the MFMAs
     float16v acc[2];
@@ -249,12 +242,12 @@ __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs
       }
     }
     if (prio) __builtin_amdgcn_s_setprio(0);
-    PP_STAMP(3)   // reads + MFMAs
+    clk.mark(3);   // reads + MFMAs
     if (wave >= 4) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                    // A (waves 4-7): Z(i - 1) has been consumed
     }
-    PP_STAMP(4)   // barrier A, waves 4-7
+    clk.mark(4);   // barrier A, waves 4-7
     // ---- Z = SiLU(acc + bias[border class of the OUTPUT pixel]) -> fp16 -> LDS [pixel][128 ch], chunk XOR (pixel & 15)
 #pragma unroll
     for (int pb = 0; pb < 2; ++pb) {
@@ -283,23 +276,18 @@ __global__ __launch_bounds__(512, 2) void proto_phase_wreg_kernel(const ConvArgs
       *(half8*)(smem + Z_OFF + zp * 256 + ((c ^ (zp & 15)) << 4)) = o0;
       *(half8*)(smem + Z_OFF + zp * 256 + (((c + 1) ^ (zp & 15)) << 4)) = o1;
     }
-    PP_STAMP(5)   // bias + SiLU + Z writes
+    clk.mark(5);   // bias + SiLU + Z writes
     // the next patch has landed for this wave (waves 0-3: their stores were issued before it), Z is written
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                      // B
-    PP_STAMP(6)   // wait patch + barrier B
+    clk.mark(6);   // wait patch + barrier B
     ptb = tb; py0 = y0; px0 = x0;
     if (!more) break;
     t += nblk;
     tb = ntb; y0 = ny0; x0 = nx0;
   }
   if (wave < 4) cv3_tile(ptb, py0, px0);               // the last tile
-  if (stamps && lane == 0) {
-    unsigned long long* o = stamps + ((long)blockIdx.x * NWAVES + wave) * 8;
-    for (int k = 0; k < 7; ++k) o[k] = tacc[k];
-    o[7] = (unsigned long long)ntile;
-  }
-#undef PP_STAMP
+  clk.flush(stamps, NWAVES, wave, (unsigned long long)ntile);
 }
 
 }  // namespace
@@ -322,7 +310,8 @@ int launch_proto_phase_wreg(const ConvArgs& a, hipStream_t s) {
   const int ntiles = B * tiles_y * tiles_x;            // per phase
   static int slots = 0;
   if (!slots) {
-    if (const int e = prepare_kernel((const void*)proto_phase_wreg_kernel, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)proto_phase_wreg_kernel<false>, LDS_BYTES)) return e;
+    if (const int e = prepare_kernel((const void*)proto_phase_wreg_kernel<true>, LDS_BYTES)) return e;
     const int cus = num_cus();
     if (cus <= 0) return -2;
     slots = cus & ~3;
@@ -332,12 +321,11 @@ int launch_proto_phase_wreg(const ConvArgs& a, hipStream_t s) {
   const int step = grid >> 2;                          // tiles between two visits of a block (= blocks per phase)
   const int sx = step % tiles_x, sy = (step / tiles_x) % tiles_y, sb = step / tiles_x / tiles_y;
   const int prio = proc_switches().protor_prio;
-  const char* st_path = proc_switches().protor_stamps;   // diagnostic: per-wave section cycles of the LAST launch [sync]
-  static StampSink sink;
-  if (st_path && !sink.alloc((size_t)slots * NWAVES * 64)) return -2;
-  hipLaunchKernelGGL(proto_phase_wreg_kernel, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, sink.d);
-  if (sink.dump(s, st_path, (size_t)grid * NWAVES * 64)) return -2;
-  return (int)hipGetLastError();
+  // probe instance (M355_PROTOR_STAMPS): per-wave section cycles of the LAST launch [sync]
+  return launch_stamped(proc_switches().protor_stamps, (size_t)slots * NWAVES * 64, (size_t)grid * NWAVES * 64, s, [&](unsigned long long* st) {
+    auto k = st ? proto_phase_wreg_kernel<true> : proto_phase_wreg_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * NWAVES), LDS_BYTES, s, a, tiles_x, tiles_y, ntiles, sx, sy, sb, prio, st);
+  });
 }
 
 }  // namespace m355
