@@ -186,6 +186,14 @@ SIGNATURES = {
     "m355_dfine_relu_dropout_forward": (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
     "m355_dfine_relu_dropout_backward": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
     "m355_dfine_dropout_mask": (C.c_int, [C.c_int64, C.c_float, C.c_uint64, C.c_int32, _P, _P]),
+    "m355_dfine_addln_clamp_forward": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "m355_dfine_addln_clamp_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P,
+                                                  _P, C.c_int64, _P]),
+    "m355_dfine_gate_ln_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P]),
+    "m355_dfine_gate_ln_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                              _P]),
+    "m355_dfine_lqe_forward": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "m355_dfine_lqe_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "m355_dfine_gru_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "m355_dfine_gru_forward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32,
                                          _P, _P]),

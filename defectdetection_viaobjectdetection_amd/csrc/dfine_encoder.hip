@@ -1,6 +1,7 @@
 // The temporal encoder of the D-FINE trainers (nn.TransformerEncoderLayer, post-norm, ReLU, head dim 32) between its GEMMs:
 //   attn_fwd / attn_bwd          softmax(q k^T / sqrt(32)) [dropout] v on the packed in-projection output (B, S, 3 D)
-//   addln_fwd / addln_bwd        LayerNorm(x + dropout(y)), with the fixed-order column sums of dweight / dbias
+//   addln_fwd / addln_bwd        LayerNorm(x + dropout(y)), with the fixed-order column sums of dweight / dbias; their CLAMP
+//                                instances are LayerNorm(clamp(x + y, lo, hi)) of the D-FINE decoder layer (dfine_decoder.hip)
 //   relu_drop_fwd / relu_drop_bwd  dropout(relu(h))
 // All fp32 in, fp32 out, fp32 accumulation.  No float atomics anywhere: every sum has one owner and a fixed order, so the
 // results are bitwise reproducible and frame b does not depend on the batch.
@@ -368,6 +369,7 @@ struct LnArgs {
   int D;
   long rows_per_block;          // backward
   float eps;
+  float lo, hi;                 // the CLAMP instances: z = clamp(x + y, lo, hi) before the statistics
   DropArgs d;
 };
 
@@ -392,7 +394,19 @@ __device__ __forceinline__ float4 ln_load_z(const LnArgs& a, long row, int v, un
   return make_float4(xv.x + yv.x, xv.y + yv.y, xv.z + yv.z, xv.w + yv.w);
 }
 
-template <bool DROP>
+// torch.clamp of one element, NaN kept; `inside` = lo <= z <= hi, the elements that torch's clamp backward lets through
+__device__ __forceinline__ float clamp1(float z, float lo, float hi, bool& inside) {
+  inside = z >= lo && z <= hi;
+  return z < lo ? lo : (z > hi ? hi : z);
+}
+// bit c of the result: component c of z was inside [lo, hi]
+__device__ __forceinline__ unsigned ln_clamp4(float4& z, float lo, float hi) {
+  bool ix, iy, iz, iw;
+  z = make_float4(clamp1(z.x, lo, hi, ix), clamp1(z.y, lo, hi, iy), clamp1(z.z, lo, hi, iz), clamp1(z.w, lo, hi, iw));
+  return (unsigned)ix | (unsigned)iy << 1 | (unsigned)iz << 2 | (unsigned)iw << 3;
+}
+
+template <bool DROP, bool CLAMP = false>
 __global__ __launch_bounds__(LN_THREADS) void addln_fwd_kernel(const LnArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = a.D >> 2;
   const long row = (long)blockIdx.x * LN_WAVES + wave;
@@ -406,6 +420,7 @@ __global__ __launch_bounds__(LN_THREADS) void addln_fwd_kernel(const LnArgs a) {
     if (v < nv) {
       unsigned keep;
       z[t] = ln_load_z<DROP>(a, row, v, keep);
+      if (CLAMP) ln_clamp4(z[t], a.lo, a.hi);
       sum += (z[t].x + z[t].y) + (z[t].z + z[t].w);
     }
   }
@@ -434,7 +449,7 @@ __global__ __launch_bounds__(LN_THREADS) void addln_fwd_kernel(const LnArgs a) {
 
 // Block `blk` owns rows [blk * rows_per_block, ...): wave w takes every fourth of them in ascending order and keeps its
 // column sums of g * zhat and g in registers; the four waves' sums are added in wave order into partial row `blk`.
-template <bool DROP>
+template <bool DROP, bool CLAMP = false>
 __global__ __launch_bounds__(LN_THREADS) void addln_bwd_kernel(const LnArgs a) {
   __shared__ float part[LN_WAVES][2][LN_MAX_D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = a.D >> 2;
@@ -450,15 +465,17 @@ __global__ __launch_bounds__(LN_THREADS) void addln_bwd_kernel(const LnArgs a) {
   for (long row = r0 + wave; row < r1; row += LN_WAVES) {
     const float mean = a.mean[row], rstd = a.rstd[row];
     float4 zh[LN_MAXV], gw[LN_MAXV];
-    unsigned keep[LN_MAXV];
+    unsigned keep[LN_MAXV], inside[LN_MAXV];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int t = 0; t < LN_MAXV; ++t) {
       const int v = lane + 64 * t;
       zh[t] = gw[t] = make_float4(0.f, 0.f, 0.f, 0.f);
       keep[t] = 0u;
+      inside[t] = 0xfu;
       if (v < nv) {
-        const float4 z = ln_load_z<DROP>(a, row, v, keep[t]);
+        float4 z = ln_load_z<DROP>(a, row, v, keep[t]);
+        if (CLAMP) inside[t] = ln_clamp4(z, a.lo, a.hi);
         const float4 g = *(const float4*)(a.g + row * a.D + 4L * v);
         zh[t] = make_float4((z.x - mean) * rstd, (z.y - mean) * rstd, (z.z - mean) * rstd, (z.w - mean) * rstd);
         gw[t] = make_float4(g.x * w[t].x, g.y * w[t].y, g.z * w[t].z, g.w * w[t].w);
@@ -474,8 +491,12 @@ __global__ __launch_bounds__(LN_THREADS) void addln_bwd_kernel(const LnArgs a) {
     for (int t = 0; t < LN_MAXV; ++t) {
       const int v = lane + 64 * t;
       if (v < nv) {
-        const float4 dz = make_float4(rstd * (gw[t].x - c1 - zh[t].x * c2), rstd * (gw[t].y - c1 - zh[t].y * c2),
-                                      rstd * (gw[t].z - c1 - zh[t].z * c2), rstd * (gw[t].w - c1 - zh[t].w * c2));
+        float4 dz = make_float4(rstd * (gw[t].x - c1 - zh[t].x * c2), rstd * (gw[t].y - c1 - zh[t].y * c2),
+                                rstd * (gw[t].z - c1 - zh[t].z * c2), rstd * (gw[t].w - c1 - zh[t].w * c2));
+        if (CLAMP) {   // no gradient through an element that the clamp moved
+          dz.x = inside[t] & 1u ? dz.x : 0.f; dz.y = inside[t] & 2u ? dz.y : 0.f;
+          dz.z = inside[t] & 4u ? dz.z : 0.f; dz.w = inside[t] & 8u ? dz.w : 0.f;
+        }
         if (a.dx) *(float4*)(a.dx + row * a.D + 4L * v) = dz;
         if (a.dy) {
           float4 dyv = dz;
@@ -592,7 +613,7 @@ int launch_dfine_attn_backward(const float* gout, const float* qkv, const float*
 
 int dfine_addln_max_d() { return LN_MAX_D; }
 
-static long addln_rows_per_block(long M) {
+long dfine_addln_rows_per_block(long M) {
   long blocks = (M + LN_WAVES - 1) / LN_WAVES;
   if (blocks > LN_MAX_BLOCKS) blocks = LN_MAX_BLOCKS;
   const long rpb = (M + blocks - 1) / blocks;
@@ -601,7 +622,7 @@ static long addln_rows_per_block(long M) {
 
 size_t dfine_addln_workspace_bytes(long M, int D) {
   if (M < 1 || D < 1) return 0;
-  const long rpb = addln_rows_per_block(M);
+  const long rpb = dfine_addln_rows_per_block(M);
   return (size_t)((M + rpb - 1) / rpb) * 2 * (size_t)D * sizeof(float);
 }
 
@@ -621,15 +642,41 @@ int launch_dfine_addln_backward(const float* g, const float* x, const float* y, 
                                 float* dbias, float* work, hipStream_t s) {
   LnArgs a{};
   a.x = x; a.y = y; a.w = w; a.g = g; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dx = dx; a.dy = dy;
-  a.part = work; a.M = M; a.D = D; a.rows_per_block = addln_rows_per_block(M);
+  a.part = work; a.M = M; a.D = D; a.rows_per_block = dfine_addln_rows_per_block(M);
   a.d = drop_args(p, seed, site);
   const int blocks = (int)((M + a.rows_per_block - 1) / a.rows_per_block);
   if (p > 0.f) hipLaunchKernelGGL(addln_bwd_kernel<true>, dim3(blocks), dim3(LN_THREADS), 0, s, a);
   else hipLaunchKernelGGL(addln_bwd_kernel<false>, dim3(blocks), dim3(LN_THREADS), 0, s, a);
   int rc = (int)hipGetLastError();
   if (rc != 0 || (!dweight && !dbias)) return rc;
-  hipLaunchKernelGGL(addln_reduce_kernel, dim3((2 * D + 255) / 256), dim3(256), 0, s, work, blocks, D, dweight, dbias);
+  return launch_dfine_addln_reduce(work, blocks, D, dweight, dbias, s);
+}
+
+int launch_dfine_addln_reduce(const float* part, int blocks, int D, float* dweight, float* dbias, hipStream_t s) {
+  hipLaunchKernelGGL(addln_reduce_kernel, dim3((2 * D + 255) / 256), dim3(256), 0, s, part, blocks, D, dweight, dbias);
   return (int)hipGetLastError();
+}
+
+// LayerNorm(clamp(x + y, lo, hi)): the CLAMP instances of the same device code, without dropout
+int launch_dfine_addln_clamp_forward(const float* x, const float* y, const float* w, const float* b, long M, int D, float eps, float lo,
+                                     float hi, float* out, float* mean, float* rstd, hipStream_t s) {
+  LnArgs a{};
+  a.x = x; a.y = y; a.w = w; a.b = b; a.out = out; a.mean = mean; a.rstd = rstd; a.M = M; a.D = D; a.eps = eps; a.lo = lo; a.hi = hi;
+  hipLaunchKernelGGL((addln_fwd_kernel<false, true>), dim3((unsigned)((M + LN_WAVES - 1) / LN_WAVES)), dim3(LN_THREADS), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_dfine_addln_clamp_backward(const float* g, const float* x, const float* y, const float* w, const float* mean,
+                                      const float* rstd, long M, int D, float lo, float hi, float* dx, float* dy, float* dweight,
+                                      float* dbias, float* work, hipStream_t s) {
+  LnArgs a{};
+  a.x = x; a.y = y; a.w = w; a.g = g; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dx = dx; a.dy = dy;
+  a.part = work; a.M = M; a.D = D; a.rows_per_block = dfine_addln_rows_per_block(M); a.lo = lo; a.hi = hi;
+  const int blocks = (int)((M + a.rows_per_block - 1) / a.rows_per_block);
+  hipLaunchKernelGGL((addln_bwd_kernel<false, true>), dim3(blocks), dim3(LN_THREADS), 0, s, a);
+  const int rc = (int)hipGetLastError();
+  if (rc != 0 || (!dweight && !dbias)) return rc;
+  return launch_dfine_addln_reduce(work, blocks, D, dweight, dbias, s);
 }
 
 int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, long n, float p, unsigned long long seed, int site,

@@ -116,6 +116,12 @@ const char* dfine_addln_check(int64_t M, int32_t D, float p, int32_t site) {
   if (D < 4 || D % 4 != 0 || D > dfine_addln_max_d()) return "D must be a multiple of 4 in [4, 1024]";
   return dfine_dropout_check(p, site);
 }
+// the LQE statistics (dfine_decoder.hip): one block per row
+const char* dfine_lqe_check(int64_t M, int32_t nb1, int32_t k) {
+  if (M < 1 || M > kGridMax) return "1 <= rows < 2^31";
+  if (k < 1 || k > 8 || nb1 < k || nb1 > 64) return "top_k in [1, 8] and top_k <= bins + 1 <= 64";
+  return nullptr;
+}
 
 }  // namespace
 
@@ -303,6 +309,68 @@ int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uin
   if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
   if (const char* why = dfine_dropout_check(p, site)) return invalid(__func__, why);
   return launched(__func__, launch_dfine_keep_mask(d_mask, n, p, seed, site, (hipStream_t)stream));
+}
+// the decoder layer between its GEMMs (dfine_decoder.hip; the clamp form is an instance of dfine_encoder.hip's add-LayerNorm)
+int m355_dfine_addln_clamp_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
+                                   float eps, float lo, float hi, float* d_out, float* d_mean, float* d_rstd, void* stream) {
+  if (any_null({d_x, d_y, d_weight, d_bias, d_out, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, 0.f, 0)) return invalid(__func__, why);
+  if (!(eps >= 0.f)) return invalid(__func__, "eps must be >= 0");
+  if (!(lo <= hi)) return invalid(__func__, "the clamp needs lo <= hi");
+  if (any_misaligned16({d_x, d_y, d_weight, d_bias, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_addln_clamp_forward(d_x, d_y, d_weight, d_bias, M, D, eps, lo, hi, d_out, d_mean, d_rstd,
+                                                             (hipStream_t)stream));
+}
+int m355_dfine_addln_clamp_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight,
+                                    const float* d_mean, const float* d_rstd, int64_t M, int32_t D, float lo, float hi,
+                                    float* d_grad_x, float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work,
+                                    int64_t work_bytes, void* stream) {
+  if (any_null({d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, 0.f, 0)) return invalid(__func__, why);
+  if (!(lo <= hi)) return invalid(__func__, "the clamp needs lo <= hi");
+  if (workspace_short(d_work, work_bytes, dfine_addln_workspace_bytes(M, D)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_addln_workspace_bytes");
+  if (any_misaligned16({d_grad_out, d_x, d_y, d_weight, d_grad_x, d_grad_y, d_work})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_addln_clamp_backward(d_grad_out, d_x, d_y, d_weight, d_mean, d_rstd, M, D, lo, hi, d_grad_x,
+                                                              d_grad_y, d_grad_weight, d_grad_bias, (float*)d_work, (hipStream_t)stream));
+}
+int m355_dfine_gate_ln_forward(const float* d_gate, const float* d_x1, const float* d_x2, const float* d_weight, const float* d_bias,
+                               int64_t M, int32_t D, float eps, float* d_out, float* d_mean, float* d_rstd, void* stream) {
+  if (any_null({d_gate, d_x1, d_x2, d_weight, d_bias, d_out, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, 0.f, 0)) return invalid(__func__, why);
+  if (!(eps >= 0.f)) return invalid(__func__, "eps must be >= 0");
+  if (any_misaligned16({d_gate, d_x1, d_x2, d_weight, d_bias, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_gate_ln_forward(d_gate, d_x1, d_x2, d_weight, d_bias, M, D, eps, d_out, d_mean, d_rstd,
+                                                         (hipStream_t)stream));
+}
+int m355_dfine_gate_ln_backward(const float* d_grad_out, const float* d_gate, const float* d_x1, const float* d_x2,
+                                const float* d_weight, const float* d_mean, const float* d_rstd, int64_t M, int32_t D,
+                                float* d_grad_gate, float* d_grad_x1, float* d_grad_x2, float* d_grad_weight, float* d_grad_bias,
+                                void* d_work, int64_t work_bytes, void* stream) {
+  if (any_null({d_grad_out, d_gate, d_x1, d_x2, d_weight, d_mean, d_rstd})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_addln_check(M, D, 0.f, 0)) return invalid(__func__, why);
+  const bool sums = d_grad_weight || d_grad_bias;   // the workspace holds their partial rows
+  if (sums && workspace_short(d_work, work_bytes, dfine_addln_workspace_bytes(M, D)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_addln_workspace_bytes");
+  if (any_misaligned16({d_grad_out, d_gate, d_x1, d_x2, d_weight, d_grad_gate, d_grad_x1, d_grad_x2, sums ? d_work : nullptr}))
+    return invalid(__func__, kAlign16);
+  if (!d_grad_gate && !d_grad_x1 && !d_grad_x2 && !sums) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_gate_ln_backward(d_grad_out, d_gate, d_x1, d_x2, d_weight, d_mean, d_rstd, M, D, d_grad_gate,
+                                                          d_grad_x1, d_grad_x2, d_grad_weight, d_grad_bias, (float*)d_work,
+                                                          (hipStream_t)stream));
+}
+int m355_dfine_lqe_forward(const float* d_pred_corners, int64_t M, int32_t num_bins_plus1, int32_t top_k, float* d_stat, uint8_t* d_index,
+                           void* stream) {
+  if (any_null({d_pred_corners, d_stat})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_lqe_check(M, num_bins_plus1, top_k)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_lqe_forward(d_pred_corners, M, num_bins_plus1, top_k, d_stat, d_index, (hipStream_t)stream));
+}
+int m355_dfine_lqe_backward(const float* d_grad_stat, const float* d_pred_corners, const uint8_t* d_index, int64_t M,
+                            int32_t num_bins_plus1, int32_t top_k, float* d_grad_pred_corners, void* stream) {
+  if (any_null({d_grad_stat, d_pred_corners, d_index, d_grad_pred_corners})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_lqe_check(M, num_bins_plus1, top_k)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_lqe_backward(d_grad_stat, d_pred_corners, d_index, M, num_bins_plus1, top_k,
+                                                      d_grad_pred_corners, (hipStream_t)stream));
 }
 // the GRU recurrence (dfine_gru.hip)
 size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return dfine_gru_workspace_bytes(B, S, H, D); }

@@ -29,6 +29,11 @@ with a HIP backward, and a counter-based dropout mask that the backward recomput
 ``gru_recurrence`` / ``gru_forward`` / ``bind_gru`` / ``gru_status`` are the context GRU of the improved trainer
 (``nn.GRU(256, 256, batch_first=True, bidirectional=True)`` on one sequence of T * Q steps): the input projection is one torch
 GEMM, the serial chain of both directions one persistent launch forward and one backward (csrc/dfine_gru.hip).
+
+``gate_layer_norm`` / ``add_layer_norm(clamp=...)`` / ``lqe_statistics`` / ``decoder_layer_forward`` / ``lqe_forward`` /
+``bind_decoder`` are the decoder layers every trainer trains (``DFineDecoderLayer``, ``DFineLQE``) between their torch GEMMs: the
+self-attention core above on a packed q | k | v projection, the fused deformable attention, DFineGate behind its Linear,
+LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch forward with a HIP backward (csrc/dfine_decoder.hip).
 """
 from __future__ import annotations
 
@@ -956,17 +961,67 @@ def _addln_forward(xs, ys, w, b, eps, p, seed, site):
     return out, mean, rstd
 
 
+class _AddClampLayerNorm(torch.autograd.Function):
+    """LayerNorm(clamp(x + y, lo, hi)): the clamp instances of the same kernels (m355_dfine_addln_clamp_*), no dropout"""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, bias, eps, lo, hi):
+        xs, ys, w, b = _f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias")
+        out, mean, rstd = _addln_clamp_forward(xs, ys, w, b, eps, lo, hi)
+        ctx.save_for_backward(xs, ys, w, mean, rstd)
+        ctx.meta = (lo, hi, [(t.shape, t.dtype) for t in (x, y, weight, bias)])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xs, ys, w, mean, rstd = ctx.saved_tensors
+        lo, hi, like = ctx.meta
+        D = xs.shape[-1]
+        M = xs.numel() // D
+        need = ctx.needs_input_grad
+        g = _f32c16(grad_out, "grad_output")
+        gx, gy = _grad_like(need[0], xs), _grad_like(need[1], ys)
+        gw = torch.empty(D, dtype=torch.float32, device=xs.device) if need[2] else None
+        gb = torch.empty(D, dtype=torch.float32, device=xs.device) if need[3] else None
+        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D))
+        work = torch.empty(wbytes, dtype=torch.uint8, device=xs.device)
+        check(lib.m355_dfine_addln_clamp_backward(_ptr(g), _ptr(xs), _ptr(ys), _ptr(w), _ptr(mean), _ptr(rstd), M, D, lo, hi, _ptr(gx),
+                                                  _ptr(gy), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
+        return tuple(_as_input(t, *sd) for t, sd in zip((gx, gy, gw, gb), like)) + (None, None, None)
+
+
+def _addln_clamp_forward(xs, ys, w, b, eps, lo, hi):
+    D = xs.shape[-1]
+    M = xs.numel() // D
+    out = torch.empty_like(xs)
+    mean = torch.empty(M, dtype=torch.float32, device=xs.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=xs.device)
+    check(lib.m355_dfine_addln_clamp_forward(_ptr(xs), _ptr(ys), _ptr(w), _ptr(b), M, D, float(eps), lo, hi, _ptr(out), _ptr(mean),
+                                             _ptr(rstd), _stream()))
+    return out, mean, rstd
+
+
 def add_layer_norm(x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, dropout_p: float = 0.0,
-                   seed=None, site: int = SITE_ATTN_OUT) -> torch.Tensor:
+                   seed=None, site: int = SITE_ATTN_OUT, clamp=None) -> torch.Tensor:
     """LayerNorm(x + dropout(y)) over the last axis (D a multiple of 4, at most 1024) in one pass: the residual, the dropout of
     the branch and the normalisation that torch runs as separate launches.  Differentiable in x, y, weight and bias; the
     backward recomputes the mask and the normalised rows from x, y and the saved per-row mean and rstd, and sums dweight and
-    dbias in a fixed order (two launches)."""
+    dbias in a fixed order (two launches).
+    clamp=(lo, hi): LayerNorm(clamp(x + y, lo, hi)), the decoder layer's final_layer_norm(hidden.clamp(-65504, 65504)); x and y get
+    no gradient where the sum lies strictly outside [lo, hi] (torch's clamp backward).  Without dropout: dropout_p must be 0."""
     D = x.shape[-1] if x.dim() else 0
     if x.dim() < 1 or x.shape != y.shape or tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
         raise ValueError("x and y must have one shape (..., D), weight and bias the shape (D,)")
     if D < 4 or D % 4 or D > ADDLN_MAX_D or x.numel() == 0:
         raise ValueError(f"add_layer_norm takes a non-empty x with D a multiple of 4 in [4, {ADDLN_MAX_D}]")
+    if clamp is not None:
+        lo, hi = (float(v) for v in clamp)
+        if not lo <= hi or float(dropout_p) != 0.0:
+            raise ValueError("clamp=(lo, hi) needs lo <= hi and dropout_p == 0")
+        if _wants_grad(x, y, weight, bias):
+            return _AddClampLayerNorm.apply(x, y, weight, bias, float(eps), lo, hi)
+        return _addln_clamp_forward(_f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, lo, hi)[0]
     p, seed = _dropout_args(dropout_p, seed)
     if _wants_grad(x, y, weight, bias):
         return _AddLayerNorm.apply(x, y, weight, bias, float(eps), p, seed, int(site))
@@ -1229,4 +1284,245 @@ def bind_gru(module):
     for m in module.modules():
         if isinstance(m, torch.nn.GRU):
             m.forward = types.MethodType(gru_forward, m)
+    return module
+
+
+# ---- D-FINE decoder layers and their quality heads (transformers' DFineDecoderLayer / DFineLQE) between their GEMMs --------------
+# Every trainer runs the six decoder layers forward and backward on every step.  The nn.Linear layers stay torch GEMMs on the
+# modules' own parameters (autograd yields their weight gradients); between them: self_attention, add_layer_norm,
+# deformable_attention, gate_layer_norm, relu_dropout, add_layer_norm(clamp=...) and lqe_statistics (csrc/dfine_decoder.hip).
+LQE_MAX_BINS1 = 64
+LQE_MAX_TOPK = 8
+DECODER_CLAMP = (-65504.0, 65504.0)   # DFineDecoderLayer.forward: final_layer_norm(hidden_states.clamp(min=-65504, max=65504))
+decoder_calls = {"kernel": 0, "torch": 0}   # decoder_layer_forward and lqe_forward calls by path (tests and tools read it)
+
+
+class _GateLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x1, x2, gate, weight, bias, eps):
+        a, b_, g = _f32c16(x1, "x1"), _f32c16(x2, "x2"), _f32c16(gate, "gate_logits")
+        w, b = _f32c16(weight, "weight"), _f32c16(bias, "bias")
+        out, mean, rstd = _gate_ln_forward(a, b_, g, w, b, eps)
+        ctx.save_for_backward(a, b_, g, w, mean, rstd)   # the inputs and per-row statistics: no sigmoid, no normalised row
+        ctx.like = [(t.shape, t.dtype) for t in (x1, x2, gate, weight, bias)]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        a, b_, g, w, mean, rstd = ctx.saved_tensors
+        D = a.shape[-1]
+        M = a.numel() // D
+        need = ctx.needs_input_grad
+        go = _f32c16(grad_out, "grad_output")
+        g1, g2, gg = _grad_like(need[0], a), _grad_like(need[1], b_), _grad_like(need[2], g)
+        gw = torch.empty(D, dtype=torch.float32, device=a.device) if need[3] else None
+        gb = torch.empty(D, dtype=torch.float32, device=a.device) if need[4] else None
+        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D)) if need[3] or need[4] else 0
+        work = torch.empty(wbytes, dtype=torch.uint8, device=a.device) if wbytes else None
+        check(lib.m355_dfine_gate_ln_backward(_ptr(go), _ptr(g), _ptr(a), _ptr(b_), _ptr(w), _ptr(mean), _ptr(rstd), M, D, _ptr(gg),
+                                              _ptr(g1), _ptr(g2), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
+        return tuple(_as_input(t, *sd) for t, sd in zip((g1, g2, gg, gw, gb), ctx.like)) + (None,)
+
+
+def _gate_ln_forward(x1, x2, g, w, b, eps):
+    D = x1.shape[-1]
+    M = x1.numel() // D
+    out = torch.empty_like(x1)
+    mean = torch.empty(M, dtype=torch.float32, device=x1.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x1.device)
+    check(lib.m355_dfine_gate_ln_forward(_ptr(g), _ptr(x1), _ptr(x2), _ptr(w), _ptr(b), M, D, float(eps), _ptr(out), _ptr(mean),
+                                         _ptr(rstd), _stream()))
+    return out, mean, rstd
+
+
+def gate_layer_norm(x1: torch.Tensor, x2: torch.Tensor, gate_logits: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                    eps: float) -> torch.Tensor:
+    """DFineGate.forward behind its nn.Linear: LayerNorm(sigmoid(g[..., :D]) * x1 + sigmoid(g[..., D:]) * x2) with
+    g = gate(cat(x1, x2)) of shape (..., 2 D), D a multiple of 4 in [4, 1024], in ONE launch.  Differentiable in x1, x2,
+    gate_logits, weight and bias; only the inputs and the per-row mean and rstd are kept, the backward (one launch, plus the
+    ordered column sums of dweight and dbias when asked for) forms the sigmoids and the normalised row again."""
+    D = x1.shape[-1] if x1.dim() else 0
+    if x1.dim() < 1 or x1.shape != x2.shape or tuple(gate_logits.shape) != tuple(x1.shape[:-1]) + (2 * D,):
+        raise ValueError("x1 and x2 must have one shape (..., D) and gate_logits the shape (..., 2 D)")
+    if tuple(weight.shape) != (D,) or tuple(bias.shape) != (D,):
+        raise ValueError("weight and bias must have the shape (D,)")
+    if D < 4 or D % 4 or D > ADDLN_MAX_D or x1.numel() == 0:
+        raise ValueError(f"gate_layer_norm takes a non-empty x1 with D a multiple of 4 in [4, {ADDLN_MAX_D}]")
+    if _wants_grad(x1, x2, gate_logits, weight, bias):
+        return _GateLayerNorm.apply(x1, x2, gate_logits, weight, bias, float(eps))
+    return _gate_ln_forward(_f32c16(x1, "x1"), _f32c16(x2, "x2"), _f32c16(gate_logits, "gate_logits"), _f32c16(weight, "weight"),
+                            _f32c16(bias, "bias"), eps)[0]
+
+
+class _LqeStatistics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_corners, nb1, k):
+        c = _f32c(pred_corners, "pred_corners")
+        stat, idx = _lqe_forward(c, nb1, k, True)
+        ctx.save_for_backward(c, idx)   # the logits and the chosen bins as bytes: no probabilities
+        ctx.meta = (nb1, k, pred_corners.dtype)
+        return stat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stat):
+        c, idx = ctx.saved_tensors
+        nb1, k, dtype = ctx.meta
+        g = _f32c(grad_stat, "grad_output")
+        gc = torch.empty_like(c)
+        check(lib.m355_dfine_lqe_backward(_ptr(g), _ptr(c), _ptr(idx), c.numel() // (4 * nb1), nb1, k, _ptr(gc), _stream()))
+        return gc.to(dtype), None, None
+
+
+def _lqe_forward(c, nb1, k, keep_index: bool):
+    M = c.numel() // (4 * nb1)
+    stat = torch.empty(tuple(c.shape[:-1]) + (4 * (k + 1),), dtype=torch.float32, device=c.device)
+    idx = torch.empty((M, 4, k), dtype=torch.uint8, device=c.device) if keep_index else None
+    check(lib.m355_dfine_lqe_forward(_ptr(c), M, nb1, k, _ptr(stat), _ptr(idx), _stream()))
+    return stat, idx
+
+
+def lqe_statistics(pred_corners: torch.Tensor, max_num_bins: int, top_k: int) -> torch.Tensor:
+    """DFineLQE.forward in front of its MLP: pred_corners (..., 4 * (max_num_bins + 1)) -> (..., 4 * (top_k + 1)), per box side the
+    softmax over its max_num_bins + 1 logits, the top_k largest probabilities in descending order and then their mean (the layout
+    reg_conf reads), in ONE launch.  Of bins with exactly equal probability the lowest bin counts as the larger one, which decides
+    where the gradient of a tie goes (the values do not depend on it).  top_k in [1, 8], top_k <= max_num_bins + 1 <= 64.
+    Differentiable; the backward (one launch) reads the logits and the chosen bins, kept as bytes."""
+    nb1, k = int(max_num_bins) + 1, int(top_k)
+    if not 1 <= k <= LQE_MAX_TOPK or not k <= nb1 <= LQE_MAX_BINS1:
+        raise ValueError(f"lqe_statistics takes top_k in [1, {LQE_MAX_TOPK}] and top_k <= max_num_bins + 1 <= {LQE_MAX_BINS1}")
+    if pred_corners.dim() < 1 or pred_corners.shape[-1] != 4 * nb1 or pred_corners.numel() == 0:
+        raise ValueError("pred_corners must be a non-empty (..., 4 * (max_num_bins + 1)) tensor")
+    if _wants_grad(pred_corners):
+        return _LqeStatistics.apply(pred_corners, nb1, k)
+    return _lqe_forward(_f32c(pred_corners, "pred_corners"), nb1, k, False)[0]
+
+
+def _fp32_cuda(*tensors) -> bool:
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _affine_norm(norm, D: int) -> bool:
+    return (isinstance(norm, torch.nn.LayerNorm) and tuple(norm.normalized_shape) == (D,) and norm.weight is not None
+            and norm.bias is not None)
+
+
+def _records_attentions(layer, kwargs) -> bool:
+    """transformers collects attention weights through forward hooks on the two attention submodules"""
+    if kwargs.get("output_attentions") or getattr(getattr(layer.self_attn, "config", None), "output_attentions", False):
+        return True
+    return any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in (layer.self_attn, layer.encoder_attn))
+
+
+def _decoder_layer_takes(layer, hidden_states, position_embeddings, encoder_hidden_states, encoder_attention_mask, kwargs) -> bool:
+    """True when the kernels cover this call of a DFineDecoderLayer; anything else goes to the class's own forward"""
+    if encoder_attention_mask is not None or _records_attentions(layer, kwargs):
+        return False
+    sa = layer.self_attn
+    if layer.training and (float(layer.dropout) > 0.0 or float(sa.attention_dropout) > 0.0):
+        return False
+    x = hidden_states
+    if not _fp32_cuda(x, encoder_hidden_states) or x.dim() != 3 or x.numel() == 0 or torch.is_autocast_enabled():
+        return False
+    if position_embeddings is not None and not (_fp32_cuda(position_embeddings) and position_embeddings.shape == x.shape):
+        return False
+    D = x.shape[-1]
+    if sa.head_dim != ENCODER_HEAD_DIM or D % ENCODER_HEAD_DIM or D != layer.hidden_size or D > ADDLN_MAX_D:
+        return False
+    if any(lin.bias is None for lin in (sa.q_proj, sa.k_proj, sa.v_proj, sa.o_proj)):
+        return False
+    mlp = layer.mlp
+    if not isinstance(mlp.act, torch.nn.ReLU) or mlp.num_layers != 2 or len(mlp.layers) != 2:
+        return False
+    if not all(_affine_norm(n, D) for n in (layer.self_attn_layer_norm, layer.gateway.norm, layer.final_layer_norm)):
+        return False
+    return all(p.is_cuda and p.dtype == torch.float32 for p in layer.parameters())
+
+
+def decoder_layer_forward(self, hidden_states, position_embeddings=None, reference_points=None, spatial_shapes=None,
+                          spatial_shapes_list=None, encoder_hidden_states=None, encoder_attention_mask=None, **kwargs):
+    """DFineDecoderLayer.forward (modeling_d_fine.py, transformers 5.15.0) on fp32 CUDA tensors, the nn.Linear products as torch
+    GEMMs on the module's own parameters and everything between them on the kernels:
+        x = add_layer_norm(x, o_proj(self_attention([q | k](x + pos), v(x))), self_attn_layer_norm)   # k without its bias
+        c = deformable_attention(x + pos, ...)
+        x = gate_layer_norm(x, c, gateway.gate(cat(x, c)), gateway.norm)
+        x = add_layer_norm(x, mlp.layers[1](relu_dropout(mlp.layers[0](x))), final_layer_norm, clamp=(-65504, 65504))
+    A call goes to the class's own forward, untouched, when encoder_attention_mask is given (the denoising groups), when the module
+    trains with config.dropout or attention_dropout above 0, when tensors or parameters are not fp32 CUDA, under autocast, on an
+    empty input, with a head dim other than 32 or D not a multiple of 4 in [4, 1024], with an activation other than ReLU, and when
+    attention weights are recorded (output_attentions, or a forward hook on either attention submodule).  2-d reference points
+    and the "discrete" method keep self.encoder_attn(...) for the cross-attention and the kernels for the rest.
+    bind_decoder(attention=False) keeps self.self_attn(...) as well.  Bound per instance by bind_decoder."""
+    if not _decoder_layer_takes(self, hidden_states, position_embeddings, encoder_hidden_states, encoder_attention_mask, kwargs):
+        decoder_calls["torch"] += 1
+        return type(self).forward(self, hidden_states, position_embeddings=position_embeddings, reference_points=reference_points,
+                                  spatial_shapes=spatial_shapes, spatial_shapes_list=spatial_shapes_list,
+                                  encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask, **kwargs)
+    decoder_calls["kernel"] += 1
+    F = torch.nn.functional
+    x, pos, sa = hidden_states, position_embeddings, self.self_attn
+    if getattr(self, "_m355_attention_kernel", False):
+        qk_in = x if pos is None else x + pos
+        # k_proj.bias adds the same q . b to every key's logit of a query, which the softmax cancels: the keys are formed without it
+        # and its gradient is the exact 0 (times 0, so that it stays in the graph) instead of fp32 rounding noise around 0
+        qk = F.linear(qk_in, torch.cat([sa.q_proj.weight, sa.k_proj.weight]), torch.cat([sa.q_proj.bias, sa.k_proj.bias * 0.0]))
+        qkv = torch.cat([qk, F.linear(x, sa.v_proj.weight, sa.v_proj.bias)], dim=-1)
+        y = F.linear(self_attention(qkv, x.shape[-1] // ENCODER_HEAD_DIM), sa.o_proj.weight, sa.o_proj.bias)
+    else:
+        y = sa(hidden_states=x, attention_mask=None, position_embeddings=pos, **kwargs)[0]
+    n = self.self_attn_layer_norm
+    x = add_layer_norm(x, y, n.weight, n.bias, n.eps)
+
+    ca = self.encoder_attn
+    q = x if pos is None else x + pos
+    pts = [int(v) for v in ca.num_points_list]
+    if (reference_points is not None and reference_points.shape[-1] == 4 and ca.decoder_method == "default" and sum(pts) <= 16
+            and len(pts) <= 8 and spatial_shapes_list is not None and _fp32_cuda(reference_points)):
+        c = deformable_attention(q, reference_points, encoder_hidden_states, spatial_shapes_list, ca.sampling_offsets,
+                                 ca.attention_weights, pts, ca.n_heads, ca.offset_scale)
+    else:
+        c = ca(hidden_states=q, encoder_hidden_states=encoder_hidden_states, reference_points=reference_points,
+               spatial_shapes=spatial_shapes, spatial_shapes_list=spatial_shapes_list)[0]
+
+    gw = self.gateway
+    g = F.linear(torch.cat([x, c], dim=-1), gw.gate.weight, gw.gate.bias)
+    x = gate_layer_norm(x, c, g, gw.norm.weight, gw.norm.bias, gw.norm.eps)
+
+    l0, l1 = self.mlp.layers
+    y = F.linear(relu_dropout(F.linear(x, l0.weight, l0.bias), 0.0), l1.weight, l1.bias)
+    n = self.final_layer_norm
+    return add_layer_norm(x, y, n.weight, n.bias, n.eps, clamp=DECODER_CLAMP)
+
+
+def lqe_forward(self, scores, pred_corners):
+    """DFineLQE.forward: scores + self.reg_conf(lqe_statistics(pred_corners, self.max_num_bins, self.top_prob_values)); reg_conf
+    stays the module's own MLP.  CPU or non-fp32 tensors, autocast, an empty input and bin or top-k counts outside the kernel's
+    limits go to the class's own forward, untouched.  Bound per instance by bind_decoder."""
+    nb1, k = int(self.max_num_bins) + 1, int(self.top_prob_values)
+    if not (_fp32_cuda(scores, pred_corners) and pred_corners.dim() == 3 and pred_corners.numel() and not torch.is_autocast_enabled()
+            and pred_corners.shape[-1] == 4 * nb1 and 1 <= k <= LQE_MAX_TOPK and k <= nb1 <= LQE_MAX_BINS1
+            and all(p.is_cuda and p.dtype == torch.float32 for p in self.parameters())):
+        decoder_calls["torch"] += 1
+        return type(self).forward(self, scores, pred_corners)
+    decoder_calls["kernel"] += 1
+    return scores + self.reg_conf(lqe_statistics(pred_corners, self.max_num_bins, k))
+
+
+def bind_decoder(module, attention: bool = False):
+    """Set decoder_layer_forward on every DFineDecoderLayer INSTANCE and lqe_forward on every DFineLQE INSTANCE inside `module` (a
+    DFineDecoder, a whole DFineForObjectDetection, a single layer, or any module that holds some); transformers' classes are never
+    touched, parameters, buffers and the state dict stay as they are, so existing checkpoints load unchanged.  Returns `module`.
+    attention=False keeps each layer's self.self_attn(...) as the class runs it and takes the other ops; attention=True runs the
+    self-attention core on dfine.self_attention too.  The default is the arm that profiles/dfine_decoder_bench.json shows faster for
+    a layer's training step (forward + backward) at (50, 300, 256): torch's scaled_dot_product_attention, 3.29 ms against 3.60 ms
+    (the attention backward kernel runs on VALU FMAs); at (16, 300, 256) and below the two are within each other's spread."""
+    import types
+    from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
+    for m in module.modules():
+        if isinstance(m, M.DFineDecoderLayer):
+            m.forward = types.MethodType(decoder_layer_forward, m)
+            m._m355_attention_kernel = bool(attention)   # a plain attribute: not a parameter, not a buffer, not in the state dict
+        elif isinstance(m, M.DFineLQE):
+            m.forward = types.MethodType(lqe_forward, m)
     return module

@@ -761,6 +761,40 @@ int m355_dfine_relu_dropout_backward(const float* d_grad_out, const float* d_out
                                      float* d_grad_h, void* stream);
 int m355_dfine_dropout_mask(int64_t n, float p, uint64_t seed, int32_t site, uint8_t* d_mask, void* stream);
 
+/* ---- A D-FINE decoder layer and its quality head between their GEMMs ------------------------------------------------------
+ * transformers' DFineDecoderLayer / DFineLQE (models/d_fine/modeling_d_fine.py) run these between their nn.Linear products;
+ * self-attention is m355_dfine_attn_*, cross-attention m355_msda_module_*, the first LayerNorm m355_dfine_addln_*.  fp32, row
+ * major, no float atomics, bitwise reproducible; a row's result does not depend on the rows around it.
+ * m355_dfine_addln_clamp_forward / _backward: m355_dfine_addln_* without dropout and with z = clamp(x + y, lo, hi) in front of
+ *   the statistics (final_layer_norm(hidden.clamp(-65504, 65504))); grad_x and grad_y are 0 where x + y lies strictly outside
+ *   [lo, hi].  Same workspace, same NULL-able gradients.
+ * m355_dfine_gate_ln_forward: out (M, D) = LayerNorm(sigmoid(gate[:, :D]) * x1 + sigmoid(gate[:, D:]) * x2) * weight + bias, gate
+ *   (M, 2 D) being DFineGate's nn.Linear output; mean, rstd (M) are written for the backward, nothing else is kept.
+ * m355_dfine_gate_ln_backward: grad_gate (M, 2 D), grad_x1, grad_x2 (M, D), grad_weight, grad_bias (D); each may be NULL and its
+ *   work is skipped.  work (m355_dfine_addln_workspace_bytes(M, D)) is needed for grad_weight / grad_bias only.
+ * m355_dfine_lqe_forward: pred_corners (M, 4 * num_bins_plus1) -> stat (M, 4 * (top_k + 1)): per side the softmax over its
+ *   num_bins_plus1 logits, the top_k largest probabilities in descending order, then their mean (what DFineLQE.reg_conf reads).
+ *   index (M, 4, top_k) bytes, NULL when no backward follows: the chosen bins; of bins with equal probability the lowest first.
+ * m355_dfine_lqe_backward: grad_pred_corners (M, 4 * num_bins_plus1) from grad_stat and the forward's index.
+ * Limits (M355_ERR_INVALID before any HIP call): no NULL among the required pointers, 16-byte alignment (not for lqe), M >= 1,
+ * D a multiple of 4 in [4, 1024], lo <= hi, top_k in [1, 8], top_k <= num_bins_plus1 <= 64, the workspace size. */
+int m355_dfine_addln_clamp_forward(const float* d_x, const float* d_y, const float* d_weight, const float* d_bias, int64_t M, int32_t D,
+                                   float eps, float lo, float hi, float* d_out, float* d_mean, float* d_rstd, void* stream);
+int m355_dfine_addln_clamp_backward(const float* d_grad_out, const float* d_x, const float* d_y, const float* d_weight,
+                                    const float* d_mean, const float* d_rstd, int64_t M, int32_t D, float lo, float hi,
+                                    float* d_grad_x, float* d_grad_y, float* d_grad_weight, float* d_grad_bias, void* d_work,
+                                    int64_t work_bytes, void* stream);
+int m355_dfine_gate_ln_forward(const float* d_gate, const float* d_x1, const float* d_x2, const float* d_weight, const float* d_bias,
+                               int64_t M, int32_t D, float eps, float* d_out, float* d_mean, float* d_rstd, void* stream);
+int m355_dfine_gate_ln_backward(const float* d_grad_out, const float* d_gate, const float* d_x1, const float* d_x2,
+                                const float* d_weight, const float* d_mean, const float* d_rstd, int64_t M, int32_t D,
+                                float* d_grad_gate, float* d_grad_x1, float* d_grad_x2, float* d_grad_weight, float* d_grad_bias,
+                                void* d_work, int64_t work_bytes, void* stream);
+int m355_dfine_lqe_forward(const float* d_pred_corners, int64_t M, int32_t num_bins_plus1, int32_t top_k, float* d_stat, uint8_t* d_index,
+                           void* stream);
+int m355_dfine_lqe_backward(const float* d_grad_stat, const float* d_pred_corners, const uint8_t* d_index, int64_t M,
+                            int32_t num_bins_plus1, int32_t top_k, float* d_grad_pred_corners, void* stream);
+
 /* ---- The recurrence of the D-FINE trainer's context GRU -----------------------------------------------------------------
  * torch's one-layer nn.GRU(*, 256, batch_first, uni- or bidirectional) without its input projection: the caller's GEMM gives
  * gi = x cat(W_ih, W_ih_reverse)^T + b_ih for all steps and both directions; these entries run the serial chain.  Gate order
