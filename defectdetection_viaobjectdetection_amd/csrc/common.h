@@ -364,6 +364,8 @@ int launch_stem_s2c32_v2(const ConvArgs& a, const StemArgs& st, hipStream_t s);
 
 int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y_bstride, int ldy,
                      int B, int H, int W, int C, hipStream_t s);
+// the instance launch_sppf_pool runs: cg | (owned << 8), or -1 where it refuses (host arithmetic only; misc_kernels.hip)
+int sppf_pool_form(int B, int H, int W, int C, int ldy);
 int launch_sppf_pool_bwd(const half_t* a, long a_bs, int lda, const half_t* y, long y_bs, int ldy, const half_t* gy, long gy_bs,
                          int ldgy, half_t* ga, long ga_bs, int ldga, int B, int H, int W, int C, int accumulate, hipStream_t s);
 int launch_upsample2x(const half_t* x, long x_bstride, int ldx, half_t* y, long y_bstride, int ldy,

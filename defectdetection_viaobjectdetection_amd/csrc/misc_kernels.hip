@@ -449,9 +449,11 @@ int launch_stem(const StemArgs& a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y_bstride, int ldy, int B, int H,
-                     int W, int C, hipStream_t s) {
-  if (C % 8 || ldx % 8 || ldy % 8) return -1;
+// The instance launch_sppf_pool runs for a shape: cg | (owned << 8), cg = 8-channel groups per block (1, 2, 4), owned = the form with
+// per-thread element ownership; -1 = refused (C or ldy no multiple of 8, a plane that does not fit the LDS).  Host arithmetic only.
+int sppf_pool_form(int B, int H, int W, int C, int ldy) {
+  if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 || ldy % 8) return -1;
+  if ((size_t)3 * H * W * 16 > 160 * 1024) return -1;
   // widest channel chunk per block that still leaves >= 256 blocks (one per CU) and fits the LDS; planes of at most 256 * SPPF_ME
   // elements take the form with per-thread element ownership
   const int min_blocks = proc_switches().sppf_minblocks;
@@ -459,9 +461,18 @@ int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y
   while (cg > 1 && ((C / 8) % cg != 0 || (long)B * (C / (8 * cg)) < min_blocks || (size_t)3 * H * W * 16 * cg > 160 * 1024 ||
                     H * W * cg > SPPF_NT * SPPF_ME))
     cg >>= 1;
-  const size_t lds = (size_t)3 * H * W * 16 * cg;
-  if (lds > 160 * 1024) return -1;
   const bool owned = H * W * cg <= SPPF_NT * SPPF_ME && (long)H * W * ldy < (1L << 30);
+  return cg | ((int)owned << 8);
+}
+
+int launch_sppf_pool(const half_t* x, long x_bstride, int ldx, half_t* y, long y_bstride, int ldy, int B, int H,
+                     int W, int C, hipStream_t s) {
+  if (ldx % 8) return -1;
+  const int form = sppf_pool_form(B, H, W, C, ldy);
+  if (form < 0) return -1;
+  const int cg = form & 0xff;
+  const bool owned = (form >> 8) != 0;
+  const size_t lds = (size_t)3 * H * W * 16 * cg;
   auto k = owned ? (cg == 4 ? sppf_pool_kernel<4> : (cg == 2 ? sppf_pool_kernel<2> : sppf_pool_kernel<1>))
                  : (cg == 4 ? sppf_pool_generic_kernel<4> : (cg == 2 ? sppf_pool_generic_kernel<2> : sppf_pool_generic_kernel<1>));
   if (lds > 65536) {

@@ -57,6 +57,61 @@ int finish_entry(int rc, hipStream_t s, const char* what) {
   return launch_status(0, se, what);
 }
 
+// Argument checks of the forward glue entries (stem, SPPF pooling, upsample, ADown front, decode).  Each entry runs them before any HIP
+// call; a failure is M355_ERR_INVALID with a message that names the entry.
+int glue_invalid(const char* entry, const std::string& why) { return set_err(M355_ERR_INVALID, std::string(entry) + ": " + why); }
+
+// One fp16 NHWC channel slice handed to a kernel of 16-byte accesses: `pixels` pixels per image, channels [0, C) of rows of ld elements,
+// images bstride elements apart.  Empty = fine, else what is wrong with operand `name`.
+std::string slice_fault(const char* name, const void* p, int64_t bstride, int32_t ld, long pixels, int C) {
+  const std::string n(name);
+  if (!p) return n + " is a null pointer";
+  if ((uintptr_t)p & 15) return n + " must be 16-byte aligned";
+  if (ld < C) return "the leading dimension of " + n + " is smaller than its channel count";
+  if (ld % 8 || bstride % 8) return "the leading dimension and the batch stride of " + n + " must be multiples of 8";
+  if (bstride < (pixels - 1) * ld + C) return "the batch stride of " + n + " is smaller than the extent of one image's slice";
+  return std::string();
+}
+
+int sppf_entry(const char* entry, const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy, int B, int H, int W,
+               int C, void* stream) {
+  if (B < 1 || H < 1 || W < 1) return glue_invalid(entry, "B, H, W must be >= 1");
+  if (C < 8 || C % 8) return glue_invalid(entry, "C must be a positive multiple of 8");
+  // three copies of the plane of one 8-channel group (launch_sppf_pool): what sppf_pool_form refuses, as a message
+  if ((long)H * W * 3 * 16 > 160 * 1024) return glue_invalid(entry, "the plane needs more than 160 KB of LDS");
+  std::string f = slice_fault("x", x, x_bstride, ldx, (long)H * W, C);
+  if (f.empty()) f = slice_fault("y", y, y_bstride, ldy, (long)H * W, 3 * C);
+  if (!f.empty()) return glue_invalid(entry, f);
+  const int rc = launch_sppf_pool((const half_t*)x, x_bstride, ldx, (half_t*)y, y_bstride, ldy, B, H, W, C, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, std::string(entry) + ": launch failed: " + std::to_string(rc));
+}
+
+int upsample_entry(const char* entry, const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy, int B, int H,
+                   int W, int C, void* stream) {
+  if (B < 1 || H < 1 || W < 1 || H > (1 << 14) || W > (1 << 14)) return glue_invalid(entry, "B, H, W must be >= 1 (H, W at most 16384)");
+  if (C < 8 || C % 8) return glue_invalid(entry, "C must be a positive multiple of 8");
+  std::string f = slice_fault("x", x, x_bstride, ldx, (long)H * W, C);
+  if (f.empty()) f = slice_fault("y", y, y_bstride, ldy, (long)4 * H * W, C);
+  if (!f.empty()) return glue_invalid(entry, f);
+  const int rc = launch_upsample2x((const half_t*)x, x_bstride, ldx, (half_t*)y, y_bstride, ldy, B, H, W, C, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, std::string(entry) + ": launch failed: " + std::to_string(rc));
+}
+
+int decode_entry(const char* entry, const float* raw, int B, int in_h, int in_w, int nc, int nm, float* preds, void* stream) {
+  if (!raw || !preds) return glue_invalid(entry, "null pointer");
+  if (B < 1) return glue_invalid(entry, "B must be >= 1");
+  if (in_h < 32 || in_w < 32 || in_h % 32 || in_w % 32 || in_h > 32768 || in_w > 32768)
+    return glue_invalid(entry, "in_h and in_w must be positive multiples of 32 (at most 32768)");
+  if (nc < 1 || nm < 0) return glue_invalid(entry, "nc must be >= 1 and nm >= 0");
+  // the kernel stages 64 anchors' raw and decoded rows in LDS (launch_head_decode)
+  if (((long)64 + nc + nm + 4 + nc + nm) * 64 * (long)sizeof(float) > 160 * 1024) return glue_invalid(entry, "nc + nm needs more than 160 KB of LDS");
+  if (((uintptr_t)raw | (uintptr_t)preds) & 15) return glue_invalid(entry, "raw and preds must be 16-byte aligned");
+  const long anchors = (long)(in_h / 8) * (in_w / 8) + (long)(in_h / 16) * (in_w / 16) + (long)(in_h / 32) * (in_w / 32);
+  if (B * anchors > (1L << 36)) return glue_invalid(entry, "too many anchors");
+  const int rc = launch_head_decode(raw, B, in_h, in_w, nc, nm, preds, (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, std::string(entry) + ": launch failed: " + std::to_string(rc));
+}
+
 // Diagnostics of the row-slab entries (conv_op_common, m355_bneck_pair_fwd), read by tools/stamps_halo.py and tools/bneck_bench.py:
 //   M355_STAMPS=<file>   the kernel's stamps go to a zeroed buffer of `words` uint64, written to <file> by dump();
 //   M355_BNECK_REPS=<n>  after a launch that succeeded, n more back to back; their mean time goes to stderr.
@@ -532,7 +587,15 @@ int m355_convt2x2_fwd(const void* d_x, int B, int H, int W, int cin, const float
 
 int m355_stem_fwd(const void* d_in, int B, int H, int W, const float* h_w, const float* h_bias, int cout, void* d_y,
                   void* stream) {
-  if (!d_in || !h_w || !h_bias || !d_y) return set_err(M355_ERR_INVALID, "null pointer");
+  // every argument before any HIP call
+  const char* entry = "m355_stem_fwd";
+  if (!d_in || !h_w || !h_bias || !d_y) return glue_invalid(entry, "null pointer");
+  if (cout != 16 && cout != 32 && cout != 48 && cout != 64 && cout != 80) return glue_invalid(entry, "cout must be 16, 32, 48, 64 or 80");
+  if (B < 1) return glue_invalid(entry, "B must be >= 1");
+  if (H < 2 || W < 2 || H % 2 || W % 2 || H > 32768 || W > 32768) return glue_invalid(entry, "H and W must be even and >= 2 (at most 32768)");
+  if ((long)B * (H / 2) > 0x7fffffffL) return glue_invalid(entry, "too many output rows");
+  if ((uintptr_t)d_in & 15) return glue_invalid(entry, "the image must be 16-byte aligned");
+  if ((uintptr_t)d_y & 7) return glue_invalid(entry, "the output must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const std::vector<half_t> sw = pack_stem3x3(h_w, cout);
   DevBuf d;
@@ -610,23 +673,19 @@ int m355_psa_attn_fwd(const void* d_qkv, int B, int H, int W, int heads, int key
 }
 
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream) {
-  if (!d_x || !d_y) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = launch_sppf_pool((const half_t*)d_x, (long)H * W * C, C, (half_t*)d_y, (long)H * W * 3 * C, 3 * C, B,
-                                  H, W, C, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "sppf launch failed: " + std::to_string(rc));
+  return sppf_entry("m355_sppf_pool", d_x, (int64_t)H * W * C, C, d_y, (int64_t)H * W * 3 * C, 3 * C, B, H, W, C, stream);
 }
 
 int m355_upsample2x(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream) {
-  if (!d_x || !d_y) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = launch_upsample2x((const half_t*)d_x, (long)H * W * C, C, (half_t*)d_y, (long)4 * H * W * C, C, B, H,
-                                   W, C, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "upsample launch failed: " + std::to_string(rc));
+  return upsample_entry("m355_upsample2x", d_x, (int64_t)H * W * C, C, d_y, (int64_t)4 * H * W * C, C, B, H, W, C, stream);
 }
 
 int m355_head_decode(const float* d_raw, int B, int in_h, int in_w, int nc, float* d_preds, void* stream) {
-  if (!d_raw || !d_preds) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = launch_head_decode(d_raw, B, in_h, in_w, nc, 32, d_preds, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "decode launch failed: " + std::to_string(rc));
+  return decode_entry("m355_head_decode", d_raw, B, in_h, in_w, nc, 32, d_preds, stream);
+}
+
+int m355_head_decode_ex(const float* d_raw, int B, int in_h, int in_w, int nc, int nm, float* d_preds, void* stream) {
+  return decode_entry("m355_head_decode_ex", d_raw, B, in_h, in_w, nc, nm, d_preds, stream);
 }
 
 // the body of m355_nms and m355_nms_ex, after their argument checks
@@ -793,10 +852,10 @@ int m355_augment_ex(const void* d_cache, int32_t n_images, const m355_aug_ex_par
 }
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
-  if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = launch_sppf_pool((const half_t*)x, x_bstride, ldx, (half_t*)y, y_bstride, ldy, B, H, W, C, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "sppf launch failed: " + std::to_string(rc));
+  return sppf_entry("m355_sppf_pool_launch", x, x_bstride, ldx, y, y_bstride, ldy, B, H, W, C, stream);
 }
+
+int m355_sppf_pool_form(int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldy) { return sppf_pool_form(B, H, W, C, ldy); }
 
 int m355_repack_launch(const m355_repack_job* d_jobs, const int32_t* d_block_job, int32_t nblocks, void* stream) {
   const int rc = launch_repack(d_jobs, d_block_job, nblocks, (hipStream_t)stream);
@@ -895,9 +954,22 @@ int m355_tal_assign_launch(const float* scores, const float* boxes, const float*
 
 int m355_upsample2x_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                            int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
-  if (!x || !y) return set_err(M355_ERR_INVALID, "null pointer");
-  const int rc = launch_upsample2x((const half_t*)x, x_bstride, ldx, (half_t*)y, y_bstride, ldy, B, H, W, C, (hipStream_t)stream);
-  return rc == 0 ? M355_OK : set_err(M355_ERR_HIP, "upsample launch failed: " + std::to_string(rc));
+  return upsample_entry("m355_upsample2x_launch", x, x_bstride, ldx, y, y_bstride, ldy, B, H, W, C, stream);
+}
+
+int m355_adown_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* a, int64_t a_bstride, int32_t lda, void* m,
+                           int64_t m_bstride, int32_t ldm, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
+  const char* entry = "m355_adown_pool_launch";
+  if (B < 1) return glue_invalid(entry, "B must be >= 1");
+  if (H < 2 || W < 2 || H % 2 || W % 2 || H > (1 << 14) || W > (1 << 14)) return glue_invalid(entry, "H and W must be even and >= 2 (at most 16384)");
+  if (C < 16 || C % 16) return glue_invalid(entry, "C must be a positive multiple of 16");
+  std::string f = slice_fault("x", x, x_bstride, ldx, (long)H * W, C);
+  if (f.empty()) f = slice_fault("a", a, a_bstride, lda, (long)(H - 1) * (W - 1), C / 2);
+  if (f.empty()) f = slice_fault("m", m, m_bstride, ldm, (long)(H / 2) * (W / 2), C / 2);
+  if (!f.empty()) return glue_invalid(entry, f);
+  const int rc = launch_adown_pool((const half_t*)x, x_bstride, ldx, (half_t*)a, a_bstride, lda, (half_t*)m, m_bstride, ldm, B, H, W, C,
+                                   (hipStream_t)stream);
+  return rc == 0 ? M355_OK : set_err(rc == -1 ? M355_ERR_INVALID : M355_ERR_HIP, std::string(entry) + ": launch failed: " + std::to_string(rc));
 }
 
 }  // extern "C"

@@ -262,7 +262,9 @@ int m355_bn_silu_train_bwd(const void* d_z, const void* d_dy, int B, int H, int 
 int m355_convt2x2_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int cin, const float* h_w,
                       const float* h_bias, int cout, void* d_y_f16_nhwc, void* stream);
 /* Stem conv: uint8 NHWC (B,H,W,3) -> fp16 NHWC (B,H/2,W/2,cout), 3x3 s2 p1 + bias + SiLU;
- * h_w fp32 (cout,3,3,3) is applied to pixel/255.                                            [sync] */
+ * h_w fp32 (cout,3,3,3) is applied to pixel/255.  cout in {16,32,48,64,80}; B >= 1; H and W even, >= 2 and at most 32768 (an odd size
+ * is not the convolution's output); the image 16-byte and the output 8-byte aligned.  Every argument is checked before any HIP
+ * call (-1 = M355_ERR_INVALID).                                                                               [sync] */
 int m355_stem_fwd(const void* d_in_u8, int B, int H, int W, const float* h_w, const float* h_bias, int cout,
                   void* d_y_f16_nhwc, void* stream);
 /* YOLOv5u stem (model.0, conv_stem6_s2.hip): uint8 NHWC (B,H,W,3) -> fp16 NHWC (B,H/2,W/2,C0),
@@ -283,12 +285,20 @@ int m355_dwconv3x3_fwd(const void* d_x_f16_nhwc, int B, int H, int W, int C, int
  * 16-byte and y 8-byte aligned.  Every argument is checked before any HIP call.                              [sync] */
 int m355_psa_attn_fwd(const void* d_qkv_f16_nhwc, int B, int H, int W, int heads, int key_dim, int head_dim,
                       const float* h_pe_w, const float* h_pe_b, void* d_y_f16_nhwc, void* stream);
-/* SPPF pooling: x fp16 NHWC (B,H,W,C) -> y (B,H,W,3C) = [mp5(x), mp5(mp5(x)), mp5^3(x)]. */
+/* SPPF pooling: x fp16 NHWC (B,H,W,C) -> y (B,H,W,3C) = [mp5(x), mp5(mp5(x)), mp5^3(x)].  The dense form of
+ * m355_sppf_pool_launch (below), with its argument checks.  Asynchronous on `stream`. */
 int m355_sppf_pool(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
-/* Nearest 2x upsample, fp16 NHWC (B,H,W,C) -> (B,2H,2W,C). */
+/* Nearest 2x upsample, fp16 NHWC (B,H,W,C) -> (B,2H,2W,C).  The dense form of m355_upsample2x_launch (below), with its
+ * argument checks.  Asynchronous on `stream`. */
 int m355_upsample2x(const void* d_x, int B, int H, int W, int C, void* d_y, void* stream);
-/* Head decode: raw (B,A,64+nc+32) f32 -> preds (B,A,4+nc+32) f32 for an in_h x in_w input. */
+/* Head decode: raw (B,A,64+nc+nm) f32 -> preds (B,A,4+nc+nm) f32 for an in_h x in_w input, A = the anchors of
+ * the three levels (strides 8, 16, 32; anchor (gx + 0.5, gy + 0.5) per cell, row-major per level): cxcywh in pixels from the
+ * DFL expectation over 16 bins, sigmoid class scores, the nm coefficients copied through.  m355_head_decode is the _ex
+ * entry with nm = 32.  M355_ERR_INVALID, before any HIP call: a NULL pointer, B < 1, in_h or in_w not a positive multiple
+ * of 32, nc < 1, nm < 0, an nc + nm whose 64-anchor stage needs more than 160 KB of LDS, raw or preds not 16-byte aligned.
+ * Asynchronous on `stream`. */
 int m355_head_decode(const float* d_raw, int B, int in_h, int in_w, int nc, float* d_preds, void* stream);
+int m355_head_decode_ex(const float* d_raw, int B, int in_h, int in_w, int nc, int nm, float* d_preds, void* stream);
 /* Batched NMS only. preds (B,A,4+nc+nm).  An anchor is a candidate when its best class score is above conf
  * (strictly); of an image's candidates only the first 30000 by score (equal scores: the lower anchor first) enter the greedy
  * pass, as upstream's max_nms: with A <= 30000 that is all of them.  A box is suppressed by a kept one when their IoU is
@@ -386,8 +396,18 @@ int m355_bn_train_fwd_launch(const void* z, int64_t npix, int32_t ldz, int32_t C
 int m355_bn_train_bwd_launch(const void* z, const void* dy, int64_t npix, int32_t ldz, int32_t lddy, int32_t C,
                              const float* mean, const float* invstd, const float* gamma, const float* beta, int32_t act,
                              void* dz, int32_t lddz, float* dbeta_dgamma, float* ws, void* stream);
+/* Forward glue on channel slices (csrc/misc_kernels.hip): SPPF pooling x (B,H,W,[C]) -> y (B,H,W,[3C]) = [mp5(x), mp5^2(x),
+ * mp5^3(x)] (5x5 / s1 / p2 max pools, clipped windows), and (further down) m355_upsample2x_launch and m355_adown_pool_launch.
+ * Every argument is checked before any HIP call (M355_ERR_INVALID, the message names the entry): B, H, W >= 1; C a
+ * positive multiple of 8; for every slice a non-NULL 16-byte aligned pointer, a leading dimension >= its channel count,
+ * leading dimension and batch stride multiples of 8, a batch stride >= the extent (pixels - 1) * ld + channels of one
+ * image's slice.  SPPF keeps a whole plane in LDS: one of more than 160 KB (H * W > 3413) is refused.
+ * m355_sppf_pool_form (host only, no HIP call) names the kernel instance m355_sppf_pool_launch runs for a shape:
+ * cg | (owned << 8), cg = 8-channel groups per block (1, 2, 4), owned = 1 the per-thread-ownership kernel (planes of at
+ * most 2048 elements), 0 the generic one; -1 where the launch refuses.  The choice depends on M355_SPPF_MINBLOCKS. */
 int m355_sppf_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                           int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+int m355_sppf_pool_form(int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldy);
 /* Re-pack of fp32 master weights into fp16 GEMM layouts, every strided convert-copy of a training step in one launch.
  * A job copies a 4-d iteration space n[0..3] (n[3] fastest) from fp32 `src` to fp16 `dst` with signed ELEMENT strides on both
  * sides; block0 = index of the job's first block; block b of the launch handles elements [(b - block0) * 1024, +1024) of job
@@ -431,8 +451,16 @@ int m355_adown_fwd_launch(const void* x, int64_t x_bstride, int32_t ldx, void* p
 int m355_adown_bwd_launch(const void* g1, int64_t g1_bstride, int32_t ld1, const void* g2, int64_t g2_bstride, int32_t ld2,
                           const uint8_t* argmax, void* gx, int64_t gx_bstride, int32_t ldg, int32_t B, int32_t H, int32_t W, int32_t c,
                           int32_t accumulate, void* stream);
+/* Nearest 2x upsample of a slice x (B,H,W,[C]) into a slice y (B,2H,2W,[C]); argument checks as m355_sppf_pool_launch
+ * (H, W at most 16384). */
 int m355_upsample2x_launch(const void* x, int64_t x_bstride, int32_t ldx, void* y, int64_t y_bstride, int32_t ldy,
                            int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+/* ADown's pooling front of inference (yolov9c; adown_pool_kernel): with t = avg_pool2d(x, 2, 1, 0) of the slice x (B,H,W,[C]),
+ * a (B,H-1,W-1,[C/2]) = t[..., :C/2] and m (B,H/2,W/2,[C/2]) = max_pool2d(t[..., C/2:], 3, 2, 1).  An average is
+ * ((p00 + p01) + (p10 + p11)) * 0.25 in fp32, rounded to fp16 once; the max runs over those fp16 values (clipped windows).
+ * H and W even, >= 2 and at most 16384, C a positive multiple of 16; the other argument checks as m355_sppf_pool_launch. */
+int m355_adown_pool_launch(const void* x, int64_t x_bstride, int32_t ldx, void* a, int64_t a_bstride, int32_t lda, void* m,
+                           int64_t m_bstride, int32_t ldm, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
 /* Gradient glue of the training step (each replaces a strided torch expression reached from yolo_seg_train.py:12's backward):
  *  colsum: out[c] = sum over b < nb, r < rows of src[b * bstride + r * ld + c] for c < cols, fp32 result, fixed summation order
  *    (bias gradients: `d_raw[:, lo:hi, :].sum((0, 1))`, `gy.float().sum((0, 1, 2))`).  src fp32 (cols <= 256) or fp16 (src_f16 = 1:
