@@ -181,9 +181,9 @@ struct DfineLossArgs {
 size_t dfine_loss_workspace_bytes(int B, int Q);
 int launch_dfine_loss_forward(const DfineLossArgs& a, hipStream_t s);    // two launches
 int launch_dfine_loss_backward(const DfineLossArgs& a, hipStream_t s);   // one launch
-// The temporal encoder layer between its GEMMs (dfine_encoder.hip): attention core on the packed (B, S, 3 * 32 H) projection,
-// LayerNorm(x + dropout(y)), dropout(relu(h)), each with its backward, and the dropout keep-mask they share (p = 0: no mask).
-// The caller has validated every argument; all tensors contiguous fp32, 16-byte aligned.
+// The temporal encoder layer between its GEMMs: attention core on the packed (B, S, 3 * 32 H) projection and dropout(relu(h))
+// (dfine_encoder.hip), LayerNorm(x + dropout(y)) (dfine_rowln.hip), each with its backward, and the dropout keep-mask they share
+// (p = 0: no mask).  The caller has validated every argument; all tensors contiguous fp32, 16-byte aligned.
 int launch_dfine_attn_forward(const float* qkv, int B, int S, int H, float p, unsigned long long seed, int site, float* out,
                               float* lse, hipStream_t s);                                  // lse may be nullptr
 int launch_dfine_attn_backward(const float* gout, const float* qkv, const float* out, const float* lse, int B, int S, int H, float p,
@@ -195,24 +195,21 @@ int launch_dfine_addln_forward(const float* x, const float* y, const float* w, c
 int launch_dfine_addln_backward(const float* g, const float* x, const float* y, const float* w, const float* mean, const float* rstd,
                                 long M, int D, float p, unsigned long long seed, int site, float* dx, float* dy, float* dweight,
                                 float* dbias, float* work, hipStream_t s);                 // two launches
-// the backward's partition of the rows and its ordered second pass, shared with the decoder's gate (dfine_decoder.hip)
-long dfine_addln_rows_per_block(long M);
-int launch_dfine_addln_reduce(const float* part, int blocks, int D, float* dweight, float* dbias, hipStream_t s);
-// LayerNorm(clamp(x + y, lo, hi)), no dropout: a second instance of the same device code; zero gradient where the sum lies
-// strictly outside [lo, hi]
+// LayerNorm(clamp(x + y, lo, hi)), no dropout: another source of the same kernels; zero gradient where the sum lies strictly
+// outside [lo, hi]
 int launch_dfine_addln_clamp_forward(const float* x, const float* y, const float* w, const float* b, long M, int D, float eps, float lo,
                                      float hi, float* out, float* mean, float* rstd, hipStream_t s);
 int launch_dfine_addln_clamp_backward(const float* g, const float* x, const float* y, const float* w, const float* mean,
                                       const float* rstd, long M, int D, float lo, float hi, float* dx, float* dy, float* dweight,
                                       float* dbias, float* work, hipStream_t s);
-// D-FINE decoder layers between their GEMMs (dfine_decoder.hip).  gate_ln: LayerNorm(sigmoid(g[:, :D]) x1 + sigmoid(g[:, D:]) x2),
+// D-FINE decoder layers between their GEMMs.  gate_ln (dfine_rowln.hip): LayerNorm(sigmoid(g[:, :D]) x1 + sigmoid(g[:, D:]) x2),
 // g (M, 2 D); the backward's dg, dx1, dx2, dweight, dbias may each be nullptr, work as for addln (dfine_addln_workspace_bytes).
 int launch_dfine_gate_ln_forward(const float* g, const float* x1, const float* x2, const float* w, const float* b, long M, int D,
                                  float eps, float* out, float* mean, float* rstd, hipStream_t s);
 int launch_dfine_gate_ln_backward(const float* gout, const float* g, const float* x1, const float* x2, const float* w, const float* mean,
                                   const float* rstd, long M, int D, float* dg, float* dx1, float* dx2, float* dweight, float* dbias,
                                   float* work, hipStream_t s);
-// lqe: per (row, side) softmax over nb1 logits, the k largest probabilities in descending order, their mean -> stat (M, 4 (k + 1));
+// lqe (dfine_decoder.hip): per (row, side) softmax over nb1 logits, the k largest probabilities in descending order, their mean -> stat (M, 4 (k + 1));
 // idx (M, 4, k) bytes (may be nullptr in the forward): the chosen bins, an exact tie to the lowest bin
 int launch_dfine_lqe_forward(const float* corners, long M, int nb1, int k, float* stat, unsigned char* idx, hipStream_t s);
 int launch_dfine_lqe_backward(const float* gstat, const float* corners, const unsigned char* idx, long M, int nb1, int k,

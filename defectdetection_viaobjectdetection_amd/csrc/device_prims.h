@@ -51,7 +51,24 @@ __device__ __forceinline__ int row_operand(int rho) {
   return 16 * (q >> 1) + 8 * h + 4 * (q & 1) + i;
 }
 
-// ---- dropout keep-mask: a pure function of (seed, site, flat element index), nothing stored (dfine_encoder.hip)
+// ---- wave-wide xor butterflies: every lane ends with the same bits (a + b == b + a at each step)
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+  return x;
+}
+__device__ __forceinline__ int wave_sum_int(int x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// ---- dropout keep-mask: a pure function of (seed, site, flat element index), nothing stored (dfine_encoder.hip, dfine_rowln.hip)
 // Philox4x32-10 (Salmon et al., SC'11; Random123's constants and round): counter c[0..3], key (k0, k1), result in c.
 __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
 #pragma unroll
@@ -72,6 +89,14 @@ struct DropArgs {
   unsigned site, thr;
   float scale;
 };
+inline DropArgs drop_args(float p, unsigned long long seed, int site) {
+  DropArgs d{};
+  d.seed = seed;
+  d.site = (unsigned)site;
+  d.thr = (unsigned)((double)p * 4294967296.0);   // p in [0, 1): below 2^32
+  d.scale = (float)(1.0 / (1.0 - (double)p));
+  return d;
+}
 // The ONE definition of the mask: bit e (0..3) of the result is set when element 4 * group + e of the site's tensor (flat,
 // row-major index) is kept.  counter = (group lo, group hi, site, 0), key = (seed lo, seed hi): one Philox call per 4 elements.
 __device__ __forceinline__ unsigned dropout_keep4(const DropArgs& d, unsigned long long group) {

@@ -1,8 +1,7 @@
 // The temporal encoder of the D-FINE trainers (nn.TransformerEncoderLayer, post-norm, ReLU, head dim 32) between its GEMMs:
 //   attn_fwd / attn_bwd          softmax(q k^T / sqrt(32)) [dropout] v on the packed in-projection output (B, S, 3 D)
-//   addln_fwd / addln_bwd        LayerNorm(x + dropout(y)), with the fixed-order column sums of dweight / dbias; their CLAMP
-//                                instances are LayerNorm(clamp(x + y, lo, hi)) of the D-FINE decoder layer (dfine_decoder.hip)
 //   relu_drop_fwd / relu_drop_bwd  dropout(relu(h))
+// (the layer's LayerNorm(x + dropout(y)) is a source of the row-LayerNorm kernels in dfine_rowln.hip.)
 // All fp32 in, fp32 out, fp32 accumulation.  No float atomics anywhere: every sum has one owner and a fixed order, so the
 // results are bitwise reproducible and frame b does not depend on the batch.
 // Every dropout mask comes from dropout_keep4 (device_prims.h) and is recomputed in the backward; none is stored.
@@ -350,193 +349,6 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_kernel(const AttnArgs a) 
   else attn_bwd_dkv<DROP>(a, T0, T1, lse_s, delta_s, blockIdx.x - tiles);
 }
 
-// ---- LayerNorm(x + dropout(y)) ---------------------------------------------------------------------------------------------
-// One wave per row; a lane holds float4 number lane + 64 t of the row, t < LN_MAXV (D <= 1024), in registers.
-constexpr int LN_THREADS = 256;
-constexpr int LN_WAVES = LN_THREADS / 64;
-constexpr int LN_MAXV = 4;
-constexpr int LN_MAX_D = 256 * LN_MAXV;
-constexpr int LN_MAX_BLOCKS = 256;   // partial rows of the backward's column sums
-
-struct LnArgs {
-  const float *x, *y, *w, *b;   // x, y (M, D); w, b (D)
-  float* out;                   // forward: (M, D)
-  float *mean, *rstd;           // (M): written by the forward, read by the backward
-  const float* g;               // backward: (M, D)
-  float *dx, *dy;               // backward: (M, D), either may be nullptr
-  float* part;                  // backward: (blocks, 2, D) partial column sums of dweight | dbias
-  long M;
-  int D;
-  long rows_per_block;          // backward
-  float eps;
-  float lo, hi;                 // the CLAMP instances: z = clamp(x + y, lo, hi) before the statistics
-  DropArgs d;
-};
-
-__device__ __forceinline__ float wave_sum(float x) {   // a butterfly: the same bits in every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
-// z = x + dropout(y) of float4 number v of row `row`
-template <bool DROP>
-__device__ __forceinline__ float4 ln_load_z(const LnArgs& a, long row, int v, unsigned& keep) {
-  const long e = row * a.D + 4L * v;
-  const float4 xv = *(const float4*)(a.x + e);
-  float4 yv = *(const float4*)(a.y + e);
-  keep = 0xfu;
-  if (DROP) {
-    keep = dropout_keep4(a.d, (unsigned long long)e >> 2);
-    yv.x = keep & 1u ? yv.x * a.d.scale : 0.f; yv.y = keep & 2u ? yv.y * a.d.scale : 0.f;
-    yv.z = keep & 4u ? yv.z * a.d.scale : 0.f; yv.w = keep & 8u ? yv.w * a.d.scale : 0.f;
-  }
-  return make_float4(xv.x + yv.x, xv.y + yv.y, xv.z + yv.z, xv.w + yv.w);
-}
-
-// torch.clamp of one element, NaN kept; `inside` = lo <= z <= hi, the elements that torch's clamp backward lets through
-__device__ __forceinline__ float clamp1(float z, float lo, float hi, bool& inside) {
-  inside = z >= lo && z <= hi;
-  return z < lo ? lo : (z > hi ? hi : z);
-}
-// bit c of the result: component c of z was inside [lo, hi]
-__device__ __forceinline__ unsigned ln_clamp4(float4& z, float lo, float hi) {
-  bool ix, iy, iz, iw;
-  z = make_float4(clamp1(z.x, lo, hi, ix), clamp1(z.y, lo, hi, iy), clamp1(z.z, lo, hi, iz), clamp1(z.w, lo, hi, iw));
-  return (unsigned)ix | (unsigned)iy << 1 | (unsigned)iz << 2 | (unsigned)iw << 3;
-}
-
-template <bool DROP, bool CLAMP = false>
-__global__ __launch_bounds__(LN_THREADS) void addln_fwd_kernel(const LnArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = a.D >> 2;
-  const long row = (long)blockIdx.x * LN_WAVES + wave;
-  if (row >= a.M) return;   // no barrier in this kernel
-  float4 z[LN_MAXV];
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < LN_MAXV; ++t) {
-    const int v = lane + 64 * t;
-    z[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (v < nv) {
-      unsigned keep;
-      z[t] = ln_load_z<DROP>(a, row, v, keep);
-      if (CLAMP) ln_clamp4(z[t], a.lo, a.hi);
-      sum += (z[t].x + z[t].y) + (z[t].z + z[t].w);
-    }
-  }
-  const float inv_d = 1.f / (float)a.D;
-  const float mean = wave_sum(sum) * inv_d;
-  float sq = 0.f;
-#pragma unroll
-  for (int t = 0; t < LN_MAXV; ++t) {
-    if (lane + 64 * t < nv) {
-      const float dx = z[t].x - mean, dy = z[t].y - mean, dz = z[t].z - mean, dw = z[t].w - mean;
-      sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(sq) * inv_d + a.eps);
-#pragma unroll
-  for (int t = 0; t < LN_MAXV; ++t) {
-    const int v = lane + 64 * t;
-    if (v < nv) {
-      const float4 w = *(const float4*)(a.w + 4 * v), bb = *(const float4*)(a.b + 4 * v);
-      *(float4*)(a.out + row * a.D + 4L * v) = make_float4((z[t].x - mean) * rstd * w.x + bb.x, (z[t].y - mean) * rstd * w.y + bb.y,
-                                                           (z[t].z - mean) * rstd * w.z + bb.z, (z[t].w - mean) * rstd * w.w + bb.w);
-    }
-  }
-  if (lane == 0) { a.mean[row] = mean; a.rstd[row] = rstd; }
-}
-
-// Block `blk` owns rows [blk * rows_per_block, ...): wave w takes every fourth of them in ascending order and keeps its
-// column sums of g * zhat and g in registers; the four waves' sums are added in wave order into partial row `blk`.
-template <bool DROP, bool CLAMP = false>
-__global__ __launch_bounds__(LN_THREADS) void addln_bwd_kernel(const LnArgs a) {
-  __shared__ float part[LN_WAVES][2][LN_MAX_D];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nv = a.D >> 2;
-  const long r0 = (long)blockIdx.x * a.rows_per_block;
-  const long r1 = r0 + a.rows_per_block < a.M ? r0 + a.rows_per_block : a.M;
-  const float inv_d = 1.f / (float)a.D;
-  float4 dw[LN_MAXV], db[LN_MAXV], w[LN_MAXV];
-#pragma unroll
-  for (int t = 0; t < LN_MAXV; ++t) {
-    dw[t] = db[t] = w[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane + 64 * t < nv) w[t] = *(const float4*)(a.w + 4 * (lane + 64 * t));
-  }
-  for (long row = r0 + wave; row < r1; row += LN_WAVES) {
-    const float mean = a.mean[row], rstd = a.rstd[row];
-    float4 zh[LN_MAXV], gw[LN_MAXV];
-    unsigned keep[LN_MAXV], inside[LN_MAXV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < LN_MAXV; ++t) {
-      const int v = lane + 64 * t;
-      zh[t] = gw[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-      keep[t] = 0u;
-      inside[t] = 0xfu;
-      if (v < nv) {
-        float4 z = ln_load_z<DROP>(a, row, v, keep[t]);
-        if (CLAMP) inside[t] = ln_clamp4(z, a.lo, a.hi);
-        const float4 g = *(const float4*)(a.g + row * a.D + 4L * v);
-        zh[t] = make_float4((z.x - mean) * rstd, (z.y - mean) * rstd, (z.z - mean) * rstd, (z.w - mean) * rstd);
-        gw[t] = make_float4(g.x * w[t].x, g.y * w[t].y, g.z * w[t].z, g.w * w[t].w);
-        s1 += (gw[t].x + gw[t].y) + (gw[t].z + gw[t].w);
-        s2 += (gw[t].x * zh[t].x + gw[t].y * zh[t].y) + (gw[t].z * zh[t].z + gw[t].w * zh[t].w);
-        dw[t].x = fmaf(g.x, zh[t].x, dw[t].x); dw[t].y = fmaf(g.y, zh[t].y, dw[t].y);
-        dw[t].z = fmaf(g.z, zh[t].z, dw[t].z); dw[t].w = fmaf(g.w, zh[t].w, dw[t].w);
-        db[t].x += g.x; db[t].y += g.y; db[t].z += g.z; db[t].w += g.w;
-      }
-    }
-    const float c1 = wave_sum(s1) * inv_d, c2 = wave_sum(s2) * inv_d;
-#pragma unroll
-    for (int t = 0; t < LN_MAXV; ++t) {
-      const int v = lane + 64 * t;
-      if (v < nv) {
-        float4 dz = make_float4(rstd * (gw[t].x - c1 - zh[t].x * c2), rstd * (gw[t].y - c1 - zh[t].y * c2),
-                                rstd * (gw[t].z - c1 - zh[t].z * c2), rstd * (gw[t].w - c1 - zh[t].w * c2));
-        if (CLAMP) {   // no gradient through an element that the clamp moved
-          dz.x = inside[t] & 1u ? dz.x : 0.f; dz.y = inside[t] & 2u ? dz.y : 0.f;
-          dz.z = inside[t] & 4u ? dz.z : 0.f; dz.w = inside[t] & 8u ? dz.w : 0.f;
-        }
-        if (a.dx) *(float4*)(a.dx + row * a.D + 4L * v) = dz;
-        if (a.dy) {
-          float4 dyv = dz;
-          if (DROP) {
-            dyv.x = keep[t] & 1u ? dz.x * a.d.scale : 0.f; dyv.y = keep[t] & 2u ? dz.y * a.d.scale : 0.f;
-            dyv.z = keep[t] & 4u ? dz.z * a.d.scale : 0.f; dyv.w = keep[t] & 8u ? dz.w * a.d.scale : 0.f;
-          }
-          *(float4*)(a.dy + row * a.D + 4L * v) = dyv;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < LN_MAXV; ++t) {
-    const int v = lane + 64 * t;
-    if (v < nv) {
-      *(float4*)&part[wave][0][4 * v] = dw[t];
-      *(float4*)&part[wave][1][4 * v] = db[t];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < 2 * a.D; c += LN_THREADS) {
-    const int which = c >= a.D, col = c - which * a.D;
-    float s = part[0][which][col];
-#pragma unroll
-    for (int wv = 1; wv < LN_WAVES; ++wv) s += part[wv][which][col];
-    a.part[(long)blockIdx.x * 2 * a.D + c] = s;
-  }
-}
-
-// dweight | dbias [c] = the partial rows added in block order
-__global__ __launch_bounds__(256) void addln_reduce_kernel(const float* part, int nblocks, int D, float* dweight, float* dbias) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= 2 * D) return;
-  float s = 0.f;
-  for (int k = 0; k < nblocks; ++k) s += part[(long)k * 2 * D + c];
-  if (c < D) { if (dweight) dweight[c] = s; }
-  else if (dbias) dbias[c - D] = s;
-}
-
 // ---- dropout(relu(h)), its backward, and the mask itself -------------------------------------------------------------------
 // One thread per group of four elements (the Philox call's four words); the last group of a tensor may be shorter.
 template <bool DROP, bool BWD>
@@ -580,15 +392,6 @@ __global__ __launch_bounds__(256) void keep_mask_kernel(unsigned char* mask, lon
   for (int t = 0; t < 4; ++t) if (e + t < n) mask[e + t] = (unsigned char)((keep >> t) & 1u);
 }
 
-DropArgs drop_args(float p, unsigned long long seed, int site) {
-  DropArgs d{};
-  d.seed = seed;
-  d.site = (unsigned)site;
-  d.thr = (unsigned)((double)p * 4294967296.0);   // p in [0, 1): below 2^32
-  d.scale = (float)(1.0 / (1.0 - (double)p));
-  return d;
-}
-
 }  // namespace
 
 int launch_dfine_attn_forward(const float* qkv, int B, int S, int H, float p, unsigned long long seed, int site, float* out,
@@ -609,74 +412,6 @@ int launch_dfine_attn_backward(const float* gout, const float* qkv, const float*
   if (p > 0.f) hipLaunchKernelGGL(attn_bwd_kernel<true>, grid, dim3(AT_THREADS), 0, s, a);
   else hipLaunchKernelGGL(attn_bwd_kernel<false>, grid, dim3(AT_THREADS), 0, s, a);
   return (int)hipGetLastError();
-}
-
-int dfine_addln_max_d() { return LN_MAX_D; }
-
-long dfine_addln_rows_per_block(long M) {
-  long blocks = (M + LN_WAVES - 1) / LN_WAVES;
-  if (blocks > LN_MAX_BLOCKS) blocks = LN_MAX_BLOCKS;
-  const long rpb = (M + blocks - 1) / blocks;
-  return (rpb + LN_WAVES - 1) / LN_WAVES * LN_WAVES;
-}
-
-size_t dfine_addln_workspace_bytes(long M, int D) {
-  if (M < 1 || D < 1) return 0;
-  const long rpb = dfine_addln_rows_per_block(M);
-  return (size_t)((M + rpb - 1) / rpb) * 2 * (size_t)D * sizeof(float);
-}
-
-int launch_dfine_addln_forward(const float* x, const float* y, const float* w, const float* b, long M, int D, float eps, float p,
-                               unsigned long long seed, int site, float* out, float* mean, float* rstd, hipStream_t s) {
-  LnArgs a{};
-  a.x = x; a.y = y; a.w = w; a.b = b; a.out = out; a.mean = mean; a.rstd = rstd; a.M = M; a.D = D; a.eps = eps;
-  a.d = drop_args(p, seed, site);
-  const dim3 grid((unsigned)((M + LN_WAVES - 1) / LN_WAVES));
-  if (p > 0.f) hipLaunchKernelGGL(addln_fwd_kernel<true>, grid, dim3(LN_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(addln_fwd_kernel<false>, grid, dim3(LN_THREADS), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int launch_dfine_addln_backward(const float* g, const float* x, const float* y, const float* w, const float* mean, const float* rstd,
-                                long M, int D, float p, unsigned long long seed, int site, float* dx, float* dy, float* dweight,
-                                float* dbias, float* work, hipStream_t s) {
-  LnArgs a{};
-  a.x = x; a.y = y; a.w = w; a.g = g; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dx = dx; a.dy = dy;
-  a.part = work; a.M = M; a.D = D; a.rows_per_block = dfine_addln_rows_per_block(M);
-  a.d = drop_args(p, seed, site);
-  const int blocks = (int)((M + a.rows_per_block - 1) / a.rows_per_block);
-  if (p > 0.f) hipLaunchKernelGGL(addln_bwd_kernel<true>, dim3(blocks), dim3(LN_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(addln_bwd_kernel<false>, dim3(blocks), dim3(LN_THREADS), 0, s, a);
-  int rc = (int)hipGetLastError();
-  if (rc != 0 || (!dweight && !dbias)) return rc;
-  return launch_dfine_addln_reduce(work, blocks, D, dweight, dbias, s);
-}
-
-int launch_dfine_addln_reduce(const float* part, int blocks, int D, float* dweight, float* dbias, hipStream_t s) {
-  hipLaunchKernelGGL(addln_reduce_kernel, dim3((2 * D + 255) / 256), dim3(256), 0, s, part, blocks, D, dweight, dbias);
-  return (int)hipGetLastError();
-}
-
-// LayerNorm(clamp(x + y, lo, hi)): the CLAMP instances of the same device code, without dropout
-int launch_dfine_addln_clamp_forward(const float* x, const float* y, const float* w, const float* b, long M, int D, float eps, float lo,
-                                     float hi, float* out, float* mean, float* rstd, hipStream_t s) {
-  LnArgs a{};
-  a.x = x; a.y = y; a.w = w; a.b = b; a.out = out; a.mean = mean; a.rstd = rstd; a.M = M; a.D = D; a.eps = eps; a.lo = lo; a.hi = hi;
-  hipLaunchKernelGGL((addln_fwd_kernel<false, true>), dim3((unsigned)((M + LN_WAVES - 1) / LN_WAVES)), dim3(LN_THREADS), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int launch_dfine_addln_clamp_backward(const float* g, const float* x, const float* y, const float* w, const float* mean,
-                                      const float* rstd, long M, int D, float lo, float hi, float* dx, float* dy, float* dweight,
-                                      float* dbias, float* work, hipStream_t s) {
-  LnArgs a{};
-  a.x = x; a.y = y; a.w = w; a.g = g; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.dx = dx; a.dy = dy;
-  a.part = work; a.M = M; a.D = D; a.rows_per_block = dfine_addln_rows_per_block(M); a.lo = lo; a.hi = hi;
-  const int blocks = (int)((M + a.rows_per_block - 1) / a.rows_per_block);
-  hipLaunchKernelGGL((addln_bwd_kernel<false, true>), dim3(blocks), dim3(LN_THREADS), 0, s, a);
-  const int rc = (int)hipGetLastError();
-  if (rc != 0 || (!dweight && !dbias)) return rc;
-  return launch_dfine_addln_reduce(work, blocks, D, dweight, dbias, s);
 }
 
 int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, long n, float p, unsigned long long seed, int site,

@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "device_prims.h"
 #include "launch_util.h"
 
 namespace m355 {
@@ -22,22 +23,6 @@ namespace {
 constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_QPB = 4;      // queries per block: one per wave
 constexpr int LOSS_SLOTS = 8;    // per-block partials: vfl, bbox, giou, fgl, ddf matched, ddf unmatched, matched count (int bits), -
-
-__device__ __forceinline__ float wave_sum(float v) {   // every lane ends with the same bits: a + b == b + a at each step
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // log_softmax of one row of n <= 64 values, lane i holding value i (z is ignored on lanes >= n).  The ONE routine behind both
 // sides of the KL term: equal input bits give equal output bits, so a teacher equal to the prediction gives exactly 0.

@@ -33,13 +33,14 @@ GEMM, the serial chain of both directions one persistent launch forward and one 
 ``gate_layer_norm`` / ``add_layer_norm(clamp=...)`` / ``lqe_statistics`` / ``decoder_layer_forward`` / ``lqe_forward`` /
 ``bind_decoder`` are the decoder layers every trainer trains (``DFineDecoderLayer``, ``DFineLQE``) between their torch GEMMs: the
 self-attention core above on a packed q | k | v projection, the fused deformable attention, DFineGate behind its Linear,
-LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch forward with a HIP backward (csrc/dfine_decoder.hip).
+LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch forward with a HIP backward (csrc/dfine_decoder.hip; the row LayerNorms of both layer kinds: csrc/dfine_rowln.hip).
 """
 from __future__ import annotations
 
 import ctypes as C
 from collections.abc import Mapping
-from typing import List, Sequence
+from operator import itemgetter
+from typing import List, NamedTuple, Sequence
 
 import torch
 
@@ -117,6 +118,48 @@ def _grad_like(need: bool, t: torch.Tensor):
 
 def _as_input(g, shape, dtype):
     return None if g is None else g.reshape(shape).to(dtype)
+
+
+def _fp32_cuda_params(module) -> bool:
+    return all(p.is_cuda and p.dtype == torch.float32 for p in module.parameters())
+
+
+def _bind_forward(module, forwards: dict):
+    """Set forwards[cls] as the bound `forward` of every INSTANCE of cls inside `module` (or `module` itself); the classes are
+    never touched, parameters, buffers and the state dict stay as they are.  Returns the bound instances."""
+    import types
+    bound = []
+    for m in module.modules():
+        for cls, forward in forwards.items():
+            if isinstance(m, cls):
+                m.forward = types.MethodType(forward, m)
+                bound.append(m)
+                break
+    return bound
+
+
+def _xyxy(b: torch.Tensor) -> torch.Tensor:
+    """(..., 4) cx, cy, w, h -> x0, y0, x1, y1 in upstream's order of operations (center_to_corners_format)"""
+    cx, cy, w, h = b.unbind(-1)
+    return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
+
+
+def _packed_targets(targets, dev, *counts):
+    """The targets of all images as the matcher and the loss kernels read them: class labels (T,) int64 on `dev`, boxes (T, 4)
+    detached but otherwise as they are (one image: its own tensors, no cat), and an int32 table on `dev` that holds, for each
+    list of per-image counts, 0 and then its running sums."""
+    if len(targets) == 1:
+        labels, tboxes = targets[0]["class_labels"], targets[0]["boxes"]
+    else:
+        labels, tboxes = torch.cat([t["class_labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+    table = []
+    for per_image in counts:
+        table.append(0)
+        for n in per_image:
+            table.append(table[-1] + n)
+    # pinned + non_blocking: the copy is queued on the stream, the host does not wait for it
+    offs = torch.tensor(table, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    return labels.to(device=dev, dtype=torch.int64).contiguous(), tboxes.detach(), offs
 
 
 class _MsdaCore(torch.autograd.Function):
@@ -344,17 +387,8 @@ def hungarian_match(logits: torch.Tensor, pred_boxes: torch.Tensor, targets: Seq
     if total == 0:   # nothing to match anywhere: no launch
         flags = torch.zeros(B, dtype=torch.int32, device=dev) if return_cost else None
     else:
-        if B == 1:
-            labels, tboxes = targets[0]["class_labels"], targets[0]["boxes"]
-        else:
-            labels, tboxes = torch.cat([t["class_labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
-        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
-        tboxes = _f32c(tboxes.detach(), "target boxes")
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + n)
-        # pinned + non_blocking: the copy is queued on the stream, the host does not wait for it
-        d_offs = torch.tensor(offs, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        labels, tboxes, d_offs = _packed_targets(targets, dev, sizes)
+        tboxes = _f32c(tboxes, "target boxes")
         h_counts = (C.c_int32 * B)(*sizes)
         flags = torch.empty(B, dtype=torch.int32, device=dev)
         wbytes = int(lib.m355_dfine_match_workspace_bytes(B, Q, nmax))
@@ -385,12 +419,7 @@ def match_cost_torch(logits, pred_boxes, labels, tboxes, class_cost=2.0, bbox_co
     else:
         cls = -logits.softmax(-1)[:, labels]
     l1 = torch.cdist(pred_boxes, tboxes, p=1)
-
-    def corners(b):
-        cx, cy, w, h = b.unbind(-1)
-        return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
-
-    a, b = corners(pred_boxes), corners(tboxes)
+    a, b = _xyxy(pred_boxes), _xyxy(tboxes)
     area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
     area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
     wh = (torch.min(a[:, None, 2:], b[:, 2:]) - torch.max(a[:, None, :2], b[:, :2])).clamp(min=0)
@@ -434,11 +463,6 @@ def matcher_forward(self, outputs, targets):
 LOSS_MAX_BINS1 = 64          # the limit of m355_dfine_loss_forward: one lane per bin
 LOSS_KEYS = ("loss_vfl", "loss_bbox", "loss_giou", "loss_fgl", "loss_ddf")
 loss_calls = {"kernel": 0, "torch": 0}   # how many detection_loss calls took which path (tests and tools read it)
-
-
-def _xyxy(b: torch.Tensor) -> torch.Tensor:
-    cx, cy, w, h = b.unbind(-1)
-    return torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], -1)
 
 
 def _pair_iou(a: torch.Tensor, b: torch.Tensor):
@@ -622,23 +646,10 @@ def detection_loss(logits: torch.Tensor, pred_boxes: torch.Tensor, targets: Sequ
     M, T = sum(lens), sum(sizes)
     mq = mt = offs = labels = tboxes = None
     if M > 0 and T > 0:
-        if B == 1:
-            mq, mt = indices[0]
-            labels, tboxes = targets[0]["class_labels"], targets[0]["boxes"]
-        else:
-            mq, mt = torch.cat([i for i, _ in indices]), torch.cat([j for _, j in indices])
-            labels, tboxes = torch.cat([t["class_labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+        mq, mt = indices[0] if B == 1 else (torch.cat([i for i, _ in indices]), torch.cat([j for _, j in indices]))
         mq, mt = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (mq, mt))
-        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
-        tboxes = _f32c(tboxes.detach().to(dev), "target boxes")
-        table = [0]
-        for n in lens:
-            table.append(table[-1] + n)
-        table.append(0)
-        for n in sizes:
-            table.append(table[-1] + n)
-        # pinned + non_blocking: the copy is queued on the stream, the host does not wait for it
-        offs = torch.tensor(table, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        labels, tboxes, offs = _packed_targets(targets, dev, lens, sizes)
+        tboxes = _f32c(tboxes.to(dev), "target boxes")
     else:
         M = 0
     if local:
@@ -733,8 +744,7 @@ def _device_sizes(target_sizes, B: int, dev) -> torch.Tensor:
 
 def _topk_torch(logits, pred_boxes, target_sizes, use_focal_loss: bool = True):
     """upstream's expression up to the per-image masks: scores (B, K), labels (B, K), boxes (B, K, 4)"""
-    cx, cy, w, h = pred_boxes.unbind(-1)
-    boxes = torch.stack([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], dim=-1)
+    boxes = _xyxy(pred_boxes)
     if target_sizes is not None:
         sizes = torch.as_tensor(target_sizes) if isinstance(target_sizes, (list, tuple)) else target_sizes
         img_h, img_w = sizes.unbind(1)
@@ -922,83 +932,64 @@ def self_attention(qkv: torch.Tensor, n_heads: int, dropout_p: float = 0.0, seed
     return _attn_forward(_f32c16(qkv, "qkv"), int(n_heads), p, seed, int(site), False)[0]
 
 
-class _AddLayerNorm(torch.autograd.Function):
+class _RowForm(NamedTuple):
+    """One form of the row LayerNorm (csrc/dfine_rowln.hip) as _RowLayerNorm needs it.  The C entries take
+    forward(sources, weight, bias, M, D, eps, scalars, out, mean, rstd, stream) and
+    backward(grad_out, sources, weight, mean, rstd, M, D, scalars, source grads, dweight, dbias, work, work bytes, stream)."""
+    forward: object
+    backward: object
+    names: tuple        # the source tensors as the public function names and takes them; the first has the output's shape (..., D)
+    order: object       # itemgetter: the sources, and their gradients, in the order the C entries take them
+    always_sums: bool   # the backward leaves its partial column sums even when neither dweight nor dbias is asked for
+
+
+_ADD_LN = _RowForm(lib.m355_dfine_addln_forward, lib.m355_dfine_addln_backward,                     # scalars: p, seed, site
+                   ("x", "y"), itemgetter(0, 1), True)
+_ADD_CLAMP_LN = _RowForm(lib.m355_dfine_addln_clamp_forward, lib.m355_dfine_addln_clamp_backward,   # scalars: lo, hi
+                         ("x", "y"), itemgetter(0, 1), True)
+_GATE_LN = _RowForm(lib.m355_dfine_gate_ln_forward, lib.m355_dfine_gate_ln_backward,                # no scalars; entries: gate, x1, x2
+                    ("x1", "x2", "gate_logits"), itemgetter(2, 0, 1), False)
+
+
+class _RowLayerNorm(torch.autograd.Function):
+    """Keeps the sources, the weight and the per-row mean and rstd: no mask, no sigmoid, no normalised row."""
+
     @staticmethod
-    def forward(ctx, x, y, weight, bias, eps, p, seed, site):
-        xs, ys, w, b = _f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias")
-        out, mean, rstd = _addln_forward(xs, ys, w, b, eps, p, seed, site)
-        ctx.save_for_backward(xs, ys, w, mean, rstd)
-        ctx.meta = (p, seed, site, [(t.shape, t.dtype) for t in (x, y, weight, bias)])
+    def forward(ctx, form, scalars, eps, weight, bias, *srcs):
+        ts = tuple(map(_f32c16, srcs, form.names))
+        w, b = _f32c16(weight, "weight"), _f32c16(bias, "bias")
+        out, mean, rstd = _rowln_forward(form.forward, form.order(ts), w, b, eps, scalars, ts[0])
+        ctx.save_for_backward(*ts, w, mean, rstd)
+        ctx.meta = (form, scalars, [(t.shape, t.dtype) for t in (weight, bias, *srcs)])
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        xs, ys, w, mean, rstd = ctx.saved_tensors
-        p, seed, site, like = ctx.meta
-        D = xs.shape[-1]
-        M = xs.numel() // D
-        need = ctx.needs_input_grad
+        *ts, w, mean, rstd = ctx.saved_tensors
+        form, scalars, like = ctx.meta
+        D = w.numel()
+        M = mean.numel()
+        need = ctx.needs_input_grad   # form, scalars, eps, weight, bias, *srcs
         g = _f32c16(grad_out, "grad_output")
-        gx, gy = _grad_like(need[0], xs), _grad_like(need[1], ys)
-        gw = torch.empty(D, dtype=torch.float32, device=xs.device) if need[2] else None
-        gb = torch.empty(D, dtype=torch.float32, device=xs.device) if need[3] else None
-        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D))
-        work = torch.empty(wbytes, dtype=torch.uint8, device=xs.device)
-        check(lib.m355_dfine_addln_backward(_ptr(g), _ptr(xs), _ptr(ys), _ptr(w), _ptr(mean), _ptr(rstd), M, D, p, seed, site, _ptr(gx),
-                                            _ptr(gy), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
-        return tuple(_as_input(t, *sd) for t, sd in zip((gx, gy, gw, gb), like)) + (None, None, None, None)
+        gs = tuple(map(_grad_like, need[5:], ts))
+        gw = torch.empty_like(w) if need[3] else None
+        gb = torch.empty_like(w) if need[4] else None
+        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D)) if form.always_sums or need[3] or need[4] else 0
+        work = torch.empty(wbytes, dtype=torch.uint8, device=w.device) if wbytes else None
+        check(form.backward(_ptr(g), *map(_ptr, form.order(ts)), _ptr(w), _ptr(mean), _ptr(rstd), M, D, *scalars,
+                            *map(_ptr, form.order(gs)), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
+        return (None, None, None) + tuple(_as_input(t, *sd) for t, sd in zip((gw, gb, *gs), like))
 
 
-def _addln_forward(xs, ys, w, b, eps, p, seed, site):
-    D = xs.shape[-1]
-    M = xs.numel() // D
-    out = torch.empty_like(xs)
-    mean = torch.empty(M, dtype=torch.float32, device=xs.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=xs.device)
-    check(lib.m355_dfine_addln_forward(_ptr(xs), _ptr(ys), _ptr(w), _ptr(b), M, D, float(eps), p, seed, site, _ptr(out), _ptr(mean),
-                                       _ptr(rstd), _stream()))
-    return out, mean, rstd
-
-
-class _AddClampLayerNorm(torch.autograd.Function):
-    """LayerNorm(clamp(x + y, lo, hi)): the clamp instances of the same kernels (m355_dfine_addln_clamp_*), no dropout"""
-
-    @staticmethod
-    def forward(ctx, x, y, weight, bias, eps, lo, hi):
-        xs, ys, w, b = _f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias")
-        out, mean, rstd = _addln_clamp_forward(xs, ys, w, b, eps, lo, hi)
-        ctx.save_for_backward(xs, ys, w, mean, rstd)
-        ctx.meta = (lo, hi, [(t.shape, t.dtype) for t in (x, y, weight, bias)])
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        xs, ys, w, mean, rstd = ctx.saved_tensors
-        lo, hi, like = ctx.meta
-        D = xs.shape[-1]
-        M = xs.numel() // D
-        need = ctx.needs_input_grad
-        g = _f32c16(grad_out, "grad_output")
-        gx, gy = _grad_like(need[0], xs), _grad_like(need[1], ys)
-        gw = torch.empty(D, dtype=torch.float32, device=xs.device) if need[2] else None
-        gb = torch.empty(D, dtype=torch.float32, device=xs.device) if need[3] else None
-        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D))
-        work = torch.empty(wbytes, dtype=torch.uint8, device=xs.device)
-        check(lib.m355_dfine_addln_clamp_backward(_ptr(g), _ptr(xs), _ptr(ys), _ptr(w), _ptr(mean), _ptr(rstd), M, D, lo, hi, _ptr(gx),
-                                                  _ptr(gy), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
-        return tuple(_as_input(t, *sd) for t, sd in zip((gx, gy, gw, gb), like)) + (None, None, None)
-
-
-def _addln_clamp_forward(xs, ys, w, b, eps, lo, hi):
-    D = xs.shape[-1]
-    M = xs.numel() // D
-    out = torch.empty_like(xs)
-    mean = torch.empty(M, dtype=torch.float32, device=xs.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=xs.device)
-    check(lib.m355_dfine_addln_clamp_forward(_ptr(xs), _ptr(ys), _ptr(w), _ptr(b), M, D, float(eps), lo, hi, _ptr(out), _ptr(mean),
-                                             _ptr(rstd), _stream()))
+def _rowln_forward(entry, srcs, w, b, eps, scalars, like):
+    """entry: a form's forward C entry; srcs, w, b: its tensors as _f32c16 leaves them, srcs in the entry's order; like: the source
+    with the output's shape -> out, mean, rstd"""
+    D = like.shape[-1]
+    M = like.numel() // D
+    out = torch.empty_like(like)
+    mean, rstd = like.new_empty(M), like.new_empty(M)
+    check(entry(*map(_ptr, srcs), _ptr(w), _ptr(b), M, D, float(eps), *scalars, _ptr(out), _ptr(mean), _ptr(rstd), _stream()))
     return out, mean, rstd
 
 
@@ -1019,14 +1010,14 @@ def add_layer_norm(x: torch.Tensor, y: torch.Tensor, weight: torch.Tensor, bias:
         lo, hi = (float(v) for v in clamp)
         if not lo <= hi or float(dropout_p) != 0.0:
             raise ValueError("clamp=(lo, hi) needs lo <= hi and dropout_p == 0")
-        if _wants_grad(x, y, weight, bias):
-            return _AddClampLayerNorm.apply(x, y, weight, bias, float(eps), lo, hi)
-        return _addln_clamp_forward(_f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, lo, hi)[0]
-    p, seed = _dropout_args(dropout_p, seed)
+        form, scalars = _ADD_CLAMP_LN, (lo, hi)
+    else:
+        p, seed = _dropout_args(dropout_p, seed)
+        form, scalars = _ADD_LN, (p, seed, int(site))
     if _wants_grad(x, y, weight, bias):
-        return _AddLayerNorm.apply(x, y, weight, bias, float(eps), p, seed, int(site))
-    return _addln_forward(_f32c16(x, "x"), _f32c16(y, "y"), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, p, seed,
-                          int(site))[0]
+        return _RowLayerNorm.apply(form, scalars, float(eps), weight, bias, x, y)
+    xs = _f32c16(x, "x")
+    return _rowln_forward(form.forward, (xs, _f32c16(y, "y")), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, scalars, xs)[0]
 
 
 class _ReluDropout(torch.autograd.Function):
@@ -1076,8 +1067,7 @@ def _layer_is_kernel_shaped(layer) -> bool:
     D = attn.embed_dim
     if attn.head_dim != ENCODER_HEAD_DIM or D > ADDLN_MAX_D:
         return False
-    return all(isinstance(n, torch.nn.LayerNorm) and tuple(n.normalized_shape) == (D,) and n.weight is not None and n.bias is not None
-               for n in (layer.norm1, layer.norm2))
+    return _affine_norm(layer.norm1, D) and _affine_norm(layer.norm2, D)
 
 
 def _encoder_layer_takes(layer, src, src_mask, src_key_padding_mask, is_causal) -> bool:
@@ -1088,7 +1078,7 @@ def _encoder_layer_takes(layer, src, src_mask, src_key_padding_mask, is_causal) 
         return False
     if torch.is_autocast_enabled() or not _layer_is_kernel_shaped(layer) or src.shape[-1] != layer.self_attn.embed_dim:
         return False
-    return all(p.is_cuda and p.dtype == torch.float32 for p in layer.parameters())
+    return _fp32_cuda_params(layer)
 
 
 def encoder_layer_forward(self, src, src_mask=None, src_key_padding_mask=None, is_causal=False):
@@ -1121,10 +1111,7 @@ def bind_encoder(encoder):
     """Set encoder_layer_forward on every nn.TransformerEncoderLayer INSTANCE inside `encoder` (an nn.TransformerEncoder, a
     single layer, or any module that holds some); torch's class is never touched, parameters, buffers and the state dict stay as
     they are, so existing checkpoints load unchanged.  Returns `encoder`."""
-    import types
-    for m in encoder.modules():
-        if isinstance(m, torch.nn.TransformerEncoderLayer):
-            m.forward = types.MethodType(encoder_layer_forward, m)
+    _bind_forward(encoder, {torch.nn.TransformerEncoderLayer: encoder_layer_forward})
     return encoder
 
 
@@ -1258,7 +1245,7 @@ def _gru_takes(gru, input, hx) -> bool:
     if hx is not None and not (torch.is_tensor(hx) and hx.is_cuda and hx.dtype == torch.float32
                                and tuple(hx.shape) == (D, input.shape[0], GRU_HIDDEN)):
         return False
-    return all(p.is_cuda and p.dtype == torch.float32 for p in gru.parameters())
+    return _fp32_cuda_params(gru)
 
 
 def gru_forward(self, input, hx=None):
@@ -1280,60 +1267,18 @@ def gru_forward(self, input, hx=None):
 def bind_gru(module):
     """Set gru_forward on every nn.GRU INSTANCE inside `module` (an nn.GRU or any module that holds some); torch's class is never
     touched, parameters and the state dict stay as they are, so existing checkpoints load unchanged.  Returns `module`."""
-    import types
-    for m in module.modules():
-        if isinstance(m, torch.nn.GRU):
-            m.forward = types.MethodType(gru_forward, m)
+    _bind_forward(module, {torch.nn.GRU: gru_forward})
     return module
 
 
 # ---- D-FINE decoder layers and their quality heads (transformers' DFineDecoderLayer / DFineLQE) between their GEMMs --------------
 # Every trainer runs the six decoder layers forward and backward on every step.  The nn.Linear layers stay torch GEMMs on the
 # modules' own parameters (autograd yields their weight gradients); between them: self_attention, add_layer_norm,
-# deformable_attention, gate_layer_norm, relu_dropout, add_layer_norm(clamp=...) and lqe_statistics (csrc/dfine_decoder.hip).
+# deformable_attention, gate_layer_norm, relu_dropout, add_layer_norm(clamp=...) (csrc/dfine_rowln.hip) and lqe_statistics (csrc/dfine_decoder.hip).
 LQE_MAX_BINS1 = 64
 LQE_MAX_TOPK = 8
 DECODER_CLAMP = (-65504.0, 65504.0)   # DFineDecoderLayer.forward: final_layer_norm(hidden_states.clamp(min=-65504, max=65504))
 decoder_calls = {"kernel": 0, "torch": 0}   # decoder_layer_forward and lqe_forward calls by path (tests and tools read it)
-
-
-class _GateLayerNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x1, x2, gate, weight, bias, eps):
-        a, b_, g = _f32c16(x1, "x1"), _f32c16(x2, "x2"), _f32c16(gate, "gate_logits")
-        w, b = _f32c16(weight, "weight"), _f32c16(bias, "bias")
-        out, mean, rstd = _gate_ln_forward(a, b_, g, w, b, eps)
-        ctx.save_for_backward(a, b_, g, w, mean, rstd)   # the inputs and per-row statistics: no sigmoid, no normalised row
-        ctx.like = [(t.shape, t.dtype) for t in (x1, x2, gate, weight, bias)]
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        a, b_, g, w, mean, rstd = ctx.saved_tensors
-        D = a.shape[-1]
-        M = a.numel() // D
-        need = ctx.needs_input_grad
-        go = _f32c16(grad_out, "grad_output")
-        g1, g2, gg = _grad_like(need[0], a), _grad_like(need[1], b_), _grad_like(need[2], g)
-        gw = torch.empty(D, dtype=torch.float32, device=a.device) if need[3] else None
-        gb = torch.empty(D, dtype=torch.float32, device=a.device) if need[4] else None
-        wbytes = int(lib.m355_dfine_addln_workspace_bytes(M, D)) if need[3] or need[4] else 0
-        work = torch.empty(wbytes, dtype=torch.uint8, device=a.device) if wbytes else None
-        check(lib.m355_dfine_gate_ln_backward(_ptr(go), _ptr(g), _ptr(a), _ptr(b_), _ptr(w), _ptr(mean), _ptr(rstd), M, D, _ptr(gg),
-                                              _ptr(g1), _ptr(g2), _ptr(gw), _ptr(gb), _ptr(work), wbytes, _stream()))
-        return tuple(_as_input(t, *sd) for t, sd in zip((g1, g2, gg, gw, gb), ctx.like)) + (None,)
-
-
-def _gate_ln_forward(x1, x2, g, w, b, eps):
-    D = x1.shape[-1]
-    M = x1.numel() // D
-    out = torch.empty_like(x1)
-    mean = torch.empty(M, dtype=torch.float32, device=x1.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=x1.device)
-    check(lib.m355_dfine_gate_ln_forward(_ptr(g), _ptr(x1), _ptr(x2), _ptr(w), _ptr(b), M, D, float(eps), _ptr(out), _ptr(mean),
-                                         _ptr(rstd), _stream()))
-    return out, mean, rstd
 
 
 def gate_layer_norm(x1: torch.Tensor, x2: torch.Tensor, gate_logits: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
@@ -1350,9 +1295,9 @@ def gate_layer_norm(x1: torch.Tensor, x2: torch.Tensor, gate_logits: torch.Tenso
     if D < 4 or D % 4 or D > ADDLN_MAX_D or x1.numel() == 0:
         raise ValueError(f"gate_layer_norm takes a non-empty x1 with D a multiple of 4 in [4, {ADDLN_MAX_D}]")
     if _wants_grad(x1, x2, gate_logits, weight, bias):
-        return _GateLayerNorm.apply(x1, x2, gate_logits, weight, bias, float(eps))
-    return _gate_ln_forward(_f32c16(x1, "x1"), _f32c16(x2, "x2"), _f32c16(gate_logits, "gate_logits"), _f32c16(weight, "weight"),
-                            _f32c16(bias, "bias"), eps)[0]
+        return _RowLayerNorm.apply(_GATE_LN, (), float(eps), weight, bias, x1, x2, gate_logits)
+    a, b, g = _f32c16(x1, "x1"), _f32c16(x2, "x2"), _f32c16(gate_logits, "gate_logits")
+    return _rowln_forward(_GATE_LN.forward, (g, a, b), _f32c16(weight, "weight"), _f32c16(bias, "bias"), eps, (), a)[0]
 
 
 class _LqeStatistics(torch.autograd.Function):
@@ -1437,7 +1382,7 @@ def _decoder_layer_takes(layer, hidden_states, position_embeddings, encoder_hidd
         return False
     if not all(_affine_norm(n, D) for n in (layer.self_attn_layer_norm, layer.gateway.norm, layer.final_layer_norm)):
         return False
-    return all(p.is_cuda and p.dtype == torch.float32 for p in layer.parameters())
+    return _fp32_cuda_params(layer)
 
 
 def decoder_layer_forward(self, hidden_states, position_embeddings=None, reference_points=None, spatial_shapes=None,
@@ -1502,7 +1447,7 @@ def lqe_forward(self, scores, pred_corners):
     nb1, k = int(self.max_num_bins) + 1, int(self.top_prob_values)
     if not (_fp32_cuda(scores, pred_corners) and pred_corners.dim() == 3 and pred_corners.numel() and not torch.is_autocast_enabled()
             and pred_corners.shape[-1] == 4 * nb1 and 1 <= k <= LQE_MAX_TOPK and k <= nb1 <= LQE_MAX_BINS1
-            and all(p.is_cuda and p.dtype == torch.float32 for p in self.parameters())):
+            and _fp32_cuda_params(self)):
         decoder_calls["torch"] += 1
         return type(self).forward(self, scores, pred_corners)
     decoder_calls["kernel"] += 1
@@ -1517,12 +1462,8 @@ def bind_decoder(module, attention: bool = False):
     self-attention core on dfine.self_attention too.  The default is the arm that profiles/dfine_decoder_bench.json shows faster for
     a layer's training step (forward + backward) at (50, 300, 256): torch's scaled_dot_product_attention, 3.29 ms against 3.60 ms
     (the attention backward kernel runs on VALU FMAs); at (16, 300, 256) and below the two are within each other's spread."""
-    import types
     from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
-    for m in module.modules():
+    for m in _bind_forward(module, {M.DFineDecoderLayer: decoder_layer_forward, M.DFineLQE: lqe_forward}):
         if isinstance(m, M.DFineDecoderLayer):
-            m.forward = types.MethodType(decoder_layer_forward, m)
             m._m355_attention_kernel = bool(attention)   # a plain attribute: not a parameter, not a buffer, not in the state dict
-        elif isinstance(m, M.DFineLQE):
-            m.forward = types.MethodType(lqe_forward, m)
     return module

@@ -1,4 +1,4 @@
-"""The decoder-layer ops on the GPU (csrc/dfine_decoder.hip and the clamp instance of csrc/dfine_encoder.hip):
+"""The decoder-layer ops on the GPU (csrc/dfine_decoder.hip and the gate and clamp sources of csrc/dfine_rowln.hip):
 dfine.gate_layer_norm, add_layer_norm(clamp=...), lqe_statistics, their gradients, and transformers' DFineDecoderLayer / DFineLQE
 bound with dfine.bind_decoder.
 
@@ -148,6 +148,66 @@ def test_clamp_none_is_the_old_call_and_an_idle_clamp_changes_no_bit(cuda_device
     with torch.no_grad():
         assert torch.equal(dfine.add_layer_norm(x, y, wt, bs, 1e-5, clamp=None), old[0])
         assert torch.equal(dfine.add_layer_norm(x, y, wt, bs, 1e-5, clamp=(LO, HI)), old[0])
+
+
+# ---- the row sources of csrc/dfine_rowln.hip against each other and at the edges of D ---------------------------------------------------
+def test_saturated_gate_is_the_add_instance_bit_for_bit(cuda_device):
+    """gate logits of +200 | -200: sigmoid is exactly 1 | 0 and its derivative exactly 0, so z = 1 * x1 + 0 * x2 has the bits of
+    x1 + 0 and the gate instance must give what the add instance gives on (x1, zeros): the shared statistics, dz expression and
+    column sums are one text in two instances, contracted alike"""
+    from defectdetection_viaobjectdetection_amd import dfine
+    dev, M, D = cuda_device, 63, 256
+    x1, x2, wt, bs, gw = (_randn(s, 90 + i).to(dev) for i, s in enumerate([(M, D), (M, D), (D,), (D,), (M, D)]))
+    g = torch.cat([torch.full((M, D), 200.0), torch.full((M, D), -200.0)], dim=-1).to(dev)
+    gate_leaves = [t.clone().requires_grad_() for t in (x1, x2, g, wt, bs)]
+    gate_out = dfine.gate_layer_norm(*gate_leaves, 1e-5)
+    dx1, _, dgate, gate_dw, gate_db = _grads(gate_out, gate_leaves, gw)
+    add_leaves = [t.clone().requires_grad_() for t in (x1, torch.zeros_like(x1), wt, bs)]
+    add_out = dfine.add_layer_norm(*add_leaves, 1e-5)
+    dx, _, add_dw, add_db = _grads(add_out, add_leaves, gw)
+    assert torch.equal(gate_out, add_out)
+    assert torch.equal(dx1, dx) and torch.equal(gate_dw, add_dw) and torch.equal(gate_db, add_db)
+    assert int((dgate != 0).sum()) == 0
+
+
+# (M, D): one live lane; two blocks and lane 0 alone in the second float4 slot; the widest row, every slot of every lane
+ROWLN_EDGES = [(1, 4), (5, 260), (63, 1024)]
+ROWLN_SEED, ROWLN_P = 0xD1CE, 0.1
+
+
+@pytest.mark.parametrize("M, D", ROWLN_EDGES)
+@pytest.mark.parametrize("form", ["add", "add_dropout", "add_clamp", "gate"])
+def test_row_layer_norms_at_the_edges_of_d(cuda_device, form, M, D):
+    """every source of the row-LayerNorm kernels where D is not 64, 128 or 256: forward and every gradient"""
+    import dfine_encoder_ref as enc_ref
+    from defectdetection_viaobjectdetection_amd import dfine
+    x, y, gw = _randn((M, D), 3 * M + D), _randn((M, D), 3 * M + D + 1), _randn((M, D), 3 * M + D + 2)
+    wt, bs = 1.0 + 0.1 * _randn((D,), 95), 0.1 * _randn((D,), 96)
+    if form == "gate":
+        inputs, names = [x, y, _randn((M, 2 * D), 3 * M + D + 3), wt, bs], GATE_NAMES
+        fn, fn_ref = (lambda *t: dfine.gate_layer_norm(*t, 1e-5)), (lambda *t: ref.gate_layer_norm(*t, 1e-5))
+    else:
+        inputs, names = [x, y, wt, bs], ("out", "dx", "dy", "dweight", "dbias")
+        if form == "add":
+            fn, fn_ref = (lambda *t: dfine.add_layer_norm(*t, 1e-5)), (lambda *t: enc_ref.add_layer_norm(*t, 1e-5))
+        elif form == "add_dropout":
+            mask = dfine.dropout_keep_mask(ROWLN_SEED, dfine.SITE_FFN_OUT, (M, D), ROWLN_P, cuda_device)
+            fn = lambda *t: dfine.add_layer_norm(*t, 1e-5, dropout_p=ROWLN_P, seed=ROWLN_SEED, site=dfine.SITE_FFN_OUT)  # noqa: E731
+            fn_ref = lambda *t: enc_ref.add_layer_norm(*t, 1e-5, mask, ROWLN_P)  # noqa: E731
+        else:   # one sum far outside each bound (no gradient), one on a bound (the gradient passes)
+            x[0, D - 1], y[0, D - 1] = 1.0e5, 0.0
+            x[M - 1, 1], y[M - 1, 1] = -7.0e4, 0.0
+            x[M // 2, 2], y[M // 2, 2] = HI, 0.0
+            fn, fn_ref = (lambda *t: dfine.add_layer_norm(*t, 1e-5, clamp=(LO, HI))), (lambda *t: ref.add_clamp_layer_norm(*t, 1e-5))
+    res = _three_ways(fn, fn_ref, inputs, gw, cuda_device)
+    failures = []
+    for name, k, t, w in zip(names, *res):
+        assert k.is_cuda and k.dtype == torch.float32 and torch.isfinite(k).all(), name
+        _judge(f"{form} {M}x{D} {name}", k, t, w, failures)
+    assert not failures, failures
+    if form == "add_clamp":
+        dx, dy = res[0][1], res[0][2]
+        assert float(dx[0, D - 1]) == 0.0 and float(dy[M - 1, 1]) == 0.0 and float(dx[M // 2, 2]) != 0.0
 
 
 # ---- the LQE statistics ----------------------------------------------------------------------------------------------------------------
