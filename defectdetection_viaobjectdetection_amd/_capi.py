@@ -169,6 +169,11 @@ SIGNATURES = {
     "m355_dfine_match": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "m355_dfine_postprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "m355_dfine_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "m355_dfine_select_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P,
+                                            _P, _P, _P, _P]),
+    "m355_dfine_select_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                             _P]),
     "m355_dfine_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "m355_dfine_loss_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
                                           C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_float,

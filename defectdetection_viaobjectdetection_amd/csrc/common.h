@@ -152,6 +152,17 @@ int launch_dfine_match(const float* logits, const float* boxes, int B, int Q, in
 // xyxy box and the {n_nan, n_keep} counts, one block per image.  The caller has validated every argument; sizes may be nullptr.
 int launch_dfine_postprocess(const float* logits, const float* boxes, int B, int Q, int C, const float* sizes, float threshold,
                              float* scores, long long* labels, float* out_boxes, int* counts, hipStream_t s);
+// Encoder query selection of DFineModel.forward (dfine_select.hip): the K tokens with the greatest row max of class_logits per image
+// (the order of topk_select.h), their indices, the gathered coordinate / class / memory rows, sigmoid of the coordinate rows and the
+// inverse map (rank or -1 per token); the backward writes the three input gradients in full through that map.  The caller has
+// validated every argument; mem / target, inverse and every pointer of the backward but `inverse` may be nullptr.  scores: the
+// forward's workspace, dfine_select_workspace_bytes(B, S).
+size_t dfine_select_workspace_bytes(int B, int S);
+int launch_dfine_select_forward(const float* cls, const float* coord, const float* mem, int B, int S, int C, int D, int K, float* scores,
+                                long long* indices, float* ref, float* boxes, float* logits, float* target, int* inverse, hipStream_t s);   // two launches
+int launch_dfine_select_backward(const float* g_ref, const float* g_boxes, const float* g_logits, const float* g_target, const float* boxes,
+                                 const int* inverse, int B, int S, int C, int D, int K, float* d_cls, float* d_coord, float* d_mem,
+                                 hipStream_t s);   // one launch
 // Loss terms of one D-FINE decoder output (dfine_loss.hip): loss_vfl, loss_bbox, loss_giou and, with the local group
 // (pred_corners != nullptr), loss_fgl and loss_ddf.  The caller has validated every argument.
 struct DfineLossArgs {

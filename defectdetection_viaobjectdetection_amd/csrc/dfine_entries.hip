@@ -116,6 +116,13 @@ const char* dfine_addln_check(int64_t M, int32_t D, float p, int32_t site) {
   if (D < 4 || D % 4 != 0 || D > dfine_addln_max_d()) return "D must be a multiple of 4 in [4, 1024]";
   return dfine_dropout_check(p, site);
 }
+// the query selection (dfine_select.hip): one block per image, K rows from the sort of topk_select.h, tokens and rows indexed with int
+const char* dfine_select_check(int32_t B, int32_t S, int32_t C, int32_t K) {
+  if (B < 1 || C < 1 || S < 1 || S >= 1 << 24) return "B >= 1, C >= 1, 1 <= S < 2^24";
+  if (K < 1 || K > S || K > 2048) return "1 <= K <= min(S, 2048)";
+  if ((int64_t)B * S > kGridMax) return "B * S must be below 2^31";
+  return nullptr;
+}
 // the LQE statistics (dfine_decoder.hip): one block per row
 const char* dfine_lqe_check(int64_t M, int32_t nb1, int32_t k) {
   if (M < 1 || M > kGridMax) return "1 <= rows < 2^31";
@@ -218,6 +225,34 @@ int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int
     return invalid(__func__, "B >= 1, Q in [1, 2048], C >= 1, Q * C < 2^24");
   return launched(__func__, launch_dfine_postprocess(d_logits, d_pred_boxes, B, Q, C, d_sizes, threshold, d_scores, (long long*)d_labels,
                                                      d_boxes, d_counts, (hipStream_t)stream));
+}
+size_t m355_dfine_select_workspace_bytes(int32_t B, int32_t S) {
+  return dfine_select_check(B, S, 1, 1) ? 0 : dfine_select_workspace_bytes(B, S);
+}
+int m355_dfine_select_forward(const float* d_class_logits, const float* d_coord_logits, const float* d_memory, int32_t B, int32_t S,
+                              int32_t C, int32_t D, int32_t K, void* d_work, int64_t work_bytes, int64_t* d_indices, float* d_ref,
+                              float* d_boxes, float* d_logits, float* d_target, int32_t* d_inverse, void* stream) {
+  if (any_null({d_class_logits, d_coord_logits, d_indices, d_ref, d_boxes, d_logits})) return invalid(__func__, "null pointer");
+  if ((d_memory == nullptr) != (d_target == nullptr)) return invalid(__func__, "memory and target come together or not at all");
+  if (const char* why = dfine_select_check(B, S, C, K)) return invalid(__func__, why);
+  if (d_memory && D < 1) return invalid(__func__, "D >= 1");
+  if (workspace_short(d_work, work_bytes, dfine_select_workspace_bytes(B, S)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_select_workspace_bytes");
+  if ((uintptr_t)d_work & 3u) return invalid(__func__, "workspace 4-byte aligned");
+  return launched(__func__, launch_dfine_select_forward(d_class_logits, d_coord_logits, d_memory, B, S, C, D, K, (float*)d_work,
+                                                        (long long*)d_indices, d_ref, d_boxes, d_logits, d_target, d_inverse,
+                                                        (hipStream_t)stream));
+}
+int m355_dfine_select_backward(const float* d_grad_ref, const float* d_grad_boxes, const float* d_grad_logits, const float* d_grad_target,
+                               const float* d_boxes, const int32_t* d_inverse, int32_t B, int32_t S, int32_t C, int32_t D, int32_t K,
+                               float* d_grad_class, float* d_grad_coord, float* d_grad_memory, void* stream) {
+  if (!d_inverse) return invalid(__func__, "null pointer");
+  if (d_grad_boxes && d_grad_coord && !d_boxes) return invalid(__func__, "null pointer (boxes, which grad_boxes needs)");
+  if (const char* why = dfine_select_check(B, S, C, K)) return invalid(__func__, why);
+  if (d_grad_memory && D < 1) return invalid(__func__, "D >= 1");
+  if (!d_grad_class && !d_grad_coord && !d_grad_memory) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_select_backward(d_grad_ref, d_grad_boxes, d_grad_logits, d_grad_target, d_boxes, d_inverse, B, S, C,
+                                                         D, K, d_grad_class, d_grad_coord, d_grad_memory, (hipStream_t)stream));
 }
 size_t m355_dfine_loss_workspace_bytes(int32_t B, int32_t Q) { return dfine_loss_workspace_bytes(B, Q); }
 int m355_dfine_loss_forward(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,

@@ -34,6 +34,12 @@ GEMM, the serial chain of both directions one persistent launch forward and one 
 ``bind_decoder`` are the decoder layers every trainer trains (``DFineDecoderLayer``, ``DFineLQE``) between their torch GEMMs: the
 self-attention core above on a packed q | k | v projection, the fused deformable attention, DFineGate behind its Linear,
 LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch forward with a HIP backward (csrc/dfine_decoder.hip; the row LayerNorms of both layer kinds: csrc/dfine_rowln.hip).
+
+``select_queries`` / ``select_queries_torch`` / ``model_forward`` / ``bind_model`` are the encoder query selection every call of
+``DFineModel.forward`` makes between the hybrid encoder and the decoder (:1804-1828): row max of the class logits, top-k, the
+gathers of the coordinate logits, class logits and memory, and the sigmoid, two launches forward and one backward
+(csrc/dfine_select.hip on the block-wide selection of csrc/topk_select.h, which the post-processing shares), with a stated order
+among equal scores (NaN first, descending, an exact tie to the lowest token) where ``torch.topk`` promises none.
 """
 from __future__ import annotations
 
@@ -1466,4 +1472,243 @@ def bind_decoder(module, attention: bool = False):
     for m in _bind_forward(module, {M.DFineDecoderLayer: decoder_layer_forward, M.DFineLQE: lqe_forward}):
         if isinstance(m, M.DFineDecoderLayer):
             m._m355_attention_kernel = bool(attention)   # a plain attribute: not a parameter, not a buffer, not in the state dict
+    return module
+
+
+# ---- encoder query selection (DFineModel.forward, modeling_d_fine.py:1804-1828) ----------------------------------------------------
+# Between the hybrid encoder's heads and the decoder every call of a D-FINE model picks its num_queries tokens: row max of the class
+# logits, top-k, three gathers and a sigmoid.  csrc/dfine_select.hip does it in two launches forward (row max on all CUs; one block
+# per image for the top-k of csrc/topk_select.h and the gathers) and one backward, with a stated order among equal scores.
+SELECT_MAX_QUERIES = 2048        # the limits of m355_dfine_select_forward; anything outside them takes select_queries_torch
+SELECT_MAX_TOKENS = 1 << 24      # S stays below it
+model_calls = {"kernel": 0, "torch": 0}   # query selections by path (tests and tools read it)
+
+
+class QuerySelection(NamedTuple):
+    indices: torch.Tensor                  # (B, K) int64, in output order
+    reference_points_unact: torch.Tensor   # (B, K, 4) rows of coord_logits
+    boxes: torch.Tensor                    # (B, K, 4) their sigmoid
+    logits: torch.Tensor                   # (B, K, C) rows of class_logits
+    target: torch.Tensor | None            # (B, K, D) rows of memory, or None without one
+
+
+def _check_select_shapes(class_logits, coord_logits, memory):
+    if class_logits.dim() != 3 or tuple(coord_logits.shape) != tuple(class_logits.shape[:2]) + (4,):
+        raise ValueError("class_logits (B, S, C) and coord_logits (B, S, 4) are expected")
+    if memory is not None and (memory.dim() != 3 or tuple(memory.shape[:2]) != tuple(class_logits.shape[:2])):
+        raise ValueError("memory (B, S, D) must have the tokens of class_logits")
+
+
+def _select_kernel_takes(class_logits, coord_logits, memory, K: int) -> bool:
+    B, S, Cn = class_logits.shape
+    tensors = (class_logits, coord_logits) if memory is None else (class_logits, coord_logits, memory)
+    return (_fp32_cuda(*tensors) and not torch.is_autocast_enabled() and B >= 1 and Cn >= 1 and (memory is None or memory.shape[-1] >= 1)
+            and 1 <= K <= min(S, SELECT_MAX_QUERIES) and S < SELECT_MAX_TOKENS and B * S < 1 << 31)
+
+
+def select_queries_torch(class_logits: torch.Tensor, coord_logits: torch.Tensor, memory=None, num_queries: int = 300) -> QuerySelection:
+    """select_queries in torch ops, on whatever device and dtype the tensors have, with the kernel's order rule: a stable descending
+    sort of the row maxima, so NaN scores come first and an exact tie goes to the lowest token (torch.topk promises no order among
+    equal scores; where the scores are distinct the two agree).  What select_queries falls back to and the baseline of the tests.
+    A num_queries above S raises as torch.topk does."""
+    _check_select_shapes(class_logits, coord_logits, memory)
+    K = int(num_queries)
+    scores = class_logits.detach().max(-1).values
+    if not 0 <= K <= scores.shape[1]:
+        torch.topk(scores, K, dim=1)   # raises torch.topk's own error
+    model_calls["torch"] += 1
+    ind = torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :K]
+    rows = lambda t: t.gather(1, ind.unsqueeze(-1).expand(-1, -1, t.shape[-1]))
+    ref = rows(coord_logits)
+    return QuerySelection(ind, ref, torch.sigmoid(ref), rows(class_logits), None if memory is None else rows(memory))
+
+
+def _select_forward(cl, co, mem, K: int, keep_inverse: bool):
+    """contiguous fp32 CUDA tensors -> indices, ref, boxes, logits, target or None, inverse map or None"""
+    B, S, Cn = cl.shape
+    D = mem.shape[-1] if mem is not None else 0
+    dev = cl.device
+    work = torch.empty((B, S), dtype=torch.float32, device=dev)   # the token scores
+    ind = torch.empty((B, K), dtype=torch.int64, device=dev)
+    ref = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    boxes = torch.empty_like(ref)
+    logits = torch.empty((B, K, Cn), dtype=torch.float32, device=dev)
+    target = torch.empty((B, K, D), dtype=torch.float32, device=dev) if mem is not None else None
+    inv = torch.empty((B, S), dtype=torch.int32, device=dev) if keep_inverse else None
+    check(lib.m355_dfine_select_forward(_ptr(cl), _ptr(co), _ptr(mem), B, S, Cn, D, K, _ptr(work), work.numel() * 4, _ptr(ind), _ptr(ref),
+                                        _ptr(boxes), _ptr(logits), _ptr(target), _ptr(inv), _stream()))
+    return ind, ref, boxes, logits, target, inv
+
+
+class _SelectQueries(torch.autograd.Function):
+    """indices, ref, boxes, logits, target = select(class_logits, coord_logits, memory); saves the boxes and the inverse map."""
+
+    @staticmethod
+    def forward(ctx, class_logits, coord_logits, memory, K):
+        cl, co = class_logits.contiguous(), coord_logits.contiguous()
+        mem = memory.contiguous() if memory is not None else None
+        ind, ref, boxes, logits, target, inv = _select_forward(cl, co, mem, K, True)
+        ctx.save_for_backward(boxes, inv)
+        ctx.meta = (tuple(cl.shape), mem.shape[-1] if mem is not None else 0, K)
+        ctx.mark_non_differentiable(ind)
+        ctx.set_materialize_grads(False)   # an output nobody differentiates arrives as None, not as a tensor of zeros
+        return ind, ref, boxes, logits, target
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _g_ind, g_ref, g_boxes, g_logits, g_target):
+        boxes, inv = ctx.saved_tensors
+        (B, S, Cn), D, K = ctx.meta
+        dev = inv.device
+        need_cl, need_co, need_mem = ctx.needs_input_grad[:3]
+        g = [None if t is None else _f32c(t, "grad_output") for t in (g_ref, g_boxes, g_logits, g_target)]
+        d_cl = torch.empty((B, S, Cn), dtype=torch.float32, device=dev) if need_cl else None
+        d_co = torch.empty((B, S, 4), dtype=torch.float32, device=dev) if need_co else None
+        d_mem = torch.empty((B, S, D), dtype=torch.float32, device=dev) if need_mem else None
+        check(lib.m355_dfine_select_backward(_ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(g[3]), _ptr(boxes), _ptr(inv), B, S, Cn, max(D, 1), K,
+                                             _ptr(d_cl), _ptr(d_co), _ptr(d_mem), _stream()))
+        return d_cl, d_co, d_mem, None
+
+
+def select_queries(class_logits: torch.Tensor, coord_logits: torch.Tensor, memory=None, num_queries: int = 300) -> QuerySelection:
+    """The query selection of DFineModel.forward: class_logits (B, S, C) = enc_score_head's output, coord_logits (B, S, 4) =
+    enc_bbox_head's output + anchors, memory (B, S, D) = enc_output's output or None.  Per image the num_queries tokens with the
+    greatest score (score = max over C) -> QuerySelection(indices (B, K) int64, reference_points_unact (B, K, 4), boxes =
+    sigmoid of those, logits (B, K, C), target (B, K, D) or None); the gathered rows are copies, bit for bit.
+
+    Order: a NaN score first (torch.topk's order; a row that holds a NaN scores NaN, as torch.max gives), then descending score,
+    -0 == +0, an exact tie to the lowest token.  Bitwise reproducible, and an image's rows do not depend on its batch.  Two launches
+    forward and one backward (no memset, no atomics: the gradients of the three inputs are written in full through an inverse
+    map), no device-to-host transfer and no synchronisation; with nothing to differentiate no inverse map is kept.  indices carry no
+    gradient.  CPU or non-fp32 tensors, autocast and shapes beyond the kernel's limits (num_queries > 2048, S >= 2^24,
+    B * S >= 2^31) take select_queries_torch, the same outputs from torch ops; model_calls counts the calls by path."""
+    _check_select_shapes(class_logits, coord_logits, memory)
+    K = int(num_queries)
+    if not _select_kernel_takes(class_logits, coord_logits, memory, K):
+        return select_queries_torch(class_logits, coord_logits, memory, K)
+    model_calls["kernel"] += 1
+    if _wants_grad(class_logits, coord_logits) or (memory is not None and _wants_grad(memory)):
+        return QuerySelection(*_SelectQueries.apply(class_logits, coord_logits, memory, K))
+    cl, co = class_logits.detach().contiguous(), coord_logits.detach().contiguous()
+    mem = memory.detach().contiguous() if memory is not None else None
+    return QuerySelection(*_select_forward(cl, co, mem, K, False)[:5])
+
+
+def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None, inputs_embeds=None, labels=None, **kwargs):
+    """DFineModel.forward (modeling_d_fine.py:1666-1861, transformers 5.15.0) with its query selection (:1804-1828: row max, top-k,
+    three gathers, sigmoid) on select_queries.  The module's own sub-modules run everything else, in upstream's order: backbone,
+    projections, encoder, enc_output, the score and box heads, anchors, the denoising group and the decoder.  The decoder's
+    inputs_embeds and init_reference_points are detached as upstream; with config.learn_initial_query the queries are
+    weight_embedding and no memory rows are gathered.  This body always runs; only the selection switches between the kernels and
+    select_queries_torch (CPU or non-fp32 tensors, autocast, shapes beyond the limits), and model_calls counts it.  Every field of
+    DFineModelOutput is filled as upstream; return_dict=False gives its tuple.  Among equal scores upstream's torch.topk promises
+    no order; this one has select_queries' rule.  Bound per instance by bind_model."""
+    from transformers.modeling_outputs import BaseModelOutput
+    from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
+    return_dict = kwargs.pop("return_dict", None)
+    if return_dict is None:
+        return_dict = getattr(self.config, "return_dict", True)
+    if pixel_values is None and inputs_embeds is None:
+        raise ValueError("You have to specify either pixel_values or inputs_embeds")
+    if inputs_embeds is None:
+        batch_size, _, height, width = pixel_values.shape
+        device = pixel_values.device
+        if pixel_mask is None:
+            pixel_mask = torch.ones((batch_size, height, width), device=device)
+        features = self.backbone(pixel_values, pixel_mask)
+        proj_feats = [self.encoder_input_proj[level](source) for level, (source, mask) in enumerate(features)]
+    else:
+        device = inputs_embeds.device
+        proj_feats = inputs_embeds
+    if encoder_outputs is None:
+        encoder_outputs = self.encoder(proj_feats, **kwargs)
+    elif not isinstance(encoder_outputs, BaseModelOutput):
+        encoder_outputs = BaseModelOutput(last_hidden_state=encoder_outputs[0],
+                                          hidden_states=encoder_outputs[1] if len(encoder_outputs) > 1 else None,
+                                          attentions=encoder_outputs[2] if len(encoder_outputs) > 2 else None)
+
+    sources = [self.decoder_input_proj[level](source) for level, source in enumerate(encoder_outputs.last_hidden_state)]
+    if self.config.num_feature_levels > len(sources):   # lowest resolutions: 3x3 stride 2 convolutions on the final stage
+        for i in range(len(sources), self.config.num_feature_levels):
+            sources.append(self.decoder_input_proj[i](encoder_outputs.last_hidden_state[-1]))
+
+    source_flatten, spatial_shapes_list = [], []
+    spatial_shapes = torch.empty((len(sources), 2), device=device, dtype=torch.long)
+    for level, source in enumerate(sources):
+        height, width = source.shape[-2:]
+        spatial_shapes[level, 0] = height
+        spatial_shapes[level, 1] = width
+        spatial_shapes_list.append((height, width))
+        source_flatten.append(source.flatten(2).transpose(1, 2))
+    source_flatten = torch.cat(source_flatten, 1)
+    level_start_index = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
+
+    if self.training and self.config.num_denoising > 0 and labels is not None:
+        denoising_class, denoising_bbox_unact, attention_mask, denoising_meta_values = M.get_contrastive_denoising_training_group(
+            targets=labels, num_classes=self.config.num_labels, num_queries=self.config.num_queries,
+            class_embed=self.denoising_class_embed, num_denoising_queries=self.config.num_denoising,
+            label_noise_ratio=self.config.label_noise_ratio, box_noise_scale=self.config.box_noise_scale)
+    else:
+        denoising_class, denoising_bbox_unact, attention_mask, denoising_meta_values = None, None, None, None
+
+    batch_size, device, dtype = len(source_flatten), source_flatten.device, source_flatten.dtype
+    if self.training or self.config.anchor_image_size is None:
+        anchors, valid_mask = self.generate_anchors(tuple(spatial_shapes_list), device=device, dtype=dtype)   # hashable: lru_cache
+    else:
+        anchors, valid_mask = self.anchors.to(device, dtype), self.valid_mask.to(device, dtype)
+    memory = valid_mask.to(source_flatten.dtype) * source_flatten
+    output_memory = self.enc_output(memory)
+    enc_outputs_class = self.enc_score_head(output_memory)
+    enc_outputs_coord_logits = self.enc_bbox_head(output_memory) + anchors
+
+    # ---- the selection: upstream's topk / gather / sigmoid chain
+    learn = bool(self.config.learn_initial_query)
+    picked = select_queries(enc_outputs_class, enc_outputs_coord_logits, None if learn else output_memory.detach(),
+                            self.config.num_queries)
+    reference_points_unact, enc_topk_bboxes, enc_topk_logits = picked.reference_points_unact, picked.boxes, picked.logits
+    if denoising_bbox_unact is not None:
+        reference_points_unact = torch.concat([denoising_bbox_unact, reference_points_unact], 1)
+    target = self.weight_embedding.tile([batch_size, 1, 1]) if learn else picked.target.detach()
+    if denoising_class is not None:
+        target = torch.concat([denoising_class, target], 1)
+    init_reference_points = reference_points_unact.detach()
+
+    decoder_outputs = self.decoder(inputs_embeds=target, encoder_hidden_states=source_flatten, encoder_attention_mask=attention_mask,
+                                   reference_points=init_reference_points, spatial_shapes=spatial_shapes,
+                                   spatial_shapes_list=spatial_shapes_list, level_start_index=level_start_index, **kwargs)
+    out = M.DFineModelOutput(
+        last_hidden_state=decoder_outputs.last_hidden_state,
+        intermediate_hidden_states=decoder_outputs.intermediate_hidden_states,
+        intermediate_logits=decoder_outputs.intermediate_logits,
+        intermediate_reference_points=decoder_outputs.intermediate_reference_points,
+        intermediate_predicted_corners=decoder_outputs.intermediate_predicted_corners,
+        initial_reference_points=decoder_outputs.initial_reference_points,
+        decoder_hidden_states=decoder_outputs.hidden_states,
+        decoder_attentions=decoder_outputs.attentions,
+        cross_attentions=decoder_outputs.cross_attentions,
+        encoder_last_hidden_state=encoder_outputs.last_hidden_state,
+        encoder_hidden_states=encoder_outputs.hidden_states,
+        encoder_attentions=encoder_outputs.attentions,
+        init_reference_points=init_reference_points,
+        enc_topk_logits=enc_topk_logits,
+        enc_topk_bboxes=enc_topk_bboxes,
+        enc_outputs_class=enc_outputs_class,
+        enc_outputs_coord_logits=enc_outputs_coord_logits,
+        denoising_meta_values=denoising_meta_values,
+    )
+    return out if return_dict else out.to_tuple()
+
+
+def bind_model(module):
+    """Set model_forward on every DFineModel INSTANCE inside `module` (a DFineForObjectDetection, a DFineModel, or any module that
+    holds some); transformers' classes are never touched, parameters, buffers and the state dict stay as they are, so existing
+    checkpoints load unchanged.  Returns `module`.  Composes with bind_decoder (different classes): bind_decoder(bind_model(m)).
+    What it buys is the selection's order rule (a bound model's queries do not depend on torch.topk's tie-break) and fewer launches;
+    measured (profiles/dfine_select_bench.json, ms per call, median of 7 blocks): the selection alone at (50, 8400, C = 80, D = 256,
+    K = 300) forward 0.092 against 0.299 for upstream's torch ops (2 against 30 device activities), forward + backward 0.146 against
+    0.366; at (16, ...) and (1, ...) with C = 80 forward + backward is host-bound and the bound median is SLOWER (0.223 against
+    0.197, 0.205 against 0.181, spreads overlapping); model.model(pixel_values) at 2 x 256 x 256 does not move: eval 18.9 against
+    18.8, training 61.8 against 64.8, inside the spread."""
+    from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
+    _bind_forward(module, {M.DFineModel: model_forward})
     return module

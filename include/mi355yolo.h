@@ -709,6 +709,37 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
 int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
                            float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream);
 
+/* ---- Encoder query selection of a D-FINE model ---------------------------------------------------------------------------
+ * m355_dfine_select_forward = the block of DFineModel.forward between the encoder's heads and the decoder (transformers 5.15.0
+ * modeling_d_fine.py:1804-1828): per image the K tokens with the greatest score, score = the max over C of class_logits, and the
+ * rows of the three tensors at those tokens.  Two launches (row max on all CUs into `work`; one block per image: top-K and
+ * gathers), asynchronous on `stream`, no host round trip.  All buffers are the caller's, fp32, dense; no alignment is required
+ * (16-byte aligned class_logits / memory rows are moved 16 bytes at a time).
+ *   class_logits (B, S, C); coord_logits (B, S, 4); memory (B, S, D) or NULL (then target is NULL too and D is not read)
+ * Order of the rows, a total order on the tokens: a NaN score first (the score is NaN when its row holds one, as torch.max
+ * gives, and torch.topk treats NaN as the greatest), then descending score (-0 == +0), an exact tie to the lowest token.
+ *   indices (B, K) int64: the tokens; ref (B, K, 4), logits (B, K, C), target (B, K, D): the rows of coord_logits,
+ *   class_logits and memory at them, copied bit for bit; boxes (B, K, 4) = 1 / (1 + expf(-ref)), fp32
+ *   inverse (B, S) int32 or NULL: the rank of a selected token, -1 elsewhere: what the backward reads
+ * Every element of every output is written.
+ * m355_dfine_select_backward: ONE launch.  grad_ref, grad_boxes (B, K, 4), grad_logits (B, K, C), grad_target (B, K, D): the
+ * upstream gradients, each may be NULL (zero); grad_class (B, S, C), grad_coord (B, S, 4), grad_memory (B, S, D): each may be NULL
+ * (not needed), the others are written in full in one streaming pass: the row of a token with rank r is grad_logits[r],
+ * grad_ref[r] + grad_boxes[r] * (1 - boxes[r]) * boxes[r], grad_target[r]; any other row is zero.  boxes: the forward's (read when
+ * grad_boxes and grad_coord are given).  The tokens of an image are distinct: no memset, no atomics, nothing is summed.
+ * work: m355_dfine_select_workspace_bytes(B, S) = 4 B S bytes (0 for a shape outside the limits), 4-byte aligned.
+ * Limits, checked on the host before any HIP call (M355_ERR_INVALID): no NULL among the required pointers, memory and target
+ * together, B >= 1, C >= 1, D >= 1 where its tensor is given, 1 <= S < 2^24, B * S < 2^31, 1 <= K <= min(S, 2048), the workspace
+ * size.  Integer LDS counters only, no float atomics: bitwise reproducible, and image b of a batch gives the bits of the same
+ * image alone. */
+size_t m355_dfine_select_workspace_bytes(int32_t B, int32_t S);
+int m355_dfine_select_forward(const float* d_class_logits, const float* d_coord_logits, const float* d_memory, int32_t B, int32_t S,
+                              int32_t C, int32_t D, int32_t K, void* d_work, int64_t work_bytes, int64_t* d_indices, float* d_ref,
+                              float* d_boxes, float* d_logits, float* d_target, int32_t* d_inverse, void* stream);
+int m355_dfine_select_backward(const float* d_grad_ref, const float* d_grad_boxes, const float* d_grad_logits, const float* d_grad_target,
+                               const float* d_boxes, const int32_t* d_inverse, int32_t B, int32_t S, int32_t C, int32_t D, int32_t K,
+                               float* d_grad_class, float* d_grad_coord, float* d_grad_memory, void* stream);
+
 /* ---- Loss terms of one D-FINE decoder output ---------------------------------------------------------------------------
  * m355_dfine_loss_forward = RTDetrLoss.loss_labels_vfl + loss_boxes (transformers/loss/loss_rt_detr.py:165-254) and, with the
  * local group, DFineLoss.loss_local (loss_d_fine.py:228-301): the five UNWEIGHTED terms, fp32, upstream's expressions.
