@@ -3,7 +3,8 @@
 // from SegmentationModel.forward in training mode (call site BscanBased/yolo_seg_train.py:12).
 // All HBM-bound: one 16-byte chunk (8 channels) per lane, per-channel fp32 partial sums in registers,
 // block reduction through LDS, then a DETERMINISTIC cross-block reduction: every block stores its 2C partial sums
-// to a workspace row and a small second kernel (one block per 64 columns) adds the rows in a fixed order.  No float
+// to a workspace row and a small second kernel (one block per 64 columns) adds the rows in a fixed order (the forward
+// statistics merge (count, mean, sum of squared deviations) the same way instead: see bn_stats_kernel).  No float
 // atomics: two runs of one batch give the same bits.  (An in-kernel "last ticket adds the rows" form was measured at
 // ~100 us per launch: one block reading 256 rows is a serial tail; the separate kernel costs what the memset of the
 // atomic version did -- one more stream operation.)
@@ -69,16 +70,62 @@ __global__ __launch_bounds__(FIN_WAVES * 64) void bn_finalize_kernel(const float
   if (w == 0 && col < n2) out[col] = wsum[0][lane];
 }
 
-// partial rows of sum_px z (columns 0:C) and sum_px z^2 (C:2C)   (ws: WS_HEAD + gridDim.x * 2C floats)
+// Forward statistics.  sum z^2 / n - mean^2 from fp32 sums cancels when |mean| >> std (a flat background channel at mean 100,
+// std 0.1: the variance came out as exactly 0), so the statistics are carried as (n, mean, M2 = sum (z - mean)^2) from the first
+// pixel on, and the mean as a pivot plus an offset (an fp32 mean of 100 is only good to 6e-6, 6e-5 of that channel's std, and
+// the merges below square differences of means):
+//   thread:  sums of (z - K) and (z - K)^2 with the pivot K = the thread's OWN first pixel (a pivot shared by a channel can be an
+//            outlier far from everything else; a thread's pivot is at worst far from that thread's few other pixels),
+//            then mean = K + off with off = s / n, and M2 = q - s^2 / n;
+//   block:   pairwise merge over the pixel lanes in LDS (Chan et al.): n = na + nb, d = (Kb - Ka) + (offb - offa) (the pivots
+//            are fp16 values: their difference is exact), offa += d nb / n, M2 = M2a + M2b + d^2 na nb / n; the merged
+//            partial keeps a's pivot; every term of M2 is >= 0, nothing cancels;
+//   grid:    one (offset, M2) row, one pivot row and one count per block, merged by bn_stats_merge_kernel.
+// The batch mean itself comes from the plain sum n K + s, added along the same merges: K + off would cancel where |mean| << std
+// (pivot 45, offset -45.02), and there the plain sum is as good as it always was.
+// Every merge order is fixed by the indices: two runs of one batch give the same bits.  z is read once.
+struct Moments {
+  float n, piv, off, m2, sum;
+};
+__device__ __forceinline__ Moments merge_moments(const Moments& a, const Moments& b) {
+  if (a.n == 0.f) return b;   // an empty partial has no pivot
+  const float n = a.n + b.n, w = b.n * __builtin_amdgcn_rcpf(n);   // a weight: 1 ulp is plenty
+  const float d = (b.piv - a.piv) + (b.off - a.off);
+  return {n, a.piv, a.off + d * w, a.m2 + (b.m2 + d * d * (a.n * w)), a.sum + b.sum};
+}
+
+// behind the partial rows and the 2C totals: the forward's per-block pixel counts, then its per-block pivot and sum rows
+__device__ __host__ inline size_t ws_counts_offset(int C) { return (size_t)WS_HEAD + (size_t)BN_ROWS * 2 * C + 2 * C; }
+__device__ __host__ inline size_t ws_pivots_offset(int C) { return ws_counts_offset(C) + BN_ROWS; }
+__device__ __host__ inline size_t ws_sums_offset(int C) { return ws_pivots_offset(C) + (size_t)BN_ROWS * C; }
+
+// row blockIdx.x of the workspace: this block's mean offset (columns 0:C) and M2 (C:2C); its pivots, its sums and its pixel
+// count in their own arrays
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const half_t* z, long npix, int ld, int C, float* ws) {
-  extern __shared__ float red[];  // [BN_THREADS][16]
+  __shared__ float red[BN_THREADS][33];  // pivot[8], offset[8], M2[8], sum[8], n (33: a wave's lanes fall on different banks)
   const int cg = C / 8;                       // channel groups
   const int lanes_px = BN_THREADS / cg;       // pixel lanes per block (threads beyond lanes_px * cg idle)
   const int cgi = threadIdx.x % cg, pl = threadIdx.x / cg;
-  float s[8], q[8];
+  float s[8], q[8], K[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+  for (int j = 0; j < 8; ++j) s[j] = q[j] = K[j] = 0.f;
+  int n = 0;
   if (pl < lanes_px) {
+    auto accumulate = [&](const half8& v) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = (float)v[j] - K[j];
+        s[j] += d;
+        q[j] += d * d;
+      }
+    };
+    // the first pixel a thread meets is its pivot (that pixel's own shifted terms are exact zeros)
+    auto pivot = [&](const half8& v) __attribute__((always_inline)) {
+      if (n == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) K[j] = (float)v[j];
+      }
+    };
     // four pixels per trip: four independent 16-byte loads in flight per thread (one per trip ran at 1.4 TB/s)
     const long stride = (long)gridDim.x * lanes_px;
     const half_t* zp = z + cgi * 8;
@@ -87,35 +134,109 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const half_t* z, l
       half8 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *(const half8*)(zp + (p + u * stride) * ld);
+      pivot(v[0]);
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float f = (float)v[u][j];
-          s[j] += f;
-          q[j] += f * f;
-        }
+      for (int u = 0; u < 4; ++u) accumulate(v[u]);
+      n += 4;
     }
     for (; p < npix; p += stride) {
       const half8 v = *(const half8*)(zp + p * ld);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j];
-        s[j] += f;
-        q[j] += f * f;
-      }
+      pivot(v);
+      accumulate(v);
+      n += 1;
     }
   }
+  {
+    const float fn = (float)n, rn = n > 0 ? 1.0f / fn : 0.f;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    red[threadIdx.x * 16 + j] = s[j];
-    red[threadIdx.x * 16 + 8 + j] = q[j];
+    for (int j = 0; j < 8; ++j) {
+      const float off = s[j] * rn;
+      red[threadIdx.x][j] = K[j];
+      red[threadIdx.x][8 + j] = off;
+      red[threadIdx.x][16 + j] = fmaxf(q[j] - s[j] * off, 0.f);
+      red[threadIdx.x][24 + j] = fn * K[j] + s[j];
+    }
+    red[threadIdx.x][32] = fn;
   }
   __syncthreads();
-  store_block_partials(red, C, cg, lanes_px, ws);
+  // pairwise over the pixel lanes: lane l takes lane l + ceil(len / 2) until one is left (len is uniform: every thread
+  // reaches every barrier)
+  for (int len = lanes_px; len > 1;) {
+    const int half = (len + 1) / 2;
+    if (pl < len / 2) {
+      // both partials to registers first: eight independent merges (through the LDS pointers every merge waited for the
+      // stores of the one before: 4 us per launch at 64 lanes)
+      float* const a = red[threadIdx.x];
+      const float* const b = red[threadIdx.x + half * cg];
+      float av[33], bv[33];
+#pragma unroll
+      for (int k = 0; k < 33; ++k) {
+        av[k] = a[k];
+        bv[k] = b[k];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const Moments m = merge_moments({av[32], av[j], av[8 + j], av[16 + j], av[24 + j]}, {bv[32], bv[j], bv[8 + j], bv[16 + j], bv[24 + j]});
+        a[j] = m.piv;
+        a[8 + j] = m.off;
+        a[16 + j] = m.m2;
+        a[24 + j] = m.sum;
+      }
+      a[32] = av[32] + bv[32];
+    }
+    __syncthreads();
+    len = half;
+  }
+  // lane 0 of every channel group (threads 0 .. cg-1) holds the block's result; all threads store it, coalesced
+  float* const dst[4] = {ws + ws_pivots_offset(C) + (long)blockIdx.x * C, ws + WS_HEAD + (long)blockIdx.x * 2 * C,
+                         ws + WS_HEAD + (long)blockIdx.x * 2 * C + C, ws + ws_sums_offset(C) + (long)blockIdx.x * C};
+#pragma unroll
+  for (int kind = 0; kind < 4; ++kind)
+    for (int c = threadIdx.x; c < C; c += BN_THREADS) dst[kind][c] = red[c / 8][kind * 8 + c % 8];
+  if (threadIdx.x == 0) ws[ws_counts_offset(C) + blockIdx.x] = red[0][32];
 }
 
-// mean / invstd from the sums (biased variance, like torch batch_norm in training mode), optional
+// out[0:C] = mean, out[C:2C] = M2 of the whole batch from the rows of bn_stats_kernel.  A merge is a chain of dependent
+// operations where bn_finalize_kernel has one add, so the rows are spread wider: a block takes 16 channels, each of its 64
+// row groups loads rows g, g + 64, ... (at most 8, all in flight at once) and merges them pairwise in registers, then the 64
+// groups merge pairwise through LDS.  (16 waves walking 32 rows each in order took 15.6 us per launch, 9 us more than the
+// finalize kernel it replaced.)
+constexpr int MERGE_COLS = 16, MERGE_GROUPS = 64, MERGE_ROWS = 8;
+static_assert(BN_ROWS <= MERGE_GROUPS * MERGE_ROWS, "every partial row needs a slot");
+__global__ __launch_bounds__(MERGE_COLS * MERGE_GROUPS) void bn_stats_merge_kernel(const float* ws, int C, int rows, float* out) {
+  __shared__ Moments wm[MERGE_GROUPS][MERGE_COLS];
+  const float* const part = ws + WS_HEAD;
+  const float* const cnt = ws + ws_counts_offset(C);
+  const float* const piv = ws + ws_pivots_offset(C);
+  const float* const sum = ws + ws_sums_offset(C);
+  const int lc = threadIdx.x % MERGE_COLS, g = threadIdx.x / MERGE_COLS;
+  const int col = blockIdx.x * MERGE_COLS + lc;
+  const int n2 = 2 * C;
+  Moments v[MERGE_ROWS];
+#pragma unroll
+  for (int u = 0; u < MERGE_ROWS; ++u) {
+    const long r = g + MERGE_GROUPS * u;
+    v[u] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (r < rows && col < C) v[u] = {cnt[r], piv[r * C + col], part[r * n2 + col], part[r * n2 + C + col], sum[r * C + col]};
+  }
+#pragma unroll
+  for (int h = 1; h < MERGE_ROWS; h *= 2)
+#pragma unroll
+    for (int u = 0; u < MERGE_ROWS; u += 2 * h) v[u] = merge_moments(v[u], v[u + h]);
+  wm[g][lc] = v[0];
+  __syncthreads();
+#pragma unroll
+  for (int h = MERGE_GROUPS / 2; h >= 1; h >>= 1) {
+    if (g < h) wm[g][lc] = merge_moments(wm[g][lc], wm[g + h][lc]);
+    __syncthreads();
+  }
+  if (g == 0 && col < C) {
+    out[col] = wm[0][lc].sum / wm[0][lc].n;
+    out[C + col] = wm[0][lc].m2;
+  }
+}
+
+// mean / invstd from the batch moments (biased variance, like torch batch_norm in training mode), optional
 // running-stat update with momentum (unbiased variance), then y = silu(gamma * (z - mean) * invstd + beta).
 // A thread owns one 8-channel group for its whole life (scale / shift live in registers) and walks pixels.
 __global__ __launch_bounds__(BN_THREADS) void bn_silu_apply_kernel(const half_t* z, long npix, int ldz, int C,
@@ -133,8 +254,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_silu_apply_kernel(const half_t*
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = cgi * 8 + j;
-    const float m = sums[c] * inv_n;
-    const float var = fmaxf(sums[C + c] * inv_n - m * m, 0.f);
+    const float m = sums[c];
+    const float var = fmaxf(sums[C + c] * inv_n, 0.f);
     const float is = rsqrtf(var + eps);
     sc[j] = gamma[c] * is;
     sh[j] = beta[c] - m * sc[j];
@@ -401,9 +522,10 @@ int grid_px(long npix, int lanes_px) {
 
 }  // namespace
 
-size_t bn_workspace_floats(int C) { return (size_t)WS_HEAD + (size_t)BN_ROWS * 2 * C + 2 * C; }
+size_t bn_workspace_floats(int C) { return ws_sums_offset(C) + (size_t)BN_ROWS * C; }
 
-// ws: bn_workspace_floats(C) floats (per-block partial rows, then the 2C batch sums at ws[WS_HEAD + BN_ROWS * 2C ...])
+// ws: bn_workspace_floats(C) floats: per-block partial rows, then the 2C batch totals (forward: mean | M2) at
+// ws[WS_HEAD + BN_ROWS * 2C ...], then the forward's per-block pixel counts, pivot rows and sum rows
 int launch_bn_silu_train_fwd(const half_t* z, long npix, int ldz, int C, const float* gamma, const float* beta,
                              float eps, half_t* y, int ldy, const half_t* res, int ldr, float* sums, float* mean_out,
                              float* invstd_out, int act, float* run_mean, float* run_var, float momentum, hipStream_t s) {
@@ -412,8 +534,8 @@ int launch_bn_silu_train_fwd(const half_t* z, long npix, int ldz, int C, const f
   float* const ws = sums;
   float* const tot = ws + WS_HEAD + (size_t)BN_ROWS * 2 * C;
   const int gr = grid_red(npix * BN_THREADS / lanes_px / 4);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(gr), dim3(BN_THREADS), BN_THREADS * 16 * sizeof(float), s, z, npix, ldz, C, ws);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((2 * C + 63) / 64), dim3(FIN_WAVES * 64), 0, s, ws, 2 * C, gr, tot);
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(gr), dim3(BN_THREADS), 0, s, z, npix, ldz, C, ws);
+  hipLaunchKernelGGL(bn_stats_merge_kernel, dim3((C + MERGE_COLS - 1) / MERGE_COLS), dim3(MERGE_COLS * MERGE_GROUPS), 0, s, ws, C, gr, tot);
   hipLaunchKernelGGL(bn_silu_apply_kernel, dim3(grid_px(npix, lanes_px)), dim3(BN_THREADS), 0, s, z, npix, ldz, C, tot,
                      gamma, beta, eps, y, ldy, res, ldr, mean_out, invstd_out, act, run_mean, run_var, momentum);
   return (int)hipGetLastError();

@@ -249,8 +249,10 @@ int m355_conv2d_wgrad(const void* d_x_f16_nhwc, const void* d_dy_f16_nhwc, int B
                       int k, int stride, float* d_dw_krsc, void* stream);
 /* Train-mode BatchNorm2d (batch statistics, biased variance, eps) + optional SiLU on fp16 NHWC (B,H,W,C)
  * (SURVEY A13): y = act(gamma * (z - mean) * invstd + beta).  gamma/beta/mean/invstd/ws are DEVICE fp32 arrays;
- * d_ws is a workspace of m355_bn_workspace_floats(C) floats (per-block partial sums; a second small kernel adds them in
- * block order: no float atomics, bitwise reproducible); d_mean/d_invstd receive the saved statistics. */
+ * d_ws is a workspace of m355_bn_workspace_floats(C) floats (per-block partial rows; a second small kernel combines them in
+ * block order: no float atomics, bitwise reproducible); d_mean/d_invstd receive the saved statistics.  The forward carries
+ * its statistics as (count, mean, sum of squared deviations) per thread, block and batch and merges those, so the variance
+ * does not cancel for channels with |mean| >> std; the backward's rows are plain sums.  The workspace need not be zeroed. */
 size_t m355_bn_workspace_floats(int C);
 int m355_bn_silu_train_fwd(const void* d_z, int B, int H, int W, int C, const float* d_gamma, const float* d_beta,
                            float eps, int act, void* d_y, float* d_mean, float* d_invstd, float* d_ws, void* stream);
