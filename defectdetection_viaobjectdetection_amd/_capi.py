@@ -205,6 +205,17 @@ SIGNATURES = {
                                          _P, _P]),
     "m355_dfine_gru_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,
                                           _P, _P]),
+    "m355_dfine_decode_guarded": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, C.c_int32, _P]),
+    "m355_dfine_decode_guarded_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, C.c_int32, _P]),
+    "m355_dfine_temporal_fuse_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "m355_dfine_temporal_fuse_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "m355_dfine_guard_logits_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P]),
+    "m355_dfine_guard_logits_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
+    "m355_dfine_noobject_loss_forward": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "m355_dfine_noobject_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "m355_dfine_consistency_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "m355_dfine_consistency_loss_forward": (C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
+    "m355_dfine_consistency_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P]),
     "m355_repack_launch": (C.c_int, [_P, _P, C.c_int32, _P]),
     "m355_sppf_pool_bwd_launch": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

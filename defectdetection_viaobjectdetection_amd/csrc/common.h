@@ -140,7 +140,23 @@ struct MsdaLevels { int L; int lh[8], lw[8], lstart[8], pend[8]; };   // per lev
 int launch_msda(const float* value, const float* loc, const float* attn, float* out, int B, int S, int H, int Q, int P,
                 const MsdaLevels& lv, int discrete, hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f);
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
-                        float reg_scale, int clamp01, hipStream_t s);
+                        float reg_scale, int clamp01, hipStream_t s, bool guard = false);   // guard: the trainers' nan_to_num chain
+// The temporal head of the D-FINE trainers (dfine_temporal.hip): frame fusion, guarded class logits, the no-object cross-entropy of
+// every frame and the frame-to-frame consistency loss, each with its backward.  The caller has validated every argument.
+int dfine_tfuse_max_t();
+int dfine_noobject_max_q();
+int launch_dfine_tfuse_forward(const float* fused, const float* scores, const float* ctx, int T, int Q, int D, float* out, float* stats,
+                               hipStream_t s);   // ctx and stats (2, Q) may be nullptr
+int launch_dfine_tfuse_backward(const float* g, const float* fused, const float* scores, const float* stats, int T, int Q, int D,
+                                float* d_fused, float* d_scores, hipStream_t s);   // either may be nullptr; fused is read for d_scores
+int launch_dfine_guard_logits(const float* cls, const float* an, long rows, int C1, float bound, float* out, hipStream_t s);
+int launch_dfine_guard_logits_backward(const float* g, const float* cls, const float* an, long rows, int C1, float bound, float* d_cls,
+                                       float* d_an, hipStream_t s);
+int launch_dfine_noobject_forward(const float* x, int T, int Q, int C, int cls, float* out, hipStream_t s);
+int launch_dfine_noobject_backward(const float* g, const float* x, int T, int Q, int C, int cls, float* dx, hipStream_t s);
+size_t dfine_consistency_workspace_bytes(int T, long N);
+int launch_dfine_consistency_forward(const float* a, int T, long N, float* work, float* out, hipStream_t s);   // two launches; T >= 2
+int launch_dfine_consistency_backward(const float* g, const float* a, int T, long N, float* da, hipStream_t s);
 // Hungarian matcher of the D-FINE loss (dfine_match.hip): cost matrix + assignment, one block per image.  The caller has
 // validated every argument; `work` holds dfine_match_workspace_bytes(B, Q, nmax) bytes (0: the matrices fit in LDS).
 size_t dfine_match_workspace_bytes(int B, int Q, int nmax);
@@ -239,7 +255,7 @@ int launch_msda_backward(const float* grad_out, const float* value, const float*
                          void* work, hipStream_t s, const float* ref = nullptr, float offset_scale = 0.f, float* grad_ref = nullptr);
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
-                                 hipStream_t s);
+                                 hipStream_t s, bool guard = false);
 // The recurrence of a one-layer GRU with hidden size 256 (dfine_gru.hip): every chain (sequence x direction) on 8 persistent
 // workgroups, one launch each way.  dfine_gru_check: nullptr = the shape is taken, else why not.  work: the exchange ring first
 // (zeroed on the stream by the launchers), then the saved gates when `keep` / in the backward; status: one sticky int32.

@@ -68,6 +68,11 @@ __device__ __forceinline__ int wave_sum_int(int x) {
   return x;
 }
 
+// ---- torch.nan_to_num(v, nan, posinf, neginf): a finite v passes unchanged
+__device__ __forceinline__ float nan_to_num(float v, float nan, float posinf, float neginf) {
+  return v != v ? nan : (v == __builtin_inff() ? posinf : (v == -__builtin_inff() ? neginf : v));
+}
+
 // ---- dropout keep-mask: a pure function of (seed, site, flat element index), nothing stored (dfine_encoder.hip, dfine_rowln.hip)
 // Philox4x32-10 (Salmon et al., SC'11; Random123's constants and round): counter c[0..3], key (k0, k1), result in c.
 __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {

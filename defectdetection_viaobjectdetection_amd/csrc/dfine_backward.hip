@@ -14,6 +14,7 @@
 //           the wave each walk their own hits), then writes its rows once.  Every element of
 //           grad_value is written, so no memset is needed, and the sum per pixel does not depend on the ownership split.
 #include "common.h"
+#include "device_prims.h"
 
 namespace m355 {
 namespace {
@@ -243,33 +244,40 @@ __global__ __launch_bounds__(256) void msda_bwd_value_kernel(const MsdaBwdArgs a
 
 // One thread per box: recompute the four softmax expectations, push grad_boxes through (clamp,) centre format and
 // distance2bbox, then through the expectation: d d / d z_k = p_k (project_k - d).
+// GUARD: the backward of dfine_decode_kernel<true>, as torch differentiates the chain: nan_to_num passes the gradient where its
+// input is finite, so a replaced box coordinate, a replaced distance and a replaced logit each receive 0.
+template <bool GUARD>
 __global__ void dfine_decode_bwd_kernel(const float* gboxes, const float* dist, const float* project, const float* ref,
                                         float* gdist, float* gref, long n, int nbins1, float reg_scale, int clamp01) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float d[4], mx[4], sum[4];
+  auto logit = [](float z) { return GUARD ? nan_to_num(z, 0.f, 1.f, 0.f) : z; };
+  float d[4], draw[4], mx[4], sum[4];   // draw: the expectation itself, d: what distance2bbox read
   for (int s = 0; s < 4; ++s) {
     const float* z = dist + (i * 4 + s) * nbins1;
-    float m = z[0];
-    for (int k = 1; k < nbins1; ++k) m = fmaxf(m, z[k]);
+    float m = logit(z[0]);
+    for (int k = 1; k < nbins1; ++k) m = fmaxf(m, logit(z[k]));
     float sm = 0.f, dot = 0.f;
     for (int k = 0; k < nbins1; ++k) {
-      const float e = expf(z[k] - m);
+      const float e = expf(logit(z[k]) - m);
       sm += e;
       dot += e * project[k];
     }
-    d[s] = dot / sm; mx[s] = m; sum[s] = sm;
+    draw[s] = dot / sm; mx[s] = m; sum[s] = sm;
+    d[s] = GUARD ? nan_to_num(draw[s], 0.f, 1.f, 0.f) : draw[s];
   }
   const float rs = fabsf(reg_scale);
   const float cx = ref[i * 4], cy = ref[i * 4 + 1], w = ref[i * 4 + 2], hh = ref[i * 4 + 3];
   float go[4];
   for (int k = 0; k < 4; ++k) go[k] = gboxes[i * 4 + k];
-  if (clamp01) {
+  if (clamp01 || GUARD) {
     const float x0 = cx - (0.5f * rs + d[0]) * (w / rs), y0 = cy - (0.5f * rs + d[1]) * (hh / rs);
     const float x1 = cx + (0.5f * rs + d[2]) * (w / rs), y1 = cy + (0.5f * rs + d[3]) * (hh / rs);
     const float o[4] = {(x0 + x1) / 2.f, (y0 + y1) / 2.f, x1 - x0, y1 - y0};
-    for (int k = 0; k < 4; ++k)
-      if (!(o[k] >= 0.f && o[k] <= 1.f)) go[k] = 0.f;   // torch.clamp: the gradient passes where min <= x <= max
+    for (int k = 0; k < 4; ++k) {
+      if (clamp01 && !(o[k] >= 0.f && o[k] <= 1.f)) go[k] = 0.f;   // torch.clamp: the gradient passes where min <= x <= max
+      if (GUARD && !__builtin_isfinite(o[k])) go[k] = 0.f;         // a replaced coordinate (with clamp01: taken above already)
+    }
   }
   // (x0 + x1) / 2, x1 - x0
   const float gx0 = go[0] * 0.5f - go[2], gx1 = go[0] * 0.5f + go[2];
@@ -285,7 +293,11 @@ __global__ void dfine_decode_bwd_kernel(const float* gboxes, const float* dist, 
     for (int s = 0; s < 4; ++s) {
       const float* z = dist + (i * 4 + s) * nbins1;
       float* gz = gdist + (i * 4 + s) * nbins1;
-      for (int k = 0; k < nbins1; ++k) gz[k] = expf(z[k] - mx[s]) / sum[s] * (project[k] - d[s]) * gd[s];
+      const bool replaced = GUARD && !__builtin_isfinite(draw[s]);   // a replaced distance passes nothing on
+      for (int k = 0; k < nbins1; ++k) {
+        const float v = expf(logit(z[k]) - mx[s]) / sum[s] * (project[k] - draw[s]) * gd[s];
+        gz[k] = (replaced || (GUARD && !__builtin_isfinite(z[k]))) ? 0.f : v;
+      }
     }
 }
 
@@ -338,10 +350,15 @@ int launch_msda_backward(const float* grad_out, const float* value, const float*
 
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
-                                 hipStream_t s) {
+                                 hipStream_t s, bool guard) {
   if (n == 0 || (!grad_dist && !grad_ref)) return 0;
-  hipLaunchKernelGGL(dfine_decode_bwd_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, grad_boxes, dist, project,
-                     ref, grad_dist, grad_ref, n, nbins1, reg_scale, clamp01);
+  const dim3 grid((unsigned)((n + 127) / 128));
+  if (guard)
+    hipLaunchKernelGGL(dfine_decode_bwd_kernel<true>, grid, dim3(128), 0, s, grad_boxes, dist, project, ref, grad_dist, grad_ref, n,
+                       nbins1, reg_scale, clamp01);
+  else
+    hipLaunchKernelGGL(dfine_decode_bwd_kernel<false>, grid, dim3(128), 0, s, grad_boxes, dist, project, ref, grad_dist, grad_ref, n,
+                       nbins1, reg_scale, clamp01);
   return (int)hipGetLastError();
 }
 

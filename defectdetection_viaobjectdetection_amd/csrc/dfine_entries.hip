@@ -129,6 +129,33 @@ const char* dfine_lqe_check(int64_t M, int32_t nb1, int32_t k) {
   if (k < 1 || k > 8 || nb1 < k || nb1 > 64) return "top_k in [1, 8] and top_k <= bins + 1 <= 64";
   return nullptr;
 }
+// the box decode, plain and guarded, forward and backward: (n + 127) / 128 blocks
+const char* dfine_decode_check(int64_t n, int32_t nb1, float reg_scale) {
+  if (n < 0 || nb1 < 2 || reg_scale == 0.f) return "n < 0, fewer than 2 bins or reg_scale == 0";
+  if (n > 128 * kGridMax) return "n is too large for one launch";
+  return nullptr;
+}
+// the temporal head (dfine_temporal.hip).  temporal_fuse: a block per query column, its T partial sums in LDS
+const char* dfine_tfuse_check(int32_t T, int32_t Q, int32_t D) {
+  if (T < 1 || T > dfine_tfuse_max_t() || D < 1 || D > 1024) return "T and D must be in [1, 1024]";
+  if (Q < 1 || Q > 1 << 20) return "1 <= Q <= 2^20";
+  return nullptr;
+}
+const char* dfine_guard_logits_check(int64_t rows, int32_t C1, bool anomaly, float bound) {
+  if (rows < 1 || C1 < 1 || rows > ((int64_t)1 << 40) / C1) return "rows >= 1, C1 >= 1, rows * C1 <= 2^40";
+  if (anomaly && C1 < 2) return "anomaly scores need C1 >= 2";
+  if (!(bound >= 0.f)) return "bound must be >= 0";
+  return nullptr;
+}
+const char* dfine_noobject_check(int32_t T, int32_t Q, int32_t C1, int32_t cls) {
+  if (T < 1 || Q < 1 || Q > dfine_noobject_max_q() || C1 < 1 || C1 > 1024) return "T >= 1, Q in [1, 2048], C1 in [1, 1024]";
+  if (cls < 0 || cls >= C1) return "0 <= class_index < C1";
+  return nullptr;
+}
+const char* dfine_consistency_check(int32_t T, int64_t N) {
+  if (T < 2 || N < 1 || N > (int64_t)1 << 27 || (int64_t)T * N > kGridMax) return "T >= 2, 1 <= N <= 2^27, T * N < 2^31";
+  return nullptr;
+}
 
 }  // namespace
 
@@ -179,18 +206,31 @@ int m355_msda_module_backward(const float* d_grad_out, const float* d_value, int
 int m355_dfine_decode(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
                       int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream) {
   if (any_null({d_dist, d_project, d_ref, d_boxes})) return invalid(__func__, "null pointer");
-  if (n < 0 || num_bins_plus1 < 2 || reg_scale == 0.f) return invalid(__func__, "n < 0, fewer than 2 bins or reg_scale == 0");
-  if (n > 128 * kGridMax) return invalid(__func__, "n is too large for one launch");   // (n + 127) / 128 blocks
+  if (const char* why = dfine_decode_check(n, num_bins_plus1, reg_scale)) return invalid(__func__, why);
   return launched(__func__, launch_dfine_decode(d_dist, d_project, d_ref, d_boxes, (long)n, num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream));
 }
 int m355_dfine_decode_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
                                float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
                                int32_t clamp01, void* stream) {
   if (any_null({d_grad_boxes, d_dist, d_project, d_ref})) return invalid(__func__, "null pointer");
-  if (n < 0 || num_bins_plus1 < 2 || reg_scale == 0.f) return invalid(__func__, "n < 0, fewer than 2 bins or reg_scale == 0");
-  if (n > 128 * kGridMax) return invalid(__func__, "n is too large for one launch");   // (n + 127) / 128 blocks
+  if (const char* why = dfine_decode_check(n, num_bins_plus1, reg_scale)) return invalid(__func__, why);
   return launched(__func__, launch_dfine_decode_backward(d_grad_boxes, d_dist, d_project, d_ref, d_grad_dist, d_grad_ref, (long)n,
                                                          num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream));
+}
+int m355_dfine_decode_guarded(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
+                              int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream) {
+  if (any_null({d_dist, d_project, d_ref, d_boxes})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_decode_check(n, num_bins_plus1, reg_scale)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_decode(d_dist, d_project, d_ref, d_boxes, (long)n, num_bins_plus1, reg_scale, clamp01,
+                                                (hipStream_t)stream, true));
+}
+int m355_dfine_decode_guarded_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
+                                       float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
+                                       int32_t clamp01, void* stream) {
+  if (any_null({d_grad_boxes, d_dist, d_project, d_ref})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_decode_check(n, num_bins_plus1, reg_scale)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_decode_backward(d_grad_boxes, d_dist, d_project, d_ref, d_grad_dist, d_grad_ref, (long)n,
+                                                         num_bins_plus1, reg_scale, clamp01, (hipStream_t)stream, true));
 }
 size_t m355_dfine_match_workspace_bytes(int32_t B, int32_t Q, int32_t max_targets) { return dfine_match_workspace_bytes(B, Q, max_targets); }
 int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C,
@@ -431,4 +471,65 @@ int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, co
     return invalid(__func__, kAlign16);
   return launched(__func__, launch_dfine_gru_backward(d_grad_out, d_grad_h_n, d_w_hh, d_h0, d_out, B, (int)S, D, d_grad_gi, d_grad_an,
                                                       d_grad_h0, d_work, d_status, (hipStream_t)stream));
+}
+// the temporal head (dfine_temporal.hip)
+int m355_dfine_temporal_fuse_forward(const float* d_fused, const float* d_scores, const float* d_context, int32_t T, int32_t Q,
+                                     int32_t D, float* d_out, float* d_stats, void* stream) {
+  if (any_null({d_fused, d_scores, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_tfuse_check(T, Q, D)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_tfuse_forward(d_fused, d_scores, d_context, T, Q, D, d_out, d_stats, (hipStream_t)stream));
+}
+int m355_dfine_temporal_fuse_backward(const float* d_grad_out, const float* d_fused, const float* d_scores, const float* d_stats,
+                                      int32_t T, int32_t Q, int32_t D, float* d_grad_fused, float* d_grad_scores, void* stream) {
+  if (any_null({d_grad_out, d_scores, d_stats})) return invalid(__func__, "null pointer");
+  if (d_grad_scores && !d_fused) return invalid(__func__, "null pointer (fused, which grad_scores needs)");
+  if (const char* why = dfine_tfuse_check(T, Q, D)) return invalid(__func__, why);
+  if (!d_grad_fused && !d_grad_scores) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_tfuse_backward(d_grad_out, d_fused, d_scores, d_stats, T, Q, D, d_grad_fused, d_grad_scores,
+                                                        (hipStream_t)stream));
+}
+int m355_dfine_guard_logits_forward(const float* d_cls, const float* d_anomaly, int64_t rows, int32_t C1, float bound, float* d_out,
+                                    void* stream) {
+  if (any_null({d_cls, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_guard_logits_check(rows, C1, d_anomaly != nullptr, bound)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_guard_logits(d_cls, d_anomaly, (long)rows, C1, bound, d_out, (hipStream_t)stream));
+}
+int m355_dfine_guard_logits_backward(const float* d_grad_out, const float* d_cls, const float* d_anomaly, int64_t rows, int32_t C1,
+                                     float bound, float* d_grad_cls, float* d_grad_anomaly, void* stream) {
+  if (any_null({d_grad_out, d_cls})) return invalid(__func__, "null pointer");
+  if (d_grad_anomaly && !d_anomaly) return invalid(__func__, "grad_anomaly without anomaly");
+  if (const char* why = dfine_guard_logits_check(rows, C1, d_anomaly != nullptr, bound)) return invalid(__func__, why);
+  if (!d_grad_cls && !d_grad_anomaly) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_guard_logits_backward(d_grad_out, d_cls, d_anomaly, (long)rows, C1, bound, d_grad_cls,
+                                                               d_grad_anomaly, (hipStream_t)stream));
+}
+int m355_dfine_noobject_loss_forward(const float* d_logits, int32_t T, int32_t Q, int32_t C1, int32_t class_index, float* d_out,
+                                     void* stream) {
+  if (any_null({d_logits, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_noobject_check(T, Q, C1, class_index)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_noobject_forward(d_logits, T, Q, C1, class_index, d_out, (hipStream_t)stream));
+}
+int m355_dfine_noobject_loss_backward(const float* d_grad_out, const float* d_logits, int32_t T, int32_t Q, int32_t C1,
+                                      int32_t class_index, float* d_grad_logits, void* stream) {
+  if (any_null({d_grad_out, d_logits, d_grad_logits})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_noobject_check(T, Q, C1, class_index)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_noobject_backward(d_grad_out, d_logits, T, Q, C1, class_index, d_grad_logits, (hipStream_t)stream));
+}
+size_t m355_dfine_consistency_workspace_bytes(int32_t T, int64_t N) {
+  return dfine_consistency_check(T, N) ? 0 : dfine_consistency_workspace_bytes(T, (long)N);
+}
+int m355_dfine_consistency_loss_forward(const float* d_a, int32_t T, int64_t N, void* d_work, int64_t work_bytes, float* d_out,
+                                        void* stream) {
+  if (any_null({d_a, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_consistency_check(T, N)) return invalid(__func__, why);
+  if (workspace_short(d_work, work_bytes, dfine_consistency_workspace_bytes(T, (long)N)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_consistency_workspace_bytes");
+  if ((uintptr_t)d_work & 3u) return invalid(__func__, "workspace 4-byte aligned");
+  return launched(__func__, launch_dfine_consistency_forward(d_a, T, (long)N, (float*)d_work, d_out, (hipStream_t)stream));
+}
+int m355_dfine_consistency_loss_backward(const float* d_grad_out, const float* d_a, int32_t T, int64_t N, float* d_grad_a,
+                                         void* stream) {
+  if (any_null({d_grad_out, d_a, d_grad_a})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_consistency_check(T, N)) return invalid(__func__, why);
+  return launched(__func__, launch_dfine_consistency_backward(d_grad_out, d_a, T, (long)N, d_grad_a, (hipStream_t)stream));
 }

@@ -7,6 +7,7 @@
 // per point, 6 KB per (b, q, h); bound by L2 / Infinity-Cache gather bandwidth, no MFMA.  Layout as the reference
 // passes it: value (B, S, heads, 32) fp32 -> a corner is one coalesced 128-byte read by 32 lanes.
 #include "common.h"
+#include "device_prims.h"
 
 namespace m355 {
 namespace {
@@ -162,22 +163,27 @@ __global__ __launch_bounds__(256) void msda_wave_kernel(const MsdaArgs a) {
 
 // One thread per box: softmax over the bins of each of the four sides, dot with the weighting function W(n),
 // distance2bbox against the (cx, cy, w, h) reference point, corners -> centre format, optional clamp to [0, 1].
+// GUARD: the trainers' nan_to_num around every stage (logits and distances: nan 0, +inf 1, -inf 0; boxes: nan 0.5, +inf 1,
+// -inf 0).  Where no guard fires its arithmetic is that of the plain instance, operation for operation.
+template <bool GUARD>
 __global__ void dfine_decode_kernel(const float* dist, const float* project, const float* ref, float* boxes, long n,
                                     int nbins1, float reg_scale, int clamp01) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  auto logit = [](float z) { return GUARD ? nan_to_num(z, 0.f, 1.f, 0.f) : z; };
   float d[4];
   for (int s = 0; s < 4; ++s) {
     const float* z = dist + (i * 4 + s) * nbins1;
-    float m = z[0];
-    for (int k = 1; k < nbins1; ++k) m = fmaxf(m, z[k]);
+    float m = logit(z[0]);
+    for (int k = 1; k < nbins1; ++k) m = fmaxf(m, logit(z[k]));
     float sum = 0.f, dot = 0.f;
     for (int k = 0; k < nbins1; ++k) {
-      const float e = expf(z[k] - m);
+      const float e = expf(logit(z[k]) - m);
       sum += e;
       dot += e * project[k];
     }
     d[s] = dot / sum;
+    if (GUARD) d[s] = nan_to_num(d[s], 0.f, 1.f, 0.f);
   }
   const float rs = fabsf(reg_scale);
   const float cx = ref[i * 4], cy = ref[i * 4 + 1], w = ref[i * 4 + 2], hh = ref[i * 4 + 3];
@@ -188,6 +194,7 @@ __global__ void dfine_decode_kernel(const float* dist, const float* project, con
     float v = o[k];
     // torch.clamp keeps NaN (the reference feeds pre-sigmoid reference points, inf - inf happens); fminf / fmaxf would not
     if (clamp01 && v == v) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+    if (GUARD) v = nan_to_num(v, 0.5f, 1.f, 0.f);
     boxes[i * 4 + k] = v;
   }
 }
@@ -209,10 +216,11 @@ int launch_msda(const float* value, const float* loc, const float* attn, float* 
 }
 
 int launch_dfine_decode(const float* dist, const float* project, const float* ref, float* boxes, long n, int nbins1,
-                        float reg_scale, int clamp01, hipStream_t s) {
+                        float reg_scale, int clamp01, hipStream_t s, bool guard) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(dfine_decode_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, dist, project, ref, boxes, n,
-                     nbins1, reg_scale, clamp01);
+  const dim3 grid((unsigned)((n + 127) / 128));
+  if (guard) hipLaunchKernelGGL(dfine_decode_kernel<true>, grid, dim3(128), 0, s, dist, project, ref, boxes, n, nbins1, reg_scale, clamp01);
+  else hipLaunchKernelGGL(dfine_decode_kernel<false>, grid, dim3(128), 0, s, dist, project, ref, boxes, n, nbins1, reg_scale, clamp01);
   return (int)hipGetLastError();
 }
 

@@ -31,13 +31,6 @@ constexpr int GATHER_ROWS = 8;   // rows per wave in flight in the gather
 __device__ __forceinline__ float nanmax(float a, float b) { return a != a ? a : ((b != b || b > a) ? b : a); }
 __device__ __forceinline__ float nanmax(float a, float4v v) { return nanmax(nanmax(nanmax(nanmax(a, v[0]), v[1]), v[2]), v[3]); }
 
-// lanes that share a row: the power of two >= units, 64 at the most
-int lanes_per_row(int units) {
-  int L = 1;
-  while (L < units && L < 64) L <<= 1;
-  return L;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // T = float4v: 16-byte loads (cls 16-byte aligned, C % 4 == 0), T = float: 4-byte loads.  units = loads per row, L = lanes per row.
 template <class T>

@@ -23,6 +23,15 @@ inline int num_cus() {
   return cus;
 }
 
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // nullptr counts as aligned
+
+// lanes of a wave that share a row of `units` loads: the power of two >= units, 64 at the most
+inline int lanes_per_row(int units) {
+  int L = 1;
+  while (L < units && L < 64) L <<= 1;
+  return L;
+}
+
 // Device buffer of a probe instance's stamps and its way to a file (the M355_*_STAMPS switches).
 struct StampSink {
   unsigned long long* d = nullptr;

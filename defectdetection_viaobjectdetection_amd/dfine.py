@@ -40,6 +40,14 @@ LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch fo
 gathers of the coordinate logits, class logits and memory, and the sigmoid, two launches forward and one backward
 (csrc/dfine_select.hip on the block-wide selection of csrc/topk_select.h, which the post-processing shares), with a stated order
 among equal scores (NaN first, descending, an exact tie to the lowest token) where ``torch.topk`` promises none.
+
+``temporal_fuse`` / ``guard_logits`` / ``decode_boxes(guard=True)`` / ``noobject_loss`` / ``consistency_loss`` / ``temporal_head``
+are the trainers' own stage between the temporal encoder / context GRU and the loss or the post-processing
+(temp_dfine_over.py:188-285, temp_dfine_over_improved.py:219-350): the softmax over the frame axis and the fusion, the anomaly
+scores and the clamp / nan_to_num of the class logits, the nan_to_num chain around the box decode, the cross-entropy of every
+frame against "no object" and the frame-to-frame consistency loss, each one launch forward and one backward
+(csrc/dfine_temporal.hip; the guarded decode is an instance of the decode kernels), with torch's gradients at the guards; CPU
+tensors take the same expressions in torch ops (``*_torch``).
 """
 from __future__ import annotations
 
@@ -280,9 +288,13 @@ def weighting_function(max_num_bins: int, up: torch.Tensor, reg_scale) -> torch.
 
 
 def decode_boxes(pred_corners: torch.Tensor, project: torch.Tensor, points: torch.Tensor, reg_scale: float,
-                 clamp01: bool = False) -> torch.Tensor:
+                 clamp01: bool = False, guard: bool = False) -> torch.Tensor:
     """integral(pred_corners, project) -> distance2bbox(points, ., reg_scale) [-> clamp(0, 1)] in one kernel
-    (temporal_dfine.py:180-181).  pred_corners (..., 4 * (bins + 1)), points (..., 4) -> boxes (..., 4)."""
+    (temporal_dfine.py:180-181).  pred_corners (..., 4 * (bins + 1)), points (..., 4) -> boxes (..., 4).
+    guard=True runs the trainers' guards in the same kernel (temp_dfine_over.py:200-222): nan_to_num(pred_corners, 0, 1, 0) ->
+    integral -> nan_to_num(distances, 0, 1, 0) -> distance2bbox [-> clamp(0, 1)] -> nan_to_num(boxes, 0.5, 1, 0), with torch's
+    gradients (0 into a replaced logit, 0 through a clamped or replaced coordinate); where no guard fires the bits are those of
+    guard=False.  With guard=True, CPU or non-fp32 tensors and autocast take decode_boxes_torch; guard=False is the old call."""
     nb1 = project.numel()
     lead = pred_corners.shape[:-1]
     if pred_corners.shape[-1] != 4 * nb1 or tuple(points.shape) != tuple(lead) + (4,):
@@ -290,39 +302,45 @@ def decode_boxes(pred_corners: torch.Tensor, project: torch.Tensor, points: torc
     if torch.is_grad_enabled() and project.requires_grad:
         raise RuntimeError("decode_boxes treats project (the weighting function W(n)) as a constant: it has no gradient; "
                            "detach it, or use integral() + distance2bbox() to train reg_scale / up")
+    if guard:
+        if not (_fp32_cuda(pred_corners, project, points) and not torch.is_autocast_enabled() and nb1 >= 2 and float(reg_scale) != 0.0):
+            return decode_boxes_torch(pred_corners, project, points, reg_scale, clamp01, True)
+        temporal_calls["kernel"] += 1
     if _wants_grad(pred_corners, points):
-        return _Decode.apply(pred_corners, project, points, float(reg_scale), bool(clamp01))
+        return _Decode.apply(pred_corners, project, points, float(reg_scale), bool(clamp01), bool(guard))
     return _decode_forward(_f32c(pred_corners, "pred_corners"), _f32c(project, "project"), _f32c(points, "points"),
-                           float(reg_scale), bool(clamp01))
+                           float(reg_scale), bool(clamp01), bool(guard))
 
 
-def _decode_forward(d, pr, pt, reg_scale: float, clamp01: bool) -> torch.Tensor:
+def _decode_forward(d, pr, pt, reg_scale: float, clamp01: bool, guard: bool = False) -> torch.Tensor:
     out = torch.empty(tuple(d.shape[:-1]) + (4,), dtype=torch.float32, device=d.device)
-    check(lib.m355_dfine_decode(_ptr(d), _ptr(pr), _ptr(pt), _ptr(out), out.numel() // 4, pr.numel(), reg_scale, int(clamp01),
-                                _stream()))
+    entry = lib.m355_dfine_decode_guarded if guard else lib.m355_dfine_decode
+    check(entry(_ptr(d), _ptr(pr), _ptr(pt), _ptr(out), out.numel() // 4, pr.numel(), reg_scale, int(clamp01), _stream()))
     return out
 
 
 class _Decode(torch.autograd.Function):
-    """decode_boxes with m355_dfine_decode_backward behind it; gradients for pred_corners and points."""
+    """decode_boxes with m355_dfine_decode_backward (guard: m355_dfine_decode_guarded_backward) behind it; gradients for
+    pred_corners and points."""
 
     @staticmethod
-    def forward(ctx, pred_corners, project, points, reg_scale, clamp01):
+    def forward(ctx, pred_corners, project, points, reg_scale, clamp01, guard=False):
         d, pr, pt = _f32c(pred_corners, "pred_corners"), _f32c(project, "project"), _f32c(points, "points")
         ctx.save_for_backward(d, pr, pt)
-        ctx.meta = (reg_scale, clamp01, [(t.shape, t.dtype) for t in (pred_corners, points)])
-        return _decode_forward(d, pr, pt, reg_scale, clamp01)
+        ctx.meta = (reg_scale, clamp01, guard, [(t.shape, t.dtype) for t in (pred_corners, points)])
+        return _decode_forward(d, pr, pt, reg_scale, clamp01, guard)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_boxes):
         d, pr, pt = ctx.saved_tensors
-        reg_scale, clamp01, like = ctx.meta
+        reg_scale, clamp01, guard, like = ctx.meta
         gd, gp = _grad_like(ctx.needs_input_grad[0], d), _grad_like(ctx.needs_input_grad[2], pt)
         gb = _f32c(grad_boxes, "grad_output")
-        check(lib.m355_dfine_decode_backward(_ptr(gb), _ptr(d), _ptr(pr), _ptr(pt), _ptr(gd), _ptr(gp), gb.numel() // 4,
-                                             pr.numel(), reg_scale, int(clamp01), _stream()))
-        return _as_input(gd, *like[0]), None, _as_input(gp, *like[1]), None, None
+        entry = lib.m355_dfine_decode_guarded_backward if guard else lib.m355_dfine_decode_backward
+        check(entry(_ptr(gb), _ptr(d), _ptr(pr), _ptr(pt), _ptr(gd), _ptr(gp), gb.numel() // 4, pr.numel(), reg_scale, int(clamp01),
+                    _stream()))
+        return _as_input(gd, *like[0]), None, _as_input(gp, *like[1]), None, None, None
 
 
 def integral(pred_corners: torch.Tensor, project: torch.Tensor) -> torch.Tensor:
@@ -1712,3 +1730,306 @@ def bind_model(module):
     from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
     _bind_forward(module, {M.DFineModel: model_forward})
     return module
+
+
+# ---- The temporal head of the trainers: between temporal_encoder / context_aggregator and the loss or the post-processing -------
+# Every trainer guards its class logits and its box decode with clamp / nan_to_num; the improved trainer also fuses the frames with a
+# softmax over the frame axis, adds anomaly scores to the class columns and adds a frame-to-frame consistency loss; every trainer
+# takes a per-frame cross-entropy against "no object" on frames without ground truth.  csrc/dfine_temporal.hip runs each as one
+# launch forward and one backward (the consistency loss: two forward), the guarded decode is decode_boxes(guard=True).
+TEMPORAL_MAX_T = 1024            # the limits of m355_dfine_temporal_fuse_*; anything outside them takes temporal_fuse_torch
+TEMPORAL_MAX_D = 1024
+TEMPORAL_MAX_Q = 1 << 20
+NOOBJECT_MAX_Q = 2048            # the limits of m355_dfine_noobject_loss_*
+NOOBJECT_MAX_C = 1024
+CONSISTENCY_MAX_N = 1 << 27      # Q * C of m355_dfine_consistency_loss_*; T * Q * C stays below 2^31
+temporal_calls = {"kernel": 0, "torch": 0}   # calls of the temporal-head ops by path (tests and tools read it)
+
+
+def _temporal_takes(*tensors) -> bool:
+    return _fp32_cuda(*tensors) and not torch.is_autocast_enabled() and all(t.numel() > 0 for t in tensors)
+
+
+def _check_fuse_shapes(fused, scores, context):
+    if fused.dim() != 3 or tuple(scores.shape) not in (tuple(fused.shape[:2]), tuple(fused.shape[:2]) + (1,)):
+        raise ValueError("fused (T, Q, D) and scores (T, Q, 1) or (T, Q) are expected")
+    if context is not None and context.shape != fused.shape:
+        raise ValueError("context must have the shape of fused")
+
+
+def temporal_fuse_torch(fused: torch.Tensor, scores: torch.Tensor, context=None) -> torch.Tensor:
+    """temporal_fuse in torch ops on whatever device and dtype the tensors have: what it falls back to."""
+    _check_fuse_shapes(fused, scores, context)
+    temporal_calls["torch"] += 1
+    out = fused * torch.softmax(scores.reshape(tuple(fused.shape[:2]) + (1,)), dim=0)
+    return out if context is None else out + context
+
+
+def _fuse_forward(f, s, c, keep_stats: bool):
+    T, Q, D = f.shape
+    out = torch.empty_like(f)
+    stats = torch.empty((2, Q), dtype=torch.float32, device=f.device) if keep_stats else None
+    check(lib.m355_dfine_temporal_fuse_forward(_ptr(f), _ptr(s), _ptr(c), T, Q, D, _ptr(out), _ptr(stats), _stream()))
+    return out, stats
+
+
+class _TemporalFuse(torch.autograd.Function):
+    """out = fused * softmax_t(scores) (+ context); saves the scores, the (max, log-sum) of every column and, for the gradient of the
+    scores, fused: no weights, no product."""
+
+    @staticmethod
+    def forward(ctx, fused, scores, context):
+        f, s = fused.contiguous(), scores.contiguous()
+        c = context.contiguous() if context is not None else None
+        out, stats = _fuse_forward(f, s, c, True)
+        ctx.save_for_backward(s, stats, f if ctx.needs_input_grad[1] else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        s, stats, f = ctx.saved_tensors
+        need_f, need_s, need_c = ctx.needs_input_grad
+        g = _f32c(grad_out, "grad_output")
+        T, Q, D = g.shape
+        d_f = torch.empty_like(g) if need_f else None
+        d_s = torch.empty_like(s) if need_s else None
+        if need_f or need_s:
+            check(lib.m355_dfine_temporal_fuse_backward(_ptr(g), _ptr(f), _ptr(s), _ptr(stats), T, Q, D, _ptr(d_f), _ptr(d_s), _stream()))
+        return d_f, d_s, (g if need_c else None)
+
+
+def temporal_fuse(fused: torch.Tensor, scores: torch.Tensor, context=None) -> torch.Tensor:
+    """The improved trainer's frame fusion (temp_dfine_over_improved.py:220, 227): fused (T, Q, D), scores (T, Q, 1) or (T, Q) = the
+    temporal_attention head's output, context (T, Q, D) or None -> fused * softmax(scores, dim=0) (+ context), ONE launch.
+    Differentiable in all three; the backward is one launch in which one block owns a query column (the sum over T in a fixed order,
+    no workspace), the gradient of context is the incoming gradient itself.  Kept for it: the scores, the per-column max and
+    log-sum, and fused only when the scores need a gradient; nothing under no_grad.  A query column does not depend on the other
+    columns of the call; bitwise reproducible.  D that is no multiple of 4 (or a view that is not 16-byte aligned) is handled in
+    the kernel by 4-byte accesses.  CPU or non-fp32 tensors, autocast, T > 1024, D > 1024 or Q > 2^20 take temporal_fuse_torch;
+    temporal_calls counts the calls by path."""
+    _check_fuse_shapes(fused, scores, context)
+    tensors = (fused, scores) if context is None else (fused, scores, context)
+    T, Q, D = fused.shape
+    if not (_temporal_takes(*tensors) and T <= TEMPORAL_MAX_T and D <= TEMPORAL_MAX_D and Q <= TEMPORAL_MAX_Q):
+        return temporal_fuse_torch(fused, scores, context)
+    temporal_calls["kernel"] += 1
+    if _wants_grad(*tensors):
+        return _TemporalFuse.apply(fused, scores, context)
+    c = context.detach().contiguous() if context is not None else None
+    return _fuse_forward(fused.detach().contiguous(), scores.detach().contiguous(), c, False)[0]
+
+
+def _check_guard_shapes(cls_logits, anomaly):
+    if cls_logits.dim() < 1 or (anomaly is not None and (cls_logits.shape[-1] < 2 or tuple(anomaly.shape) != tuple(
+            cls_logits.shape[:-1]) + (cls_logits.shape[-1] - 1,))):
+        raise ValueError("cls_logits (..., C1) and anomaly (..., C1 - 1) are expected")
+
+
+def guard_logits_torch(cls_logits: torch.Tensor, anomaly=None, bound: float = 20.0) -> torch.Tensor:
+    """guard_logits in torch ops (the trainers' lines) on whatever device and dtype the tensors have: what it falls back to."""
+    _check_guard_shapes(cls_logits, anomaly)
+    temporal_calls["torch"] += 1
+    v = cls_logits if anomaly is None else torch.cat([cls_logits[..., :-1] + anomaly, cls_logits[..., -1:]], dim=-1)
+    return torch.nan_to_num(v.clamp(-bound, bound), nan=0.0, posinf=bound, neginf=-bound)
+
+
+class _GuardLogits(torch.autograd.Function):
+    """guard_logits; saves its inputs (no copy of a contiguous input) and forms the mask again in the backward."""
+
+    @staticmethod
+    def forward(ctx, cls_logits, anomaly, bound):
+        c = cls_logits.contiguous()
+        a = anomaly.contiguous() if anomaly is not None else None
+        ctx.save_for_backward(c, a)
+        ctx.bound = bound
+        return _guard_forward(c, a, bound)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        c, a = ctx.saved_tensors
+        g = _f32c(grad_out, "grad_output")
+        d_c = torch.empty_like(c) if ctx.needs_input_grad[0] else None
+        d_a = torch.empty_like(a) if a is not None and ctx.needs_input_grad[1] else None
+        check(lib.m355_dfine_guard_logits_backward(_ptr(g), _ptr(c), _ptr(a), c.numel() // c.shape[-1], c.shape[-1], ctx.bound, _ptr(d_c),
+                                                   _ptr(d_a), _stream()))
+        return d_c, d_a, None
+
+
+def _guard_forward(c, a, bound: float) -> torch.Tensor:
+    out = torch.empty_like(c)
+    check(lib.m355_dfine_guard_logits_forward(_ptr(c), _ptr(a), c.numel() // c.shape[-1], c.shape[-1], bound, _ptr(out), _stream()))
+    return out
+
+
+def guard_logits(cls_logits: torch.Tensor, anomaly=None, bound: float = 20.0) -> torch.Tensor:
+    """The trainers' guarded class logits (temp_dfine_over.py:189-195; with anomaly scores temp_dfine_over_improved.py:237-247):
+    cls_logits (..., C1), anomaly (..., C1 - 1) or None -> nan_to_num((cls_logits, with anomaly added to all but the last column)
+    .clamp(-bound, bound), nan=0, posinf=bound, neginf=-bound) in ONE launch, without the slice and the cat.  One rounding per
+    element: torch's fp32 bits, forward and backward.  The gradient (one launch for both inputs) passes where -bound <= v <= bound
+    and is 0 for NaN, +-inf and clamped values, as torch's clamp and nan_to_num give.  CPU or non-fp32 tensors and autocast take
+    guard_logits_torch; temporal_calls counts the calls by path."""
+    _check_guard_shapes(cls_logits, anomaly)
+    bound = float(bound)
+    tensors = (cls_logits,) if anomaly is None else (cls_logits, anomaly)
+    if not (_temporal_takes(*tensors) and bound >= 0.0 and cls_logits.numel() <= 1 << 40):
+        return guard_logits_torch(cls_logits, anomaly, bound)
+    temporal_calls["kernel"] += 1
+    if _wants_grad(*tensors):
+        return _GuardLogits.apply(cls_logits, anomaly, bound)
+    return _guard_forward(cls_logits.detach().contiguous(), anomaly.detach().contiguous() if anomaly is not None else None, bound)
+
+
+def decode_boxes_torch(pred_corners: torch.Tensor, project: torch.Tensor, points: torch.Tensor, reg_scale: float,
+                       clamp01: bool = False, guard: bool = False) -> torch.Tensor:
+    """decode_boxes in torch ops (DFineIntegral.forward, distance2bbox and, with guard, the trainers' nan_to_num lines) on whatever
+    device and dtype the tensors have: what decode_boxes(guard=True) falls back to."""
+    temporal_calls["torch"] += 1
+    nb1 = project.numel()
+    c = torch.nan_to_num(pred_corners, nan=0.0, posinf=1.0, neginf=0.0) if guard else pred_corners
+    p = torch.softmax(c.reshape(-1, nb1), dim=1)
+    d = torch.nn.functional.linear(p, project.to(p.device).reshape(1, -1)).reshape(tuple(pred_corners.shape[:-1]) + (4,))
+    if guard:
+        d = torch.nan_to_num(d, nan=0.0, posinf=1.0, neginf=0.0)
+    boxes = distance2bbox(points, d, reg_scale)
+    if clamp01:
+        boxes = boxes.clamp(0, 1)
+    return torch.nan_to_num(boxes, nan=0.5, posinf=1.0, neginf=0.0) if guard else boxes
+
+
+def _noobject_class(cls_logits, class_index) -> int:
+    if cls_logits.dim() != 3:
+        raise ValueError("cls_logits (T, Q, C1) is expected")
+    C1 = cls_logits.shape[-1]
+    c = int(class_index)
+    if not -C1 <= c < C1:
+        raise IndexError(f"class_index {c} is out of range for {C1} classes")
+    return c % C1
+
+
+def noobject_loss_torch(cls_logits: torch.Tensor, class_index: int = -1) -> torch.Tensor:
+    """noobject_loss in torch ops: F.cross_entropy of every frame against the one class; what it falls back to."""
+    c = _noobject_class(cls_logits, class_index)
+    temporal_calls["torch"] += 1
+    T, Q, _ = cls_logits.shape
+    target = torch.full((Q,), c, dtype=torch.long, device=cls_logits.device)
+    return torch.stack([torch.nn.functional.cross_entropy(cls_logits[t], target) for t in range(T)]) if T else cls_logits.new_zeros((0,))
+
+
+class _NoObjectLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cls_logits, c):
+        x = cls_logits.contiguous()
+        ctx.save_for_backward(x)   # the input alone: the backward forms the softmax again
+        ctx.c = c
+        return _noobject_forward(x, c)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, = ctx.saved_tensors
+        T, Q, C1 = x.shape
+        g = _f32c(grad_out, "grad_output")
+        dx = torch.empty_like(x)
+        check(lib.m355_dfine_noobject_loss_backward(_ptr(g), _ptr(x), T, Q, C1, ctx.c, _ptr(dx), _stream()))
+        return dx, None
+
+
+def _noobject_forward(x, c: int) -> torch.Tensor:
+    T, Q, C1 = x.shape
+    out = torch.empty((T,), dtype=torch.float32, device=x.device)
+    check(lib.m355_dfine_noobject_loss_forward(_ptr(x), T, Q, C1, c, _ptr(out), _stream()))
+    return out
+
+
+def noobject_loss(cls_logits: torch.Tensor, class_index: int = -1) -> torch.Tensor:
+    """The trainers' loss of a frame without ground truth (temp_dfine_over.py:278-281), for every frame at once: cls_logits
+    (T, Q, C1) -> (T,), entry t = F.cross_entropy(cls_logits[t], full((Q,), class_index)).  The loss loop indexes it where it now
+    calls cross_entropy; an entry nobody uses receives a zero gradient, so its frame's logits do too.  ONE launch (a block per
+    frame, fixed order) and one backward, g[t] / Q * (softmax - onehot), which reads the logits alone.  CPU or non-fp32 tensors,
+    autocast, Q > 2048 or C1 > 1024 take noobject_loss_torch; temporal_calls counts the calls by path."""
+    c = _noobject_class(cls_logits, class_index)
+    T, Q, C1 = cls_logits.shape
+    if not (_temporal_takes(cls_logits) and Q <= NOOBJECT_MAX_Q and C1 <= NOOBJECT_MAX_C):
+        return noobject_loss_torch(cls_logits, c)
+    temporal_calls["kernel"] += 1
+    if _wants_grad(cls_logits):
+        return _NoObjectLoss.apply(cls_logits, c)
+    return _noobject_forward(cls_logits.detach().contiguous(), c)
+
+
+def consistency_loss_torch(a: torch.Tensor) -> torch.Tensor:
+    """consistency_loss as the improved trainer's loop of mse_loss calls (temp_dfine_over_improved.py:291-299): what it falls back to."""
+    if a.dim() != 3:
+        raise ValueError("a (T, Q, C) is expected")
+    temporal_calls["torch"] += 1
+    T = a.shape[0]
+    if T <= 1:
+        return a.new_zeros(())
+    loss = 0.0
+    for t in range(1, T):
+        loss = loss + torch.nn.functional.mse_loss(a[t], a[t - 1])
+    return loss / (T - 1)
+
+
+class _ConsistencyLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a):
+        x = a.contiguous()
+        ctx.save_for_backward(x)
+        return _consistency_forward(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, = ctx.saved_tensors
+        g = _f32c(grad_out, "grad_output")
+        dx = torch.empty_like(x)
+        check(lib.m355_dfine_consistency_loss_backward(_ptr(g), _ptr(x), x.shape[0], x[0].numel(), _ptr(dx), _stream()))
+        return dx
+
+
+def _consistency_forward(x) -> torch.Tensor:
+    T, N = x.shape[0], x[0].numel()
+    work = torch.empty(int(lib.m355_dfine_consistency_workspace_bytes(T, N)), dtype=torch.uint8, device=x.device)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    check(lib.m355_dfine_consistency_loss_forward(_ptr(x), T, N, _ptr(work), work.numel(), _ptr(out), _stream()))
+    return out
+
+
+def consistency_loss(a: torch.Tensor) -> torch.Tensor:
+    """The improved trainer's anomaly consistency loss (temp_dfine_over_improved.py:291-299) without its Python loop: a (T, Q, C) ->
+    a scalar, (1 / (T - 1)) sum_{t >= 1} mean((a[t] - a[t - 1]) ** 2); T = 1 gives a zero tensor.  Two launches forward (per-frame
+    partial sums into a workspace, then a fixed-order sum) and one backward,
+    g * 2 / ((T - 1) Q C) * ((a[t] - a[t - 1]) [t >= 1] - (a[t + 1] - a[t]) [t < T - 1]), instead of T - 1 small graphs.  CPU or
+    non-fp32 tensors, autocast, Q * C > 2^27 or T * Q * C >= 2^31 take consistency_loss_torch; temporal_calls counts the calls."""
+    if a.dim() != 3:
+        raise ValueError("a (T, Q, C) is expected")
+    T, N = a.shape[0], a.shape[1] * a.shape[2]
+    if not (_temporal_takes(a) and N <= CONSISTENCY_MAX_N and T * N < 1 << 31):
+        return consistency_loss_torch(a)
+    temporal_calls["kernel"] += 1
+    if T == 1:
+        return a.new_zeros(())
+    if _wants_grad(a):
+        return _ConsistencyLoss.apply(a)
+    return _consistency_forward(a.detach().contiguous())
+
+
+def temporal_head(fused: torch.Tensor, init_ref: torch.Tensor, class_head, bbox_head, project: torch.Tensor, reg_scale: float, *,
+                  scores=None, context=None, anomaly_head=None, bound: float = 20.0):
+    """What the three trainers and their eval / predict scripts run between the temporal encoder and the loss or the
+    post-processing, from the ops above: [temporal_fuse(fused, scores, context)] -> class_head, bbox_head and anomaly_head (the
+    callers' nn.Modules, torch GEMMs, with their own parameters) -> guard_logits(cls, anomaly, bound) ->
+    decode_boxes(bbox_dist, project, init_ref, reg_scale, clamp01=True, guard=True).
+    fused (T, Q, D); init_ref (T, Q, 4); project (bins + 1,): the trainers' Wn, a constant here; scores (T, Q, 1) or (T, Q) with
+    an optional context (T, Q, D): the improved trainer's attention scores and GRU context; anomaly_head: its anomaly_detector.
+    Returns (cls_logits (T, Q, C1), bbox_pred (T, Q, 4), anomaly_scores (T, Q, C1 - 1) or None)."""
+    if scores is None and context is not None:
+        raise ValueError("context comes with scores: the fusion is fused * softmax(scores) + context")
+    x = fused if scores is None else temporal_fuse(fused, scores, context)
+    anomaly = anomaly_head(x) if anomaly_head is not None else None
+    cls_logits = guard_logits(class_head(x), anomaly, bound)
+    bbox_pred = decode_boxes(bbox_head(x), project, init_ref, reg_scale, clamp01=True, guard=True)
+    return cls_logits, bbox_pred, anomaly

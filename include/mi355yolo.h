@@ -888,6 +888,63 @@ int m355_dfine_gru_backward(const float* d_grad_out, const float* d_grad_h_n, co
                             int32_t B, int64_t S, int32_t H, int32_t D, float* d_grad_gi, float* d_grad_an, float* d_grad_h0,
                             void* d_work, int64_t work_bytes, int32_t* d_status, void* stream);
 
+/* ---- The temporal head of the D-FINE trainers ------------------------------------------------------------------------------
+ * What the trainers run between the temporal encoder / context GRU and the loss or the post-processing, besides the nn.Linear
+ * heads: the guarded box decode, the frame fusion of the improved trainer, the guarded class logits, the no-object cross-entropy
+ * of every frame and the frame-to-frame consistency loss.  All tensors contiguous fp32 on the device; asynchronous on `stream`;
+ * no float atomics, every reduction in a fixed order: bitwise reproducible.  Every entry checks on the host before any HIP call
+ * (M355_ERR_INVALID): no NULL among the required pointers, then the limits stated with it.
+ *
+ * m355_dfine_decode_guarded / _backward: m355_dfine_decode / _backward with the trainers' guards in the same kernel:
+ *   nan_to_num(dist, 0, 1, 0) -> integral -> nan_to_num(distances, 0, 1, 0) -> distance2bbox [-> clamp(0, 1)] ->
+ *   nan_to_num(boxes, 0.5, 1, 0) (nan, posinf, neginf).  Gradients as torch gives them: 0 into a replaced logit, 0 through a
+ *   clamped or replaced box coordinate, nothing from a replaced distance.  Where no guard fires the bits are those of the
+ *   unguarded entries.  Arguments and limits as there. */
+int m355_dfine_decode_guarded(const float* d_dist, const float* d_project, const float* d_ref, float* d_boxes, int64_t n,
+                              int32_t num_bins_plus1, float reg_scale, int32_t clamp01, void* stream);
+int m355_dfine_decode_guarded_backward(const float* d_grad_boxes, const float* d_dist, const float* d_project, const float* d_ref,
+                                       float* d_grad_dist, float* d_grad_ref, int64_t n, int32_t num_bins_plus1, float reg_scale,
+                                       int32_t clamp01, void* stream);
+/* m355_dfine_temporal_fuse_forward: fused (T, Q, D), scores (T, Q), context (T, Q, D) or NULL -> out (T, Q, D) =
+ *   fused * w (+ context), w = softmax of scores over T; stats (2, Q) or NULL: the column's max and the log of its sum of
+ *   exp(score - max), all the backward keeps.  ONE launch; a query column does not depend on the other columns of the call.
+ * m355_dfine_temporal_fuse_backward: ONE launch, one block per column.  grad_fused = g * w and grad_scores =
+ *   w * (dw - sum_t w * dw) with dw[t] = sum_d g * fused; each may be NULL, fused may be NULL without grad_scores.  The gradient
+ *   of context is grad_out itself.
+ * Limits: 1 <= T <= 1024, 1 <= D <= 1024, 1 <= Q <= 2^20.  D % 4 != 0 or a base that is not 16-byte aligned is handled by
+ *   4-byte accesses. */
+int m355_dfine_temporal_fuse_forward(const float* d_fused, const float* d_scores, const float* d_context, int32_t T, int32_t Q,
+                                     int32_t D, float* d_out, float* d_stats, void* stream);
+int m355_dfine_temporal_fuse_backward(const float* d_grad_out, const float* d_fused, const float* d_scores, const float* d_stats,
+                                      int32_t T, int32_t Q, int32_t D, float* d_grad_fused, float* d_grad_scores, void* stream);
+/* m355_dfine_guard_logits_forward: v = cls (rows, C1), plus anomaly (rows, C1 - 1) on all but the last column when it is given;
+ *   out = nan_to_num(clamp(v, -bound, bound), nan = 0, posinf = bound, neginf = -bound).  One rounding per element: torch's bits.
+ * m355_dfine_guard_logits_backward: grad_cls (rows, C1) and grad_anomaly (rows, C1 - 1), each may be NULL: grad_out where
+ *   -bound <= v <= bound, 0 elsewhere (NaN, +-inf, clamped), which is torch's mask.  ONE launch each.
+ * Limits: rows >= 1, C1 >= 1 (>= 2 with anomaly), rows * C1 <= 2^40, bound >= 0. */
+int m355_dfine_guard_logits_forward(const float* d_cls, const float* d_anomaly, int64_t rows, int32_t C1, float bound, float* d_out,
+                                    void* stream);
+int m355_dfine_guard_logits_backward(const float* d_grad_out, const float* d_cls, const float* d_anomaly, int64_t rows, int32_t C1,
+                                     float bound, float* d_grad_cls, float* d_grad_anomaly, void* stream);
+/* m355_dfine_noobject_loss_forward: logits (T, Q, C1) -> out (T): the mean over q of logsumexp(logits[t, q]) - logits[t, q,
+ *   class_index], which is F.cross_entropy(logits[t], full((Q,), class_index)), one block per frame.
+ * m355_dfine_noobject_loss_backward: grad_out (T) -> grad_logits (T, Q, C1) = grad_out[t] / Q * (softmax - onehot); reads the
+ *   logits alone.  ONE launch each.  Limits: T >= 1, 1 <= Q <= 2048, 1 <= C1 <= 1024, 0 <= class_index < C1. */
+int m355_dfine_noobject_loss_forward(const float* d_logits, int32_t T, int32_t Q, int32_t C1, int32_t class_index, float* d_out,
+                                     void* stream);
+int m355_dfine_noobject_loss_backward(const float* d_grad_out, const float* d_logits, int32_t T, int32_t Q, int32_t C1,
+                                      int32_t class_index, float* d_grad_logits, void* stream);
+/* m355_dfine_consistency_loss_forward: a (T, N) -> out (1) = (1 / (T - 1)) sum_{t >= 1} mean((a[t] - a[t - 1])^2).  TWO launches:
+ *   the partial sums of every (frame, chunk of 4096 elements) into work (m355_dfine_consistency_workspace_bytes(T, N) bytes,
+ *   every word written before it is read), then one wave adds them in a fixed order that depends on the shape alone.
+ * m355_dfine_consistency_loss_backward: grad_out (1), read on the device -> grad_a (T, N).  ONE launch.
+ * Limits: 2 <= T, 1 <= N <= 2^27, T * N < 2^31. */
+size_t m355_dfine_consistency_workspace_bytes(int32_t T, int64_t N);
+int m355_dfine_consistency_loss_forward(const float* d_a, int32_t T, int64_t N, void* d_work, int64_t work_bytes, float* d_out,
+                                        void* stream);
+int m355_dfine_consistency_loss_backward(const float* d_grad_out, const float* d_a, int32_t T, int64_t N, float* d_grad_a,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
