@@ -241,6 +241,23 @@ int launch_dfine_gate_ln_backward(const float* gout, const float* g, const float
 int launch_dfine_lqe_forward(const float* corners, long M, int nb1, int k, float* stat, unsigned char* idx, hipStream_t s);
 int launch_dfine_lqe_backward(const float* gstat, const float* corners, const unsigned char* idx, long M, int nb1, int k,
                               float* gcorners, hipStream_t s);
+// The decoder's own loop around its layers (dfine_loop.hip).  query_pos: out (N, H) = relu(ref (N, 4) @ w (H, 4)^T + b), H % 4 == 0;
+// the backward's dref, dweight, dbias may each be nullptr, work (dfine_query_pos_workspace_bytes) holds the slabs' partial rows of
+// dweight | dbias.  refine_reference: sigmoid(delta + inverse_sigmoid(ref, eps)) on n elements; its backward reads the output.
+// refine_boxes: pred = delta + prev (prev == nullptr: nothing written, pred is delta) and boxes = distance2bbox(points,
+// integral(pred, project), reg_scale); the backward writes gcorners = gpred (may be nullptr) + d boxes / d pred . gboxes and gpoints
+// (may be nullptr).
+int launch_dfine_query_pos_forward(const float* ref, const float* w, const float* b, long N, int H, float* out, hipStream_t s);
+size_t dfine_query_pos_workspace_bytes(long N, int H);
+int launch_dfine_query_pos_backward(const float* gout, const float* out, const float* ref, const float* w, long N, int H, float* dref,
+                                    float* dweight, float* dbias, float* work, hipStream_t s);
+int launch_dfine_refine_reference_forward(const float* delta, const float* ref, long n, float eps, float* out, hipStream_t s);
+int launch_dfine_refine_reference_backward(const float* gout, const float* out, long n, float* gdelta, hipStream_t s);
+int launch_dfine_refine_boxes_forward(const float* delta, const float* prev, const float* project, const float* points, long N, int nb1,
+                                      float reg_scale, float* pred, float* boxes, hipStream_t s);
+int launch_dfine_refine_boxes_backward(const float* gpred, const float* gboxes, const float* pred, const float* project,
+                                       const float* points, long N, int nb1, float reg_scale, float* gcorners, float* gpoints,
+                                       hipStream_t s);
 // saved == nullptr: out = dropout(relu(in)); else the backward: in = grad_out, saved = the forward's output
 int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, long n, float p, unsigned long long seed, int site,
                               hipStream_t s);

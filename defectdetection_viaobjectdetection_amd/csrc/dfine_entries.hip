@@ -135,6 +135,18 @@ const char* dfine_decode_check(int64_t n, int32_t nb1, float reg_scale) {
   if (n > 128 * kGridMax) return "n is too large for one launch";
   return nullptr;
 }
+// the decoder's own loop (dfine_loop.hip).  query_pos: (ceil(N / 4) * H / 4 + 255) / 256 blocks forward
+const char* dfine_query_pos_check(int64_t N, int32_t H) {
+  if (H < 4 || H % 4 != 0 || H > 2048) return "H must be a multiple of 4 in [4, 2048]";
+  if (N < 1 || N > (int64_t)1 << 31) return "1 <= rows <= 2^31";
+  return nullptr;
+}
+// refine_boxes, forward and backward: (N + 31) / 32 blocks
+const char* dfine_refine_boxes_check(int64_t N, int32_t nb1, float reg_scale) {
+  if (N < 1 || N > (int64_t)1 << 31) return "1 <= rows <= 2^31";
+  if (nb1 < 2 || nb1 > 64 || reg_scale == 0.f) return "2 <= bins + 1 <= 64 and reg_scale != 0";
+  return nullptr;
+}
 // the temporal head (dfine_temporal.hip).  temporal_fuse: a block per query column, its T partial sums in LDS
 const char* dfine_tfuse_check(int32_t T, int32_t Q, int32_t D) {
   if (T < 1 || T > dfine_tfuse_max_t() || D < 1 || D > 1024) return "T and D must be in [1, 1024]";
@@ -446,6 +458,60 @@ int m355_dfine_lqe_backward(const float* d_grad_stat, const float* d_pred_corner
   if (const char* why = dfine_lqe_check(M, num_bins_plus1, top_k)) return invalid(__func__, why);
   return launched(__func__, launch_dfine_lqe_backward(d_grad_stat, d_pred_corners, d_index, M, num_bins_plus1, top_k,
                                                       d_grad_pred_corners, (hipStream_t)stream));
+}
+// the decoder's own loop around its layers (dfine_loop.hip)
+int m355_dfine_query_pos_forward(const float* d_ref, const float* d_weight, const float* d_bias, int64_t N, int32_t H, float* d_out,
+                                 void* stream) {
+  if (any_null({d_ref, d_weight, d_bias, d_out})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_query_pos_check(N, H)) return invalid(__func__, why);
+  if (any_misaligned16({d_ref, d_weight, d_bias, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_query_pos_forward(d_ref, d_weight, d_bias, (long)N, H, d_out, (hipStream_t)stream));
+}
+size_t m355_dfine_query_pos_workspace_bytes(int64_t N, int32_t H) {
+  return dfine_query_pos_check(N, H) ? 0 : dfine_query_pos_workspace_bytes((long)N, H);
+}
+int m355_dfine_query_pos_backward(const float* d_grad_out, const float* d_out, const float* d_ref, const float* d_weight, int64_t N,
+                                  int32_t H, float* d_grad_ref, float* d_grad_weight, float* d_grad_bias, void* d_work,
+                                  int64_t work_bytes, void* stream) {
+  if (any_null({d_grad_out, d_out, d_ref, d_weight})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_query_pos_check(N, H)) return invalid(__func__, why);
+  const bool sums = d_grad_weight || d_grad_bias;   // the workspace holds their partial rows
+  if (sums && workspace_short(d_work, work_bytes, dfine_query_pos_workspace_bytes((long)N, H)))
+    return invalid(__func__, "workspace missing or smaller than m355_dfine_query_pos_workspace_bytes");
+  if (any_misaligned16({d_grad_out, d_out, d_ref, d_weight, d_grad_ref, sums ? d_work : nullptr})) return invalid(__func__, kAlign16);
+  if (!d_grad_ref && !sums) return M355_OK;   // nothing asked for
+  return launched(__func__, launch_dfine_query_pos_backward(d_grad_out, d_out, d_ref, d_weight, (long)N, H, d_grad_ref, d_grad_weight,
+                                                            d_grad_bias, (float*)d_work, (hipStream_t)stream));
+}
+int m355_dfine_refine_reference_forward(const float* d_delta, const float* d_ref, int64_t n, float eps, float* d_out, void* stream) {
+  if (any_null({d_delta, d_ref, d_out})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 38) return invalid(__func__, "1 <= n <= 2^38");
+  if (!(eps >= 0.f)) return invalid(__func__, "eps must be >= 0");
+  return launched(__func__, launch_dfine_refine_reference_forward(d_delta, d_ref, (long)n, eps, d_out, (hipStream_t)stream));
+}
+int m355_dfine_refine_reference_backward(const float* d_grad_out, const float* d_out, int64_t n, float* d_grad_delta, void* stream) {
+  if (any_null({d_grad_out, d_out, d_grad_delta})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 38) return invalid(__func__, "1 <= n <= 2^38");
+  return launched(__func__, launch_dfine_refine_reference_backward(d_grad_out, d_out, (long)n, d_grad_delta, (hipStream_t)stream));
+}
+int m355_dfine_refine_boxes_forward(const float* d_delta, const float* d_prev, const float* d_project, const float* d_points, int64_t N,
+                                    int32_t num_bins_plus1, float reg_scale, float* d_pred, float* d_boxes, void* stream) {
+  if (any_null({d_delta, d_project, d_points, d_boxes})) return invalid(__func__, "null pointer");
+  if ((d_prev == nullptr) != (d_pred == nullptr)) return invalid(__func__, "prev and pred come together or not at all");
+  if (const char* why = dfine_refine_boxes_check(N, num_bins_plus1, reg_scale)) return invalid(__func__, why);
+  if (any_misaligned16({d_delta, d_prev, d_points, d_pred})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_refine_boxes_forward(d_delta, d_prev, d_project, d_points, (long)N, num_bins_plus1, reg_scale,
+                                                              d_pred, d_boxes, (hipStream_t)stream));
+}
+int m355_dfine_refine_boxes_backward(const float* d_grad_pred, const float* d_grad_boxes, const float* d_pred, const float* d_project,
+                                     const float* d_points, int64_t N, int32_t num_bins_plus1, float reg_scale, float* d_grad_corners,
+                                     float* d_grad_points, void* stream) {
+  if (any_null({d_grad_boxes, d_pred, d_project, d_points, d_grad_corners})) return invalid(__func__, "null pointer");
+  if (const char* why = dfine_refine_boxes_check(N, num_bins_plus1, reg_scale)) return invalid(__func__, why);
+  if (any_misaligned16({d_grad_pred, d_grad_boxes, d_pred, d_points, d_grad_corners})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_refine_boxes_backward(d_grad_pred, d_grad_boxes, d_pred, d_project, d_points, (long)N,
+                                                               num_bins_plus1, reg_scale, d_grad_corners, d_grad_points,
+                                                               (hipStream_t)stream));
 }
 // the GRU recurrence (dfine_gru.hip)
 size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return dfine_gru_workspace_bytes(B, S, H, D); }

@@ -35,6 +35,12 @@ GEMM, the serial chain of both directions one persistent launch forward and one 
 self-attention core above on a packed q | k | v projection, the fused deformable attention, DFineGate behind its Linear,
 LayerNorm(clamp(x + y)) and the LQE's softmax / top-k / mean, each one launch forward with a HIP backward (csrc/dfine_decoder.hip; the row LayerNorms of both layer kinds: csrc/dfine_rowln.hip).
 
+``query_pos_hidden`` / ``refine_reference`` / ``refine_boxes`` / ``decoder_forward`` / ``bind_decoder_loop`` are the decoder's own
+loop around those layers (``DFineDecoder.forward``, :1184-1293), six times per call: the K = 4 Linear + ReLU of ``query_pos_head``,
+inverse_sigmoid + sigmoid at layer 0, and the corner accumulation + integral + distance2bbox of every layer with contiguous
+16-byte accesses, each one launch forward and one backward (csrc/dfine_loop.hip), with W(n) cached on the instance; CPU tensors
+take the same expressions in torch ops (``*_torch``).
+
 ``select_queries`` / ``select_queries_torch`` / ``model_forward`` / ``bind_model`` are the encoder query selection every call of
 ``DFineModel.forward`` makes between the hybrid encoder and the decoder (:1804-1828): row max of the class logits, top-k, the
 gathers of the coordinate logits, class logits and memory, and the sigmoid, two launches forward and one backward
@@ -1490,6 +1496,335 @@ def bind_decoder(module, attention: bool = False):
     for m in _bind_forward(module, {M.DFineDecoderLayer: decoder_layer_forward, M.DFineLQE: lqe_forward}):
         if isinstance(m, M.DFineDecoderLayer):
             m._m355_attention_kernel = bool(attention)   # a plain attribute: not a parameter, not a buffer, not in the state dict
+    return module
+
+
+# ---- the decoder's own loop around its layers (DFineDecoder.forward, modeling_d_fine.py:1184-1293) ------------------------------
+# Six times per call, between the layers bind_decoder covers: query_pos_head, pre_bbox_head / bbox_embed[i], the corner accumulation,
+# the integral and distance2bbox, and at layer 0 inverse_sigmoid + sigmoid.  The nn.Linear products stay torch GEMMs on the module's
+# own parameters; between them query_pos_hidden, relu_dropout, refine_reference and refine_boxes (csrc/dfine_loop.hip).
+QUERY_POS_MAX_H = 2048           # the limits of m355_dfine_query_pos_*; anything outside them takes query_pos_hidden_torch
+loop_calls = {"kernel": 0, "torch": 0}   # decoder_forward calls by path (tests and tools read it)
+
+
+def query_pos_hidden_torch(ref: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """query_pos_hidden in torch ops, any device and dtype"""
+    return torch.relu(torch.nn.functional.linear(ref, weight, bias))
+
+
+def _qp_forward(r, w, b) -> torch.Tensor:
+    H = w.shape[0]
+    out = torch.empty(tuple(r.shape[:-1]) + (H,), dtype=torch.float32, device=r.device)
+    check(lib.m355_dfine_query_pos_forward(_ptr(r), _ptr(w), _ptr(b), r.numel() // 4, H, _ptr(out), _stream()))
+    return out
+
+
+class _QueryPosHidden(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ref, weight, bias):
+        r, w = _f32c16(ref, "ref"), _f32c16(weight, "weight")
+        out = _qp_forward(r, w, _f32c16(bias, "bias"))
+        ctx.save_for_backward(out, r, w)   # the mask is the sign of the output
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        out, r, w = ctx.saved_tensors
+        N, H = r.numel() // 4, w.shape[0]
+        g = _f32c16(grad_out, "grad_output")
+        need = ctx.needs_input_grad
+        gr, gw = _grad_like(need[0], r), _grad_like(need[1], w)
+        gb = torch.empty(H, dtype=torch.float32, device=w.device) if need[2] else None
+        work, nbytes = None, 0
+        if need[1] or need[2]:   # the slabs' partial rows of dweight | dbias
+            nbytes = int(lib.m355_dfine_query_pos_workspace_bytes(N, H))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        check(lib.m355_dfine_query_pos_backward(_ptr(g), _ptr(out), _ptr(r), _ptr(w), N, H, _ptr(gr), _ptr(gw), _ptr(gb), _ptr(work),
+                                                nbytes, _stream()))
+        return gr, gw, gb
+
+
+def query_pos_hidden(ref: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """relu(ref @ weight.T + bias), the first Linear + ReLU of DFineDecoder.query_pos_head: ref (..., 4), weight (H, 4), bias (H,) ->
+    (..., H) in ONE launch (N H floats written, 4 FMAs each).  Differentiable in all three; the backward reads the saved output for
+    the mask (gradient 0 where the pre-activation is <= 0, as torch's ReLU), leaves per-slab partial rows of dweight | dbias and adds
+    them in slab order (one launch + the ordered sum); dref is formed only where asked, a gradient not asked for is a null pointer.
+    CPU or non-fp32 tensors, autocast, an empty ref and H outside the multiples of 4 in [4, 2048] take query_pos_hidden_torch."""
+    H = weight.shape[0] if weight.dim() == 2 else -1
+    if ref.dim() < 1 or ref.shape[-1] != 4 or weight.dim() != 2 or weight.shape[1] != 4 or tuple(bias.shape) != (H,):
+        raise ValueError("ref must be (..., 4), weight (H, 4) and bias (H,)")
+    if not (_fp32_cuda(ref, weight, bias) and not torch.is_autocast_enabled() and ref.numel() and H % 4 == 0
+            and 4 <= H <= QUERY_POS_MAX_H):
+        return query_pos_hidden_torch(ref, weight, bias)
+    if _wants_grad(ref, weight, bias):
+        return _QueryPosHidden.apply(ref, weight, bias)
+    return _qp_forward(_f32c16(ref, "ref"), _f32c16(weight, "weight"), _f32c16(bias, "bias"))
+
+
+def refine_reference_torch(delta: torch.Tensor, ref: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """refine_reference in torch ops: upstream's inverse_sigmoid (modeling_d_fine.py:1084-1088) operation for operation"""
+    x = ref.clamp(min=0, max=1)
+    x1 = x.clamp(min=eps)
+    x2 = (1 - x).clamp(min=eps)
+    return torch.sigmoid(delta + torch.log(x1 / x2))
+
+
+def _refine_reference_forward(d, r, eps: float) -> torch.Tensor:
+    out = torch.empty_like(d)
+    check(lib.m355_dfine_refine_reference_forward(_ptr(d), _ptr(r), d.numel(), eps, _ptr(out), _stream()))
+    return out
+
+
+class _RefineReference(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, delta, ref, eps):
+        out = _refine_reference_forward(_f32c(delta, "delta"), _f32c(ref, "ref"), eps)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (out,) = ctx.saved_tensors
+        g = _f32c(grad_out, "grad_output")
+        gd = torch.empty_like(out)
+        check(lib.m355_dfine_refine_reference_backward(_ptr(g), _ptr(out), out.numel(), _ptr(gd), _stream()))
+        return gd, None, None
+
+
+def refine_reference(delta: torch.Tensor, ref: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """sigmoid(delta + inverse_sigmoid(ref, eps)), the reference points DFineDecoder.forward forms at layer 0, in ONE launch; delta
+    and ref have one shape.  The gradient goes to delta only (one launch, from the saved output): a ref that requires grad, CPU or
+    non-fp32 tensors, autocast and an empty input take refine_reference_torch."""
+    if delta.shape != ref.shape:
+        raise ValueError("delta and ref must have one shape")
+    if not (_fp32_cuda(delta, ref) and not torch.is_autocast_enabled() and delta.numel() and float(eps) >= 0.0
+            and not _wants_grad(ref)):
+        return refine_reference_torch(delta, ref, eps)
+    if _wants_grad(delta):
+        return _RefineReference.apply(delta, ref, float(eps))
+    return _refine_reference_forward(_f32c(delta, "delta"), _f32c(ref, "ref"), float(eps))
+
+
+def refine_boxes_torch(delta_corners: torch.Tensor, prev_corners, project: torch.Tensor, points: torch.Tensor, reg_scale):
+    """refine_boxes in torch ops: upstream's add, DFineIntegral.forward (softmax + linear) and distance2bbox"""
+    pred = delta_corners if prev_corners is None else delta_corners + prev_corners
+    nb1 = project.numel()
+    p = torch.softmax(pred.reshape(-1, nb1), dim=1)
+    d = torch.nn.functional.linear(p, project.to(p.device).reshape(1, -1)).reshape(tuple(pred.shape[:-1]) + (4,))
+    return pred, distance2bbox(points, d, reg_scale)
+
+
+def _refine_boxes_forward(d, pv, pr, pt, reg_scale: float):
+    pred = torch.empty_like(d) if pv is not None else None
+    boxes = torch.empty(tuple(d.shape[:-1]) + (4,), dtype=torch.float32, device=d.device)
+    check(lib.m355_dfine_refine_boxes_forward(_ptr(d), _ptr(pv), _ptr(pr), _ptr(pt), boxes.numel() // 4, pr.numel(), reg_scale,
+                                              _ptr(pred), _ptr(boxes), _stream()))
+    return (d if pred is None else pred), boxes
+
+
+class _RefineBoxes(torch.autograd.Function):
+    """refine_boxes with m355_dfine_refine_boxes_backward behind it.  Without prev_corners the one output is boxes: pred_corners is
+    delta_corners itself, and autograd adds what flows into it elsewhere."""
+
+    @staticmethod
+    def forward(ctx, delta, prev, project, points, reg_scale):
+        d, pv = _f32c16(delta, "delta_corners"), None if prev is None else _f32c16(prev, "prev_corners")
+        pr, pt = _f32c(project, "project"), _f32c16(points, "points")
+        pred, boxes = _refine_boxes_forward(d, pv, pr, pt, reg_scale)
+        ctx.save_for_backward(pred, pr, pt)
+        ctx.meta = (reg_scale, prev is not None)
+        ctx.set_materialize_grads(False)
+        return (pred, boxes) if prev is not None else boxes
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        pred, pr, pt = ctx.saved_tensors
+        reg_scale, has_prev = ctx.meta
+        g_pred, g_boxes = grads if has_prev else (None, grads[0])
+        gc = gp = None
+        if g_boxes is None:
+            gc = g_pred   # nothing came through the boxes
+        else:
+            gq = None if g_pred is None else _f32c16(g_pred, "grad_output")
+            gb = _f32c16(g_boxes, "grad_output")
+            gc, gp = torch.empty_like(pred), _grad_like(ctx.needs_input_grad[3], pt)
+            check(lib.m355_dfine_refine_boxes_backward(_ptr(gq), _ptr(gb), _ptr(pred), _ptr(pr), _ptr(pt), gb.numel() // 4, pr.numel(),
+                                                       reg_scale, _ptr(gc), _ptr(gp), _stream()))
+        return (gc if ctx.needs_input_grad[0] else None, gc if has_prev and ctx.needs_input_grad[1] else None, None, gp, None)
+
+
+def refine_boxes(delta_corners: torch.Tensor, prev_corners, project: torch.Tensor, points: torch.Tensor, reg_scale: float):
+    """One layer's box refinement of DFineDecoder.forward in ONE launch: pred_corners = delta_corners + prev_corners (torch's bits)
+    and boxes = distance2bbox(points, integral(pred_corners, project), reg_scale); returns (pred_corners, boxes).  At layer 0
+    prev_corners is None and pred_corners is delta_corners itself.  delta_corners, prev_corners (..., 4 * (bins + 1)), points
+    (..., 4).  The backward (one launch) writes the one gradient g_pred_corners + d boxes / d pred_corners . g_boxes, which serves
+    both addends, and dpoints where asked.  project is a constant, as in decode_boxes.  CPU or non-fp32 tensors, autocast, an empty
+    input, bins + 1 outside [2, 64] and reg_scale == 0 take refine_boxes_torch."""
+    nb1 = project.numel()
+    lead = delta_corners.shape[:-1]
+    if delta_corners.dim() < 1 or delta_corners.shape[-1] != 4 * nb1 or tuple(points.shape) != tuple(lead) + (4,):
+        raise ValueError("delta_corners must be (..., 4 * len(project)) and points (..., 4)")
+    if prev_corners is not None and prev_corners.shape != delta_corners.shape:
+        raise ValueError("prev_corners must have the shape of delta_corners")
+    if torch.is_grad_enabled() and project.requires_grad:
+        raise RuntimeError("refine_boxes treats project (the weighting function W(n)) as a constant: it has no gradient; "
+                           "detach it, or use integral() + distance2bbox() to train reg_scale / up")
+    tensors = (delta_corners, project, points) + (() if prev_corners is None else (prev_corners,))
+    if not (_fp32_cuda(*tensors) and not torch.is_autocast_enabled() and delta_corners.numel() and 2 <= nb1 <= LQE_MAX_BINS1
+            and not torch.is_tensor(reg_scale) and float(reg_scale) != 0.0):
+        return refine_boxes_torch(delta_corners, prev_corners, project, points, reg_scale)
+    if _wants_grad(*tensors):
+        out = _RefineBoxes.apply(delta_corners, prev_corners, project, points, float(reg_scale))
+        return out if prev_corners is not None else (delta_corners, out)
+    d = _f32c16(delta_corners, "delta_corners")
+    pred, boxes = _refine_boxes_forward(d, None if prev_corners is None else _f32c16(prev_corners, "prev_corners"),
+                                        _f32c(project, "project"), _f32c16(points, "points"), float(reg_scale))
+    return (delta_corners if prev_corners is None else pred), boxes
+
+
+def _loop_project(decoder):
+    """(project, reg_scale as a float) of a DFineDecoder, cached on the instance as a plain attribute (not a buffer) under the
+    _version, device and dtype of `up` and `reg_scale`: weighting_function's own bits, rebuilt after either parameter changes"""
+    up, rs = decoder.up, decoder.reg_scale
+    key = (up._version, up.device, up.dtype, rs._version, rs.device, rs.dtype)
+    cached = getattr(decoder, "_m355_project", None)
+    if cached is None or cached[0] != key:
+        with torch.no_grad():
+            cached = (key, weighting_function(decoder.max_num_bins, up, rs), float(rs))
+        decoder._m355_project = cached
+    return cached[1], cached[2]
+
+
+def _relu_mlp_shaped(mlp, in_features=None) -> bool:
+    layers = list(getattr(mlp, "layers", ()))
+    if not layers or not all(isinstance(l, torch.nn.Linear) and l.bias is not None for l in layers):
+        return False
+    if hasattr(mlp, "act") and not isinstance(mlp.act, torch.nn.ReLU):
+        return False
+    return getattr(mlp, "num_layers", len(layers)) == len(layers) and (in_features is None or layers[0].in_features == in_features)
+
+
+def _relu_mlp(mlp, x: torch.Tensor) -> torch.Tensor:
+    """DFineMLP.forward with ReLU: the Linears as torch GEMMs on the module's parameters, relu_dropout(., 0.0) between them"""
+    last = len(mlp.layers) - 1
+    for j, layer in enumerate(mlp.layers):
+        x = torch.nn.functional.linear(x, layer.weight, layer.bias)
+        if j < last:
+            x = relu_dropout(x, 0.0)
+    return x
+
+
+def _decoder_loop_takes(dec, encoder_hidden_states, reference_points, inputs_embeds, kwargs) -> bool:
+    """True when the kernels cover this call of a DFineDecoder; anything else goes to the class's own forward"""
+    if dec.bbox_embed is None or dec.class_embed is None:
+        return False
+    cfg = getattr(dec, "config", None)
+    if any(kwargs.get(k) or getattr(cfg, k, False) for k in ("output_hidden_states", "output_attentions")):
+        return False
+    if kwargs.get("return_dict") is False:
+        return False
+    x, ref = inputs_embeds, reference_points
+    if not _fp32_cuda(x, ref, encoder_hidden_states) or torch.is_autocast_enabled() or x.dim() != 3 or x.numel() == 0:
+        return False
+    if ref.dim() != 3 or ref.shape[-1] != 4 or ref.shape[:2] != x.shape[:2]:
+        return False
+    qp = dec.query_pos_head
+    if not _relu_mlp_shaped(qp, 4) or len(qp.layers) != 2:
+        return False
+    if not _relu_mlp_shaped(dec.pre_bbox_head) or not hasattr(dec.pre_bbox_head, "act"):
+        return False
+    if len(dec.bbox_embed) < len(dec.layers) or not all(_relu_mlp_shaped(m) and hasattr(m, "act") for m in dec.bbox_embed):
+        return False
+    nb1 = int(dec.max_num_bins) + 1
+    if not 2 <= nb1 <= LQE_MAX_BINS1 or any(m.layers[-1].out_features != 4 * nb1 for m in dec.bbox_embed):
+        return False
+    if dec.up.requires_grad or dec.reg_scale.requires_grad:   # project is a constant of refine_boxes
+        return False
+    own = [dec.up, dec.reg_scale]
+    for m in (qp, dec.pre_bbox_head, dec.bbox_embed, dec.class_embed):
+        own.extend(m.parameters())
+    return _fp32_cuda(*own)
+
+
+def decoder_forward(self, encoder_hidden_states, reference_points, inputs_embeds, spatial_shapes, level_start_index=None,
+                    spatial_shapes_list=None, encoder_attention_mask=None, memory_mask=None, **kwargs):
+    """DFineDecoder.forward (modeling_d_fine.py:1184-1293, transformers 5.15.0) on fp32 CUDA tensors, in upstream's order and with its
+    detach points; the nn.Linear products as torch GEMMs on the module's own parameters and between them
+        pos = query_pos_head.layers[1](query_pos_hidden(ref, query_pos_head.layers[0])).clamp(-10, 10)
+        new_ref = refine_reference(pre_bbox_head(x), ref)                            # layer 0; the inner ReLUs: relu_dropout(., 0.0)
+        pred_corners, boxes = refine_boxes(bbox_embed[i](x + x_prev.detach()), pred_corners, project, new_ref.detach(), reg_scale)
+    The layers and lqe_layers[i] are called as modules (bind_decoder composes), class_embed[i] runs where upstream runs it, the
+    final stacks stay torch; every field of DFineDecoderOutput is filled as upstream.  project = weighting_function(...) and
+    float(reg_scale) are cached on the instance (_loop_project), so a call rebuilds neither.
+    A call goes to the class's own forward, untouched and with its decorators, when bbox_embed or class_embed is None, when tensors
+    or the loop's parameters are not fp32 CUDA, under autocast, with reference points that are not (B, Q, 4), when query_pos_head is
+    not a two-layer head of input width 4, an MLP's activation is not ReLU, `up` or `reg_scale` requires grad, recorded outputs are
+    asked for (output_hidden_states / output_attentions in kwargs or config) and on an empty input.  A denoising mask does not force
+    it: the layers decide for themselves.  Bound per instance by bind_decoder_loop."""
+    if not _decoder_loop_takes(self, encoder_hidden_states, reference_points, inputs_embeds, kwargs):
+        loop_calls["torch"] += 1
+        return type(self).forward(self, encoder_hidden_states=encoder_hidden_states, reference_points=reference_points,
+                                  inputs_embeds=inputs_embeds, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
+                                  spatial_shapes_list=spatial_shapes_list, encoder_attention_mask=encoder_attention_mask,
+                                  memory_mask=memory_mask, **kwargs)
+    loop_calls["kernel"] += 1
+    from transformers.models.d_fine.modeling_d_fine import DFineDecoderOutput
+    F = torch.nn.functional
+    project, reg_scale = _loop_project(self)
+    q0, q1 = self.query_pos_head.layers
+    hidden_states = inputs_embeds
+    intermediate, intermediate_reference_points, intermediate_logits = (), (), ()
+    intermediate_predicted_corners, initial_reference_points = (), ()
+    output_detach = pred_corners_undetach = None
+    ref_points_detach = torch.sigmoid(reference_points)
+
+    for i, decoder_layer in enumerate(self.layers):
+        ref_points_input = ref_points_detach.unsqueeze(2)
+        query_pos_embed = F.linear(query_pos_hidden(ref_points_detach, q0.weight, q0.bias), q1.weight, q1.bias).clamp(min=-10, max=10)
+        hidden_states = decoder_layer(hidden_states, position_embeddings=query_pos_embed, reference_points=ref_points_input,
+                                      spatial_shapes=spatial_shapes, spatial_shapes_list=spatial_shapes_list,
+                                      encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask,
+                                      **kwargs)
+        if i == 0:
+            new_reference_points = refine_reference(_relu_mlp(self.pre_bbox_head, hidden_states), ref_points_detach)
+            ref_points_initial = new_reference_points.detach()
+        delta = _relu_mlp(self.bbox_embed[i], hidden_states if output_detach is None else hidden_states + output_detach)
+        pred_corners, inter_ref_bbox = refine_boxes(delta, pred_corners_undetach, project, ref_points_initial, reg_scale)
+        pred_corners_undetach = pred_corners
+        ref_points_detach = inter_ref_bbox.detach()
+        output_detach = hidden_states.detach()
+        intermediate += (hidden_states,)
+
+        if self.training or i == self.eval_idx:
+            scores = self.class_embed[i](hidden_states)
+            if i == 0:
+                intermediate_logits += (scores,)
+                intermediate_reference_points += (new_reference_points,)
+            scores = self.lqe_layers[i](scores, pred_corners)
+            intermediate_logits += (scores,)
+            intermediate_reference_points += (inter_ref_bbox,)
+            initial_reference_points += (ref_points_initial,)
+            intermediate_predicted_corners += (pred_corners,)
+
+    return DFineDecoderOutput(
+        last_hidden_state=hidden_states,
+        intermediate_hidden_states=torch.stack(intermediate),
+        intermediate_logits=torch.stack(intermediate_logits, dim=1),
+        intermediate_reference_points=torch.stack(intermediate_reference_points, dim=1),
+        intermediate_predicted_corners=torch.stack(intermediate_predicted_corners, dim=1),
+        initial_reference_points=torch.stack(initial_reference_points, dim=1),
+    )
+
+
+def bind_decoder_loop(module):
+    """Set decoder_forward on every DFineDecoder INSTANCE inside `module` (a DFineDecoder, a whole DFineForObjectDetection, or any
+    module that holds some); transformers' classes are never touched, parameters, buffers and the state dict stay as they are.
+    Composes with bind_decoder and bind_model.  Returns `module`."""
+    from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
+    _bind_forward(module, {M.DFineDecoder: decoder_forward})
     return module
 
 

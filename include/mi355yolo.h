@@ -856,6 +856,39 @@ int m355_dfine_lqe_forward(const float* d_pred_corners, int64_t M, int32_t num_b
 int m355_dfine_lqe_backward(const float* d_grad_stat, const float* d_pred_corners, const uint8_t* d_index, int64_t M,
                             int32_t num_bins_plus1, int32_t top_k, float* d_grad_pred_corners, void* stream);
 
+/* ---- The loop of a D-FINE decoder around its layers, between its GEMMs ------------------------------------------------------
+ * What transformers' DFineDecoder.forward runs per layer besides the layers, the LQE heads and its nn.Linear products.  fp32, row
+ * major, contiguous, asynchronous on `stream`; no atomics, every sum in a fixed order: bitwise reproducible; a row's result does
+ * not depend on the rows around it.
+ * m355_dfine_query_pos_forward: out (N, H) = relu(ref (N, 4) @ weight (H, 4)^T + bias (H)), the first Linear + ReLU of query_pos_head.
+ * m355_dfine_query_pos_backward: from grad_out and the forward's out (gradient 0 where out <= 0): grad_ref (N, 4), grad_weight (H, 4),
+ *   grad_bias (H); each may be NULL and its work is skipped.  grad_weight / grad_bias are per-slab partial rows in work
+ *   (m355_dfine_query_pos_workspace_bytes(N, H) bytes, every word written before it is read; 0 for a shape outside the limits),
+ *   added in slab order by a second launch.
+ * m355_dfine_refine_reference_forward: out = sigmoid(delta + log(max(x, eps) / max(1 - x, eps))), x = clamp(ref, 0, 1), on n
+ *   elements: the reference points of layer 0.  _backward: grad_delta = grad_out * (1 - out) * out.  ONE launch each.
+ * m355_dfine_refine_boxes_forward: delta, prev (N, 4 * num_bins_plus1), project (num_bins_plus1), points (N, 4) -> pred = delta +
+ *   prev and boxes (N, 4) = distance2bbox(points, integral(pred, project), reg_scale) in ONE launch.  prev and pred NULL together:
+ *   pred is delta and is not written.
+ * m355_dfine_refine_boxes_backward: grad_corners (N, 4 * num_bins_plus1) = grad_pred (or 0 when NULL) + d boxes / d pred . grad_boxes,
+ *   the gradient of delta and of prev alike; grad_points (N, 4) or NULL.  pred: the forward's pred (or delta).  ONE launch.
+ * Limits (M355_ERR_INVALID before any HIP call): no NULL among the required pointers, 1 <= N <= 2^31, H a multiple of 4 in
+ * [4, 2048], 1 <= n <= 2^38, eps >= 0, 2 <= num_bins_plus1 <= 64, reg_scale != 0, the workspace size, 16-byte alignment of every
+ * tensor but project, boxes, grad_points and those of refine_reference. */
+int m355_dfine_query_pos_forward(const float* d_ref, const float* d_weight, const float* d_bias, int64_t N, int32_t H, float* d_out,
+                                 void* stream);
+size_t m355_dfine_query_pos_workspace_bytes(int64_t N, int32_t H);
+int m355_dfine_query_pos_backward(const float* d_grad_out, const float* d_out, const float* d_ref, const float* d_weight, int64_t N,
+                                  int32_t H, float* d_grad_ref, float* d_grad_weight, float* d_grad_bias, void* d_work,
+                                  int64_t work_bytes, void* stream);
+int m355_dfine_refine_reference_forward(const float* d_delta, const float* d_ref, int64_t n, float eps, float* d_out, void* stream);
+int m355_dfine_refine_reference_backward(const float* d_grad_out, const float* d_out, int64_t n, float* d_grad_delta, void* stream);
+int m355_dfine_refine_boxes_forward(const float* d_delta, const float* d_prev, const float* d_project, const float* d_points, int64_t N,
+                                    int32_t num_bins_plus1, float reg_scale, float* d_pred, float* d_boxes, void* stream);
+int m355_dfine_refine_boxes_backward(const float* d_grad_pred, const float* d_grad_boxes, const float* d_pred, const float* d_project,
+                                     const float* d_points, int64_t N, int32_t num_bins_plus1, float reg_scale, float* d_grad_corners,
+                                     float* d_grad_points, void* stream);
+
 /* ---- The recurrence of the D-FINE trainer's context GRU -----------------------------------------------------------------
  * torch's one-layer nn.GRU(*, 256, batch_first, uni- or bidirectional) without its input projection: the caller's GEMM gives
  * gi = x cat(W_ih, W_ih_reverse)^T + b_ih for all steps and both directions; these entries run the serial chain.  Gate order
