@@ -86,6 +86,22 @@ class LetterboxImage(C.Structure):
                 ("top", C.c_int32), ("left", C.c_int32)]
 
 
+class DfinePreImage(C.Structure):
+    """m355_dfine_pre_image (include/mi355yolo.h)."""
+    _fields_ = [("offset", C.c_int64), ("in_h", C.c_int32), ("in_w", C.c_int32), ("htab", C.c_int32), ("vtab", C.c_int32),
+                ("mid_row", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DfinePreAxis(C.Structure):
+    """m355_dfine_pre_axis (include/mi355yolo.h)."""
+    _fields_ = [("in_size", C.c_int32), ("out_size", C.c_int32), ("ksize", C.c_int32), ("offset", C.c_int32)]
+
+
+DFINE_PRE_MAX_TAPS = 64       # M355_DFINE_PRE_MAX_TAPS
+DFINE_PRE_MAX_W = 4096        # M355_DFINE_PRE_MAX_W
+DFINE_PRE_MAX_H = 16384       # M355_DFINE_PRE_MAX_H
+
+
 # symbol -> (restype, argtypes); every entry of include/mi355yolo.h
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -169,6 +185,8 @@ SIGNATURES = {
     "m355_dfine_match": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_float, C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "m355_dfine_postprocess": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "m355_dfine_preprocess": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32, C.c_int32,
+                                        _P, C.c_int64, _P, _P]),
     "m355_dfine_select_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "m355_dfine_select_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P,
                                             _P, _P, _P, _P]),

@@ -168,6 +168,15 @@ int launch_dfine_match(const float* logits, const float* boxes, int B, int Q, in
 // xyxy box and the {n_nan, n_keep} counts, one block per image.  The caller has validated every argument; sizes may be nullptr.
 int launch_dfine_postprocess(const float* logits, const float* boxes, int B, int Q, int C, const float* sizes, float threshold,
                              float* scores, long long* labels, float* out_boxes, int* counts, hipStream_t s);
+// Image pre-processing of a D-FINE / RT-DETR model (dfine_preprocess.hip): Pillow's 8-bit BILINEAR resize + rescale of T packed
+// uint8 RGB images into fp32 (T, 3, out_h, out_w), the horizontal pass into the uint8 scratch `mid` and the vertical pass, two
+// launches (one when h_max_rows == 0: no image has a horizontal pass).  d_images / d_axes: device arrays of m355_dfine_pre_image /
+// m355_dfine_pre_axis; h_max_rows, h_max_w: the largest in_h and in_w among the images with a horizontal pass.  The caller has
+// validated every argument and table; dfine_preprocess_lds_bytes(h_max_w) is the horizontal launch's dynamic LDS.
+size_t dfine_preprocess_lds_bytes(int max_in_w);
+int launch_dfine_preprocess(const uint8_t* src, const void* d_images, int T, const void* d_axes, const int* d_pool,
+                            const float* rescale, int out_h, int out_w, uint8_t* mid, int h_max_rows, int h_max_w, float* out,
+                            hipStream_t s);
 // Encoder query selection of DFineModel.forward (dfine_select.hip): the K tokens with the greatest row max of class_logits per image
 // (the order of topk_select.h), their indices, the gathered coordinate / class / memory rows, sigmoid of the coordinate rows and the
 // inverse map (rank or -1 per token); the backward writes the three input gradients in full through that map.  The caller has

@@ -278,6 +278,73 @@ int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int
   return launched(__func__, launch_dfine_postprocess(d_logits, d_pred_boxes, B, Q, C, d_sizes, threshold, d_scores, (long long*)d_labels,
                                                      d_boxes, d_counts, (hipStream_t)stream));
 }
+int m355_dfine_preprocess(const uint8_t* d_src, int64_t src_bytes, const m355_dfine_pre_image* h_images,
+                          const m355_dfine_pre_image* d_images, int32_t T, const m355_dfine_pre_axis* h_axes,
+                          const m355_dfine_pre_axis* d_axes, int32_t n_axes, const int32_t* h_pool, const int32_t* d_pool,
+                          int64_t pool_len, const float* d_rescale, int32_t out_h, int32_t out_w, void* d_work, int64_t work_bytes,
+                          float* d_out, void* stream) {
+  if (any_null({d_src, h_images, d_images, d_rescale, d_out})) return invalid(__func__, "null pointer");
+  if (n_axes < 0 || pool_len < 0 || (n_axes > 0 && any_null({h_axes, d_axes, h_pool, d_pool})))
+    return invalid(__func__, "axis tables missing");
+  if (T < 1 || T > 65535) return invalid(__func__, "T in [1, 65535]");
+  if (out_h < 1 || out_h > M355_DFINE_PRE_MAX_H || out_w < 4 || out_w > M355_DFINE_PRE_MAX_W || out_w % 4)
+    return invalid(__func__, "out_h in [1, 16384], out_w a multiple of 4 in [4, 4096]");
+  if (src_bytes < 0 || src_bytes % 16) return invalid(__func__, "src_bytes must be a multiple of 16");
+  // every value a kernel indexes with comes from these tables: none is used unchecked
+  constexpr int32_t kCoefMax = 1 << 23;
+  for (int a = 0; a < n_axes; ++a) {
+    const m355_dfine_pre_axis& ax = h_axes[a];
+    const std::string which = "axis " + std::to_string(a) + ": ";
+    if (ax.in_size < 1 || ax.in_size > M355_DFINE_PRE_MAX_H || ax.out_size < 1 || ax.out_size > M355_DFINE_PRE_MAX_H)
+      return invalid(__func__, which + "sizes in [1, 16384]");
+    if (ax.ksize < 1 || ax.ksize > M355_DFINE_PRE_MAX_TAPS) return invalid(__func__, which + "tap count above the kernel's maximum of 64 (or below 1)");
+    if (ax.offset < 0 || (int64_t)ax.offset + (int64_t)ax.out_size * (2 + ax.ksize) > pool_len)
+      return invalid(__func__, which + "the table leaves the pool");
+    const int32_t* const xmin = h_pool + ax.offset;
+    const int32_t* const count = xmin + ax.out_size;
+    const int32_t* const coef = count + ax.out_size;
+    for (int i = 0; i < ax.out_size; ++i) {
+      if (count[i] < 1 || count[i] > ax.ksize) return invalid(__func__, which + "tap count outside [1, ksize]");
+      if (xmin[i] < 0 || xmin[i] > ax.in_size - count[i]) return invalid(__func__, which + "xmin + count > in");
+      int64_t sum = 0;
+      for (int t = 0; t < count[i]; ++t) {
+        const int32_t c = coef[(size_t)i * ax.ksize + t];
+        if (c < 0 || c > kCoefMax) return invalid(__func__, which + "coefficient outside [0, 2^23]");
+        sum += c;
+      }
+      if (sum > kCoefMax) return invalid(__func__, which + "coefficients of an output sum above 2^23");
+    }
+  }
+  int64_t mid_rows = 0;
+  int h_max_rows = 0, h_max_w = 0;
+  for (int i = 0; i < T; ++i) {
+    const m355_dfine_pre_image& im = h_images[i];
+    const std::string which = "image " + std::to_string(i) + ": ";
+    if (im.in_h < 1 || im.in_h > M355_DFINE_PRE_MAX_H || im.in_w < 1 || im.in_w > M355_DFINE_PRE_MAX_W)
+      return invalid(__func__, which + "in_h in [1, 16384], in_w in [1, 4096]");
+    if (im.offset < 0 || im.offset % 16 || im.offset > src_bytes - 3LL * im.in_h * im.in_w)
+      return invalid(__func__, which + "offset negative, not a multiple of 16, or the image leaves the packed buffer");
+    const struct { int32_t tab, in, out; const char* name; } pass[2] = {{im.htab, im.in_w, out_w, "horizontal"},
+                                                                       {im.vtab, im.in_h, out_h, "vertical"}};
+    for (const auto& p : pass) {
+      if (p.tab == -1 ? p.in != p.out
+                      : (p.tab < 0 || p.tab >= n_axes || h_axes[p.tab].in_size != p.in || h_axes[p.tab].out_size != p.out))
+        return invalid(__func__, which + p.name + " table index is neither -1 with in == out nor an axis of its (in, out)");
+    }
+    if (im.htab >= 0) {
+      if (im.mid_row != mid_rows) return invalid(__func__, which + "mid_row is not the sum of the earlier images' rows");
+      mid_rows += im.in_h;
+      if (mid_rows > INT32_MAX) return invalid(__func__, "the scratch rows must stay below 2^31");
+      h_max_rows = im.in_h > h_max_rows ? im.in_h : h_max_rows;
+      h_max_w = im.in_w > h_max_w ? im.in_w : h_max_w;
+    }
+  }
+  if (mid_rows > 0 && workspace_short(d_work, work_bytes, (size_t)mid_rows * out_w * 3))
+    return invalid(__func__, "scratch missing or smaller than 3 * out_w bytes per row of every image with a horizontal pass");
+  if (any_misaligned16({d_src, d_work, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_preprocess(d_src, d_images, T, d_axes, d_pool, d_rescale, out_h, out_w, (uint8_t*)d_work,
+                                                    h_max_rows, h_max_w, d_out, (hipStream_t)stream));
+}
 size_t m355_dfine_select_workspace_bytes(int32_t B, int32_t S) {
   return dfine_select_check(B, S, 1, 1) ? 0 : dfine_select_workspace_bytes(B, S);
 }

@@ -21,6 +21,11 @@ two launches forward and one backward per output, without a synchronisation; on 
 (``RTDetrImageProcessor.post_process_object_detection``, models/rt_detr/image_processing_rt_detr.py:482-552): sigmoid, top-K, labels,
 scaled xyxy boxes and the threshold in one launch for a whole sequence of frames, with one read-back of the kept counts.
 
+``preprocess_images`` / ``resize_tables`` / ``preprocess_images_torch`` / ``bind_processor`` are the stage in front of the model
+(``RTDetrImageProcessorPil.preprocess`` with its defaults, models/rt_detr/image_processing_pil_rt_detr.py:380-505): Pillow's 8-bit
+BILINEAR resize to a fixed size and the rescale for a whole sequence of decoded frames of mixed sizes, one uint8 upload and two
+launches (csrc/dfine_preprocess.hip), bit for bit the processor's pixel_values; the host path builds the same bytes in numpy.
+
 ``self_attention`` / ``add_layer_norm`` / ``relu_dropout`` / ``encoder_layer_forward`` / ``bind_encoder`` are the temporal
 encoder the D-FINE trainers train (``nn.TransformerEncoderLayer``, post-norm, ReLU, head dim 32) between its torch GEMMs:
 attention core with online softmax on the packed in-projection output, LayerNorm(x + dropout(y)) and dropout(relu(h)), each
@@ -58,13 +63,16 @@ tensors take the same expressions in torch ops (``*_torch``).
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import math
 from collections.abc import Mapping
 from operator import itemgetter
 from typing import List, NamedTuple, Sequence
 
+import numpy as np
 import torch
 
-from ._capi import check, lib
+from ._capi import DFINE_PRE_MAX_H, DFINE_PRE_MAX_TAPS, DFINE_PRE_MAX_W, DfinePreAxis, DfinePreImage, check, lib
 
 _raise_on_error = check   # for hungarian_match, whose keyword `check` is upstream-facing
 
@@ -867,6 +875,289 @@ def post_process_object_detection(self, outputs, threshold: float = 0.5, target_
     if not use_focal_loss:
         return post_process_torch(logits, pred_boxes, target_sizes, threshold, use_focal_loss=False)
     return post_process_detections(logits, pred_boxes, target_sizes, threshold)
+
+
+# ---- image pre-processing (RTDetrImageProcessorPil.preprocess with its defaults, image_processing_pil_rt_detr.py:380-505) -------
+# Every D-FINE script starts a sequence with processor(images=frames, return_tensors="pt")["pixel_values"].to(device): Pillow's
+# 8-bit BILINEAR resize to a fixed size and a rescale, a frame at a time on the host, then an fp32 upload.  Here the raw frames go
+# up once as bytes and csrc/dfine_preprocess.hip writes the model's input batch, bit for bit the processor's.
+PRE_MAX_TAPS, PRE_MAX_W, PRE_MAX_H = DFINE_PRE_MAX_TAPS, DFINE_PRE_MAX_W, DFINE_PRE_MAX_H   # the limits of m355_dfine_preprocess
+PRE_MAX_FRAMES = 65535
+PRE_MAX_ASPECT = 64      # Pillow resizes very tall, thin images (in_h / in_w of 125 and more, measured) vertical pass first
+PRE_PRECISION_BITS = 22  # Pillow's fixed point
+preprocess_calls = {"kernel": 0, "original": 0}   # how many bound preprocess calls took which path (tests and tools read it)
+
+
+@functools.lru_cache(maxsize=256)
+def resize_tables(in_size: int, out_size: int):
+    """Pillow's coefficients of one axis of an 8-bit BILINEAR resize (precompute_coeffs + normalize_coeffs_8bpc), float64 in its
+    order of operations: (xmin (out,) int32, counts (out,) int32, coefficients (out, ksize) int32, zero behind a row's count).
+    Output xx = clip((2^21 + sum_t coefficients[xx, t] * pixel[xmin[xx] + t]) >> 22, 0, 255).  Cached per (in, out); read-only."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("sizes must be >= 1")
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = fs                                   # bilinear: support 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)            # C's (int): towards zero
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    counts = xmax - xmin
+    taps = np.arange(ksize, dtype=np.int64)[None, :]
+    arg = np.abs(((taps + xmin[:, None]) - center[:, None] + 0.5) / fs)
+    w = np.where((arg < 1.0) & (taps < counts[:, None]), 1.0 - arg, 0.0)
+    total = np.zeros(out_size, np.float64)
+    for t in range(ksize):                         # summed in tap order, as Pillow does
+        total += w[:, t]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    coef = (w * float(1 << PRE_PRECISION_BITS) + 0.5).astype(np.int32)
+    out = (xmin.astype(np.int32), counts.astype(np.int32), coef)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def rescale_table(rescale_factor: float = 1 / 255) -> torch.Tensor:
+    """the fp32 value of every byte: float32(float64(b) * rescale_factor), what the processor's numpy rescale gives"""
+    return torch.from_numpy((np.arange(256, dtype=np.float64) * float(rescale_factor)).astype(np.float32))
+
+
+def preprocess_in_domain(in_h: int, in_w: int, out_h: int, out_w: int) -> bool:
+    """Whether preprocess_images takes a source of (in_h, in_w) for an output of (out_h, out_w): an aspect ratio within 64 : 1
+    either way (the shapes whose pass order in Pillow is known to be horizontal-first), sizes and tap counts within the kernel's
+    limits.  bind_processor sends everything else to the original processor ("falls back")."""
+    if not (1 <= in_h <= PRE_MAX_H and 1 <= in_w <= PRE_MAX_W and 1 <= out_h <= PRE_MAX_H and 4 <= out_w <= PRE_MAX_W and out_w % 4 == 0):
+        return False
+    if in_h > PRE_MAX_ASPECT * in_w or in_w > PRE_MAX_ASPECT * in_h:
+        return False
+    return all(int(math.ceil(max(i / o, 1.0))) * 2 + 1 <= PRE_MAX_TAPS for i, o in ((in_h, out_h), (in_w, out_w)))
+
+
+def _as_rgb_array(image):
+    """uint8 (h, w, 3) ndarray of a PIL image in mode RGB or of such an ndarray, else None"""
+    if isinstance(image, np.ndarray):
+        return image if image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3 else None
+    if getattr(image, "mode", None) == "RGB" and hasattr(image, "resize") and hasattr(image, "size"):
+        return np.asarray(image)
+    return None
+
+
+def _pre_size(size):
+    out_h, out_w = (int(size["height"]), int(size["width"])) if isinstance(size, Mapping) else (int(size[0]), int(size[1]))
+    return out_h, out_w
+
+
+def _pre_arrays(images, out_h, out_w):
+    if not isinstance(images, (list, tuple)):
+        images = [images]
+    arrays = [_as_rgb_array(im) for im in images]
+    if not arrays or len(arrays) > PRE_MAX_FRAMES or any(a is None for a in arrays):
+        raise ValueError("images: 1..65535 PIL images in mode RGB or uint8 (h, w, 3) arrays are expected")
+    for a in arrays:
+        if not preprocess_in_domain(a.shape[0], a.shape[1], out_h, out_w):
+            raise ValueError(f"a {a.shape[0]} x {a.shape[1]} image to {out_h} x {out_w} is outside the kernel's domain "
+                             "(aspect ratio within 64 : 1, sizes and tap counts within the limits of m355_dfine_preprocess)")
+    return arrays
+
+
+def _pass_torch(img: np.ndarray, out_size: int, axis: int) -> np.ndarray:
+    in_size = img.shape[axis]
+    if in_size == out_size:
+        return img
+    xmin, counts, coef = resize_tables(in_size, out_size)
+    src = np.moveaxis(img, axis, 0).astype(np.int64)
+    acc = np.full((out_size,) + src.shape[1:], 1 << (PRE_PRECISION_BITS - 1), np.int64)
+    lift = (slice(None),) + (None,) * (src.ndim - 1)
+    for t in range(coef.shape[1]):                 # a coefficient behind a row's count is 0: its clamped tap adds nothing
+        acc += coef[:, t].astype(np.int64)[lift] * src[np.minimum(xmin.astype(np.int64) + t, in_size - 1)]
+    return np.moveaxis(np.clip(acc >> PRE_PRECISION_BITS, 0, 255).astype(np.uint8), 0, axis)
+
+
+def preprocess_images_torch(images, size=(640, 640), rescale_factor: float = 1 / 255) -> torch.Tensor:
+    """preprocess_images on the host in numpy, from the same tables: (T, 3, H, W) fp32 on the CPU, the processor's bits.  The
+    fallback where there is no device, and the tests' second opinion."""
+    out_h, out_w = _pre_size(size)
+    table = rescale_table(rescale_factor).numpy()
+    frames = [table[_pass_torch(_pass_torch(a, out_w, 1), out_h, 0)].transpose(2, 0, 1) for a in _pre_arrays(images, out_h, out_w)]
+    return torch.from_numpy(np.ascontiguousarray(np.stack(frames)))
+
+
+class _PreBuffers:
+    """pinned staging, its device copy and the uint8 scratch of preprocess_images on one device, kept and grown"""
+
+    def __init__(self):
+        self.host = self.dev = self.mid = None
+        self.copied = self.done = None   # events: the last upload has left the staging buffer / the last kernels have read dev and mid
+
+    def reserve(self, device, total: int, mid_bytes: int):
+        grow_stage = self.host is None or self.host.numel() < total
+        grow_mid = self.mid is None or self.mid.numel() < mid_bytes
+        if (grow_stage or grow_mid) and self.done is not None:
+            self.done.synchronize()              # nothing in flight reads the buffers that are let go
+        if grow_stage:
+            cap = (total + (1 << 22) - 1) >> 22 << 22
+            self.host = torch.empty((cap,), dtype=torch.uint8, pin_memory=True)
+            self.dev = torch.empty((cap,), dtype=torch.uint8, device=device)
+            self.copied, self.done = torch.cuda.Event(), torch.cuda.Event()
+        else:
+            self.copied.synchronize()            # the previous upload has read the staging buffer
+            torch.cuda.current_stream().wait_event(self.done)
+        if grow_mid:
+            self.mid = torch.empty(((max(mid_bytes, 1) + (1 << 22) - 1) >> 22 << 22,), dtype=torch.uint8, device=device)
+
+
+_pre_buffers: dict = {}
+
+
+def _align16(n: int) -> int:
+    return (n + 15) & ~15
+
+
+class _PrePlan:
+    """The staging layout of one preprocess_images call: image table | axis table | int32 pool | rescale table | frames, each part
+    and each frame at a multiple of 16 bytes.  One axis entry per distinct (in, out) pair, its xmin | counts | coefficients in the
+    pool; a pass with in == out has no table (-1)."""
+
+    def __init__(self, arrays, out_h: int, out_w: int):
+        self.out_h, self.out_w, self.T = out_h, out_w, len(arrays)
+        axis_of, axis_rows, parts, self.pool_len = {}, [], [], 0
+        passes = []
+        for a in arrays:
+            tabs = []
+            for key in ((a.shape[1], out_w), (a.shape[0], out_h)):
+                if key[0] == key[1]:
+                    tabs.append(-1)
+                    continue
+                if key not in axis_of:
+                    xmin, counts, coef = resize_tables(*key)
+                    axis_of[key] = len(axis_rows)
+                    axis_rows.append(DfinePreAxis(key[0], key[1], coef.shape[1], self.pool_len))
+                    parts.extend((xmin, counts, coef.reshape(-1)))
+                    self.pool_len += key[1] * (2 + coef.shape[1])
+                tabs.append(axis_of[key])
+            passes.append(tabs)
+        self.n_axes = len(axis_rows)
+        self.axes = (DfinePreAxis * max(self.n_axes, 1))(*axis_rows)
+        self.pool = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        self.images = (DfinePreImage * self.T)()
+        self.o_images = 0
+        self.o_axes = _align16(C.sizeof(self.images))
+        self.o_pool = _align16(self.o_axes + C.sizeof(self.axes))
+        self.o_rescale = _align16(self.o_pool + 4 * self.pool_len)
+        self.o_frames = _align16(self.o_rescale + 1024)
+        offset = mid_rows = 0
+        for i, (a, (htab, vtab)) in enumerate(zip(arrays, passes)):
+            self.images[i] = DfinePreImage(offset, a.shape[0], a.shape[1], htab, vtab, mid_rows if htab >= 0 else 0, 0)
+            offset = _align16(offset + a.size)
+            mid_rows += a.shape[0] if htab >= 0 else 0
+        self.src_bytes = offset
+        self.total = self.o_frames + offset
+        self.mid_bytes = mid_rows * out_w * 3
+
+    def fill(self, host: np.ndarray, arrays, rescale_factor: float):
+        """write the tables and the frames into the uint8 staging array"""
+        C.memmove(host.ctypes.data + self.o_images, self.images, C.sizeof(self.images))
+        C.memmove(host.ctypes.data + self.o_axes, self.axes, C.sizeof(self.axes))
+        host[self.o_pool:self.o_pool + 4 * self.pool_len].view(np.int32)[:] = self.pool
+        host[self.o_rescale:self.o_rescale + 1024].view(np.float32)[:] = rescale_table(rescale_factor).numpy()
+        for r, a in zip(self.images, arrays):
+            at = self.o_frames + r.offset
+            np.copyto(host[at:at + a.size].reshape(a.shape), a)
+
+    def launch(self, host_ptr: int, dev_ptr: int, mid_ptr: int, mid_bytes: int, out_ptr: int, stream) -> int:
+        """m355_dfine_preprocess on a staging buffer at host_ptr and its device copy at dev_ptr; returns the status"""
+        at = lambda base, off, used=True: C.c_void_p(base + off) if used else None
+        return lib.m355_dfine_preprocess(
+            at(dev_ptr, self.o_frames), self.src_bytes, at(host_ptr, self.o_images), at(dev_ptr, self.o_images), self.T,
+            at(host_ptr, self.o_axes, self.n_axes), at(dev_ptr, self.o_axes, self.n_axes), self.n_axes,
+            at(host_ptr, self.o_pool, self.n_axes), at(dev_ptr, self.o_pool, self.n_axes), self.pool_len,
+            at(dev_ptr, self.o_rescale), self.out_h, self.out_w, C.c_void_p(mid_ptr), mid_bytes, C.c_void_p(out_ptr), stream)
+
+
+def preprocess_images(images, size=(640, 640), rescale_factor: float = 1 / 255, device=None) -> torch.Tensor:
+    """RTDetrImageProcessorPil's pixel_values of a list of frames, on the device: (T, 3, H, W) fp32, bit for bit
+    processor(images=images, return_tensors="pt")["pixel_values"] for resize-to-`size` (BILINEAR) + rescale, no normalise, no pad.
+    images: PIL images in mode RGB or uint8 (h, w, 3) ndarrays of any mix of sizes inside `preprocess_in_domain` (ValueError
+    otherwise); size (H, W) or {"height", "width"}.  The frames, the per-image table, one coefficient table per distinct
+    (in, out) pair and the rescale table are packed into one pinned buffer and go up in one copy; then at most two launches
+    (csrc/dfine_preprocess.hip), asynchronous on the current stream.  Staging, device copy and scratch are kept and grown."""
+    out_h, out_w = _pre_size(size)
+    arrays = _pre_arrays(images, out_h, out_w)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("preprocess_images runs on a CUDA device; preprocess_images_torch is the host path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    plan = _PrePlan(arrays, out_h, out_w)
+    with torch.cuda.device(device):
+        buf = _pre_buffers.setdefault(device, _PreBuffers())
+        buf.reserve(device, plan.total, plan.mid_bytes)
+        plan.fill(buf.host.numpy(), arrays, rescale_factor)
+        buf.dev[:plan.total].copy_(buf.host[:plan.total], non_blocking=True)
+        buf.copied.record()
+        out = torch.empty((len(arrays), 3, out_h, out_w), dtype=torch.float32, device=device)
+        check(plan.launch(buf.host.data_ptr(), buf.dev.data_ptr(), buf.mid.data_ptr(), buf.mid.numel(), out.data_ptr(), _stream()))
+        buf.done.record()
+    return out
+
+
+def _processor_fast_path(processor, images, annotations, kwargs):
+    """(frames, (H, W), rescale_factor) where bind_processor's preprocess takes the kernel path, else None"""
+    known = {"do_resize", "size", "resample", "do_rescale", "rescale_factor", "do_normalize", "do_pad", "return_tensors",
+             "image_mean", "image_std", "do_convert_annotations", "format", "pad_size"}
+    if annotations is not None or not set(kwargs) <= known or not torch.cuda.is_available():
+        return None
+    opt = lambda name: kwargs[name] if name in kwargs else getattr(processor, name, None)   # upstream's setdefault from self
+    if not opt("do_resize") or not opt("do_rescale") or opt("do_normalize") or opt("do_pad") or opt("return_tensors") != "pt":
+        return None
+    try:
+        size = {k: v for k, v in dict(opt("size")).items() if v is not None}
+        if set(size) != {"height", "width"} or int(opt("resample")) != 2:   # PIL.Image.BILINEAR
+            return None
+        out_h, out_w = int(size["height"]), int(size["width"])
+        factor = float(opt("rescale_factor"))
+    except (TypeError, ValueError):
+        return None
+    frames = list(images) if isinstance(images, (list, tuple)) else [images]
+    arrays = [_as_rgb_array(im) for im in frames]
+    if not arrays or len(arrays) > PRE_MAX_FRAMES or any(a is None for a in arrays):
+        return None
+    if not all(preprocess_in_domain(a.shape[0], a.shape[1], out_h, out_w) for a in arrays):
+        return None
+    return arrays, (out_h, out_w), factor
+
+
+def processor_preprocess(self, images, annotations=None, return_segmentation_masks=None, masks_path=None, **kwargs):
+    """RTDetrImageProcessorPil.preprocess of a processor bound by bind_processor: the kernel path where `_processor_fast_path`
+    holds (pixel_values come back on the current CUDA device), upstream's own method with its result untouched otherwise."""
+    fast = _processor_fast_path(self, images, annotations, kwargs)
+    if fast is None:
+        preprocess_calls["original"] += 1
+        return self._m355_unbound.preprocess(self, images, annotations, return_segmentation_masks, masks_path, **kwargs)
+    from transformers.image_processing_base import BatchFeature
+    arrays, size, factor = fast
+    preprocess_calls["kernel"] += 1
+    return BatchFeature({"pixel_values": preprocess_images(arrays, size, factor)})
+
+
+_bound_processor_classes: dict = {}
+
+
+def bind_processor(processor):
+    """Make processor(images=frames, return_tensors="pt") return a BatchFeature whose pixel_values is already on the GPU
+    (INTEGRATION.md): the INSTANCE gets a subclass of its own class, under the same name, whose `preprocess` is
+    `processor_preprocess`.  Its class, its attributes, its config (to_dict) and what save_pretrained writes stay as they are;
+    every call outside the fast path runs upstream's method.  Returns the processor."""
+    cls = type(processor)
+    if cls in _bound_processor_classes.values():
+        return processor
+    if cls not in _bound_processor_classes:
+        _bound_processor_classes[cls] = type(cls.__name__, (cls,), {
+            "preprocess": processor_preprocess, "_m355_unbound": cls,   # class attributes: the instance's __dict__ is its config
+            "__module__": cls.__module__, "__qualname__": cls.__qualname__, "__doc__": cls.__doc__})
+    processor.__class__ = _bound_processor_classes[cls]
+    return processor
 
 
 # ---- temporal encoder layers (nn.TransformerEncoderLayer, post-norm, ReLU, head dim 32) between their GEMMs ---------------------

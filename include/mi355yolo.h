@@ -711,6 +711,53 @@ int m355_dfine_match(const float* d_logits, const float* d_pred_boxes, int32_t B
 int m355_dfine_postprocess(const float* d_logits, const float* d_pred_boxes, int32_t B, int32_t Q, int32_t C, const float* d_sizes,
                            float threshold, float* d_scores, int64_t* d_labels, float* d_boxes, int32_t* d_counts, void* stream);
 
+/* ---- Image pre-processing of a D-FINE / RT-DETR model --------------------------------------------------------------------
+ * m355_dfine_preprocess = RTDetrImageProcessorPil.preprocess with its defaults (transformers
+ * models/rt_detr/image_processing_pil_rt_detr.py: resize to a fixed (out_h, out_w) with Pillow's BILINEAR, rescale, no normalise,
+ * no pad), which every D-FINE script of the reference runs on the host for each sequence of frames: T decoded uint8 RGB images
+ * (h, w, 3) of any mix of sizes, packed in the device buffer d_src, become the model's input d_out fp32 (T, 3, out_h, out_w),
+ * contiguous and planar, bit for bit what the processor returns.  At most TWO launches whatever T and however many sizes:
+ * the horizontal pass of every image that needs one into the uint8 scratch d_work (rows of 3 * out_w bytes), then the vertical
+ * pass and the rescale; asynchronous on `stream`, no host round trip.
+ *
+ * Pillow's 8-bit resize is a separable fixed-point filter; its per-axis tables are built by the caller
+ * (dfine.resize_tables) and shared by all images of one (in, out) pair.  Axis table a lies in the int32 pool at
+ * axes[a].offset: xmin[out_size], count[out_size], coef[out_size][ksize].  A pass computes
+ * clip((2^21 + sum_{t < count} coef[t] * pixel[xmin + t]) >> 22, 0, 255) in int32 into uint8: horizontal first, the uint8 result
+ * feeds the vertical pass; the final byte b becomes rescale[b] (256 fp32 values of the caller, no device arithmetic).  A pass
+ * whose sizes are equal has table index -1 and is a copy.
+ *
+ * The three tables are passed twice: h_* on the HOST, which this call validates before any HIP call, and d_* their DEVICE
+ * copies with the same bytes, which the kernels read (the caller keeps both in one staging buffer and uploads it once).
+ * M355_ERR_INVALID: a NULL pointer; T outside [1, 65535]; out_h outside [1, M355_DFINE_PRE_MAX_H], out_w outside
+ * [4, M355_DFINE_PRE_MAX_W] or not a multiple of 4 (16-byte stores); d_src, d_work or d_out not 16-byte aligned; src_bytes not a
+ * multiple of 16 (rows are staged in 16-byte loads); an axis with in_size or out_size out of range, ksize outside
+ * [1, M355_DFINE_PRE_MAX_TAPS], a table that leaves the pool, count outside [1, ksize], xmin < 0 or xmin + count > in_size, a
+ * coefficient outside [0, 2^23] or a row of coefficients summing above 2^23 (the int32 sums stay below 2^31); an image whose
+ * offset is negative or not a multiple of 16, whose bytes leave [0, src_bytes), whose in_h is outside [1, M355_DFINE_PRE_MAX_H]
+ * or in_w outside [1, M355_DFINE_PRE_MAX_W], whose table index is neither -1 with in == out nor an axis of its (in, out), or
+ * whose mid_row is not the sum of in_h over the earlier images with a horizontal pass; a scratch smaller than those rows. */
+#define M355_DFINE_PRE_MAX_TAPS 64
+#define M355_DFINE_PRE_MAX_W 4096
+#define M355_DFINE_PRE_MAX_H 16384
+typedef struct {
+  int64_t offset;            /* byte offset of the image's first pixel in d_src, a multiple of 16; 3 * in_h * in_w bytes */
+  int32_t in_h, in_w;        /* source size */
+  int32_t htab, vtab;        /* axis table of the horizontal / vertical pass, -1: skipped (in_w == out_w / in_h == out_h) */
+  int32_t mid_row;           /* first of the image's in_h rows in d_work (read only where htab >= 0) */
+  int32_t reserved;
+} m355_dfine_pre_image;
+typedef struct {
+  int32_t in_size, out_size;
+  int32_t ksize;             /* coefficients stored per output index */
+  int32_t offset;            /* index of the table's first int32 in the pool */
+} m355_dfine_pre_axis;
+int m355_dfine_preprocess(const uint8_t* d_src, int64_t src_bytes, const m355_dfine_pre_image* h_images,
+                          const m355_dfine_pre_image* d_images, int32_t T, const m355_dfine_pre_axis* h_axes,
+                          const m355_dfine_pre_axis* d_axes, int32_t n_axes, const int32_t* h_pool, const int32_t* d_pool,
+                          int64_t pool_len, const float* d_rescale, int32_t out_h, int32_t out_w, void* d_work, int64_t work_bytes,
+                          float* d_out, void* stream);
+
 /* ---- Encoder query selection of a D-FINE model ---------------------------------------------------------------------------
  * m355_dfine_select_forward = the block of DFineModel.forward between the encoder's heads and the decoder (transformers 5.15.0
  * modeling_d_fine.py:1804-1828): per image the K tokens with the greatest score, score = the max over C of class_logits, and the
