@@ -97,6 +97,17 @@ class DfinePreAxis(C.Structure):
     _fields_ = [("in_size", C.c_int32), ("out_size", C.c_int32), ("ksize", C.c_int32), ("offset", C.c_int32)]
 
 
+class DfineOptimRow(C.Structure):
+    """m355_dfine_optim_row (include/mi355yolo.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_int64),
+                ("chunk0", C.c_int32), ("lr", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("one_minus_beta1", C.c_float),
+                ("one_minus_beta2", C.c_float), ("decay", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+DFINE_OPTIM_CHUNK = 4096          # M355_DFINE_OPTIM_CHUNK
+DFINE_OPTIM_MAX_TENSORS = 65536   # M355_DFINE_OPTIM_MAX_TENSORS
+DFINE_OPTIM_ADAM, DFINE_OPTIM_ADAMW = 0, 1
 DFINE_PRE_MAX_TAPS = 64       # M355_DFINE_PRE_MAX_TAPS
 DFINE_PRE_MAX_W = 4096        # M355_DFINE_PRE_MAX_W
 DFINE_PRE_MAX_H = 16384       # M355_DFINE_PRE_MAX_H
@@ -241,6 +252,9 @@ SIGNATURES = {
     "m355_dfine_consistency_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "m355_dfine_consistency_loss_forward": (C.c_int, [_P, C.c_int32, C.c_int64, _P, C.c_int64, _P, _P]),
     "m355_dfine_consistency_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P]),
+    "m355_dfine_grad_sumsq_launch": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "m355_dfine_clip_scale_launch": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int64, C.c_float, _P, _P]),
+    "m355_dfine_adam_launch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_float, _P, _P]),
     "m355_repack_launch": (C.c_int, [_P, _P, C.c_int32, _P]),
     "m355_sppf_pool_bwd_launch": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -282,6 +282,13 @@ int launch_msda_backward(const float* grad_out, const float* value, const float*
 int launch_dfine_decode_backward(const float* grad_boxes, const float* dist, const float* project, const float* ref,
                                  float* grad_dist, float* grad_ref, long n, int nbins1, float reg_scale, int clamp01,
                                  hipStream_t s, bool guard = false);
+// The end of the trainers' step (dfine_optim.hip): squared gradient norm, clip and Adam / AdamW update over a device table of
+// m355_dfine_optim_row (count rows, `chunks` chunks in all = the grid).  norm: two floats, the norm and the clip coefficient, written
+// by launch_dfine_grad_norm from the chunks' partial sums; launch_dfine_adam applies the coefficient when norm is not nullptr.
+int launch_dfine_grad_sumsq(const void* d_table, int count, int chunks, float* partials, hipStream_t s);
+int launch_dfine_grad_norm(const float* partials, int chunks, float max_norm, float* norm, hipStream_t s);
+int launch_dfine_clip_scale(const void* d_table, int count, int chunks, const float* norm, hipStream_t s);
+int launch_dfine_adam(const void* d_table, int count, int chunks, bool adamw, const float* norm, hipStream_t s);
 // The recurrence of a one-layer GRU with hidden size 256 (dfine_gru.hip): every chain (sequence x direction) on 8 persistent
 // workgroups, one launch each way.  dfine_gru_check: nullptr = the shape is taken, else why not.  work: the exchange ring first
 // (zeroed on the stream by the launchers), then the saved gates when `keep` / in the backward; status: one sticky int32.

@@ -169,6 +169,26 @@ const char* dfine_consistency_check(int32_t T, int64_t N) {
   return nullptr;
 }
 
+// the table of the optimizer entries (dfine_optim.hip): one block per chunk, found from the rows' chunk0 prefix.  adam: p, m, v are
+// used too.  nullptr = accepted and *chunks = the grid, else the message
+const char* dfine_optim_check(const m355_dfine_optim_row* h, const m355_dfine_optim_row* d, int32_t count, bool adam, int* chunks) {
+  if (!h || !d) return "null table";
+  if (count < 1 || count > M355_DFINE_OPTIM_MAX_TENSORS) return "the tensor count must be in [1, 65536]";
+  int64_t total = 0;
+  for (int i = 0; i < count; ++i) {
+    const m355_dfine_optim_row& r = h[i];
+    if (r.numel < 0) return "negative numel";
+    if (((uintptr_t)r.p | (uintptr_t)r.g | (uintptr_t)r.m | (uintptr_t)r.v) & 3u) return "pointers must be 4-byte aligned";
+    if (r.numel > 0 && (!r.g || (adam && (!r.p || !r.m || !r.v)))) return "null pointer in a row with elements";
+    if (r.chunk0 != total) return "chunk0 is not the number of chunks of the rows before it";
+    total += (r.numel + M355_DFINE_OPTIM_CHUNK - 1) / M355_DFINE_OPTIM_CHUNK;   // numel <= 2^63 - 1: no overflow before the test
+    if (total > kGridMax) return "more chunks than one launch can index (2^31 - 1)";
+  }
+  if (total < 1) return "no elements";
+  *chunks = (int)total;
+  return nullptr;
+}
+
 }  // namespace
 
 int m355_msda_forward(const float* d_value, int32_t B, int32_t S, int32_t heads, int32_t head_dim, const int32_t* shapes_hw,
@@ -665,4 +685,35 @@ int m355_dfine_consistency_loss_backward(const float* d_grad_out, const float* d
   if (any_null({d_grad_out, d_a, d_grad_a})) return invalid(__func__, "null pointer");
   if (const char* why = dfine_consistency_check(T, N)) return invalid(__func__, why);
   return launched(__func__, launch_dfine_consistency_backward(d_grad_out, d_a, T, (long)N, d_grad_a, (hipStream_t)stream));
+}
+// the end of the trainers' step (dfine_optim.hip)
+int m355_dfine_grad_sumsq_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count,
+                                 float* d_partials, int64_t partials_len, void* stream) {
+  int chunks = 0;
+  if (const char* why = dfine_optim_check(h_table, d_table, count, false, &chunks)) return invalid(__func__, why);
+  if (!d_partials || partials_len < chunks) return invalid(__func__, "partials missing or shorter than the number of chunks");
+  if ((uintptr_t)d_partials & 3u) return invalid(__func__, "pointers must be 4-byte aligned");
+  return launched(__func__, launch_dfine_grad_sumsq(d_table, count, chunks, d_partials, (hipStream_t)stream));
+}
+int m355_dfine_clip_scale_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count,
+                                 const float* d_partials, int64_t partials_len, float max_norm, float* d_norm, void* stream) {
+  int chunks = 0;
+  if (const char* why = dfine_optim_check(h_table, d_table, count, false, &chunks)) return invalid(__func__, why);
+  if (!d_partials || partials_len < chunks) return invalid(__func__, "partials missing or shorter than the number of chunks");
+  if (!d_norm) return invalid(__func__, "null pointer (norm)");
+  if (((uintptr_t)d_partials & 3u) || ((uintptr_t)d_norm & 7u)) return invalid(__func__, "partials must be 4-byte aligned, norm 8-byte aligned");
+  if (int rc = launch_dfine_grad_norm(d_partials, chunks, max_norm, d_norm, (hipStream_t)stream)) return launched(__func__, rc);
+  return launched(__func__, launch_dfine_clip_scale(d_table, count, chunks, d_norm, (hipStream_t)stream));
+}
+int m355_dfine_adam_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count, int32_t mode,
+                           const float* d_partials, int64_t partials_len, float max_norm, float* d_norm, void* stream) {
+  int chunks = 0;
+  if (const char* why = dfine_optim_check(h_table, d_table, count, true, &chunks)) return invalid(__func__, why);
+  if (mode != M355_DFINE_OPTIM_ADAM && mode != M355_DFINE_OPTIM_ADAMW) return invalid(__func__, "mode is neither ADAM (0) nor ADAMW (1)");
+  if ((d_partials == nullptr) != (d_norm == nullptr)) return invalid(__func__, "partials and norm come together or not at all");
+  if (d_partials && partials_len < chunks) return invalid(__func__, "partials shorter than the number of chunks");
+  if (((uintptr_t)d_partials & 3u) || ((uintptr_t)d_norm & 7u)) return invalid(__func__, "partials must be 4-byte aligned, norm 8-byte aligned");
+  if (d_partials)
+    if (int rc = launch_dfine_grad_norm(d_partials, chunks, max_norm, d_norm, (hipStream_t)stream)) return launched(__func__, rc);
+  return launched(__func__, launch_dfine_adam(d_table, count, chunks, mode == M355_DFINE_OPTIM_ADAMW, d_norm, (hipStream_t)stream));
 }

@@ -59,6 +59,12 @@ scores and the clamp / nan_to_num of the class logits, the nan_to_num chain arou
 frame against "no object" and the frame-to-frame consistency loss, each one launch forward and one backward
 (csrc/dfine_temporal.hip; the guarded decode is an instance of the decode kernels), with torch's gradients at the guards; CPU
 tensors take the same expressions in torch ops (``*_torch``).
+
+``clip_grad_norm_`` / ``bind_optimizer`` are the three lines every trainer ends its step with (``loss.backward()``,
+``torch.nn.utils.clip_grad_norm_(params, 1.0)``, ``optimizer.step()`` of ``torch.optim.Adam`` / ``AdamW``): the squared norm of all
+gradients, the clip and the update as multi-tensor launches over a device table with one row per tensor (csrc/dfine_optim.hip),
+a number of launches that does not depend on the number of tensors, no synchronisation, the optimizer's state in torch's own
+layout; anything outside the kernels' domain runs torch's own function.
 """
 from __future__ import annotations
 
@@ -72,7 +78,8 @@ from typing import List, NamedTuple, Sequence
 import numpy as np
 import torch
 
-from ._capi import DFINE_PRE_MAX_H, DFINE_PRE_MAX_TAPS, DFINE_PRE_MAX_W, DfinePreAxis, DfinePreImage, check, lib
+from ._capi import (DFINE_OPTIM_ADAM, DFINE_OPTIM_ADAMW, DFINE_OPTIM_CHUNK, DFINE_OPTIM_MAX_TENSORS, DFINE_PRE_MAX_H,
+                    DFINE_PRE_MAX_TAPS, DFINE_PRE_MAX_W, DfineOptimRow, DfinePreAxis, DfinePreImage, check, lib)
 
 _raise_on_error = check   # for hungarian_match, whose keyword `check` is upstream-facing
 
@@ -2659,3 +2666,334 @@ def temporal_head(fused: torch.Tensor, init_ref: torch.Tensor, class_head, bbox_
     cls_logits = guard_logits(class_head(x), anomaly, bound)
     bbox_pred = decode_boxes(bbox_head(x), project, init_ref, reg_scale, clamp01=True, guard=True)
     return cls_logits, bbox_pred, anomaly
+
+
+# ---- the end of the trainers' step: clip_grad_norm_ and the Adam / AdamW update (csrc/dfine_optim.hip) ----
+
+OPTIM_CHUNK = DFINE_OPTIM_CHUNK                # elements of a tensor that one block takes
+OPTIM_MAX_TENSORS = DFINE_OPTIM_MAX_TENSORS    # rows of one table; a longer list takes torch's own function
+OPTIM_RING = 4                                 # pinned tables in flight before a step waits for the oldest copy
+optim_calls = {"kernel": 0, "torch": 0}        # clip_grad_norm_ calls and bound steps by path (tests and tools read it)
+_OPTIM_ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i8"), ("chunk0", "<i4"), ("lr", "<f4"),
+                       ("weight_decay", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"), ("step_size", "<f4"),
+                       ("bc2_sqrt", "<f4"), ("one_minus_beta1", "<f4"), ("one_minus_beta2", "<f4"), ("decay", "<f4"),
+                       ("reserved", "<i4", (3,))])
+assert _OPTIM_ROW.itemsize == C.sizeof(DfineOptimRow) == 96
+
+
+class _OptimTables:
+    """The tables of one caller on one device: a ring of pinned buffers, each with its device copy and the event after the
+    launches that read it, and the partial sums of the norm.  A pinned buffer is rewritten only after its event has passed."""
+
+    def __init__(self, device):
+        self.device = device
+        self.slots = [None] * OPTIM_RING   # [host tensor, rows (numpy view of it), device tensor, event]
+        self.turn = 0
+        self.partials = None
+
+    def take(self, n: int):
+        """the next slot with room for n rows, its earlier upload and launches behind it"""
+        if self.slots[0] is None or self.slots[0][1].shape[0] < n:   # all slots at once: no pinned allocation in a later step
+            cap = max(64, 1 << (n - 1).bit_length())
+            for i in range(OPTIM_RING):
+                host = torch.empty((cap * _OPTIM_ROW.itemsize,), dtype=torch.uint8, pin_memory=True)
+                self.slots[i] = [host, host.numpy().view(_OPTIM_ROW), torch.empty_like(host, device=self.device, pin_memory=False),
+                                 torch.cuda.Event()]
+        slot = self.slots[self.turn]
+        self.turn = (self.turn + 1) % OPTIM_RING
+        if not slot[3].query():
+            slot[3].synchronize()          # the GPU is OPTIM_RING steps behind: wait for the oldest
+        return slot
+
+    def reserve_partials(self, chunks: int) -> torch.Tensor:
+        if self.partials is None or self.partials.numel() < chunks:
+            self.partials = torch.empty((max(1024, 1 << (chunks - 1).bit_length()),), dtype=torch.float32, device=self.device)
+        return self.partials
+
+
+def _optim_upload(slot, n: int):
+    """rows [0, n) of the slot's pinned table to its device copy, one asynchronous copy; -> (host pointer, device pointer)"""
+    nbytes = n * _OPTIM_ROW.itemsize
+    slot[2][:nbytes].copy_(slot[0][:nbytes], non_blocking=True)
+    return C.c_void_p(slot[0].data_ptr()), C.c_void_p(slot[2].data_ptr())
+
+
+def _optim_chunks(numel: np.ndarray, rows: np.ndarray) -> int:
+    """write numel and the chunk prefix of the rows; -> the number of chunks (the grid)"""
+    chunks = (numel + (OPTIM_CHUNK - 1)) // OPTIM_CHUNK
+    ends = np.cumsum(chunks)
+    total = int(ends[-1])
+    if total > 0x7fffffff:
+        raise ValueError("the tensors have more chunks than one launch can index")
+    rows["numel"] = numel
+    rows["chunk0"] = ends - chunks
+    return total
+
+
+_clip_tables: dict = {}
+
+
+def _clip_takes(grads, norm_type, error_if_nonfinite) -> bool:
+    if not grads or len(grads) > OPTIM_MAX_TENSORS or error_if_nonfinite:
+        return False
+    try:
+        if float(norm_type) != 2.0:
+            return False
+    except (TypeError, ValueError):
+        return False
+    dev = grads[0].device
+    return dev.type == "cuda" and all(g.device == dev and g.dtype is torch.float32 and g.layout is torch.strided and
+                                      g.is_contiguous() for g in grads)
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ for contiguous fp32 CUDA gradients and the 2-norm, three launches and one table upload
+    whatever the number of tensors: the squared sums of all chunks, their sum in a fixed order with the norm and the coefficient
+    c = min(1, max_norm / (norm + 1e-6)) in double, and g = g c in place, rounded once (c == 1 gives every bit back).  Returns
+    the total norm as a 0-d device tensor and does not synchronise; bitwise reproducible.  Non-finite gradients behave as with
+    error_if_nonfinite=False.  Any other norm_type, error_if_nonfinite=True, CPU, non-fp32, sparse or non-contiguous gradients
+    and lists over OPTIM_MAX_TENSORS take torch's function; `foreach` only matters there."""
+    parameters = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not _clip_takes(grads, norm_type, error_if_nonfinite):
+        optim_calls["torch"] += 1
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type, error_if_nonfinite, foreach)
+    dev = grads[0].device
+    grads = [g for g in grads if g.numel() > 0]
+    out = torch.empty((4,), dtype=torch.float32, device=dev)
+    if not grads:
+        return out.zero_()[0]
+    n = len(grads)
+    with torch.cuda.device(dev):
+        tables = _clip_tables.get(dev)
+        if tables is None:
+            tables = _clip_tables[dev] = _OptimTables(dev)
+        slot = tables.take(n)
+        rows = slot[1][:n]
+        rows["g"] = [g.data_ptr() for g in grads]
+        chunks = _optim_chunks(np.array([g.numel() for g in grads], np.int64), rows)
+        partials = tables.reserve_partials(chunks)
+        h, d = _optim_upload(slot, n)
+        stream = _stream()
+        check(lib.m355_dfine_grad_sumsq_launch(h, d, n, _ptr(partials), partials.numel(), stream))
+        check(lib.m355_dfine_clip_scale_launch(h, d, n, _ptr(partials), partials.numel(), float(max_norm), _ptr(out), stream))
+        slot[3].record()
+    optim_calls["kernel"] += 1
+    return out[0]
+
+
+def _optim_group_takes(group) -> bool:
+    """the default flags of torch.optim.Adam / AdamW, python-number hyper-parameters"""
+    if group.get("amsgrad") or group.get("maximize") or group.get("capturable") or group.get("differentiable") or group.get("fused"):
+        return False
+    betas = group["betas"]
+    return not any(isinstance(x, torch.Tensor) for x in (group["lr"], group["weight_decay"], group["eps"], betas[0], betas[1]))
+
+
+def _optim_tensor_takes(t, device) -> bool:
+    return (isinstance(t, torch.Tensor) and t.device == device and t.dtype is torch.float32 and t.layout is torch.strided and
+            t.is_contiguous())
+
+
+class _OptimEntry:
+    """a parameter of a bound optimizer as its step last saw it: the state tensors it has checked, their pointers, and the
+    parameter's slot in the host buffer of step counts.  Compared by identity."""
+    __slots__ = ("ptr", "m", "v", "step", "m_ptr", "v_ptr", "numel", "slot")
+
+
+class _BoundAdam:
+    """What a bound optimizer keeps between steps: its tables, one entry per parameter that has had a gradient, and the rows of
+    the last step that do not change while the same parameters have gradients (p, m, v, numel, the chunk prefix).
+    The `step` tensors of the optimizer's state are 0-d views of ONE host buffer: torch keeps a 0-d fp32 host tensor per
+    parameter and adds 1 to each, which for some hundred tensors costs more than the whole update on the device; as views they
+    are incremented and read with one numpy operation.  To torch, to state_dict() and to a checkpoint each is the 0-d tensor it
+    always was; a `step` that came in through load_state_dict() is copied into the buffer and replaced by its view."""
+
+    def __init__(self, device, max_norm, n_params: int):
+        self.device = device
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.tables = _OptimTables(device)
+        self.entries = {}
+        self.slot_of = {}
+        self.steps = torch.zeros((max(64, n_params),), dtype=torch.float64 if torch.get_default_dtype() is torch.float64 else torch.float32)
+        self.steps_np = self.steps.numpy()
+        self.cached = None
+
+    def _step_view(self, optimizer, p, value: float) -> int:
+        """the slot of p in the buffer of step counts, holding `value`"""
+        i = self.slot_of.get(p)
+        if i is None:
+            i = self.slot_of[p] = len(self.slot_of)
+            if i >= self.steps.numel():              # parameters added after the binding: a larger buffer, every view moved
+                old = self.steps
+                self.steps = torch.zeros((2 * (i + 1),), dtype=old.dtype)
+                self.steps[:old.numel()] = old
+                self.steps_np = self.steps.numpy()
+                for q, e in self.entries.items():
+                    if optimizer.state[q].get("step") is e.step:
+                        e.step = optimizer.state[q]["step"] = self.steps[e.slot]
+        self.steps_np[i] = value
+        return i
+
+    def entry(self, optimizer, p):
+        """the checked entry of a parameter that has a gradient, its state created as torch creates it; None: outside the domain"""
+        st = optimizer.state[p]
+        e = self.entries.get(p)
+        if len(st) == 0:
+            i = self._step_view(optimizer, p, 0.0)
+            st["step"] = self.steps[i]
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            e = None
+        ptr = p.data_ptr()
+        m, v, step = st.get("exp_avg"), st.get("exp_avg_sq"), st.get("step")
+        if e is not None and e.ptr == ptr and e.m is m and e.v is v and e.step is step:
+            return e
+        if not (_optim_tensor_takes(p, self.device) and _optim_tensor_takes(m, self.device) and _optim_tensor_takes(v, self.device) and
+                m.shape == p.shape and v.shape == p.shape and isinstance(step, torch.Tensor) and step.device.type == "cpu" and
+                step.numel() == 1 and step.dtype in (torch.float32, torch.float64)):
+            return None
+        e = self.entries[p] = _OptimEntry()
+        e.ptr, e.m, e.v, e.m_ptr, e.v_ptr, e.numel = ptr, m, v, m.data_ptr(), v.data_ptr(), p.numel()
+        e.slot = self._step_view(optimizer, p, float(step))
+        e.step = st["step"] = self.steps[e.slot]
+        return e
+
+    def collect(self, optimizer):
+        """-> (entries, gradients, group index of each, mode, entries without elements) of the parameters that have a gradient,
+        or None when this step is outside the kernels' domain; parameters without elements get no row (torch updates nothing of
+        them but `step`)"""
+        if getattr(optimizer, "grad_scale", None) is not None or getattr(optimizer, "found_inf", None) is not None:
+            return None
+        ents, grads, gidx, empty = [], [], [], []
+        mode = None
+        for gi, group in enumerate(optimizer.param_groups):
+            if not _optim_group_takes(group):
+                return None
+            m = DFINE_OPTIM_ADAMW if group.get("decoupled_weight_decay") else DFINE_OPTIM_ADAM
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.layout is not torch.strided or not g.is_contiguous():
+                    return None
+                e = self.entry(optimizer, p)
+                if e is None or (mode is not None and mode != m):
+                    return None
+                mode = m
+                if e.numel == 0:
+                    empty.append(e)
+                    continue
+                ents.append(e)
+                grads.append(g)
+                gidx.append(gi)
+        if len(ents) > OPTIM_MAX_TENSORS:
+            return None
+        return ents, grads, gidx, mode, empty
+
+    def static_rows(self, ents, gidx):
+        """-> (rows with p, m, v, numel and chunk0 filled, chunks, group index array, step slot array), kept while the same
+        entries come in the same order"""
+        c = self.cached
+        if c is None or c[0] != ents or c[1] != gidx:
+            rows = np.zeros((len(ents),), _OPTIM_ROW)
+            rows["p"] = [e.ptr for e in ents]
+            rows["m"] = [e.m_ptr for e in ents]
+            rows["v"] = [e.v_ptr for e in ents]
+            chunks = _optim_chunks(np.array([e.numel for e in ents], np.int64), rows)
+            c = self.cached = (ents, gidx, rows, chunks, np.asarray(gidx, np.intp), np.array([e.slot for e in ents], np.intp))
+        return c[2:]
+
+    def bump(self, slots) -> np.ndarray:
+        """add 1 to the step counts in `slots`; -> the new counts in double"""
+        self.steps_np[slots] += 1
+        return self.steps_np[slots].astype(np.float64)
+
+
+def _optimizer_step(self, closure=None):
+    """`step` of an optimizer bound by bind_optimizer"""
+    bound = self._m355_optim
+    loss = None
+    if closure is not None:
+        with torch.enable_grad():
+            loss = closure()
+    with torch.no_grad():
+        plan = bound.collect(self)
+        if plan is None:
+            # torch's own clip and step on the same state, without a second round of the step hooks (this call runs inside them)
+            optim_calls["torch"] += 1
+            self.last_grad_norm = None
+            if bound.max_norm is not None:
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_([p for g in self.param_groups for p in g["params"]],
+                                                                     bound.max_norm)
+            torch_step = type(self).step
+            getattr(torch_step, "__wrapped__", torch_step)(self)
+            return loss
+        ents, grads, gidx, mode, empty = plan
+        self.last_grad_norm = None
+        if empty:
+            bound.bump(np.array([e.slot for e in empty], np.intp))
+        n = len(ents)
+        if n == 0:
+            return loss
+        static, chunks, gidx, slots = bound.static_rows(ents, gidx)
+        t = bound.bump(slots)
+        hyper = np.array([(g["lr"], g["weight_decay"], g["betas"][0], g["betas"][1], g["eps"]) for g in self.param_groups], np.float64)
+        lr, wd, beta1, beta2, eps = hyper[gidx].T
+        with torch.cuda.device(bound.device):
+            slot = bound.tables.take(n)
+            rows = slot[1][:n]
+            rows[:] = static
+            rows["g"] = [g.data_ptr() for g in grads]
+            rows["lr"], rows["weight_decay"], rows["beta1"], rows["beta2"], rows["eps"] = lr, wd, beta1, beta2, eps
+            rows["step_size"] = lr / (1.0 - beta1 ** t)            # in double, each tensor with its own step count
+            rows["bc2_sqrt"] = np.sqrt(1.0 - beta2 ** t)
+            rows["one_minus_beta1"], rows["one_minus_beta2"], rows["decay"] = 1.0 - beta1, 1.0 - beta2, 1.0 - lr * wd
+            h, d = _optim_upload(slot, n)
+            stream = _stream()
+            if bound.max_norm is None:
+                check(lib.m355_dfine_adam_launch(h, d, n, mode, None, 0, 0.0, None, stream))
+            else:
+                partials = bound.tables.reserve_partials(chunks)
+                norm = torch.empty((4,), dtype=torch.float32, device=bound.device)
+                check(lib.m355_dfine_grad_sumsq_launch(h, d, n, _ptr(partials), partials.numel(), stream))
+                check(lib.m355_dfine_adam_launch(h, d, n, mode, _ptr(partials), partials.numel(), bound.max_norm, _ptr(norm), stream))
+                self.last_grad_norm = norm[0]
+            slot[3].record()
+        optim_calls["kernel"] += 1
+    return loss
+
+
+def _hooked_optimizer_step(self, closure=None):
+    self._opt_called = True              # what an lr_scheduler's wrapper of `step` sets: its call-order check reads it
+    return _optimizer_step_with_hooks(self, closure)
+
+
+_optimizer_step_with_hooks = torch.optim.Optimizer.profile_hook_step(_optimizer_step)   # torch's step pre- and post-hooks
+_hooked_optimizer_step._wrapped_by_lr_sched = True   # a scheduler constructed later finds `step` wrapped and leaves it alone
+
+
+def bind_optimizer(optimizer, max_norm=None):
+    """Give THIS optimizer instance a `step` that runs the update of all its parameters as one launch (csrc/dfine_optim.hip);
+    returns its argument.  Bound: torch.optim.Adam and torch.optim.AdamW with their default flags (no amsgrad, maximize,
+    capturable, differentiable, fused) whose parameters are all contiguous fp32 tensors on one CUDA device; anything else comes
+    back untouched and runs torch's step.  The state is torch's own (`step` a 0-d tensor on the host, exp_avg, exp_avg_sq,
+    created lazily; the `step` tensors of one bound optimizer are views of one host buffer, so that all of them are incremented at
+    once), so state_dict() / load_state_dict() and checkpoints interchange with an unbound optimizer; parameters without a gradient are
+    skipped, the groups' hyper-parameters are read on every call (schedulers work, bound before or after their construction),
+    and the step does not synchronise: the table goes up as one asynchronous copy from a ring of pinned buffers.
+    max_norm: fold torch.nn.utils.clip_grad_norm_(all parameters, max_norm) into the step: one launch for the squared norm, and
+    the coefficient applied inside the update.  The trainer drops its clip line; `.grad` stays as backward left it (it is not
+    scaled in place, unlike clip_grad_norm_) and `optimizer.last_grad_norm` is the total norm as a 0-d device tensor.
+    A step that meets something outside the domain (a non-contiguous gradient, a flag switched on later) runs torch's
+    clip_grad_norm_ and step for that call."""
+    import types
+    if type(optimizer) not in (torch.optim.Adam, torch.optim.AdamW) or not all(_optim_group_takes(g) for g in optimizer.param_groups):
+        return optimizer
+    params = [p for g in optimizer.param_groups for p in g["params"]]
+    if not params or params[0].device.type != "cuda" or not all(_optim_tensor_takes(p, params[0].device) for p in params):
+        return optimizer
+    optimizer._m355_optim = _BoundAdam(params[0].device, max_norm, len(params))
+    optimizer.last_grad_norm = None
+    optimizer.step = types.MethodType(_hooked_optimizer_step, optimizer)
+    return optimizer

@@ -1025,6 +1025,59 @@ int m355_dfine_consistency_loss_forward(const float* d_a, int32_t T, int64_t N, 
 int m355_dfine_consistency_loss_backward(const float* d_grad_out, const float* d_a, int32_t T, int64_t N, float* d_grad_a,
                                          void* stream);
 
+/* ---- The end of the D-FINE trainers' step: gradient clipping and the Adam / AdamW update ---------------------------------------
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) (2-norm) and the step of torch.optim.Adam / AdamW with their default flags,
+ * over a whole list of fp32 tensors per launch.  The kernels work from a table of m355_dfine_optim_row, one row per tensor, which
+ * the caller passes twice: h_table on the host, read and checked by the entry, and d_table, the same bytes on the device, read by
+ * the kernels (the caller's asynchronous copy, ordered before the entry on `stream`).  A tensor of numel elements is
+ * ceil(numel / M355_DFINE_OPTIM_CHUNK) chunks, one block each; chunk0 of a row is the number of chunks of the rows before it.
+ * Asynchronous on `stream`; no float atomics, every sum in an order the table alone decides: bitwise reproducible.  Pointers
+ * need 4-byte alignment only: a chunk whose pointers share their offset from 16 bytes is accessed 16 bytes at a time between a
+ * head and a tail of at most 3 elements, any other chunk 4 bytes at a time.
+ *
+ * m355_dfine_grad_sumsq_launch: d_partials[c] = the sum of g^2 over chunk c, added in double and rounded once, every one of the
+ *   table's chunks written.  ONE launch.
+ *   Reads g and numel of the rows; partials_len >= the number of chunks.
+ * m355_dfine_clip_scale_launch: d_norm (16 bytes, 8-byte aligned): the norm = sqrt(sum of the partials), summed in double in a
+ *   fixed order, as float in d_norm[0]; c = min(1, max_norm / (norm + 1e-6)) (a NaN stays NaN) as float in d_norm[1] and as the
+ *   double in bytes 8..15; then g = g c in place for every row, the product taken in double and rounded once.  TWO launches:
+ *   one block for the norm, one block per chunk for the scaling (c == 1 gives every bit back).  d_partials as grad_sumsq left
+ *   it for the same table.
+ * m355_dfine_adam_launch: one step of every row, per element and in this order (torch 2.10's _multi_tensor_adam, one rounding per
+ *   pass of it):  g' = g c (with d_partials: d_norm is written as by clip_scale and c applied here; g itself is not written);
+ *   weight_decay != 0: mode ADAMW p *= decay, mode ADAM g' += weight_decay p;  m += (g' - m) one_minus_beta1;
+ *   v = v beta2 + one_minus_beta2 g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps).  sqrt and the divisions are correctly
+ *   rounded.  The caller computes the derived scalars in double: decay = 1 - lr weight_decay, step_size = lr / (1 - beta1^t),
+ *   bc2_sqrt = sqrt(1 - beta2^t), with the row's own step count t.  ONE launch, TWO with d_partials (the norm block first).
+ *   d_partials and d_norm come together or not at all; max_norm is ignored without them.
+ * Every entry refuses on the host, before any HIP call (M355_ERR_INVALID): a NULL table (either copy) or output; a count outside
+ *   [1, M355_DFINE_OPTIM_MAX_TENSORS]; a negative numel; a pointer that is not 4-byte aligned; a NULL among the pointers the
+ *   entry uses (g; adam: p, g, m, v) in a row with numel > 0; a chunk0 that is not the sum before it; more chunks than
+ *   2^31 - 1, which is what a launch can index, or none at all; partials_len below the number of chunks; d_norm not 8-byte aligned; a mode
+ *   that is neither constant. */
+#define M355_DFINE_OPTIM_CHUNK 4096
+#define M355_DFINE_OPTIM_MAX_TENSORS 65536
+#define M355_DFINE_OPTIM_ADAM 0
+#define M355_DFINE_OPTIM_ADAMW 1
+typedef struct {
+  float* p;                 /* parameter, exp_avg and exp_avg_sq: read and written by adam alone */
+  float* g;                 /* gradient: read by all three, written by clip_scale */
+  float* m;
+  float* v;
+  int64_t numel;
+  int32_t chunk0;
+  float lr, weight_decay, beta1, beta2, eps;             /* the group's values, as torch holds them */
+  float step_size, bc2_sqrt;                             /* of this tensor's step count */
+  float one_minus_beta1, one_minus_beta2, decay;         /* rounded from double, as torch passes them to its kernels */
+  int32_t reserved[3];
+} m355_dfine_optim_row;     /* 96 bytes */
+int m355_dfine_grad_sumsq_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count,
+                                 float* d_partials, int64_t partials_len, void* stream);
+int m355_dfine_clip_scale_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count,
+                                 const float* d_partials, int64_t partials_len, float max_norm, float* d_norm, void* stream);
+int m355_dfine_adam_launch(const m355_dfine_optim_row* h_table, const m355_dfine_optim_row* d_table, int32_t count, int32_t mode,
+                           const float* d_partials, int64_t partials_len, float max_norm, float* d_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
