@@ -236,7 +236,11 @@ SIGNATURES = {
     "m355_dfine_refine_reference_backward": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "m355_dfine_refine_boxes_forward": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
     "m355_dfine_refine_boxes_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P, _P]),
-    "m355_dfine_gru_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "m355_dfine_maps_to_tokens": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "m355_dfine_tokens_to_maps": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "m355_dfine_gelu_forward": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "m355_dfine_gelu_backward": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "m355_dfine_gru_workspace_bytes":(C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "m355_dfine_gru_forward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32,
                                          _P, _P]),
     "m355_dfine_gru_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64,

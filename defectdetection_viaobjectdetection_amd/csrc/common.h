@@ -271,6 +271,18 @@ int launch_dfine_refine_boxes_backward(const float* gpred, const float* gboxes, 
 int launch_dfine_relu_dropout(const float* in, const float* saved, float* out, long n, float p, unsigned long long seed, int site,
                               hipStream_t s);
 int launch_dfine_keep_mask(unsigned char* mask, long n, float p, unsigned long long seed, int site, hipStream_t s);
+// NCHW maps <-> token rows and the exact GELU (dfine_layout.hip).  Levels: pixels and first token per level, S tokens in all.
+// maps_to_tokens: maps[l] (B, D, h_l, w_l) -> tokens (B, S, D) and, with pos (S, D) or mask (S), extra = tokens + pos or mask * tokens.
+// tokens_to_maps: maps[l] = tokens (+ extra (* mask)); tokens or extra may be nullptr, not both.  gelu: saved == nullptr: out =
+// gelu(in); else the backward: in = grad_out, saved = the forward's input.  The caller has validated every argument, the grid
+// (dfine_layout_blocks) included; maps, tokens, extra and pos 16-byte aligned.
+struct DfineLayoutLevels { int L; int hw[8], start[8]; long S; };
+long dfine_layout_blocks(const DfineLayoutLevels& lv, int B, int D);
+int launch_dfine_maps_to_tokens(const float* const* maps, const DfineLayoutLevels& lv, int B, int D, const float* pos, const float* mask,
+                                float* tokens, float* extra, hipStream_t s);
+int launch_dfine_tokens_to_maps(const float* tokens, const float* extra, const float* mask, const DfineLayoutLevels& lv, int B, int D,
+                                float* const* maps, hipStream_t s);
+int launch_dfine_gelu(const float* in, const float* saved, float* out, long n, hipStream_t s);
 // their backward (dfine_backward.hip).  Any grad_* may be nullptr (not needed); `work` holds the contribution list of
 // grad_value and the per-head partials of grad_ref (msda_backward_workspace_bytes, needed for those two only).  The caller has
 // validated every argument.  msda_backward_value_blocks: the grid of the grad_value pass and its ownership split (own, blk0[9]).

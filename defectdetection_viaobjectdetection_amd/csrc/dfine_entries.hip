@@ -169,6 +169,28 @@ const char* dfine_consistency_check(int32_t T, int64_t N) {
   return nullptr;
 }
 
+// the map / token layout kernels (dfine_layout.hip): the level table from the caller's (h, w) pairs, and everything the two entries
+// check after their top-level null pointers.  nullptr = accepted and lv filled, else the reason
+const char* dfine_layout_check(const float* const* maps, const int32_t* shapes_hw, int L, int B, int D, DfineLayoutLevels& lv) {
+  if (L < 1 || L > 8) return "1..8 levels";
+  for (int l = 0; l < L; ++l) if (!maps[l]) return "null pointer";
+  if (B < 1) return "B >= 1";
+  if (D < 4 || D % 4 != 0 || D > 1024) return "D must be a multiple of 4 in [4, 1024]";
+  lv = {}; lv.L = L;
+  long start = 0;
+  for (int l = 0; l < L; ++l) {
+    const int h = shapes_hw[2 * l], w = shapes_hw[2 * l + 1];
+    if (h < 1 || w < 1) return "every level needs h, w >= 1";
+    if ((long)h * w > 0x7fffffffL - start) return "S must be below 2^31";
+    lv.hw[l] = h * w; lv.start[l] = (int)start;
+    start += (long)h * w;
+  }
+  lv.S = start;
+  if (dfine_layout_blocks(lv, B, D) > kGridMax) return "B * S * D is too large for one launch";
+  for (int l = 0; l < L; ++l) if ((uintptr_t)maps[l] & 15u) return kAlign16;
+  return nullptr;
+}
+
 // the table of the optimizer entries (dfine_optim.hip): one block per chunk, found from the rows' chunk0 prefix.  adam: p, m, v are
 // used too.  nullptr = accepted and *chunks = the grid, else the message
 const char* dfine_optim_check(const m355_dfine_optim_row* h, const m355_dfine_optim_row* d, int32_t count, bool adam, int* chunks) {
@@ -599,6 +621,38 @@ int m355_dfine_refine_boxes_backward(const float* d_grad_pred, const float* d_gr
   return launched(__func__, launch_dfine_refine_boxes_backward(d_grad_pred, d_grad_boxes, d_pred, d_project, d_points, (long)N,
                                                                num_bins_plus1, reg_scale, d_grad_corners, d_grad_points,
                                                                (hipStream_t)stream));
+}
+// NCHW maps <-> token rows and the exact GELU (dfine_layout.hip)
+int m355_dfine_maps_to_tokens(const float* const* h_maps, const int32_t* shapes_hw, int32_t num_levels, int32_t B, int32_t D,
+                              const float* d_pos, const float* d_mask, float* d_tokens, float* d_extra, void* stream) {
+  if (any_null({h_maps, shapes_hw, d_tokens})) return invalid(__func__, "null pointer");
+  if (d_pos && d_mask) return invalid(__func__, "pos and mask exclude each other");
+  if ((d_extra != nullptr) != (d_pos || d_mask)) return invalid(__func__, "extra comes with pos or mask and not without");
+  DfineLayoutLevels lv;
+  if (const char* why = dfine_layout_check(h_maps, shapes_hw, num_levels, B, D, lv)) return invalid(__func__, why);
+  if (any_misaligned16({d_pos, d_tokens, d_extra}) || ((uintptr_t)d_mask & 3u)) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_maps_to_tokens(h_maps, lv, B, D, d_pos, d_mask, d_tokens, d_extra, (hipStream_t)stream));
+}
+int m355_dfine_tokens_to_maps(const float* d_tokens, const float* d_extra, const float* d_mask, const int32_t* shapes_hw,
+                              int32_t num_levels, int32_t B, int32_t D, float* const* h_maps, void* stream) {
+  if (any_null({h_maps, shapes_hw}) || (!d_tokens && !d_extra)) return invalid(__func__, "null pointer");
+  if (d_mask && !d_extra) return invalid(__func__, "mask without extra");
+  DfineLayoutLevels lv;
+  if (const char* why = dfine_layout_check(h_maps, shapes_hw, num_levels, B, D, lv)) return invalid(__func__, why);
+  if (any_misaligned16({d_tokens, d_extra}) || ((uintptr_t)d_mask & 3u)) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_tokens_to_maps(d_tokens, d_extra, d_mask, lv, B, D, h_maps, (hipStream_t)stream));
+}
+int m355_dfine_gelu_forward(const float* d_h, int64_t n, float* d_out, void* stream) {
+  if (any_null({d_h, d_out})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
+  if (any_misaligned16({d_h, d_out})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_gelu(d_h, nullptr, d_out, (long)n, (hipStream_t)stream));
+}
+int m355_dfine_gelu_backward(const float* d_grad_out, const float* d_h, int64_t n, float* d_grad_h, void* stream) {
+  if (any_null({d_grad_out, d_h, d_grad_h})) return invalid(__func__, "null pointer");
+  if (n < 1 || n > (int64_t)1 << 40) return invalid(__func__, "1 <= n <= 2^40");
+  if (any_misaligned16({d_grad_out, d_h, d_grad_h})) return invalid(__func__, kAlign16);
+  return launched(__func__, launch_dfine_gelu(d_grad_out, d_h, d_grad_h, (long)n, (hipStream_t)stream));
 }
 // the GRU recurrence (dfine_gru.hip)
 size_t m355_dfine_gru_workspace_bytes(int32_t B, int64_t S, int32_t H, int32_t D) { return dfine_gru_workspace_bytes(B, S, H, D); }

@@ -52,6 +52,12 @@ gathers of the coordinate logits, class logits and memory, and the sigmoid, two 
 (csrc/dfine_select.hip on the block-wide selection of csrc/topk_select.h, which the post-processing shares), with a stated order
 among equal scores (NaN first, descending, an exact tie to the lowest token) where ``torch.topk`` promises none.
 
+``maps_to_tokens`` / ``tokens_to_maps`` / ``gelu`` / ``aifi_forward`` / ``bind_aifi`` / ``bind_model(assembly=...)`` / ``bind_all``
+are the hybrid encoder's AIFI layer (``DFineAIFILayer``, ``DFineEncoderLayer``, :542-610, :699-753) between its torch GEMMs and the
+memory assembly of ``DFineModel.forward`` (:1750-1797): NCHW maps to token rows for all levels in one launch, with ``tokens + pos``
+or ``valid_mask * tokens`` from the same read, its adjoint, and the erf GELU with a backward from the saved input
+(csrc/dfine_layout.hip); the layer's training clamp is unconditional, so nothing between the backbone and the loss synchronises.
+
 ``temporal_fuse`` / ``guard_logits`` / ``decode_boxes(guard=True)`` / ``noobject_loss`` / ``consistency_loss`` / ``temporal_head``
 are the trainers' own stage between the temporal encoder / context GRU and the loss or the post-processing
 (temp_dfine_over.py:188-285, temp_dfine_over_improved.py:219-350): the softmax over the frame axis and the fusion, the anomaly
@@ -2126,6 +2132,315 @@ def bind_decoder_loop(module):
     return module
 
 
+# ---- NCHW maps <-> token rows, the exact GELU and the AIFI layer of the hybrid encoder (DFineAIFILayer, DFineEncoderLayer) --------
+# The trainers freeze only the backbone, so the AIFI layer runs forward and backward on every step.  Its nn.Linear products stay
+# torch GEMMs; between them the kernels above (self_attention, add_layer_norm) and csrc/dfine_layout.hip: the map -> token transpose
+# with x + pos from the same read, its adjoint, and the erf GELU.  The same transpose with a level table and valid_mask is the memory
+# assembly of DFineModel.forward.
+LAYOUT_MAX_LEVELS = 8            # the limits of m355_dfine_maps_to_tokens / _tokens_to_maps; anything outside them takes the *_torch form
+LAYOUT_MAX_TOKENS = (1 << 31) - 1
+layout_calls = {"kernel": 0, "torch": 0}   # maps_to_tokens and tokens_to_maps calls by path (tests and tools read it)
+aifi_calls = {"kernel": 0, "torch": 0}     # aifi_forward calls by path
+
+
+def _level_shapes(maps):
+    if not isinstance(maps, (list, tuple)) or not maps or not all(torch.is_tensor(m) and m.dim() == 4 for m in maps):
+        raise ValueError("maps must be a non-empty list of (B, D, h, w) tensors")
+    B, D = maps[0].shape[:2]
+    if any(m.shape[:2] != (B, D) or m.device != maps[0].device or m.dtype != maps[0].dtype for m in maps):
+        raise ValueError("the maps must agree in batch size, channels, device and dtype")
+    return [(int(m.shape[2]), int(m.shape[3])) for m in maps]
+
+
+def _layout_takes(B: int, D: int, shapes, *tensors) -> bool:
+    S = sum(h * w for h, w in shapes)
+    return (_fp32_cuda(*tensors) and not torch.is_autocast_enabled() and B >= 1 and S >= 1 and all(h * w for h, w in shapes)
+            and D % 4 == 0 and 4 <= D <= ADDLN_MAX_D and len(shapes) <= LAYOUT_MAX_LEVELS and S <= LAYOUT_MAX_TOKENS
+            and len({t.device for t in tensors}) == 1)
+
+
+def maps_to_tokens_torch(maps, pos=None, mask=None):
+    """upstream's expressions: torch.cat([m.flatten(2).transpose(1, 2) for m in maps], 1), tokens + pos, mask * tokens"""
+    tokens = torch.cat([m.flatten(2).transpose(1, 2) for m in maps], 1)
+    if pos is not None:
+        return tokens, tokens + pos
+    if mask is not None:
+        return tokens, mask.to(tokens.dtype).reshape(1, -1, 1) * tokens
+    return tokens, None
+
+
+def tokens_to_maps_torch(tokens, shapes):
+    """upstream's expression per level: transpose(1, 2).reshape(B, D, h, w).contiguous()"""
+    B, _, D = tokens.shape
+    out, s = [], 0
+    for h, w in shapes:
+        out.append(tokens[:, s:s + h * w].transpose(1, 2).reshape(B, D, h, w).contiguous())
+        s += h * w
+    return out
+
+
+def _shape_table(shapes):
+    return (C.c_int32 * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
+
+
+def _maps_to_tokens_forward(maps, shapes, pos, mask):
+    """maps, pos, mask as _f32c16 leaves them (mask: fp32 (S,)) -> tokens, extra or None"""
+    B, D = maps[0].shape[:2]
+    S = sum(h * w for h, w in shapes)
+    tokens = torch.empty((B, S, D), dtype=torch.float32, device=maps[0].device)
+    extra = torch.empty_like(tokens) if pos is not None or mask is not None else None
+    ptrs = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+    check(lib.m355_dfine_maps_to_tokens(ptrs, _shape_table(shapes), len(shapes), B, D, _ptr(pos), _ptr(mask), _ptr(tokens), _ptr(extra),
+                                        _stream()))
+    return tokens, extra
+
+
+def _tokens_to_maps_forward(tokens, extra, mask, shapes, B, D):
+    """tokens and extra (either may be None) as _f32c16 leaves them -> the maps of tokens (+ extra (* mask))"""
+    dev = (tokens if tokens is not None else extra).device
+    maps = [torch.empty((B, D, h, w), dtype=torch.float32, device=dev) for h, w in shapes]
+    ptrs = (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+    check(lib.m355_dfine_tokens_to_maps(_ptr(tokens), _ptr(extra), _ptr(mask), _shape_table(shapes), len(shapes), B, D, ptrs, _stream()))
+    return maps
+
+
+class _MapsToTokens(torch.autograd.Function):
+    """Saves nothing but the mask: the backward is tokens_to_maps of both gradients."""
+
+    @staticmethod
+    def forward(ctx, shapes, pos, mask, *maps):
+        tokens, extra = _maps_to_tokens_forward([_f32c16(m, "maps") for m in maps], shapes, pos, mask)
+        ctx.meta = (shapes, mask, maps[0].shape[0], maps[0].shape[1])
+        ctx.set_materialize_grads(False)   # an unused output's gradient stays None: 0 + mask * g would turn a -0 into +0
+        if extra is None:
+            return tokens
+        return tokens, extra
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_tokens, g_extra=None):
+        shapes, mask, B, D = ctx.meta
+        gt = _f32c16(g_tokens, "grad_tokens") if g_tokens is not None else None
+        ge = _f32c16(g_extra, "grad_extra") if g_extra is not None else None
+        if gt is None and ge is None:
+            return (None, None, None) + (None,) * len(shapes)
+        return (None, None, None) + tuple(_tokens_to_maps_forward(gt, ge, mask if ge is not None else None, shapes, B, D))
+
+
+class _TokensToMaps(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tokens, shapes):
+        B, _, D = tokens.shape
+        ctx.meta = (shapes, tokens.shape)
+        ctx.set_materialize_grads(False)   # backward fills the levels nobody used with zeros itself
+        return tuple(_tokens_to_maps_forward(_f32c16(tokens, "tokens"), None, None, shapes, B, D))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g_maps):
+        shapes, (B, _, D) = ctx.meta
+        like = next((g for g in g_maps if g is not None), None)
+        if like is None:
+            return None, None
+        gs = [_f32c16(g, "grad_maps") if g is not None else like.new_zeros((B, D, h, w)) for g, (h, w) in zip(g_maps, shapes)]
+        return _maps_to_tokens_forward(gs, shapes, None, None)[0], None
+
+
+def maps_to_tokens(maps, pos=None, mask=None):
+    """maps: a list of L <= 8 (B, D, h_l, w_l) feature maps -> (tokens, extra): tokens (B, S, D) = torch.cat([m.flatten(2)
+    .transpose(1, 2) for m in maps], 1) in ONE launch for all levels (a tiled transpose through LDS), and from the same read of the
+    maps extra = tokens + pos for pos (S, D) (the AIFI layer's q / k input) or mask * tokens for a mask of S elements (the 0 / 1
+    valid_mask of DFineModel.forward, any dtype: a true multiply, 0 * inf is NaN); None without either.  pos and mask are constants
+    and exclude each other.  Differentiable in the maps: the backward is tokens_to_maps of grad_tokens + grad_extra (* mask), one
+    launch.  Maps that are not contiguous (channels-last) or not 16-byte aligned are copied once.  CPU or non-fp32 tensors,
+    autocast, D not a multiple of 4 in [4, 1024], more than 8 levels and an empty level take maps_to_tokens_torch; layout_calls
+    counts the path."""
+    shapes = _level_shapes(maps)
+    B, D = (int(v) for v in maps[0].shape[:2])
+    S = sum(h * w for h, w in shapes)
+    if pos is not None and mask is not None:
+        raise ValueError("pos and mask exclude each other")
+    if (pos is not None and pos.requires_grad) or (mask is not None and mask.requires_grad):
+        raise ValueError("pos and mask are constants: neither may require grad")
+    if pos is not None:
+        if pos.numel() != S * D or pos.shape[-1] != D:
+            raise ValueError("pos must be (S, D)")
+        pos = pos.reshape(S, D)
+    if mask is not None and mask.numel() != S:
+        raise ValueError("mask must have S elements")
+    extras = [t for t in (pos,) if t is not None]
+    if not _layout_takes(B, D, shapes, *maps, *extras) or (mask is not None and mask.device != maps[0].device):
+        layout_calls["torch"] += 1
+        return maps_to_tokens_torch(maps, pos, mask)
+    layout_calls["kernel"] += 1
+    p = _f32c16(pos, "pos") if pos is not None else None
+    m = mask.reshape(S).to(torch.float32).contiguous() if mask is not None else None
+    if _wants_grad(*maps):
+        out = _MapsToTokens.apply(shapes, p, m, *maps)
+        return out if isinstance(out, tuple) else (out, None)
+    return _maps_to_tokens_forward([_f32c16(t, "maps") for t in maps], shapes, p, m)
+
+
+def tokens_to_maps(tokens, shapes):
+    """tokens (B, S, D), shapes [(h_l, w_l)] with sum h_l w_l == S -> the list of contiguous (B, D, h_l, w_l) maps,
+    map_l[b, c, y, x] = tokens[b, start_l + y w_l + x, c]: transpose(1, 2).reshape(B, D, h, w).contiguous() for every level in ONE
+    launch; differentiable, the backward is maps_to_tokens.  The fallbacks of maps_to_tokens apply (tokens_to_maps_torch)."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    if not torch.is_tensor(tokens) or tokens.dim() != 3 or sum(h * w for h, w in shapes) != tokens.shape[1]:
+        raise ValueError("tokens must be (B, S, D) and the shapes must add up to S")
+    B, _, D = (int(v) for v in tokens.shape)
+    if not _layout_takes(B, D, shapes, tokens):
+        layout_calls["torch"] += 1
+        return tokens_to_maps_torch(tokens, shapes)
+    layout_calls["kernel"] += 1
+    if _wants_grad(tokens):
+        return list(_TokensToMaps.apply(tokens, shapes))
+    return _tokens_to_maps_forward(_f32c16(tokens, "tokens"), None, None, shapes, B, D)
+
+
+def gelu_torch(h: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.gelu(h)
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h):
+        hs = _f32c16(h, "h")
+        ctx.save_for_backward(hs)   # the input alone: the backward recomputes Phi(h) and phi(h)
+        return _gelu_forward(hs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (hs,) = ctx.saved_tensors
+        g = _f32c16(grad_out, "grad_output")
+        gh = torch.empty_like(hs)
+        check(lib.m355_dfine_gelu_backward(_ptr(g), _ptr(hs), hs.numel(), _ptr(gh), _stream()))
+        return gh
+
+
+def _gelu_forward(hs):
+    out = torch.empty_like(hs)
+    check(lib.m355_dfine_gelu_forward(_ptr(hs), hs.numel(), _ptr(out), _stream()))
+    return out
+
+
+def gelu(h: torch.Tensor) -> torch.Tensor:
+    """The exact GELU h * Phi(h) = h * 0.5 * (1 + erf(h / sqrt(2))), F.gelu with its default arguments, in one elementwise launch;
+    the backward (one launch) is g * (Phi(h) + h * phi(h)) from the saved input, the only tensor kept.  CPU or non-fp32 tensors,
+    autocast and an empty tensor take gelu_torch."""
+    if not _fp32_cuda(h) or h.numel() == 0 or torch.is_autocast_enabled():
+        return gelu_torch(h)
+    if _wants_grad(h):
+        return _Gelu.apply(h)
+    return _gelu_forward(_f32c16(h, "h"))
+
+
+def _is_exact_gelu(act) -> bool:
+    """transformers' ACT2CLS["gelu"] (GELUActivation on F.gelu) or nn.GELU() with approximate="none" """
+    F = torch.nn.functional
+    if isinstance(act, torch.nn.GELU):
+        return act.approximate == "none"
+    return type(act).__name__ == "GELUActivation" and getattr(act, "act", None) is F.gelu
+
+
+def _records_outputs(layer, kwargs) -> bool:
+    """transformers collects hidden states and attention weights through forward hooks on the layers and their attention"""
+    cfg = getattr(layer, "config", None)
+    if any(kwargs.get(k) or getattr(cfg, k, False) for k in ("output_hidden_states", "output_attentions")):
+        return True
+    mods = [layer, *layer.layers, *(enc.self_attn for enc in layer.layers)]
+    return any(len(m._forward_hooks) or len(m._forward_pre_hooks) for m in mods)
+
+
+def _aifi_takes(layer, x, kwargs) -> bool:
+    """True when the kernels cover this call of a DFineAIFILayer; anything else goes to the class's own forward"""
+    if not _fp32_cuda(x) or x.dim() != 4 or x.numel() == 0 or torch.is_autocast_enabled():
+        return False
+    D = x.shape[1]
+    if D != layer.encoder_hidden_dim or D % 4 or not 4 <= D <= ADDLN_MAX_D or len(layer.layers) < 1:
+        return False
+    if _records_outputs(layer, kwargs):
+        return False
+    for enc in layer.layers:
+        sa, mlp = enc.self_attn, enc.mlp
+        if enc.normalize_before or enc.hidden_size != D:
+            return False
+        if layer.training and (float(enc.dropout) > 0.0 or float(sa.attention_dropout) > 0.0):
+            return False
+        if not _is_exact_gelu(mlp.act) or mlp.num_layers != 2 or len(mlp.layers) != 2:
+            return False
+        if not (_affine_norm(enc.self_attn_layer_norm, D) and _affine_norm(enc.final_layer_norm, D)):
+            return False
+        if getattr(layer, "_m355_attention_kernel", False) and (
+                sa.head_dim != ENCODER_HEAD_DIM or D % ENCODER_HEAD_DIM
+                or any(lin.bias is None for lin in (sa.q_proj, sa.k_proj, sa.v_proj, sa.o_proj))):
+            return False
+    return _fp32_cuda_params(layer)
+
+
+def aifi_forward(self, hidden_states, **kwargs):
+    """DFineAIFILayer.forward with its DFineEncoderLayer(s) (modeling_d_fine.py:542-610, 699-753, transformers 5.15.0) on fp32 CUDA
+    tensors, the nn.Linear products as torch GEMMs on the module's own parameters and everything between them on the kernels:
+        x, xp = maps_to_tokens([map], pos=pos_embed)              # tokens and tokens + pos from one read of the map
+        y = o_proj(self_attention([q | k](xp), v(x)))             # k without its bias; attention=False: self.self_attn(...)
+        x = add_layer_norm(x, y, self_attn_layer_norm)
+        x = add_layer_norm(x, mlp.layers[1](gelu(mlp.layers[0](x))), final_layer_norm)
+        x = x.clamp(-max, max) when training                      # unconditional: no isfinite().all(), no synchronisation
+        return tokens_to_maps(x, [(h, w)])[0]
+    The clamp is the identity on finite values and on NaN and its backward passes every element it did not move, so it equals
+    upstream's conditional one in value and gradient.  A call goes to the class's own forward, untouched, with normalize_before,
+    when the module trains with config.dropout above 0, with an activation other than the exact GELU or an MLP that is not two
+    layers, on non-fp32, CPU or empty tensors, under autocast, with D not a multiple of 4 in [4, 1024], when outputs are recorded
+    (output_hidden_states / output_attentions, or a forward hook on the layer, its encoder layers or their self_attn) and, with
+    attention=True, with a head dim other than 32 or a projection without bias.  Bound per instance by bind_aifi."""
+    if not _aifi_takes(self, hidden_states, kwargs):
+        aifi_calls["torch"] += 1
+        return type(self).forward(self, hidden_states, **kwargs)
+    aifi_calls["kernel"] += 1
+    F = torch.nn.functional
+    H, W = hidden_states.shape[2:]
+    pos = None
+    if self.training or self.eval_size is None:
+        pos = self.position_embedding(width=W, height=H, device=hidden_states.device, dtype=hidden_states.dtype)   # (1, H W, D), cached
+    attention = getattr(self, "_m355_attention_kernel", False)
+    x, xp = maps_to_tokens([hidden_states], pos=pos[0] if attention and pos is not None else None)
+    for i, enc in enumerate(self.layers):
+        sa = enc.self_attn
+        if attention:
+            qk_in = x if pos is None else (xp if i == 0 else x + pos)
+            # k_proj.bias shifts every logit of a query by the same q . b, which the softmax cancels (decoder_layer_forward)
+            qk = F.linear(qk_in, torch.cat([sa.q_proj.weight, sa.k_proj.weight]), torch.cat([sa.q_proj.bias, sa.k_proj.bias * 0.0]))
+            qkv = torch.cat([qk, F.linear(x, sa.v_proj.weight, sa.v_proj.bias)], dim=-1)
+            y = F.linear(self_attention(qkv, x.shape[-1] // ENCODER_HEAD_DIM), sa.o_proj.weight, sa.o_proj.bias)
+        else:
+            y = sa(hidden_states=x, attention_mask=None, position_embeddings=pos, **kwargs)[0]
+        n = enc.self_attn_layer_norm
+        x = add_layer_norm(x, y, n.weight, n.bias, n.eps)
+        l0, l1 = enc.mlp.layers
+        y = F.linear(gelu(F.linear(x, l0.weight, l0.bias)), l1.weight, l1.bias)
+        n = enc.final_layer_norm
+        x = add_layer_norm(x, y, n.weight, n.bias, n.eps)
+        if self.training:
+            c = torch.finfo(x.dtype).max   # upstream's finfo.max - 1000 is finfo.max in fp32
+            x = x.clamp(-c, c)
+    return tokens_to_maps(x, [(int(H), int(W))])[0]
+
+
+def bind_aifi(module, attention: bool = False):
+    """Set aifi_forward on every DFineAIFILayer INSTANCE inside `module` (a DFineHybridEncoder, a whole DFineForObjectDetection, a
+    single layer, or any module that holds some); transformers' classes are never touched, parameters, buffers and the state dict
+    stay as they are.  Returns `module`.  attention=False keeps each encoder layer's self.self_attn(...) as the class runs it;
+    attention=True runs the attention core on dfine.self_attention with the packed [q | k](x + pos), v(x) projection.  The default
+    is the arm that profiles/dfine_aifi_bench.json shows faster for the layer's training step (forward + backward) at
+    (50, 256, 20, 20): 3.60 ms against 3.72 ms (the unbound layer: 3.92 ms); at (1, 256, 20, 20) attention=False is SLOWER than the
+    unbound layer (1.32 against 1.15 ms, host-bound) and attention=True faster (0.98 ms)."""
+    from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
+    for m in _bind_forward(module, {M.DFineAIFILayer: aifi_forward}):
+        m._m355_attention_kernel = bool(attention)   # a plain attribute: not a parameter, not a buffer, not in the state dict
+    return module
+
+
 # ---- encoder query selection (DFineModel.forward, modeling_d_fine.py:1804-1828) ----------------------------------------------------
 # Between the hybrid encoder's heads and the decoder every call of a D-FINE model picks its num_queries tokens: row max of the class
 # logits, top-k, three gathers and a sigmoid.  csrc/dfine_select.hip does it in two launches forward (row max on all CUs; one block
@@ -2245,6 +2560,17 @@ def select_queries(class_logits: torch.Tensor, coord_logits: torch.Tensor, memor
     return QuerySelection(*_select_forward(cl, co, mem, K, False)[:5])
 
 
+def _mask_is_all_ones(model, valid_mask) -> bool:
+    """Whether this valid_mask tensor is all ones, found once (one synchronisation, as _loop_project's float(reg_scale)) and cached
+    on the instance by the tensor's identity and version; the cache holds the tensor, so its id cannot be reused while it counts"""
+    cached = getattr(model, "_m355_valid_mask_ones", None)
+    if cached is not None and cached[0] is valid_mask and cached[1] == valid_mask._version:
+        return cached[2]
+    ones = bool(valid_mask.all())
+    model._m355_valid_mask_ones = (valid_mask, valid_mask._version, ones)
+    return ones
+
+
 def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None, inputs_embeds=None, labels=None, **kwargs):
     """DFineModel.forward (modeling_d_fine.py:1666-1861, transformers 5.15.0) with its query selection (:1804-1828: row max, top-k,
     three gathers, sigmoid) on select_queries.  The module's own sub-modules run everything else, in upstream's order: backbone,
@@ -2253,7 +2579,10 @@ def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None
     weight_embedding and no memory rows are gathered.  This body always runs; only the selection switches between the kernels and
     select_queries_torch (CPU or non-fp32 tensors, autocast, shapes beyond the limits), and model_calls counts it.  Every field of
     DFineModelOutput is filled as upstream; return_dict=False gives its tuple.  Among equal scores upstream's torch.topk promises
-    no order; this one has select_queries' rule.  Bound per instance by bind_model."""
+    no order; this one has select_queries' rule.  With bind_model(assembly=True) the memory assembly (:1750-1797: three
+    flatten(2).transpose(1, 2) views materialised by torch.cat, then valid_mask * source_flatten) is one maps_to_tokens call:
+    source_flatten is its tokens and memory its masked second output, or the tokens themselves for a valid_mask that is all ones
+    (found once per mask tensor, _mask_is_all_ones).  Bound per instance by bind_model."""
     from transformers.modeling_outputs import BaseModelOutput
     from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
     return_dict = kwargs.pop("return_dict", None)
@@ -2283,6 +2612,7 @@ def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None
         for i in range(len(sources), self.config.num_feature_levels):
             sources.append(self.decoder_input_proj[i](encoder_outputs.last_hidden_state[-1]))
 
+    assembly = getattr(self, "_m355_assembly", False)
     source_flatten, spatial_shapes_list = [], []
     spatial_shapes = torch.empty((len(sources), 2), device=device, dtype=torch.long)
     for level, source in enumerate(sources):
@@ -2290,8 +2620,10 @@ def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None
         spatial_shapes[level, 0] = height
         spatial_shapes[level, 1] = width
         spatial_shapes_list.append((height, width))
-        source_flatten.append(source.flatten(2).transpose(1, 2))
-    source_flatten = torch.cat(source_flatten, 1)
+        if not assembly:
+            source_flatten.append(source.flatten(2).transpose(1, 2))
+    if not assembly:
+        source_flatten = torch.cat(source_flatten, 1)
     level_start_index = torch.cat((spatial_shapes.new_zeros((1,)), spatial_shapes.prod(1).cumsum(0)[:-1]))
 
     if self.training and self.config.num_denoising > 0 and labels is not None:
@@ -2302,12 +2634,21 @@ def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None
     else:
         denoising_class, denoising_bbox_unact, attention_mask, denoising_meta_values = None, None, None, None
 
-    batch_size, device, dtype = len(source_flatten), source_flatten.device, source_flatten.dtype
+    like = sources[0] if assembly else source_flatten
+    batch_size, device, dtype = len(like), like.device, like.dtype
     if self.training or self.config.anchor_image_size is None:
         anchors, valid_mask = self.generate_anchors(tuple(spatial_shapes_list), device=device, dtype=dtype)   # hashable: lru_cache
+        mask_key = valid_mask
     else:
-        anchors, valid_mask = self.anchors.to(device, dtype), self.valid_mask.to(device, dtype)
-    memory = valid_mask.to(source_flatten.dtype) * source_flatten
+        anchors, valid_mask, mask_key = self.anchors.to(device, dtype), self.valid_mask.to(device, dtype), self.valid_mask
+    if assembly:   # one launch: the levels' tokens and valid_mask * tokens from one read of the maps
+        if _mask_is_all_ones(self, mask_key):
+            source_flatten, _ = maps_to_tokens(sources)
+            memory = source_flatten   # 1.0 * x is x, bit for bit
+        else:
+            source_flatten, memory = maps_to_tokens(sources, mask=valid_mask)
+    else:
+        memory = valid_mask.to(source_flatten.dtype) * source_flatten
     output_memory = self.enc_output(memory)
     enc_outputs_class = self.enc_score_head(output_memory)
     enc_outputs_coord_logits = self.enc_bbox_head(output_memory) + anchors
@@ -2350,7 +2691,7 @@ def model_forward(self, pixel_values=None, pixel_mask=None, encoder_outputs=None
     return out if return_dict else out.to_tuple()
 
 
-def bind_model(module):
+def bind_model(module, assembly: bool = True):
     """Set model_forward on every DFineModel INSTANCE inside `module` (a DFineForObjectDetection, a DFineModel, or any module that
     holds some); transformers' classes are never touched, parameters, buffers and the state dict stay as they are, so existing
     checkpoints load unchanged.  Returns `module`.  Composes with bind_decoder (different classes): bind_decoder(bind_model(m)).
@@ -2359,9 +2700,27 @@ def bind_model(module):
     K = 300) forward 0.092 against 0.299 for upstream's torch ops (2 against 30 device activities), forward + backward 0.146 against
     0.366; at (16, ...) and (1, ...) with C = 80 forward + backward is host-bound and the bound median is SLOWER (0.223 against
     0.197, 0.205 against 0.181, spreads overlapping); model.model(pixel_values) at 2 x 256 x 256 does not move: eval 18.9 against
-    18.8, training 61.8 against 64.8, inside the spread."""
+    18.8, training 61.8 against 64.8, inside the spread.
+    assembly=True also runs the memory assembly (cat of the flattened levels, valid_mask * source_flatten) as one maps_to_tokens
+    launch; assembly=False keeps the torch lines.  The default is the arm profiles/dfine_aifi_bench.json shows faster at
+    (50, 8400, 256) with the generated mask: forward + backward 0.51 against 2.26 ms; at 2 x 256 x 256 the model's step does not move
+    (training 53.5 against 52.7, the bound median SLOWER inside the spread)."""
     from transformers.models.d_fine import modeling_d_fine as M   # lazily: the package does not need transformers otherwise
-    _bind_forward(module, {M.DFineModel: model_forward})
+    for m in _bind_forward(module, {M.DFineModel: model_forward}):
+        m._m355_assembly = bool(assembly)   # a plain attribute: not a parameter, not a buffer, not in the state dict
+    return module
+
+
+def bind_all(module, attention: bool = False):
+    """bind_model, bind_decoder, bind_decoder_loop, bind_aifi, bind_encoder and bind_gru on whatever `module` holds (each binds the
+    instances of its own classes and leaves everything else alone); `attention` goes to bind_decoder and bind_aifi.  Returns
+    `module`: one line for a trainer in place of six."""
+    bind_model(module)
+    bind_decoder(module, attention=attention)
+    bind_decoder_loop(module)
+    bind_aifi(module, attention=attention)
+    bind_encoder(module)
+    bind_gru(module)
     return module
 
 

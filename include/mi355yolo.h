@@ -936,6 +936,29 @@ int m355_dfine_refine_boxes_backward(const float* d_grad_pred, const float* d_gr
                                      const float* d_points, int64_t N, int32_t num_bins_plus1, float reg_scale, float* d_grad_corners,
                                      float* d_grad_points, void* stream);
 
+/* ---- NCHW feature maps <-> token rows, and the exact GELU (the AIFI layer and the decoder's memory assembly) ----------------
+ * transformers' DFineAIFILayer turns its map into tokens and back around one encoder layer whose MLP uses the exact (erf) GELU, and
+ * DFineModel.forward concatenates the flattened levels and multiplies them by valid_mask.  All tensors fp32, contiguous,
+ * asynchronous on `stream`; no atomics, one writer per element: bitwise reproducible, an image does not depend on its batch.
+ * m355_dfine_maps_to_tokens: h_maps is a HOST array of num_levels device pointers, map l (B, D, h_l, w_l) with (h_l, w_l) =
+ *   shapes_hw[2 l], shapes_hw[2 l + 1] (host) -> tokens (B, S, D), S = sum h_l w_l, tokens[b, start_l + y w_l + x, c] =
+ *   map_l[b, c, y, x], in ONE launch for all levels.  With pos (S, D): extra = tokens + pos; with mask (S): extra =
+ *   mask[s] * tokens, a true multiply (0 * inf is NaN, 0 * -x is -0); the maps are read once for both outputs.  pos and mask
+ *   exclude each other and extra is NULL exactly when both are.
+ * m355_dfine_tokens_to_maps: the adjoint, map_l[b, c, y, x] = tokens[b, s, c] (+ extra[b, s, c] (* mask[s])) in ONE launch; tokens
+ *   or extra may be NULL (not both), mask only with extra.
+ * m355_dfine_gelu_forward: out (n) = h * 0.5 * (1 + erf(h / sqrt(2))).  _backward: grad_h = grad_out * (Phi(h) + h phi(h)) from the
+ *   saved input h.
+ * Limits (M355_ERR_INVALID before any HIP call): no NULL among the required pointers (the map table's entries included),
+ * 1 <= num_levels <= 8, B >= 1, D a multiple of 4 in [4, 1024], h, w >= 1, S < 2^31, a grid below 2^31 blocks, 1 <= n <= 2^40,
+ * 16-byte alignment of every tensor but mask (4-byte). */
+int m355_dfine_maps_to_tokens(const float* const* h_maps, const int32_t* shapes_hw, int32_t num_levels, int32_t B, int32_t D,
+                              const float* d_pos, const float* d_mask, float* d_tokens, float* d_extra, void* stream);
+int m355_dfine_tokens_to_maps(const float* d_tokens, const float* d_extra, const float* d_mask, const int32_t* shapes_hw,
+                              int32_t num_levels, int32_t B, int32_t D, float* const* h_maps, void* stream);
+int m355_dfine_gelu_forward(const float* d_h, int64_t n, float* d_out, void* stream);
+int m355_dfine_gelu_backward(const float* d_grad_out, const float* d_h, int64_t n, float* d_grad_h, void* stream);
+
 /* ---- The recurrence of the D-FINE trainer's context GRU -----------------------------------------------------------------
  * torch's one-layer nn.GRU(*, 256, batch_first, uni- or bidirectional) without its input projection: the caller's GEMM gives
  * gi = x cat(W_ih, W_ih_reverse)^T + b_ih for all steps and both directions; these entries run the serial chain.  Gate order
